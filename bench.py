@@ -28,6 +28,11 @@ of a timed region has been solved before, nothing of its solution is known.  Rep
 (exact foreknowledge: the upper bound a fleet of recurring robots approaches; round 2's headline), and the strictly sequential
 one-batch-per-launch figure as `one_batch_in_flight_*`.  Weak scaling.
 
+A plain run sets up, warms up, times ONE region of exactly `--steps` steps (`value`, `ms_per_step`) and prints the line.  Everything
+else -- `RUNS` timed regions (`value_runs`), the other queue orders, second_order 2, one batch in flight, two launches per region, the
+CPU baselines, the MPC-tick loops and the 4-wave batches -- runs with `--full` only.  `--dump-outputs DIR` writes what the last timed
+step computed (DIR/<name>.npy, float64: x, u, cost, iters, status of its instances).
+
 Rank 0 prints ONE JSON line; `roofline` and `cpu_baseline` are defined in DESIGN.md ("Measurement").
 """
 import argparse
@@ -35,6 +40,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
 
@@ -180,7 +186,70 @@ def cpu_tick_baseline(model, trace, gpu_iters):
             "sample": f"{len(trace)} recorded ticks, each solved from the same x0 / parameters / warm start as the GPU tick"}
 
 
-RUNS = 3     # timed regions per bench run, each over seed blocks of its own: `value` is their median
+RUNS = 3     # timed regions of a --full run, each over seed blocks of its own: the first is the headline, `value_runs` all of them
+GEN_CHUNK = 4                                          # seed blocks one worker process generates at a time
+GEN_WORKERS = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
+DUMP_BYTES = 64 << 20                                  # --dump-outputs: at most this much in all
+
+
+def gen_blocks(N, B, blocks, x0_draw, signed):
+    """Host arrays [len(blocks), B, ...] of the seed blocks' srbd13 instances -- x0, params and their queue-order-3 class labels
+    (workload.srbd13_schedule_classes) -- and the static input.  The warm start is x0 and the static input at every node: it is
+    checked here and rebuilt on the device by load_blocks instead of being shipped (half the bytes of a block)."""
+    from srbd_horizon_amd import workload
+    h = workload.make_srbd13_batch(N, np.concatenate([b * B + np.arange(B) for b in blocks]), x0_draw=x0_draw)
+    u_static = h["us"][0, 0]
+    if not (np.array_equal(h["xs"], np.broadcast_to(h["x0"][:, None], h["xs"].shape))
+            and np.array_equal(h["us"], np.broadcast_to(u_static, h["us"].shape))):
+        raise RuntimeError("make_srbd13_batch's warm start is no longer x0 / the static input at every node")
+    lab, ncls = workload.srbd13_schedule_classes(h["params"], signed=signed)
+    out = {k: h[k].reshape((len(blocks), B) + h[k].shape[1:]) for k in ("x0", "params")}
+    out["classes"] = lab.reshape(len(blocks), B)
+    return out, u_static, ncls
+
+
+def load_blocks(N, B, blocks, dev, x0_draw=0, signed=True):
+    """Device tensors [len(blocks), B, ...] of the seed blocks' instances (x0, xs, us, params, classes; n_classes), the same as one
+    workload.make_srbd13_batch call over all their seeds.  Every instance depends on its own seed alone, and the generator costs
+    ~45 us an instance on one core (minutes for a long run), so chunks of GEN_CHUNK blocks are generated by fresh worker processes
+    (spawned: this process has the GPU open) and copied to the device one by one."""
+    import multiprocessing
+    import torch
+    chunks = [blocks[i:i + GEN_CHUNK] for i in range(0, len(blocks), GEN_CHUNK)]
+    args = [(N, B, c, x0_draw, signed) for c in chunks]
+    workers = min(len(chunks), GEN_WORKERS)
+    pool = ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) if workers > 1 else None
+    try:
+        d, lo, u_first = {}, 0, None
+        for h, u_static, ncls in (pool.map(gen_blocks, *zip(*args)) if pool else (gen_blocks(*a) for a in args)):
+            for k, v in h.items():
+                if k not in d:
+                    d[k] = torch.empty((len(blocks),) + v.shape[1:], dtype=torch.from_numpy(v).dtype, device=dev)
+                d[k][lo:lo + len(v)].copy_(torch.from_numpy(v))
+            lo += len(h["x0"])
+            u_first = u_static if u_first is None else u_first
+            if not np.array_equal(u_static, u_first):
+                raise RuntimeError("the static input differs between seed blocks")
+            d["n_classes"] = ncls
+    finally:
+        if pool:
+            pool.shutdown()
+    d["xs"] = d["x0"][:, :, None, :].expand(-1, -1, N + 1, -1).contiguous()
+    d["us"] = torch.from_numpy(u_first).to(dev).expand(len(blocks), B, N, -1).contiguous()
+    return d
+
+
+def dump_outputs(out_dir, x, u, st):
+    """The solution of one step's instances as float64 .npy files; a fixed, seeded sample of the instances when they exceed
+    DUMP_BYTES (--batch / --horizon far above the defaults)."""
+    B = x.shape[0]
+    arrays = {"x": x, "u": u, "cost": st["cost"], "iters": st["iters"], "status": st["status"]}
+    per_instance = 8 * sum(a[0].size for a in arrays.values())
+    keep = DUMP_BYTES // per_instance
+    rows = np.arange(B) if B <= keep else np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
 
 
 def seed_block(rank, world, steps, warmup, phase, i, run=0):
@@ -230,7 +299,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--batch", type=int, default=1024, help="MPC instances per GPU and step")
     ap.add_argument("--horizon", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline and the single-instance extras")
+    ap.add_argument("--full", action="store_true", help=f"also everything beside the headline: {RUNS} timed regions (value_runs), the "
+                                                         "other queue orders, second_order 2, one batch in flight, two launches per "
+                                                         "region, the CPU baselines, the MPC-tick loops and the 4-wave batches")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write x, u, cost, iters and status of the last timed step's instances "
+                                                          "(rank 0's) as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the single-instance extras")
     ap.add_argument("--queue-depth", type=int, default=64, help="steps (batches) one engine handle holds = most steps per launch")
     ap.add_argument("--class-signs", type=int, default=1, help="queue order 3: class labels with the SIGN of the commanded velocity (0: zero / non-zero only)")
     ap.add_argument("--waves-per-simd", type=int, default=2, help="kernel build: 1 = one wavefront per SIMD, 2 = two")
@@ -242,7 +316,7 @@ def main():
                          "the wire while launch k + 1 solves, at the price of two drains)")
     ap.add_argument("--gather", default="full", choices=("full", "first_knot"),
                     help="what the N > 1 all-gather carries per instance: the whole plan (SURVEY 8(e), 4 680 B) or u_0 | x_1 | cost | iterations (168 B)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the index-order, replay and one-batch-in-flight measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the index-order, replay and one-batch-in-flight measurements")
     args = ap.parse_args()
 
     import torch
@@ -283,20 +357,16 @@ def main():
     wps = args.waves_per_simd
 
     # every step solves its OWN instances: timed step i of this rank = seed block rank*steps + i, warm-up steps = other blocks
-    def load_blocks(blocks, x0_draw=0):
-        seeds = np.concatenate([b * B + np.arange(B) for b in blocks])
-        h = workload.make_srbd13_batch(N, seeds, x0_draw=x0_draw)
-        d = {k: torch.from_numpy(h[k]).to(dev).reshape((len(blocks), B) + h[k].shape[1:]) for k in ("x0", "xs", "us", "params")}
-        lab, ncls = workload.srbd13_schedule_classes(h["params"], signed=bool(args.class_signs))   # what kind of problem each instance is (queue order 3)
-        d["classes"], d["n_classes"] = torch.from_numpy(lab).to(dev).reshape(len(blocks), B), ncls
-        return d
+    def load(blocks, x0_draw=0):
+        return load_blocks(N, B, blocks, dev, x0_draw=x0_draw, signed=bool(args.class_signs))   # classes: what kind of problem each instance is (queue order 3)
 
-    run_blocks = [[seed_block(rank, world, steps, warmup, "timed", i, run=r) for i in range(steps)] for r in range(RUNS)]
+    n_runs = RUNS if args.full else 1
+    run_blocks = [[seed_block(rank, world, steps, warmup, "timed", i, run=r) for i in range(steps)] for r in range(n_runs)]
     timed_blocks = run_blocks[0]
     warm_blocks = [seed_block(rank, world, steps, warmup, "warmup", i) for i in range(warmup)]
-    d_runs = [load_blocks(bl) for bl in run_blocks]
+    d_runs = [load(bl) for bl in run_blocks]
     d_t = d_runs[0]
-    d_w = load_blocks(warm_blocks) if warmup else None
+    d_w = load(warm_blocks) if warmup else None
 
     def make_queue(order, depth=None, **over):
         e = DdpEngine("srbd13", N, (depth or Q) * B, opts=dict(opts, waves_per_simd=wps, queue_order=order, **over))
@@ -344,11 +414,12 @@ def main():
     acc += fleet.si[:1, _lib.STATS_I32_ITERS].sum()                              # (first use of these device ops is never inside the timed region)
     acc.zero_()
     barrier()
-    # RUNS timed regions, each EXACTLY `steps` steps over seed blocks of its own, each bracketed by barrier + synchronize and
-    # reduced with MAX over the ranks; `value` is the median region (a launch ends with its slowest instance: one region is one
-    # draw of the stragglers), all of them are reported
+    # timed regions (one; RUNS with --full), each EXACTLY `steps` steps over seed blocks of its own, each bracketed by barrier +
+    # synchronize and reduced with MAX over the ranks; `value` is the first region.  A launch ends with its slowest instance: one
+    # region is one draw of the stragglers, and --full reports all of them
+    n_last = (steps - Q * ((steps - 1) // Q)) * B              # instances of the last launch: what the handle still holds
     regions = []
-    for r in range(RUNS):
+    for r in range(n_runs):
         acc.zero_()
         eng.synchronize()
         eng.kernel_time_stats(reset=True)
@@ -363,18 +434,16 @@ def main():
         ks, kc = eng.kernel_time_stats(reset=True)
         it_r, ro_r = (int(v) for v in acc.tolist())
         x, u, st_r = eng.fetch()
+        if r == 0 and rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, x[n_last - B:n_last], u[n_last - B:n_last], st_r[n_last - B:n_last])   # the last timed step's batch
         regions.append(dict(elapsed=el, ksum=ks, kcnt=kc, launches=fleet.launches - l0, gbytes=fleet.gather_bytes - g0, iters=it_r,
                             rollouts=ro_r, stats=st_r, drain=drain_profile(eng.slot_times()), blocks=[run_blocks[r][0], run_blocks[r][-1]]))
-    order_el = sorted(range(RUNS), key=lambda r: regions[r]["elapsed"])
-    med = regions[order_el[RUNS // 2]]
-    elapsed, ksum, kcnt, launches = med["elapsed"], med["ksum"], med["kcnt"], med["launches"]
-    tot_iters, tot_roll = med["iters"], med["rollouts"]
-    timed_blocks = run_blocks[order_el[RUNS // 2]]
-    d_t = d_runs[order_el[RUNS // 2]]
+    head = regions[0]
+    elapsed, ksum, kcnt, launches = head["elapsed"], head["ksum"], head["kcnt"], head["launches"]
+    tot_iters, tot_roll = head["iters"], head["rollouts"]
     slots, last_grid, last_queued = eng.queue_info()
 
-    n_last = (steps - Q * ((steps - 1) // Q)) * B              # instances of the last launch: what the handle still holds
-    st = med["stats"][:n_last]
+    st = head["stats"][:n_last]
     iters = st["iters"].astype(np.int64)
     kms = ksum / max(kcnt, 1)
     n_solves = steps * B
@@ -385,12 +454,10 @@ def main():
     out = {
         "metric": "SRBD-DDP solves/sec (N=30, nx=13, nu=6)", "value": world * n_solves / elapsed, "unit": "solves/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-        "value_runs": [world * n_solves / r["elapsed"] for r in regions],
-        "value_note": f"median of {RUNS} timed regions of exactly {steps} steps each, every region on seed blocks of its own "
-                      "(value_runs: all of them, in execution order; ms_per_step, mean_iters, roofline and last_launch are the median region's)",
-        "drain": med["drain"], "drain_runs": [r["drain"] for r in regions],
-        "mean_iters_runs": [r["iters"] / n_solves for r in regions],
-        "kernel_ms_runs": [r["ksum"] / max(r["kcnt"], 1) for r in regions],
+        "value_note": f"one timed region of exactly {steps} steps on seed blocks no earlier step has solved (--full: {RUNS} such "
+                      "regions, each on blocks of its own, in value_runs etc.; value, ms_per_step, mean_iters, roofline and "
+                      "last_launch are the first region's)",
+        "drain": head["drain"],
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": f"SRBD N={N} nx=13 nu=6, batch={B} independent MPC instances per GPU and step "
                                "(BASELINE configs[2]; x8 GPUs = configs[3]), cold start, whole line-search ladder "
@@ -405,8 +472,7 @@ def main():
                    "collective": (f"asynchronous double-buffered all_gather of the '{args.gather}' record per launch (packed by one HIP kernel behind "
                                   "the solve); the gather of launch k is on the wire while launch k + 1 solves; all waited for inside the timed region")
                                  if collective else "none",
-                   "gather_bytes_per_launch_per_rank": (med["gbytes"] // max(launches, 1)) if collective else 0,
-                   "seed_blocks_of_the_runs": [r["blocks"] for r in regions]},
+                   "gather_bytes_per_launch_per_rank": (head["gbytes"] // max(launches, 1)) if collective else 0},
         "mean_iters": tot_iters / n_solves, "mean_rollouts": tot_roll / n_solves,
         "last_launch": {"instances": int(n_last), "mean_iters": float(np.mean(iters)), "max_iters": int(np.max(iters)),
                         "max_iters_hit_frac": float(np.mean(st["status"] == 1)), "converged_frac": float(np.mean(st["converged"] == 1)),
@@ -427,7 +493,13 @@ def main():
                              "one launch at a time on one stream; traffic is not measured in this run: it is read from the committed "
                              "rocprofv3 PMC passes named in traffic_source"},
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full:
+        value_runs = [world * n_solves / r["elapsed"] for r in regions]
+        out.update({"value_runs": value_runs, "value_median_of_runs": float(np.median(value_runs)),
+                    "drain_runs": [r["drain"] for r in regions], "mean_iters_runs": [r["iters"] / n_solves for r in regions],
+                    "kernel_ms_runs": [r["ksum"] / max(r["kcnt"], 1) for r in regions]})
+        out["config"]["seed_blocks_of_the_runs"] = [r["blocks"] for r in regions]
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         n_x = min(steps, Q)
         # the same instances in plain index order and (as a REPLAY: the handle has solved these very instances once before, so
         # the history is exact foreknowledge -- what a fleet of recurring robots approaches, not a cold-start figure) longest
@@ -435,7 +507,7 @@ def main():
         # history order as a recurring fleet would see it: the handle has solved the same ROBOTS before (same schedule, command and
         # footsteps) from another draw of the initial-state perturbation -- a similar problem, not the same one
         e_o, f_o = make_queue(1)
-        d_sim = load_blocks(timed_blocks[:n_x], x0_draw=1)
+        d_sim = load(timed_blocks[:n_x], x0_draw=1)
         run_steps(f_o, d_sim, n_x)
         out["history_order_similar_problems_solves_per_s"] = B * n_x / timed(f_o, d_t, n_x)
         del f_o, e_o, d_sim
@@ -479,7 +551,7 @@ def main():
             run_steps(f_o, d_w if warmup else d_t, min(max(warmup, 1), -(-steps // 2)))
             out["two_launches_per_region_solves_per_s"] = B * steps / timed(f_o, d_t, steps)
             del f_o, e_o
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # The tick loops below report a p99 / max per tick.  CPython's generation-2 garbage collection walks every tracked object
         # of the process (31 ms with torch imported) once per ~70 k container allocations: the "one-time 20-45 ms stall" of rounds
         # 2-3 (profiles/r04/experiments/host_stall_hiptrace.txt: no HIP call is in flight during it).  A real-time loop freezes

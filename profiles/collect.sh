@@ -25,7 +25,7 @@ passes "" python3 bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --no-extr
 passes mw_srbd37_n20_ python3 profiles/run_mw_batch.py srbd37 20 2048 2
 passes mw_srbd37_n60_ python3 profiles/run_mw_batch.py srbd37 60 1024 2
 passes mw_srbd61_n20_ python3 profiles/run_mw_batch.py srbd61 20 1024 1
-python3 bench.py --steps $STEPS --warmup 5 > $O/bench.log 2> $O/bench.err
+python3 bench.py --full --steps $STEPS --warmup 5 > $O/bench.log 2> $O/bench.err
 echo "bench done"
 python3 profiles/make_summary.py $R $O $STEPS | tee $O/summary.txt
 mkdir -p gpurun_out/profiles_$R && find profiles/$R -maxdepth 1 -type f -exec cp {} gpurun_out/profiles_$R/ \;

@@ -110,3 +110,43 @@ def test_class_labels_use_nothing_but_the_schedule():
     lu, nu = workload.srbd13_schedule_classes(a["params"], signed=False)
     assert n == 4 * 32 * 9 and nu == 4 * 32 * 4 and len(np.unique(la)) > len(np.unique(lu))
     assert all(len(np.unique(lu[la == c])) == 1 for c in np.unique(la))
+
+
+def test_parallel_block_loading_equals_one_generator_call(monkeypatch):
+    """bench.load_blocks generates the seed blocks in chunks, in worker processes: the same tensors as one make_srbd13_batch call
+    over all the seeds (and the labels of srbd13_schedule_classes over them)."""
+    import sys
+    import torch
+    from srbd_horizon_amd import workload
+    monkeypatch.setitem(sys.modules, "bench", bench)              # the workers find gen_blocks by its module name
+    monkeypatch.setattr(bench, "GEN_CHUNK", 2)
+    N, B, blocks = 12, 16, [7, 3, 11, 0, 5]
+    d = bench.load_blocks(N, B, blocks, "cpu")
+    h = workload.make_srbd13_batch(N, np.concatenate([b * B + np.arange(B) for b in blocks]))
+    lab, ncls = workload.srbd13_schedule_classes(h["params"])
+    for k in ("x0", "xs", "us", "params"):
+        assert torch.equal(d[k], torch.from_numpy(h[k]).reshape((len(blocks), B) + h[k].shape[1:])), k
+    assert torch.equal(d["classes"], torch.from_numpy(lab).reshape(len(blocks), B)) and d["n_classes"] == ncls
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_cap(tmp_path, monkeypatch):
+    from srbd_horizon_amd import _lib
+    B, N = 40, 5
+    x, u = np.random.default_rng(1).random((B, N + 1, 13)), np.random.default_rng(2).random((B, N, 6))
+    st = np.zeros(B, dtype=_lib.STATS_DTYPE)
+    st["cost"], st["iters"], st["status"] = np.arange(B) * 0.5, np.arange(B), 1
+    bench.dump_outputs(str(tmp_path / "all"), x, u, st)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("x", "u", "cost", "iters", "status")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["x"], x)
+    np.testing.assert_array_equal(got["u"], u)
+    np.testing.assert_array_equal(got["iters"], np.arange(B))
+    per_instance = 8 * ((N + 1) * 13 + N * 6 + 3)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * per_instance)                  # a fixed sample of 10 instances, the same every time
+    bench.dump_outputs(str(tmp_path / "a"), x, u, st)
+    bench.dump_outputs(str(tmp_path / "b"), x, u, st)
+    rows = (np.load(tmp_path / "a" / "cost.npy") * 2).astype(int)
+    assert len(rows) == 10 and len(set(rows)) == 10
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x.npy"), x[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "x.npy"), x[rows])
+    assert sum((tmp_path / "a" / (n + ".npy")).stat().st_size - 128 for n in got) <= 10 * per_instance
