@@ -6,6 +6,7 @@ upstream, python/prb.py:184-204; the reference's stage costs sum whatever the co
 
 The analytic HIP models take up to 8 user-declared LINEAR residual rows `sqrt(gain) * (A z - ref)` (problem.LinearTerm;
 include/sddp.h `extra_*`): here the left-upper contact point is asked to follow a reference in x / y while its foot swings.
+A non-linear residual: examples/nonlinear_residual.py.
 Needs a GPU: the engine has no CPU fallback.
 """
 import os

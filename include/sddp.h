@@ -269,6 +269,15 @@ int  sddp_solve_resident_first(sddp_handle* h, double* u0_out /*[B][nu]*/, doubl
 int  sddp_model_step(sddp_handle* h, const double* x /*[B][nx]*/, const double* u /*[B][nu]*/, const double* p /*[B][np]*/, int k,
                      double* x_next /*[B][nx]*/);
 
+/* ---- user builds (srbd_horizon_amd/userterms.py) ------------------------------------------------------------
+ * A user build is a shared object holding one more build of srbd13 or srbd37 whose user rows are compiled from the user's own
+ * (non-linear) expressions.  sddp_register_user_build loads it (dlopen), checks that it was compiled against the same headers as
+ * this library, and returns its model id (>= 16; the same id again for a path already registered).  The id is accepted wherever a
+ * model id is: sddp_create, sddp_model_dims, sddp_default_consts_for (the base model's constants) and sddp_eval_knots.  Its
+ * handles need consts->n_extra = the build's row count (extra_weight / extra_kind / extra_const: the rows' weights, kinds and
+ * constant parts of their references; extra_a is unused) and have the plain build only (no barrier, no second_order = 2). */
+int  sddp_register_user_build(const char* path, int* model_id);
+
 /* ---- building blocks exposed for parity tests (host pointers) ------------------------------------------------
  * The same device code the fused solve kernel uses, one phase at a time.
  * sddp_eval_knots: per-knot model evaluation (reference: CasADi evaluation of f_k / L_k and their derivatives

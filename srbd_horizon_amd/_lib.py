@@ -105,6 +105,7 @@ SYMBOLS = {
     "sddp_enable_timing": (C.c_int, [_vp, C.c_int]),
     "sddp_kernel_time_stats": (C.c_int, [_vp, _P(C.c_double), _P(C.c_longlong), C.c_int]),
     "sddp_eval_knots": (C.c_int, [C.c_int, _P(SddpModelConsts), C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sddp_register_user_build": (C.c_int, [C.c_char_p, _P(C.c_int)]),
     "sddp_backward": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp]),
     "sddp_forward": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp, _vp]),
 }
@@ -126,6 +127,16 @@ INSTANCES = [
 # but slower), srbd37 +2.3 % in the two-per-SIMD build and -3 % in the other, which share a translation unit.
 INSTANCE_FLAGS = {k: ["-mllvm", "-sink-insts-to-avoid-spills"] for k in ("srbd61", "srbd61_x", "srbd61_b")}
 HEADERS = ["sddp_kernels.hpp", "sddp_kernels_mw.hpp", "sddp_models.hpp", "sddp_sort.hpp", "sddp_handle.hpp", "sddp_launch.hpp", "sddp_kernels_host.hpp"]
+
+
+def header_stamp(root: str = ROOT) -> str:
+    """Stamp of the headers a model build is compiled against (csrc/*.hpp of HEADERS, include/sddp.h): the core library and every
+    user build carry it (-DSDDP_HEADER_STAMP), and sddp_register_user_build refuses a build whose stamp differs."""
+    import hashlib
+    h = hashlib.sha1()
+    for p in [os.path.join(root, "srbd_horizon_amd", "csrc", n) for n in HEADERS] + [os.path.join(root, "include", "sddp.h")]:
+        h.update(open(p, "rb").read())
+    return "0x" + h.hexdigest()[:15]
 
 
 def _newer(target: str, deps) -> bool:
@@ -169,7 +180,8 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
     for name in ("sddp_api", "sddp_sort"):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(objdir, name + ".o")
-        jobs.append((obj, src, base + [src, "-o", obj]))
+        stamp = [f"-DSDDP_HEADER_STAMP={header_stamp()}ULL"] if name == "sddp_api" else []   # (user builds: userterms.py)
+        jobs.append((obj, src, base + stamp + [src, "-o", obj]))
     inst = os.path.join(CSRC, "sddp_inst.hip")
     for fn, model, mname in INSTANCES:
         obj = os.path.join(objdir, "inst_" + fn + ".o")

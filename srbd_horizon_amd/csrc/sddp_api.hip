@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <dlfcn.h>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -15,6 +17,10 @@
 #include "sddp_handle.hpp"
 #include "sddp_kernels_host.hpp"
 #include "sddp_sort.hpp"
+
+#ifndef SDDP_HEADER_STAMP
+#define SDDP_HEADER_STAMP 0ULL      // (srbd_horizon_amd/_lib.py passes the stamp of the headers; 0: no user build is accepted)
+#endif
 
 using namespace sddp;
 
@@ -84,8 +90,33 @@ int alloc_cold_queue(sddp_handle* h) {
 
 namespace {
 
+// user builds (sddp_register_user_build): model ids kUserId0, kUserId0 + 1, ... in registration order.  Never unloaded: a handle or a
+// kernel of the build may outlive any caller's interest in it.
+constexpr int kUserId0 = 16;
+struct UserBuild {
+    std::string path;
+    const ModelOps* ops;
+    int base, rows;
+};
+std::mutex& user_mutex() { static std::mutex m; return m; }
+std::vector<UserBuild>& user_builds() { static std::vector<UserBuild> v; return v; }
+const UserBuild* user_build(int id) {
+    std::lock_guard<std::mutex> g(user_mutex());
+    const auto& v = user_builds();
+    return (id >= kUserId0 && id - kUserId0 < (int)v.size()) ? &v[id - kUserId0] : nullptr;
+}
+// the built-in model a model id stands for (a user build: the model it was generated for)
+int base_model(int id) {
+    const UserBuild* u = user_build(id);
+    return u ? u->base : id;
+}
+
 // bar: the barrier build of the SRBD models (friction cone and / or variable bounds), so2: the full second-order build
 const ModelOps* model_ops(int id, bool bar = false, bool so2 = false, bool xr = false) {
+    if (id >= kUserId0) {   // a user build: its plain build only, with its user rows
+        const UserBuild* u = user_build(id);
+        return (u && !bar && !so2) ? u->ops : nullptr;
+    }
     if (xr) {     // user rows: plain builds only
         if (bar || so2) return nullptr;
         switch (id) {
@@ -106,6 +137,14 @@ const ModelOps* model_ops(int id, bool bar = false, bool so2 = false, bool xr = 
 }
 // models whose only build is the default one: linear-quadratic (lip30), or no barrier / second_order = 2 build instantiated (srbd61)
 bool single_build(int id) { return id == SDDP_MODEL_LIP30; }
+
+// a user build's handles carry exactly its rows (weights / kinds / constant parts in the extra_* table)
+const char* check_user_rows(int id, const sddp_model_consts* c) {
+    const UserBuild* u = user_build(id);
+    if (!u) return nullptr;
+    if (!c || c->n_extra != u->rows) return "a user build needs consts->n_extra = its row count (the rows' weights and kinds)";
+    return nullptr;
+}
 
 // user rows of a constants struct: validation, and the device table of DevConsts::xr
 const char* check_extra(const sddp_model_consts& c, int nx, int nu) {
@@ -192,6 +231,40 @@ extern "C" {
 
 int sddp_abi_version(void) { return SDDP_ABI_VERSION; }
 
+int sddp_register_user_build(const char* path, int* model_id) {
+    if (!path || !model_id) return fail(nullptr, SDDP_ERR_ARG, "path and model_id must not be NULL");
+    std::lock_guard<std::mutex> g(user_mutex());
+    auto& v = user_builds();
+    for (size_t i = 0; i < v.size(); ++i)
+        if (v[i].path == path) { *model_id = kUserId0 + int(i); return SDDP_OK; }
+    void* dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!dl) { const char* e = dlerror(); return fail(nullptr, SDDP_ERR_ARG, std::string("user build: dlopen failed: ") + (e ? e : "?")); }
+    using OpsFn = const ModelOps* (*)();
+    using IntFn = int (*)();
+    using StampFn = unsigned long long (*)();
+    auto ops_fn = reinterpret_cast<OpsFn>(dlsym(dl, "sddp_user_ops"));
+    auto base_fn = reinterpret_cast<IntFn>(dlsym(dl, "sddp_user_base_model"));
+    auto rows_fn = reinterpret_cast<IntFn>(dlsym(dl, "sddp_user_rows"));
+    auto stamp_fn = reinterpret_cast<StampFn>(dlsym(dl, "sddp_user_header_stamp"));
+    auto bind_fn = reinterpret_cast<void (*)(const CoreHooks*)>(dlsym(dl, "sddp_user_bind"));
+    const char* err = nullptr;
+    if (!ops_fn || !base_fn || !rows_fn || !stamp_fn || !bind_fn) err = "user build: an accessor is missing (not a user build?)";
+    else if (SDDP_HEADER_STAMP == 0ULL || stamp_fn() != SDDP_HEADER_STAMP)
+        err = "user build: compiled against other headers than this library (rebuild it)";
+    else if (base_fn() != SDDP_MODEL_SRBD13 && base_fn() != SDDP_MODEL_SRBD37) err = "user build: base model must be srbd13 or srbd37";
+    else if (rows_fn() < 1 || rows_fn() > SDDP_MAX_EXTRA) err = "user build: 1..8 user rows";
+    if (err) { dlclose(dl); return fail(nullptr, SDDP_ERR_ARG, err); }
+    static const CoreHooks hooks{&create_error, &alloc_cold_queue, &launch_queue_order, &launch_class_keys, &launch_class_update};
+    bind_fn(&hooks);
+    try {
+        v.push_back(UserBuild{std::string(path), ops_fn(), base_fn(), rows_fn()});
+    } catch (...) {
+        return fail(nullptr, SDDP_ERR_NOMEM, "out of host memory");
+    }
+    *model_id = kUserId0 + int(v.size()) - 1;
+    return SDDP_OK;
+}
+
 int sddp_model_dims(int model_id, int* nx, int* nu, int* np) {
     const ModelOps* ops = model_ops(model_id);
     if (!ops) return SDDP_ERR_MODEL;
@@ -243,7 +316,7 @@ int sddp_default_consts_for(int model_id, sddp_model_consts* c) {
     // the points d_initial_1/2 of prb.py:153-154 name whatever nc is
     const double feet[12] = {0.08, 0.1, 0.0, -0.08, 0.1, 0.0, 0.08, -0.1, 0.0, -0.08, -0.1, 0.0};
     const double feet8[12] = {0.08, 0.13, 0.0, -0.08, 0.13, 0.0, 0.08, 0.07, 0.0, -0.08, 0.07, 0.0};
-    std::memcpy(c->feet, model_id == SDDP_MODEL_SRBD61 ? feet8 : feet, sizeof(feet));
+    std::memcpy(c->feet, base_model(model_id) == SDDP_MODEL_SRBD61 ? feet8 : feet, sizeof(feet));
     c->dt = 0.05;
     c->force_scaling = 1000.0;
     c->r_tracking_gain = 1e3; c->rdot_tracking_gain = 1e4; c->w_tracking_gain = 1e4; c->rel_pos_gain = 1e4;
@@ -279,6 +352,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
                                                     : "this model has no such build (srbd61: no second_order = 2 build)");
     const Dims d = ops->dims;
     if (N < 1 || batch < 1) return fail(nullptr, SDDP_ERR_ARG, "N and batch must be >= 1");
+    if (const char* msg = check_user_rows(model_id, consts)) return fail(nullptr, SDDP_ERR_ARG, msg);
     if (xr) { const char* msg = check_extra(*consts, d.nx, d.nu); if (msg) return fail(nullptr, SDDP_ERR_ARG, msg); }
     if (consts && (consts->friction_barrier_weight < 0.0 || (consts->friction_barrier_weight > 0.0 && !(consts->friction_cone_coefficient > 0.0))))
         return fail(nullptr, SDDP_ERR_ARG, "friction_barrier_weight must be >= 0 and friction_cone_coefficient > 0");
@@ -872,6 +946,7 @@ int sddp_eval_knots(int model_id, const sddp_model_consts* consts, int N, int nk
     const ModelOps* ops = model_ops(model_id, bar, false, xr);
     if (!ops) return fail(nullptr, SDDP_ERR_ARG, "this model has no such build (barrier / user rows)");
     const Dims d = ops->dims;
+    if (const char* msg = check_user_rows(model_id, &cc)) return fail(nullptr, SDDP_ERR_ARG, msg);
     if (nk < 1 || !k || !x || !u || !p) return fail(nullptr, SDDP_ERR_ARG, "bad argument");
     if (xr) { const char* msg = check_extra(cc, d.nx, d.nu); if (msg) return fail(nullptr, SDDP_ERR_ARG, msg); }
     DevConsts dc = make_dev_consts(cc);

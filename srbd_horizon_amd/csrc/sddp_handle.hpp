@@ -131,4 +131,14 @@ int launch_queue_order(sddp_handle* h, int first, int count);
 int launch_class_keys(sddp_handle* h, int count);
 int launch_class_update(sddp_handle* h, int first, int count);
 
+// the services above as a user build reaches them (srbd_horizon_amd/userterms.py): it is loaded RTLD_LOCAL and cannot resolve this
+// library's symbols, so sddp_register_user_build hands it this table and the build's own definitions of them call through it
+struct CoreHooks {
+    std::string& (*create_error)();
+    int (*alloc_cold_queue)(sddp_handle*);
+    int (*launch_queue_order)(sddp_handle*, int, int);
+    int (*launch_class_keys)(sddp_handle*, int);
+    int (*launch_class_update)(sddp_handle*, int, int);
+};
+
 }  // namespace sddp

@@ -346,6 +346,7 @@ __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restri
         const double* rN = rec + size_t(N) * NREC;
         if (lane < NXP) s[L::VX + lane] = lane < NX ? rN[M::REC_G + lane] : 0.0;
         if (lane < NP) s[L::PK + lane] = P[N * NP + lane];
+        if constexpr (M::HAS_UR) M::expand_term(rN, s + L::FT, NIP, lane, kWave);   // user build: the user rows' Jacobian at node N
         wave_sync();
         for (int e = lane; e < NXP * NXP; e += kWave) {
             const int a = e / NXP, b = e % NXP;

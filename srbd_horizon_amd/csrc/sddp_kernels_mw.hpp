@@ -312,6 +312,7 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
     // ---- terminal node: Vx = lx_N, Vxx = lxx_N = diag(D_state) + Je^T Lambda_state Je  (ddp.py:216-226)
     if (tid < SV) s[L::VX + tid] = tid < NX ? rec[size_t(N) * NREC + M::REC_G + tid] : 0.0;
     if (tid < NP) s[L::PK + tid] = P[N * NP + tid];
+    if constexpr (M::HAS_UR) M::template expand_term<true>(rec + size_t(N) * NREC, s + L::FC, SC, tid, kThreadsMW);   // user build
     __syncthreads();
     for (int e = tid; e < NX * NX; e += kThreadsMW) {
         const int a = e / NX, b = e % NX;

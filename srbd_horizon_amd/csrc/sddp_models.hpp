@@ -73,6 +73,23 @@ __device__ __forceinline__ double xr_eval(const DevConsts& c, XV x, UV u, bool h
     return L;
 }
 
+// User rows compiled from the user's own expressions (srbd_horizon_amd/userterms.py writes the struct UR): NR rows, their values
+// e_j(x, u, p) and the NNZ structural non-zeros of de/dz (row(n), col(n)), evaluated by UR::eval.  UR = void: no such rows.
+template <class UR>
+struct UrInfo {
+    static constexpr bool ON = true;
+    static constexpr int NR = UR::NR, NNZ = UR::NNZ;
+    __host__ __device__ static constexpr int row(int n) { return UR::row(n); }
+    __host__ __device__ static constexpr int col(int n) { return UR::col(n); }
+};
+template <>
+struct UrInfo<void> {
+    static constexpr bool ON = false;
+    static constexpr int NR = 0, NNZ = 0;
+    __host__ __device__ static constexpr int row(int) { return 0; }
+    __host__ __device__ static constexpr int col(int) { return 0; }
+};
+
 inline DevConsts make_dev_consts(const sddp_model_consts& c) {
     DevConsts d;
     d.dt = c.dt;
@@ -300,12 +317,20 @@ struct QSplit {
 // (reference problem, prb.py:32-68) -- NC=4: srbd37 (contact_model = 2, the launch file's), NC=8: srbd61 (contact_model = 4,
 // the default in the code, prb.py:39-41).  Two legs (number_of_legs = 2), CM = NC / 2 contact points per foot.
 // ---------------------------------------------------------------------------------------------------------
-template <int NC_, bool CS_, bool BAR_ = false, bool SO2_ = false, int XR_ = 0>
+template <int NC_, bool CS_, bool BAR_ = false, bool SO2_ = false, int XR_ = 0, class UR_ = void>
 struct SrbdModel {
     static constexpr int NC = NC_;
     static constexpr int NXR = XR_;        // user-declared linear residual rows ("_x" builds, sddp.h extra_*): 0 or kXrRows; their per-knot
                                            // references are NXR further parameter columns behind the model's own
     static_assert(XR_ == 0 || (XR_ == kXrRows && !BAR_ && !SO2_), "the _x builds are plain builds with kXrRows user rows");
+    // user builds (UR_ != void): the user rows are per-knot VARIABLE extra rows like wdot -- values and Jacobian from UR::eval, the
+    // Jacobian's NUJ structural non-zeros stored in the record (REC_UJ) and expanded into F~ by expand_var; weights and constant parts
+    // of the references stay in the device table of the _x builds (DevConsts::xr)
+    using UR = UR_;
+    static constexpr bool HAS_UR = UrInfo<UR_>::ON;
+    static constexpr int NUJ = UrInfo<UR_>::NNZ;
+    static_assert(!HAS_UR || (XR_ == kXrRows && UrInfo<UR_>::NR >= 1 && UrInfo<UR_>::NR <= kXrRows),
+                  "a user build is a plain build (no BAR, no SO2) with 1..kXrRows user rows");
     static constexpr bool CS = CS_;
     static constexpr bool BAR = BAR_;      // friction-cone exponential barrier on the contact forces (sddp.h), separate builds
     static constexpr bool SO2 = SO2_;      // full second-order builds (sddp_options.second_order = 2): the record also carries the
@@ -341,7 +366,8 @@ struct SrbdModel {
                          REC_COO = REC_DM + 36,                    //   w x (d2I_w/do_a do_b w) + d2I_w/do_a do_b wdot for the 10
                          REC_W = REC_COO + 30,                     //   pairs a >= b (10 x 3) | w (3)
                          NTRI = NA * (NA + 1) / 2,
-                         NREC = SO2 ? REC_W + 3 : REC_WD,
+                         REC_UJ = REC_WD,                          // user builds: the NUJ non-zeros of the user rows' Jacobian
+                         NREC = SO2 ? REC_W + 3 : REC_WD + NUJ,
                          // SO2: per-knot factors of the contraction, computed once per knot in LDS (so2_prepare): y (3) | dI_a y
                          // (4 x 3) | h_b = (dI_b w) x y + dI_b (y x w) (4 x 3) | P[a][b] = (I_w e_b x y)_a (9) | y . c_ab (10)
                          //   then two zero words (the slot of "no term")
@@ -521,6 +547,33 @@ struct SrbdModel {
         return L;
     }
 
+    // user builds: cost sum_j w_j e_j^2 of the user rows, e_j = UR's value - the constant part of its reference (c.xr, kXrC), w_j the
+    // row's weight where its kind is active; g != nullptr: also the gradient 2 w_j e_j J_j into g and the Jacobian's non-zeros into rj.
+    // !has_u (terminal node): UR::eval gives the stage rows 0 and reads no input.  Every index below is compile-time after unrolling.
+    template <class XV, class UV>
+    __device__ __forceinline__ static double ur_eval(const DevConsts& c, XV x, UV u, bool has_u, const double* p, bool state_on,
+                                                     bool stage_on, double* g = nullptr, double* rj = nullptr) {
+        constexpr int NR = UrInfo<UR>::NR;
+        double e[NR], jv[NUJ > 0 ? NUJ : 1], t[NR];
+        if (g) UR::eval(x, u, has_u, p, e, jv); else UR::eval(x, u, has_u, p, e, static_cast<double*>(nullptr));
+        double L = 0.0;
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            const double w = (state_on ? c.xr[kXrWS + j] : 0.0) + (stage_on ? c.xr[kXrWG + j] : 0.0);
+            const double ej = e[j] - c.xr[kXrC + j];
+            L = fma(w * ej, ej, L);
+            t[j] = 2.0 * w * ej;
+        }
+        if (g) {
+#pragma unroll
+            for (int n = 0; n < NUJ; ++n) {
+                g[UR::col(n)] = fma(t[UR::row(n)], jv[n], g[UR::col(n)]);
+                rj[n] = jv[n];
+            }
+        }
+        return L;
+    }
+
     // x+ = x + dt*xdot (explicit Euler, ddp.py:228-230) and L_k(x,u,p) (ddp.py:179-214) in one pass
     template <class XV, class UV, class XN>
     __device__ __forceinline__ static double step(const DevConsts& c, XV x, UV u, const double* p, int k, XN xn) {
@@ -533,7 +586,8 @@ struct SrbdModel {
         double L = input_cost(c, x, u, p, f, q);
         if (BAR) L += bound_cost(c, x, u);
         if (k >= 1) L += state_cost(c, x, p);
-        if (NXR) L += xr_eval<NX, NU>(c, x, u, true, p + NPB, k >= 1, true);
+        if constexpr (HAS_UR) L += ur_eval(c, x, u, true, p, k >= 1, true);
+        else if (NXR) L += xr_eval<NX, NU>(c, x, u, true, p + NPB, k >= 1, true);
         // every component of x+ is formed from values read BEFORE the first store: x and xn may be the same array (in-place
         // rollout) or LDS columns the compiler cannot tell apart (then interleaved loads and stores would serialise)
         const double dt = c.dt;
@@ -565,7 +619,8 @@ struct SrbdModel {
     template <class XV>
     __device__ __forceinline__ static double term_cost(const DevConsts& c, XV x, const double* p) {
         double L = state_cost(c, x, p);  // ddp.py:216-226: residuals only, no constraints
-        if (NXR) L += xr_eval<NX, NU>(c, x, x, false, p + NPB, true, false);
+        if constexpr (HAS_UR) L += ur_eval(c, x, x, false, p, true, false);
+        else if (NXR) L += xr_eval<NX, NU>(c, x, x, false, p + NPB, true, false);
         return L;
     }
 
@@ -736,12 +791,14 @@ struct SrbdModel {
                 }
             }
             if (BAR) (void)bound_cost(c, x, u, g, rec + REC_BB);   // bound barrier (off: zeros): gradient into g, GN Hessian diagonal into the record
-            if (NXR) (void)xr_eval<NX, NU>(c, x, u, true, p + NPB, k >= 1, true, g);   // user rows: their gradient
+            if constexpr (HAS_UR) (void)ur_eval(c, x, u, true, p, k >= 1, true, g, rec + REC_UJ);   // user rows: gradient, Jacobian
+            else if (NXR) (void)xr_eval<NX, NU>(c, x, u, true, p + NPB, k >= 1, true, g);   // user rows: their gradient
 #pragma unroll
             for (int i = 0; i < NZ; ++i) rec[REC_G + i] = g[i];
             return;                                     // (SO2 builds: the second-order factors are a pass of their own, so2_knot)
         }
-        if (NXR) (void)xr_eval<NX, NU>(c, x, x, false, p + NPB, true, false, g);       // terminal node: the state rows
+        if constexpr (HAS_UR) (void)ur_eval(c, x, x, false, p, true, false, g, rec + REC_UJ);   // terminal node: the state rows
+        else if (NXR) (void)xr_eval<NX, NU>(c, x, x, false, p + NPB, true, false, g);       // terminal node: the state rows
 #pragma unroll
         for (int i = 0; i < NZ; ++i) rec[REC_G + i] = g[i];
     }
@@ -949,7 +1006,17 @@ struct SrbdModel {
                 v += 2 * c.gq * (rec[REC_A + a] * rec[REC_A + b] + rec[REC_A + NA + a] * rec[REC_A + NA + b] +
                                  rec[REC_A + 2 * NA + a] * rec[REC_A + 2 * NA + b]);
         }
-        if (NXR) {   // user rows: 2 w_j a_j a_j^T with the weight of the node
+        if constexpr (HAS_UR) {   // user build: 2 w_r J_r^T J_r with the Jacobian of the record
+            for (int a = 0; a < NUJ; ++a) {
+                if (UR::col(a) != i) continue;
+                for (int b = 0; b < NUJ; ++b) {
+                    if (UR::row(b) != UR::row(a) || UR::col(b) != j) continue;
+                    const int r = UR::row(a);
+                    const double w = (state ? c.xr[kXrWS + r] : 0.0) + (stage ? c.xr[kXrWG + r] : 0.0);
+                    v += 2 * w * rec[REC_UJ + a] * rec[REC_UJ + b];
+                }
+            }
+        } else if (NXR) {   // user rows: 2 w_j a_j a_j^T with the weight of the node
             for (int r = 0; r < c.xr_n; ++r) {
                 const double w = (state ? c.xr[kXrWS + r] : 0.0) + (stage ? c.xr[kXrWG + r] : 0.0);
                 v += 2 * w * c.xr[r * kXrStride + i] * c.xr[r * kXrStride + j];
@@ -987,13 +1054,13 @@ struct SrbdModel {
         if (m < 10) return m - 4;                // rddot     (definition rows 3..5)
         return m;                                // rel_vel   (definition rows 10..13)
     }
-    static constexpr int NVAR = 28 + 3 * NA;           // per-knot variable entries: quaternion blocks + A
+    static constexpr int NVAR = 28 + 3 * NA + NUJ;     // per-knot variable entries: quaternion blocks + A [+ user-row Jacobian]
 
     // constant entry of extra row m w.r.t. z_j (one-time table fill; variable wdot rows are 0 here)
     __device__ static double E_const(const DevConsts& c, int mrow, int j) {
         const int m = erow(mrow);
-        if (NXR && m >= NEB) return (c.xr && m - NEB < c.xr_n) ? c.xr[(m - NEB) * kXrStride + j] : 0.0;   // user rows
-        int cls, ci, ax;
+        if (NXR && m >= NEB) return (!HAS_UR && c.xr && m - NEB < c.xr_n) ? c.xr[(m - NEB) * kXrStride + j] : 0.0;   // user rows
+        int cls, ci, ax;                                                                    // (user builds: per knot, expand_var)
         decode(j, cls, ci, ax);
         if (m < 3) return 0.0;
         if (m < 6) return (cls == V_F && ax == m - 3) ? c.inv_ms : 0.0;                    // rddot rows   prb.py:200
@@ -1084,12 +1151,18 @@ struct SrbdModel {
                 const bool isq = t < 4;
                 col = isq ? XO + t : XW + (t - 4);
                 src = isq ? REC_JO + 4 * a + t : REC_JW + 3 * a + (t - 4);
-            } else {
+            } else if (!HAS_UR || e < 28 + 3 * NA) {
                 const int m = (e - 28) / NA, j = (e - 28) % NA;
                 row = XW + m;
                 row2 = NX + m;                                   // the same A entry is also extra row m (wdot residual)
                 col = zcol(j);
                 src = REC_A + m * NA + j;
+            } else {                                             // user build: a Jacobian entry of a user row (sweep row NEVB + r)
+                const int n = e - 28 - 3 * NA;
+                row = -1;                                        // (no dynamics row)
+                row2 = NX + NEVB + UrInfo<UR>::row(n);
+                col = UrInfo<UR>::col(n);
+                src = REC_UJ + n;
             }
         };
         for (int e0 = tid; e0 < NVAR; e0 += 2 * nthreads) {
@@ -1110,11 +1183,23 @@ struct SrbdModel {
             for (int q = 0; q < 2; ++q) {
                 if (q == 1 && !two) break;
                 const int r1 = COMPACT ? dense_col(row[q]) : row[q], r2 = COMPACT ? dense_col(row2[q] >= 0 ? row2[q] : NX) : row2[q];
-                FT[col[q] * NIP + r1] = (row[q] == col[q] ? 1.0 : 0.0) + c.dt * raw[q];
+                if (!HAS_UR || row[q] >= 0) FT[col[q] * NIP + r1] = (row[q] == col[q] ? 1.0 : 0.0) + c.dt * raw[q];
                 if (row2[q] >= 0) {
                     FT[col[q] * NIP + r2] = raw[q];
                     if (WT) WT[col[q] * NIP + r2] = lm[q] * raw[q];
                 }
+            }
+        }
+    }
+
+    // user builds, terminal node of the sweep: the user rows' Jacobian entries of F~^T from the terminal record recN (global memory);
+    // the stage rows' entries are 0 there and their state weights are 0
+    template <bool COMPACT = false>
+    __device__ __forceinline__ static void expand_term(const double* recN, double* FT, int NIP, int tid, int nthreads) {
+        if constexpr (HAS_UR) {
+            for (int n = tid; n < NUJ; n += nthreads) {
+                const int r = NX + NEVB + UR::row(n);
+                FT[UR::col(n) * NIP + (COMPACT ? dense_col(r) : r)] = recN[REC_UJ + n];
             }
         }
     }
@@ -1332,6 +1417,7 @@ struct LipModel {
     static constexpr int NXR = XR_;        // user-declared linear residual rows (see SrbdModel)
     static_assert(XR_ == 0 || XR_ == kXrRows, "0 or kXrRows user rows");
     static constexpr bool BAR = false;
+    static constexpr bool HAS_UR = false;  // (no user build of this model)
     template <class QM> __device__ __forceinline__ static void add_barrier(const double*, QM, int, int, double = 0.0) {}
     template <class QM> __device__ __forceinline__ static void add_const_rows(const DevConsts&, QM, int, int) {}   // (one Q block per thread: unused)
     static constexpr int NX = 30, NU = 15, NZ = 45, NPB = 11, NP = NPB + NXR;

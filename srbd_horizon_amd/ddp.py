@@ -20,7 +20,7 @@ from typing import Dict
 import numpy as np
 
 from .engine import DdpEngine
-from .problem import LinearTerm, Problem
+from .problem import LinearTerm, NonlinearTerm, Problem
 
 # option keys the reference forwards to pyddp.DdpSolverOptions (ddp.py:16-35) + engine extras
 _REFERENCE_KEYS = ("max_iters", "alpha_0", "alpha_converge_threshold", "line_search_decrease_factor", "beta",
@@ -89,7 +89,14 @@ class DDPSolver:
             consts.update(barrier)
             consts["lower"] = np.concatenate([v.getLowerBounds() for v in list(self.state_var) + list(self.input_var)])
             consts["upper"] = np.concatenate([v.getUpperBounds() for v in list(self.state_var) + list(self.input_var)])
-        self.ddp_solver = DdpEngine(prb.model, prb.nodes - 1, 1, opts=self.opts, consts=consts)
+        if self._user is not None:
+            if barrier.get("bound_barrier_weight", 0.0) > 0.0 or consts.get("friction_barrier_weight", 0.0) > 0.0:
+                raise NotImplementedError("non-linear residuals exist for the plain builds only (no barrier)")
+            if int(self.opts.get("second_order", 1)) == 2:
+                raise NotImplementedError("non-linear residuals exist for the plain builds only (no second_order = 2)")
+        from . import userterms
+        mid = None if self._user is None else userterms.register(self._user)
+        self.ddp_solver = DdpEngine(prb.model, prb.nodes - 1, 1, opts=self.opts, consts=consts, model_id=mid)
         if (self.ddp_solver.nx, self.ddp_solver.nu) != (self.state_size, self.input_size):
             raise ValueError("problem variables do not match the registered model's dimensions")
         from . import _lib
@@ -103,8 +110,8 @@ class DDPSolver:
         refs = {id(r[0]) for r in self._extra_refs if r is not None}
         if own != self._np_model or any(id(p) not in refs for p in user):
             raise ValueError("problem parameters do not match the registered model's parameter vector (further parameters must be "
-                             "references of declared LinearTerm residuals)")
-        if self.ddp_solver.np_ != self._np_model + (8 if self._extra_refs else 0):
+                             "references of declared LinearTerm residuals or read by NonlinearTerm residuals)")
+        if self.ddp_solver.np_ != self._np_model + (8 if self._wide() else 0):
             raise ValueError("engine / problem parameter widths disagree")
         self.var_solution = None
         self._have_x0 = self._have_x = self._have_u = False
@@ -222,16 +229,24 @@ class DDPSolver:
         ns = prb.nodes - 1
         ranges = {"state": list(range(1, ns + 1)), "stage": list(range(0, ns))}
         cost = self.fun_container.getCost()
+        # self._extra_refs[j]: the (Parameter, row) whose per-node values fill user parameter column j (or None);
+        # self._user: the user rows of a user build (any NonlinearTerm declared), else None
+        self._extra_refs, self._user = [], None
         if not cost and not self.fun_container.getCnstr():
             return consts                                       # a problem without declarations: the model's built-in defaults
-        self._extra_refs = []
         linear = {n: fn for n, fn in cost.items() if isinstance(fn.term, LinearTerm)}
-        if linear:
+        nonlinear = {n: fn for n, fn in cost.items() if isinstance(fn.term, NonlinearTerm)}
+        if nonlinear:                                           # one user build carries the linear and the non-linear rows
+            from . import userterms
+            self._user = userterms.spec_from_problem(prb, self.state_size, self.input_size)
+            consts["extra_rows"] = self._user.extra_rows()
+            self._extra_refs = list(self._user.cols)
+        elif linear:
             consts["extra_rows"] = self._linear_rows(linear, ranges)
-        unknown = [n for n in cost if n not in table["cost"] and n not in linear]
+        unknown = [n for n in cost if n not in table["cost"] and n not in linear and n not in nonlinear]
         if unknown:
             raise NotImplementedError(f"model {prb.model} has no analytic term for residual(s) {unknown}: declare a linear residual "
-                                      "as problem.LinearTerm, anything else needs a model term")
+                                      "as problem.LinearTerm, a non-linear one as problem.NonlinearTerm")
         gains = {}
         for name, (ckey, kind) in table["cost"].items():
             fn = cost.get(name)
@@ -304,7 +319,7 @@ class DDPSolver:
     def _parameter_matrix(self):
         """[N+1, np]: the model's own parameters (ddp.py:165-177, creation order); with user rows, 8 more columns: their references"""
         P = self.prb.parameter_matrix()
-        if not self._extra_refs:
+        if not self._wide():
             return P
         out = np.zeros((P.shape[0], self._np_model + 8))
         out[:, :self._np_model] = P[:, :self._np_model]
@@ -312,6 +327,10 @@ class DDPSolver:
             if ref is not None:
                 out[:, self._np_model + j] = ref[0].values[ref[1], :]
         return out
+
+    def _wide(self):
+        """whether the handle carries user rows (an _x build or a user build): 8 more parameter columns"""
+        return bool(self._extra_refs) or self._user is not None
 
     def _createVarSolDict(self, x, u):
         """ddp.py:125-151: walk the variables in creation order; states first, then inputs."""

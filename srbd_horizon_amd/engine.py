@@ -14,15 +14,18 @@ from . import _lib
 
 
 class DdpEngine:
-    def __init__(self, model: str, N: int, batch: int = 1, opts: dict | None = None, consts: dict | None = None):
+    def __init__(self, model: str, N: int, batch: int = 1, opts: dict | None = None, consts: dict | None = None,
+                 model_id: int | None = None):
+        """model_id: a user build of `model` (srbd_horizon_amd/userterms.py register) instead of the model's own builds."""
         self.lib = _lib.load()
         self.model = model
+        self.model_id = _lib.MODEL_IDS[model] if model_id is None else int(model_id)
         self.N, self.B = int(N), int(batch)
         self.nx, self.nu, self.np_ = _lib.model_dims(model)
         self.opts = _lib.default_options(**(opts or {}))
         self.consts = _lib.default_consts(model, **(consts or {}))
         h = C.c_void_p()
-        _lib.check(self.lib.sddp_create(C.byref(h), _lib.MODEL_IDS[model], self.N, self.B,
+        _lib.check(self.lib.sddp_create(C.byref(h), self.model_id, self.N, self.B,
                                         C.byref(self.opts), C.byref(self.consts)))
         self.h = h
         npar = C.c_int()                     # a handle with user rows (consts extra_rows) has MAX_EXTRA more parameter columns
@@ -322,8 +325,8 @@ class DdpEngine:
         return out
 
 
-def eval_knots(model: str, N: int, k, x, u, p, consts: dict | None = None):
-    """Per-knot model evaluation on the GPU: f, [fx fu], GN Hessian, gradient, cost (parity tests)."""
+def eval_knots(model: str, N: int, k, x, u, p, consts: dict | None = None, model_id: int | None = None):
+    """Per-knot model evaluation on the GPU: f, [fx fu], GN Hessian, gradient, cost (parity tests).  model_id: a user build."""
     lib = _lib.load()
     nx, nu, npar = _lib.model_dims(model)
     nz = nx + nu
@@ -336,6 +339,6 @@ def eval_knots(model: str, N: int, k, x, u, p, consts: dict | None = None):
         npar += _lib.MAX_EXTRA               # the user rows' reference columns
     p = np.ascontiguousarray(p, dtype=np.float64).reshape(nk, npar)
     f = np.empty((nk, nx)); F = np.empty((nk, nx, nz)); H = np.empty((nk, nz, nz)); g = np.empty((nk, nz)); L = np.empty(nk)
-    _lib.check(lib.sddp_eval_knots(_lib.MODEL_IDS[model], C.byref(cst), int(N), nk, _lib.ptr(k), _lib.ptr(x), _lib.ptr(u),
+    _lib.check(lib.sddp_eval_knots(_lib.MODEL_IDS[model] if model_id is None else int(model_id), C.byref(cst), int(N), nk, _lib.ptr(k), _lib.ptr(x), _lib.ptr(u),
                                    _lib.ptr(p), _lib.ptr(f), _lib.ptr(F), _lib.ptr(H), _lib.ptr(g), _lib.ptr(L)))
     return f, F, H, g, L

@@ -13,9 +13,20 @@ registered model plus the gain it is scaled with.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 
 import numpy as np
+
+# names of the symbols handed out by Variable.sym() / Parameter.sym(): NonlinearTerm accepts no other free symbol
+_SYM_NAMES = set()
+
+
+def _sym_column(name: str, dim: int):
+    import sympy                                   # lazily: only user-term code needs sympy
+    names = [f"{name}_{i}" for i in range(dim)]
+    _SYM_NAMES.update(names)
+    return sympy.Matrix([sympy.Symbol(n, real=True) for n in names])
 
 
 class Variable:
@@ -57,6 +68,10 @@ class Variable:
     def getDim(self):
         return self._dim
 
+    def sym(self):
+        """sympy column [dim, 1] of this variable's entries, symbols ``<name>_<i>`` (for NonlinearTerm expressions)."""
+        return _sym_column(self._name, self._dim)
+
     def size(self):
         return (self._dim, 1)
 
@@ -81,6 +96,10 @@ class Parameter:
 
     def getDim(self):
         return self._dim
+
+    def sym(self):
+        """sympy column [dim, 1] of this parameter's entries at the node, symbols ``<name>_<i>`` (for NonlinearTerm expressions)."""
+        return _sym_column(self._name, self._dim)
 
     def assign(self, val, nodes=None):
         v = np.asarray(val, dtype=float)
@@ -194,6 +213,68 @@ class LinearTerm(Term):
         self.const = np.broadcast_to(np.asarray(const, dtype=float).reshape(-1), (dim,)).copy()
 
 
+# the sympy functions a NonlinearTerm may use besides + - * / and powers with a constant real exponent: smooth where they are
+# defined (a DDP cost must be C2 here -- Piecewise, Abs, Max, Min, sign, atan2 are refused)
+_ALLOWED_FUNCS = ("exp", "log", "sin", "cos", "tan", "tanh", "atan")
+
+
+def _check_expr(e, where):
+    import sympy
+    for node in sympy.preorder_traversal(e):
+        if isinstance(node, sympy.Symbol):
+            if node.name not in _SYM_NAMES:
+                raise ValueError(f"{where}: free symbol {node} is not an entry of a Variable.sym() / Parameter.sym()")
+        elif isinstance(node, (sympy.Add, sympy.Mul)):
+            continue
+        elif isinstance(node, sympy.Pow):
+            if not (node.exp.is_number and node.exp.is_real):
+                raise ValueError(f"{where}: only powers with a constant real exponent are allowed, got {node}")
+        elif isinstance(node, sympy.Number):
+            if not node.is_finite or not node.is_real:
+                raise ValueError(f"{where}: non-finite or complex constant {node}")
+        elif isinstance(node, sympy.NumberSymbol):
+            continue
+        elif isinstance(node, sympy.Function) and type(node).__name__ in _ALLOWED_FUNCS:
+            continue
+        else:
+            raise ValueError(f"{where}: {type(node).__name__} is not allowed in a NonlinearTerm (allowed: + - * /, real powers, sqrt, "
+                             f"{', '.join(_ALLOWED_FUNCS)})")
+
+
+class NonlinearTerm(Term):
+    """A user-declared NON-LINEAR residual e(x, u, p): what ``createResidual(name, sqrt(gain) * e)`` with any CasADi expression is
+    in the reference (ddp.py:183-196, :216-226).  Cost gain * sum_j e_j^2, Gauss-Newton Hessian 2 gain J^T J.  The expression is
+    compiled into a user build of the model (srbd_horizon_amd/userterms.py); the gain and the parameters' per-node values stay
+    runtime data.
+
+    expr: a sympy scalar, list or column matrix over the entries of ``Variable.sym()`` / ``Parameter.sym()`` of the problem;
+    gain >= 0.  Node range: 1..N (state term: states and parameters only, it is active at the terminal node) or 0..N-1 (stage term)."""
+
+    def __init__(self, expr, gain: float):
+        import sympy
+        if isinstance(expr, sympy.MatrixBase):
+            if expr.shape[1] != 1 and expr.shape[0] != 1:
+                raise ValueError("NonlinearTerm: expr must be a scalar, a list or a column matrix")
+            rows = list(expr)
+        elif isinstance(expr, (list, tuple)):
+            rows = list(expr)
+        else:
+            rows = [expr]
+        if not rows:
+            raise ValueError("NonlinearTerm: expr has no rows")
+        rows = [sympy.sympify(r) for r in rows]
+        for i, r in enumerate(rows):
+            _check_expr(r, f"NonlinearTerm row {i}")
+        g = float(gain)
+        if not (math.isfinite(g) and g >= 0.0):
+            raise ValueError("NonlinearTerm: gain must be finite and >= 0")
+        super().__init__("nonlinear", None, g, len(rows))
+        self.exprs = rows
+
+    def symbols(self):
+        return sorted({s.name for r in self.exprs for s in r.free_symbols})
+
+
 class Function:
     """A cost term or constraint of the problem (Horizon ``Function`` / ``Constraint`` as ddp.py:42-48, :184-196 use them)."""
 
@@ -256,6 +337,11 @@ class Problem:
     def createResidual(self, name, term: Term, nodes=None):
         if not isinstance(term, Term):
             raise TypeError("createResidual needs a Term naming an analytic term of the registered model (no CasADi here)")
+        if isinstance(term, NonlinearTerm):
+            mine = {f"{o.getName()}_{i}" for o in list(self._vars) + list(self._params.values()) for i in range(o.getDim())}
+            alien = [n for n in term.symbols() if n not in mine]
+            if alien:
+                raise ValueError(f"residual {name!r}: symbols {alien} belong to no variable or parameter of this problem")
         f = Function(name, term, range(self.nodes) if nodes is None else nodes)
         self.function_container._cost[name] = f
         return f
