@@ -453,7 +453,7 @@ void sddp_destroy(sddp_handle* h) {
     if (!h) return;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* bufs[] = {h->x0, h->P, h->xs /* | us | stats */, h->xn, h->un, h->xc, h->uc, h->tick_in, h->step_buf, h->dft, h->gains, h->rec, h->scal,
-                    h->qhead, h->order, h->hist, h->qkey, h->qkey2, h->order_in, h->sort_tmp};
+                    h->qhead, h->order, h->hist, h->qkey, h->qkey2, h->order_in, h->sort_tmp, h->policy};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
@@ -576,6 +576,7 @@ int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, i
     if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
     SolveArgs a = make_args(h, d_params);
     rc = h->ops->launch_solve(h, a, first, count);
+    if (rc == SDDP_OK) h->last_params = d_params;      // what sddp_policy_range_device differentiates against
     return rc;
 }
 
@@ -828,20 +829,82 @@ int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* s
 
 int sddp_record_words(sddp_handle* h, int mode, int* words) {
     if (!h || !words) return SDDP_ERR_ARG;
-    if (mode != 0 && mode != 1) return fail(h, SDDP_ERR_ARG, "record mode must be 0 (whole plan) or 1 (first knot)");
-    *words = mode == 0 ? (h->N + 1) * h->d.nx + h->N * h->d.nu + 2 : h->d.nu + h->d.nx + 2;
+    if (mode < 0 || mode > 2) return fail(h, SDDP_ERR_ARG, "record mode must be 0 (whole plan), 1 (first knot) or 2 (first knot and its gains)");
+    if (mode == 2 && !h->policy) return fail(h, SDDP_ERR_ARG, "record mode 2 carries the first knot's gains: call sddp_enable_policy first");
+    *words = mode == 0 ? (h->N + 1) * h->d.nx + h->N * h->d.nu + 2 : h->d.nu + h->d.nx + 2 + (mode == 2 ? h->d.nu * (h->d.nx + 1) : 0);
     return SDDP_OK;
 }
 
 int sddp_pack_records_device(sddp_handle* h, int first, int count, int mode, double* d_out) {
     if (!h || !d_out) return SDDP_ERR_ARG;
-    if (mode != 0 && mode != 1) return fail(h, SDDP_ERR_ARG, "record mode must be 0 (whole plan) or 1 (first knot)");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
     int w = 0;
-    sddp_record_words(h, mode, &w);
+    const int rc = sddp_record_words(h, mode, &w);
+    if (rc != SDDP_OK) return rc;
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
     const int grid = int(std::min<size_t>((size_t(count) * w + 255) / 256, 2048));
     hipLaunchKernelGGL(pack_records_kernel, dim3(grid), dim3(256), 0, h->stream, h->N, h->d.nx, h->d.nu, first, count, mode, h->xs, h->us,
-                       h->stats, d_out);
+                       h->stats, d_out, h->policy, h->policy ? h->policy_words() : 0);
+    HIP_TRY(h, hipGetLastError());
+    return SDDP_OK;
+}
+
+// ---- policy export ------------------------------------------------------------------------------------------------------
+int sddp_enable_policy(sddp_handle* h, int knots) {
+    if (!h) return SDDP_ERR_ARG;
+    if (knots < 0 || knots > h->N) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy: knots must be in 1..N (0 frees the buffer)");
+    if (knots > 0 && !h->ops->launch_policy)
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_policy: no policy kernel for this build (barrier and second_order = 2 builds have none)");
+    if (knots == h->policy_knots) return SDDP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still write the old buffer
+    if (h->policy) { (void)hipFree(h->policy); h->policy = nullptr; }
+    h->policy_knots = 0;
+    if (knots == 0) return SDDP_OK;
+    const size_t bytes = size_t(h->B) * (size_t(knots) * h->d.nu * (h->d.nx + 1) + 4) * sizeof(double);
+    if (hipMalloc((void**)&h->policy, bytes) != hipSuccess) {
+        h->policy = nullptr;
+        (void)hipGetLastError();
+        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_policy: out of device memory");
+    }
+    h->policy_knots = knots;
+    HIP_TRY(h, hipMemsetAsync(h->policy, 0, bytes, h->stream));      // ok = 0 until a policy launch covered the instance
+    return SDDP_OK;
+}
+
+int sddp_policy_words(sddp_handle* h, int* words, int* knots) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (words) *words = h->policy_words();
+    if (knots) *knots = h->policy_knots;
+    return SDDP_OK;
+}
+
+int sddp_policy_range_device(sddp_handle* h, int first, int count) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_range_device: no solve has run on this handle");
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    SolveArgs a = make_args(h, h->last_params);
+    return h->ops->launch_policy(h, a, first, count, h->policy, h->policy_knots);
+}
+
+int sddp_fetch_policy(sddp_handle* h, int first, int count, double* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    const size_t w = size_t(h->policy_words());
+    HIP_TRY(h, hipMemcpyAsync(out, h->policy + size_t(first) * w, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
+}
+
+int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double* d_x_meas, double* d_u_out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!d_x_meas || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    const int grid = int(std::min<size_t>((size_t(count) * h->d.nu + 255) / 256, 2048));
+    hipLaunchKernelGGL(apply_policy_kernel, dim3(grid), dim3(256), 0, h->stream, h->N, h->d.nx, h->d.nu, first, count, h->xs, h->us, h->policy,
+                       h->policy_words(), d_x_meas, d_u_out);
     HIP_TRY(h, hipGetLastError());
     return SDDP_OK;
 }
@@ -911,6 +974,9 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
         case 7:   // per slot of the last solve launch: (start, queue found empty) on the 100 MHz constant-rate clock
             if (h->last_grid < 1) return fail(h, SDDP_ERR_ARG, "no solve launch yet");
             *ptr = h->hist + ((h->B + 1) & ~1); n = (long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;
+        case 8:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
+            if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+            *ptr = h->policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");
     }
     if (bytes) *bytes = n;

@@ -31,6 +31,7 @@ struct ModelOps {
     int (*launch_solve)(sddp_handle*, SolveArgs, int, int);
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
+    int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);
@@ -96,12 +97,19 @@ struct sddp_handle {
     double* xr_dev = nullptr;       // user rows: coefficients | weights | constants (DevConsts::xr, "_x" builds)
     double* first_dev = nullptr;    // [B][nu + nx + 3] packed first knots of sddp_solve_resident_first, and its pinned host image
     double* first_pin = nullptr;
+    // policy export (sddp_enable_policy): [B][policy_knots * nu * (nx + 1) + 4], the parameter tensor of the last solve launch,
+    // resident workgroups of the policy kernel on this device (0: not asked yet) and that kernel
+    double* policy = nullptr;
+    int policy_knots = 0, policy_slots = 0;
+    const double* last_params = nullptr;
+    const void* policy_kernel = nullptr;
     char* up_pin = nullptr;         // pinned ring for small host->device uploads of the setters (no wait per call)
     size_t up_off = 0;
 
     size_t n_x() const { return size_t(B) * (N + 1) * d.nx; }
     size_t n_u() const { return size_t(B) * N * d.nu; }
     size_t n_p() const { return size_t(B) * (N + 1) * d.np; }
+    int policy_words() const { return policy_knots * d.nu * (d.nx + 1) + 4; }
     size_t n_g() const { return size_t(B) * N * d.nu * (d.nx + 1); }
 };
 

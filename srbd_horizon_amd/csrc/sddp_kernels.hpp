@@ -281,11 +281,12 @@ __device__ void sweep_tables(const DevConsts& c, double* s, int lane) {
 // Requires sweep_tables() to have run in this kernel.  One knot per loop trip; the next knot's record / parameters /
 // defect are prefetched into registers while the current knot is processed.
 // -----------------------------------------------------------------------------------------------------------------
-template <class M>
+template <class M, bool KEEP = false>
 __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restrict__ P, const double* __restrict__ dft,
                                const double* __restrict__ rec, double* __restrict__ gains, double mu, double theta, double* s,
-                               int lane, double& dV1, double& G1, double& G2, double& qu_inf, bool has_gap SDDP_T_ARG) {
+                               int lane, double& dV1, double& G1, double& G2, double& qu_inf, bool has_gap SDDP_T_ARG, int keep = 0) {
     // has_gap = false: all defects are zero (every iteration after the first full step): v' = Vx, no Vxx d product
+    // KEEP (policy export, policy_kernel): only the gains of the knots < keep are stored; `gains` then holds `keep` knots
     using L = Lds<M>;
     constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NE = M::NE, NEV = M::NEV, NREC = M::NREC, NP = M::NP;
     constexpr int NXP = L::NXP, NIP = L::NIP, NZP = L::NZP, NUP = L::NUP, SQ = L::SQ;
@@ -395,6 +396,7 @@ __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restri
         g_src[t] = ec < NU ? L::KF + ec : L::KT + ((ec - NU) % NX) * NUP + (ec - NU) / NX;
     }
     auto store_gains = [&](int kk) {
+        if constexpr (KEEP) { if (kk >= keep) return; }
         double* gk = gains + size_t(kk) * NGW;
         double v[RGW];
 #pragma unroll
@@ -996,6 +998,82 @@ template <class M>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     solve_queue<M>(A, s);
+}
+
+// -----------------------------------------------------------------------------------------------------------------
+// Policy export (sddp_policy_range_device): ONE backward sweep per instance at the RETURNED iterate, behind the solve launch; the
+// gains of the first `keep` knots of every instance go to a compact per-instance record
+//     pol [B][keep * NU * (NX + 1) + kPolicyTail]:  knot 0 .. keep - 1: kff (NU) then K (NU x NX) row-major  |  mu_used | theta_used |
+//                                                   expected = -(dV1 + dV2) | ok
+// The sweep is the solve's own device code (backward_sweep<M, KEEP>: same knot loop, same Gauss-Jordan, same expand_var); what it
+// carries in is what the solve would carry into its NEXT sweep: mu = stats.mu, theta = 1 iff second_order and the last step was a
+// full one, the defects of the returned trajectory -- exact zeros once the gaps are closed (stats.gap <= gap_tol: the engines carry
+// exact zeros from the first full step on) -- and on a non-positive pivot the solve's rule (theta -> 0, then mu <- 10 max(mu, 0) +
+// mu_min, give up above mu_max: ok = 0 and the record's gains are zeros).  dft / rec are the work buffers of the queue SLOT; the
+// slot's gains buffer (sddp_device_ptr(3)) is not touched.
+// -----------------------------------------------------------------------------------------------------------------
+constexpr int kPolicyTail = 4;
+template <class M>
+__device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, const int b, const int slot, double* __restrict__ pol,
+                                                const int keep) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC, NGW = NU * (NX + 1);
+    const int lane = threadIdx.x;
+    const int N = A.N;
+    const sddp_options& o = A.o;
+    const double* P = A.P + size_t(b) * (N + 1) * NP;
+    const double* xs = A.xs + size_t(b) * (N + 1) * NX;
+    const double* us = A.us + size_t(b) * N * NU;
+    double* dft = A.dft + size_t(slot) * N * NX;
+    double* rec = A.rec + size_t(slot) * (N + 1) * NREC;
+    double* out = pol + size_t(b) * (size_t(keep) * NGW + kPolicyTail);
+    const sddp_stats st = A.stats[b];
+    sweep_tables<M>(A.c, s, lane);
+    const bool has_gap = st.gap > o.gap_tol;
+    if (has_gap) {
+        double J, gap;
+        phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
+    }
+    phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
+    wave_sync();
+    double mu = st.mu, theta = (o.second_order && st.alpha == o.alpha_0) ? 1.0 : 0.0;
+    double dV1, G1, G2, qu_inf;
+    bool ok;
+    SDDP_T_DECL
+    while (true) {
+        ok = backward_sweep<M, true>(A.c, N, P, dft, rec, out, mu, theta, s, lane, dV1, G1, G2, qu_inf, has_gap SDDP_T_PASS, keep);
+        if (ok) break;
+        if (theta != 0.0) { theta = 0.0; continue; }
+        mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
+        if (!(mu <= o.mu_max)) break;
+    }
+    if (!ok) {   // regularisation overflow: zeros, never the rows a failed sweep left behind
+        drain_vmem();
+        for (int e = lane; e < keep * NGW; e += kWave) out[e] = 0.0;
+    }
+    if (lane == 0) {
+        double* tail = out + size_t(keep) * NGW;
+        tail[0] = mu; tail[1] = theta; tail[2] = ok ? -0.5 * dV1 : 0.0; tail[3] = ok ? 1.0 : 0.0;
+    }
+    wave_sync();
+}
+
+// a work queue like the solve launch (solve_queue), in index order: every instance costs one sweep
+template <class M>
+__global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __restrict__ pol, int keep) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    int i = slot;
+    if (queued) {
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
+    while (i < A.count) {
+        policy_instance<M>(A, s, A.first + i, slot, pol, keep);
+        if (!queued) break;
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
 }
 
 // Queue order for a COLD queue (sddp_options.queue_order = 2): the key of an instance is the total cost of its warm start

@@ -78,13 +78,16 @@ __global__ __launch_bounds__(256) void first_knot_kernel(int N, int B, int nx, i
 // The record an instance-sharded fleet exchanges after a launch: per instance
 //   mode 0: x [N+1][nx] | u [N][nu] | cost | iterations            ((N+1) nx + N nu + 2 doubles: the whole plan)
 //   mode 1: u_0 [nu] | x_1 [nx] | cost | iterations                (nu + nx + 2 doubles: what a closed loop applies next)
+//   mode 2: mode 1 | kff_0 [nu] | K_0 [nu][nx]                       (+ nu (nx + 1): the first knot's feedback policy, from the policy
+//           buffer `pol` [B][pol_words] of sddp_policy_range_device)
 // written [count][words] contiguous into the collective's send buffer: one kernel, whole-wave contiguous stores (the trajectories
 // of consecutive instances are consecutive in xs / us, so the loads are contiguous runs too).
 __global__ __launch_bounds__(256) void pack_records_kernel(int N, int nx, int nu, int first, int count, int mode,
                                                            const double* __restrict__ xs, const double* __restrict__ us,
-                                                           const sddp_stats* __restrict__ st, double* __restrict__ out) {
+                                                           const sddp_stats* __restrict__ st, double* __restrict__ out,
+                                                           const double* __restrict__ pol, int pol_words) {
     const int nxw = mode == 0 ? (N + 1) * nx : nx, nuw = mode == 0 ? N * nu : nu;
-    const int w = nxw + nuw + 2;
+    const int w = nxw + nuw + 2 + (mode == 2 ? nu * (nx + 1) : 0);
     for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < size_t(count) * w; e += size_t(gridDim.x) * 256) {
         const int i = int(e / w), j = int(e % w), b = first + i;
         double v;
@@ -95,9 +98,27 @@ __global__ __launch_bounds__(256) void pack_records_kernel(int N, int nx, int nu
         } else {
             if (j < nu) v = us[size_t(b) * N * nu + j];
             else if (j < nu + nx) v = xs[(size_t(b) * (N + 1) + 1) * nx + (j - nu)];
-            else v = j == nu + nx ? st[b].cost : double(st[b].iters);
+            else if (j < nu + nx + 2) v = j == nu + nx ? st[b].cost : double(st[b].iters);
+            else v = pol[size_t(b) * pol_words + (j - nu - nx - 2)];
         }
         out[e] = v;
+    }
+}
+
+// The feedback policy between two ticks of a fleet (sddp_apply_policy_device): u[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]) for the
+// instances b = first + i of a range, from the policy buffer (knot 0: kff [nu] then K [nu][nx] row-major) and the handle's xs / us.
+// A B x nu x nx mat-vec: nu lanes per instance, one row of K_0 each (nx <= 61 terms, fp64 FMA chain); no LDS.
+__global__ __launch_bounds__(256) void apply_policy_kernel(int N, int nx, int nu, int first, int count, const double* __restrict__ xs,
+                                                           const double* __restrict__ us, const double* __restrict__ pol, int pol_words,
+                                                           const double* __restrict__ x_meas, double* __restrict__ u_out) {
+    for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < size_t(count) * nu; e += size_t(gridDim.x) * 256) {
+        const int i = int(e / nu), r = int(e % nu), b = first + i;
+        const double* K = pol + size_t(b) * pol_words + nu + size_t(r) * nx;
+        const double* x0 = xs + size_t(b) * (N + 1) * nx;
+        const double* xm = x_meas + size_t(i) * nx;
+        double acc = us[size_t(b) * N * nu + r];
+        for (int j = 0; j < nx; ++j) acc = fma(K[j], xm[j] - x0[j], acc);
+        u_out[e] = acc;
     }
 }
 

@@ -282,11 +282,12 @@ __device__ void mw_const_block(const DevConsts& c, int tid, double (&qconst)[Lds
 }
 
 // backward Riccati sweep on 4 waves; every thread gets the same return value and the same dV1 / G1 / G2 / qu_inf.
-template <class M, bool SINK = false>
+template <class M, bool SINK = false, bool KEEP = false>
 __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, const double* __restrict__ P, const double* __restrict__ dft,
                                   const double* __restrict__ rec, double* __restrict__ gains, double mu, double theta,
                                   double* s, int tid, double& dV1, double& G1, double& G2, double& qu_inf,
-                                  const double (&qconst)[LdsMW<M>::TQ][3][3] SDDP_T_ARG) {
+                                  const double (&qconst)[LdsMW<M>::TQ][3][3] SDDP_T_ARG, int keep = 0) {
+    // KEEP (policy export, policy_kernel_mw): only the gains of the knots < keep are stored; `gains` then holds `keep` knots
     // qconst: the constant extra rows' share of this thread's 3x3 Q blocks (mw_const_block, once per kernel)
     using L = LdsMW<M>;
     constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NE = M::NE, NEV = M::NEV, NREC = M::NREC, NP = M::NP;
@@ -356,6 +357,7 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
     // load into a full vmcnt(0) (one counter for loads and stores on gfx9), so they are issued right after such a wait, not before it
     constexpr int NGW = NU * (NX + 1);
     auto store_gains = [&](int kk) {
+        if constexpr (KEEP) { if (kk >= keep) return; }
         double* gk = gains + size_t(kk) * NGW;
         for (int e = tid; e < NGW; e += kThreadsMW) gk[e] = e < NU ? s[L::KF + e] : s[L::KT + ((e - NU) % NX) * SK + (e - NU) / NX];
     };
@@ -1404,6 +1406,74 @@ template <class M>
 __global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(SDDP_MW_W2_WAVES))) void solve_kernel_mw_w2(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     solve_queue_mw<M, mw_sink<M>(true)>(A, s);
+}
+
+// policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread
+template <class M, bool SINK>
+__device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, double* __restrict__ pol,
+                                                   const int keep) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC, NGW = NU * (NX + 1);
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const int N = A.N;
+    const sddp_options& o = A.o;
+    const double* P = A.P + size_t(b) * (N + 1) * NP;
+    const double* xs = A.xs + size_t(b) * (N + 1) * NX;
+    const double* us = A.us + size_t(b) * N * NU;
+    double* dft = A.dft + size_t(slot) * N * NX;
+    double* rec = A.rec + size_t(slot) * (N + 1) * NREC;
+    double* out = pol + size_t(b) * (size_t(keep) * NGW + kPolicyTail);
+    const sddp_stats st = A.stats[b];
+    SDDP_T_DECL
+    sweep_tables_mw<M>(A.c, s, tid);
+    double qconst[LdsMW<M>::TQ][3][3];
+    mw_const_block<M>(A.c, tid, qconst);
+    if (st.gap > o.gap_tol) {
+        double J, gap;
+        if (wave == 0) phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
+    } else {
+        for (int e = tid; e < N * NX; e += kThreadsMW) dft[e] = 0.0;
+    }
+    if (wave == 0) phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
+    __syncthreads();
+    double mu = st.mu, theta = (o.second_order && st.alpha == o.alpha_0) ? 1.0 : 0.0;
+    double dV1, G1, G2, qu_inf;
+    bool ok;
+    while (true) {
+        ok = backward_sweep_mw<M, SINK, true>(A.c, N, P, dft, rec, out, mu, theta, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS, keep);
+        if (ok) break;
+        if (theta != 0.0) { theta = 0.0; continue; }
+        mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
+        if (!(mu <= o.mu_max)) break;
+    }
+    if (!ok) {   // regularisation overflow: zeros, never the rows a failed sweep left behind
+        __syncthreads();
+        for (int e = tid; e < keep * NGW; e += kThreadsMW) out[e] = 0.0;
+    }
+    if (tid == 0) {
+        double* tail = out + size_t(keep) * NGW;
+        tail[0] = mu; tail[1] = theta; tail[2] = ok ? -0.5 * dV1 : 0.0; tail[3] = ok ? 1.0 : 0.0;
+    }
+    __syncthreads();
+}
+
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, double* __restrict__ pol, int keep) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);      // the queue position travels through LDS (solve_queue_mw)
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    if (queued && threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+    __syncthreads();
+    int i = queued ? *q_pos : slot;
+    __syncthreads();
+    while (i < A.count) {
+        policy_instance_mw<M, mw_sink<M>(false)>(A, s, A.first + i, slot, pol, keep);
+        if (!queued) break;
+        if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+        __syncthreads();
+        i = *q_pos;
+        __syncthreads();
+    }
 }
 
 template <class M>

@@ -169,6 +169,35 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
     return SDDP_OK;
 }
 
+// policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
+// policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel; the work buffers dft / rec are the solve's,
+// per slot.  Plain builds only (no barrier, no second_order = 2): make_ops leaves the entry null elsewhere.
+template <class M>
+int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
+    constexpr bool MW = use_mw<M>();
+    constexpr size_t lds = lds_bytes<M>();
+    constexpr int threads = MW ? kThreadsMW : kWave;
+    auto kern = []() { if constexpr (MW) return policy_kernel_mw<M>; else return policy_kernel<M>; }();
+    if (h->policy_slots == 0) {
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0;
+        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        if (!MW) per_cu = std::min(per_cu, 8);
+        h->policy_slots = std::max(1, std::min(per_cu, 32)) * std::max(1, h->cus);
+    }
+    int grid = std::min(count, std::min(h->policy_slots, h->wslots));
+    if (h->opts.max_slots > 0) grid = std::min(grid, h->opts.max_slots);
+    a.first = first; a.count = count; a.order = nullptr; a.qhead = nullptr;
+    if (count > grid) {
+        HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
+        a.qhead = h->qhead;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep);
+    HIP_TRY(h, hipGetLastError());
+    h->policy_kernel = reinterpret_cast<const void*>(kern);
+    return SDDP_OK;
+}
+
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
     hipLaunchKernelGGL(model_step_kernel<M>, dim3((h->B + kWave - 1) / kWave), dim3(kWave), 0, h->stream, h->dc, h->B, k, dx, du, dp, dxn);
@@ -193,6 +222,7 @@ ModelOps make_ops(const char* name) {
     o.launch_solve = launch_solve<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
+    if constexpr (!M::BAR && !M::SO2) o.launch_policy = launch_policy<M>;
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

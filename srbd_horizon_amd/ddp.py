@@ -200,6 +200,17 @@ class DDPSolver:
     def getSolutionDict(self):
         return self.var_solution
 
+    def get_feedback_gains(self, knots: int | None = None):
+        """The feedback policy of the last solve, u = u_k + K_k (x - x_k): a list of K_k [nu, nx] for the first `knots` knots
+        (default: all), from one backward sweep at the RETURNED iterate (sddp_policy_range_device)."""
+        eng = self.ddp_solver
+        M = eng.N if knots is None else int(knots)
+        eng.enable_policy(M)
+        eng.policy_range_device(0, 1)
+        _, K, info = eng.policy(0, 1)
+        self.policy_info = dict(mu_used=info[0, 0], theta_used=info[0, 1], expected=info[0, 2], ok=bool(info[0, 3]))
+        return [K[0, k] for k in range(M)]
+
     def is_equality_constraint(self, constr):                               # ddp.py:108-111
         upper = np.array(constr.getUpperBounds())
         lower = np.array(constr.getLowerBounds())

@@ -18,8 +18,11 @@ def shard_range(total: int, rank: int, world: int):
 
 
 def record_words(N: int, nx: int, nu: int, mode: str = "full") -> int:
-    """doubles per instance record: "full" x | u | cost | iterations; "first_knot" u_0 | x_1 | cost | iterations"""
-    return (N + 1) * nx + N * nu + 2 if mode == "full" else nu + nx + 2
+    """doubles per instance record: "full" x | u | cost | iterations; "first_knot" u_0 | x_1 | cost | iterations;
+    "first_knot_policy" the first-knot record | kff_0 | K_0 (row-major): sddp_record_words modes 0, 1, 2"""
+    if mode == "full":
+        return (N + 1) * nx + N * nu + 2
+    return nu + nx + 2 + (nu * (nx + 1) if mode == "first_knot_policy" else 0)
 
 
 def pack_records(x, u, cost, iters):
@@ -34,12 +37,14 @@ def pack_records(x, u, cost, iters):
                       iters.reshape(B, 1).to(torch.float64)], dim=1).contiguous()
 
 
-def pack_records_into(out, x, u, cost, iters, mode: str = "full"):
+def pack_records_into(out, x, u, cost, iters, mode: str = "full", policy=None):
     """pack_records into a preallocated [B, words] torch tensor (host-side form of csrc pack_records_kernel, which the HIP engine
-    uses: engine.pack_records_device); -> out"""
+    uses: engine.pack_records_device); -> out.  policy [B, >= nu (nx + 1)]: the policy records ("first_knot_policy")"""
     B = x.shape[0]
-    if mode == "first_knot":
+    if mode in ("first_knot", "first_knot_policy"):
         nu, nx = u.shape[2], x.shape[2]
+        if mode == "first_knot_policy":
+            out[:, nu + nx + 2:].copy_(policy[:, :nu * (nx + 1)])
         out[:, :nu].copy_(u[:, 0])
         out[:, nu:nu + nx].copy_(x[:, 1])
         out[:, nu + nx].copy_(cost)

@@ -111,9 +111,11 @@ class DdpEngine:
         self.stats = st
         return x, u
 
-    def solve_resident_first(self):
+    def solve_resident_first(self, policy: bool = False):
         """One tick of a fleet in closed loop: solve on the resident data, fetch only u_0 [B,nu], x_1 [B,nx], cost, iterations and
-        status per robot (the trajectories stay on the device as the next warm start).  -> (u0, x1); self.first_stats"""
+        status per robot (the trajectories stay on the device as the next warm start).  -> (u0, x1); self.first_stats
+        policy=True (needs enable_policy): one policy launch behind the solve; -> (u0, x1, K0 [B,nu,nx]), the feedback gains of the
+        first knot at the returned iterate; self.first_policy = (kff, K, info) of every kept knot."""
         u0 = np.empty((self.B, self.nu))
         x1 = np.empty((self.B, self.nx))
         cost = np.empty(self.B)
@@ -121,7 +123,51 @@ class DdpEngine:
         status = np.empty(self.B, dtype=np.int32)
         self._chk(self.lib.sddp_solve_resident_first(self.h, _lib.ptr(u0), _lib.ptr(x1), _lib.ptr(cost), _lib.ptr(iters), _lib.ptr(status)))
         self.first_stats = dict(cost=cost, iters=iters, status=status)
+        if policy:
+            self.policy_range_device()
+            self.first_policy = self.policy()
+            return u0, x1, self.first_policy[1][:, 0].copy()
         return u0, x1
+
+    # ---- policy export: the feedback policy u_k + K_k (x - x_k) of the RETURNED iterate (include/sddp.h) -------------------------
+    def enable_policy(self, knots: int):
+        """Allocate the per-instance policy buffer for the first `knots` knots (1..N; 0 frees it)."""
+        self._chk(self.lib.sddp_enable_policy(self.h, int(knots)))
+
+    def policy_words(self):
+        """-> (doubles per instance record, knots kept)"""
+        w, k = C.c_int(), C.c_int()
+        self._chk(self.lib.sddp_policy_words(self.h, C.byref(w), C.byref(k)))
+        return w.value, k.value
+
+    def policy_range_device(self, first: int = 0, count: int | None = None):
+        """One sweep per instance of [first, first + count) at the iterate the last solve returned; asynchronous, behind the solve."""
+        self._chk(self.lib.sddp_policy_range_device(self.h, int(first), int(self.B - first if count is None else count)))
+
+    def fetch_policy(self, first: int = 0, count: int | None = None):
+        """The raw policy records [count, words] of the last policy launch (waits for the stream)."""
+        n = int(self.B - first if count is None else count)
+        out = np.empty((max(n, 0), self.policy_words()[0]))
+        self._chk(self.lib.sddp_fetch_policy(self.h, int(first), n, _lib.ptr(out)))
+        return out
+
+    def split_policy(self, rec):
+        """records [n, words] -> (kff [n, M, nu], K [n, M, nu, nx], info [n, 4] = mu_used, theta_used, expected, ok)"""
+        n, M = rec.shape[0], (rec.shape[1] - 4) // (self.nu * (self.nx + 1))
+        g = rec[:, :-4].reshape(n, M, self.nu * (self.nx + 1))
+        return g[:, :, :self.nu].copy(), g[:, :, self.nu:].reshape(n, M, self.nu, self.nx).copy(), rec[:, -4:].copy()
+
+    def policy(self, first: int = 0, count: int | None = None):
+        """-> (kff [n, M, nu], K [n, M, nu, nx], info [n, 4]) of the instances [first, first + count), as the last policy launch
+        (policy_range_device) left them: the gains of the sweep at the RETURNED iterate, u = u_k + kff_k + K_k (x - x_k) being the
+        solver's next step and u_k + K_k (x - x_k) the feedback law around the plan."""
+        return self.split_policy(self.fetch_policy(first, count))
+
+    def apply_policy_device(self, x_meas, u_out, first: int = 0, count: int | None = None):
+        """u_out[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]), b = first + i: device tensors [count, nx] -> [count, nu]; asynchronous."""
+        n = int(self.B - first if count is None else count)
+        self._chk(self.lib.sddp_apply_policy_device(self.h, int(first), n, self._dev(x_meas, (n, self.nx)), self._dev(u_out, (n, self.nu))))
+        return u_out
 
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
@@ -260,7 +306,7 @@ class DdpEngine:
         self._chk(self.lib.sddp_class_history(self.h, int(cls), C.byref(m), C.byref(n)))
         return m.value, n.value
 
-    RECORD_MODES = {"full": 0, "first_knot": 1}
+    RECORD_MODES = {"full": 0, "first_knot": 1, "first_knot_policy": 2}
 
     def record_words(self, mode="full"):
         w = C.c_int()

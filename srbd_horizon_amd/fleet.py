@@ -18,7 +18,8 @@ buffers are allocated once, in ``__init__`` (``depth * batch`` records per rank)
 would overwrite them, so the caller decides when to launch and when the results have been consumed (``flush`` / ``wait``).
 
 This is the step function of ``bench.py``; ``tests/test_fleet_gloo.py`` drives the same class at world size 2 on CPU with an
-engine stand-in.  The engine only needs ``load_range_device``, ``solve_range_device`` and ``fetch_device_views`` (and, on a
+engine stand-in.  The engine only needs ``load_range_device``, ``solve_range_device`` and ``fetch_device_views`` (with
+``policy=True`` also ``policy_range_device`` and, for a stand-in, a ``policy_records`` tensor [B, words]) (and, on a
 GPU, ``use_torch_stream``: packing and the collective are torch operations on torch's current stream, so the engine is bound to
 that stream here).
 """
@@ -29,14 +30,20 @@ from . import dist as sdist
 
 
 class FleetQueue:
-    def __init__(self, engine, params_all, batch: int, depth: int, collective: bool = False, gather: str = "full"):
+    def __init__(self, engine, params_all, batch: int, depth: int, collective: bool = False, gather: str = "full",
+                 policy: bool = False):
         """gather: what the closing all-gather carries per instance -- "full": x | u | cost | iterations, the whole plan
         (4 680 B at (30, 13, 6)); "first_knot": u_0 | x_1 | cost | iterations (168 B), what a fleet in
-        closed loop needs from the other ranks."""
+        closed loop needs from the other ranks.
+        policy: every flush runs the policy launch behind the solve (the engine's enable_policy must have been called) and the
+        first-knot record carries the first knot's gains behind it: u_0 | x_1 | cost | iterations | kff_0 | K_0."""
         self.eng, self.P, self.batch, self.depth, self.collective = engine, params_all, int(batch), int(depth), bool(collective)
         if gather not in ("full", "first_knot"):
             raise ValueError("gather must be 'full' or 'first_knot'")
-        self.gather = gather
+        if policy and gather != "first_knot":
+            raise ValueError("policy=True extends the 'first_knot' record")
+        self.policy = bool(policy)
+        self.gather = "first_knot_policy" if policy else gather
         if tuple(params_all.shape[:1]) != (self.batch * self.depth,):
             raise ValueError("params_all must hold depth * batch instances")
         self.pending = 0            # batches loaded and not yet solved
@@ -56,7 +63,7 @@ class FleetQueue:
             import torch
             import torch.distributed as dist
             self.world = dist.get_world_size()
-            words = sdist.record_words(self.x.shape[1] - 1, self.x.shape[2], self.u.shape[2], gather)
+            words = sdist.record_words(self.x.shape[1] - 1, self.x.shape[2], self.u.shape[2], self.gather)
             cap = self.batch * self.depth
             mk = lambda rows: torch.empty((rows, words), dtype=torch.float64, device=self.x.device)
             self._pack = [mk(cap), mk(cap)]
@@ -87,6 +94,8 @@ class FleetQueue:
         if n == 0:
             return 0
         self.eng.solve_range_device(self.P, 0, n)
+        if self.policy:
+            self.eng.policy_range_device(0, n)                               # one sweep per instance at the returned iterate
         self.launches += 1
         if self.collective:
             import torch.distributed as dist
@@ -96,7 +105,8 @@ class FleetQueue:
                 local = self.eng.pack_records_device(self._pack[k][:n], 0, n, self.gather)
             else:                                                            # engine stand-in of the CPU tests
                 local = sdist.pack_records_into(self._pack[k][:n], self.x[:n], self.u[:n], self.sf[:n, _lib.STATS_F64_COST],
-                                                self.si[:n, _lib.STATS_I32_ITERS], self.gather)
+                                                self.si[:n, _lib.STATS_I32_ITERS], self.gather,
+                                                self.eng.policy_records[:n] if self.policy else None)
             self._work[k] = dist.all_gather_into_tensor(self._out[k][:self.world * n], local, async_op=True)
             self._n[k] = n
             self.gather_bytes += local.numel() * local.element_size()

@@ -24,8 +24,13 @@ EXAMPLE_OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 
 class MpcLoop:
     def __init__(self, model: str = "srbd37", ns: int = 20, T: float | None = None, opts: dict | None = None, robot=None,
-                 warm_start: str = "shift", number_of_legs: int = 2, contact_model: int | None = None):
-        """warm_start: "shift" = previous solution advanced by one knot (last knot repeated),
+                 warm_start: str = "shift", number_of_legs: int = 2, contact_model: int | None = None, feedback_substeps: int = 0,
+                 feedback: bool = True):
+        """feedback_substeps: 0 (default) = the reference loop, the first input applied open loop over one Euler step.  n > 0: the
+        simulator step of a tick is split into n Euler sub-steps of dt / n and the input applied at each of them is the solver's
+        feedback policy u_0 + K_0 (x - x_0) at the sub-step's state x (K_0: the first knot's gain at the returned iterate,
+        DDPSolver.get_feedback_gains; feedback=False keeps the sub-steps and applies u_0 alone: the open-loop twin of a comparison).
+        warm_start: "shift" = previous solution advanced by one knot (last knot repeated),
         "device" = the same, with the parameter tensor and the warm start resident on the GPU and shifted there (only the new
         last parameter column and the state cross PCIe), "previous" = previous solution as is (what a stateful pyddp object
         would keep), "reset" = x0 repeated / static input."""
@@ -57,6 +62,9 @@ class MpcLoop:
             raise ValueError(model)
         self.model, self.ns = model, ns
         self.warm_start = warm_start
+        if feedback_substeps < 0:
+            raise ValueError("feedback_substeps must be >= 0")
+        self.feedback_substeps, self.feedback = int(feedback_substeps), bool(feedback)
         self.solver = DDPSolver(self.srbd.prb, opts=dict(EXAMPLE_OPTS if opts is None else opts))
         self.state = self.srbd.getInitialState().astype(float)
         c_init_z = float(self.srbd.initial_foot_position[0][2])
@@ -71,8 +79,34 @@ class MpcLoop:
         self.trace = None          # set to a list to record every tick's solver inputs (x0, params, warm start): bench.py replays them
         self._last = None
 
-    def tick(self, motion: str = "standing", axes=(0.0, 0.0)):
+    def _rdot_slice(self):
+        o = 0
+        for v in self.solver.state_var:
+            if v.getName() == "rdot":
+                return slice(o, o + 3)
+            o += v.getDim()
+        raise KeyError("rdot")
+
+    def _substeps(self, u0, x0, p0, push):
+        """n Euler sub-steps of dt / n through the solver's device model (x + (f(x, u) - x) / n), the input re-evaluated from the
+        policy at each; push: a CoM acceleration [3] acting over the tick (a force disturbance / m), unknown to the solver."""
+        n, x = self.feedback_substeps, self.state
+        K0 = self.solver.get_feedback_gains(knots=1)[0] if self.feedback else None
+        dt = float(self.srbd.prb.getDt())
+        for _ in range(n):
+            u = u0 + K0 @ (x - x0) if K0 is not None else u0
+            x = x + (self.solver.ddp_solver.model_step(x[None], u[None], p0[None], 0)[0] - x) / n
+            if push is not None:
+                x[self._rdot_slice()] += np.asarray(push, dtype=float) * dt / n
+            if self.model != "lip30":
+                x[3:7] /= np.linalg.norm(x[3:7])
+        return x
+
+    def tick(self, motion: str = "standing", axes=(0.0, 0.0), push=None):
+        """push (feedback_substeps > 0 only): CoM acceleration [3] disturbing the simulator during this tick."""
         s, ns = self.srbd, self.ns
+        if push is not None and self.feedback_substeps == 0:
+            raise ValueError("push needs feedback_substeps > 0")
         if self.warm_start != "device":
             self.solver.setInitialState(self.state)                                    # :84
         shifted = (s.rdot_ref,) if self.model == "lip30" else (s.rdot_ref, s.w_ref, s.oref, s.orientation_tracking_gain)
@@ -106,9 +140,12 @@ class MpcLoop:
         self._last = sol
         u0 = sol["u_opt"][:, 0]                                                        # :158
         p0 = s.prb.parameter_matrix()[0]
-        self.state = self.solver.ddp_solver.model_step(self.state[None], u0[None], p0[None], 0)[0]   # :159 Euler step (same HIP model)
-        if self.model != "lip30":
-            self.state[3:7] /= np.linalg.norm(self.state[3:7])                         # :160 (the LIP state has no quaternion)
+        if self.feedback_substeps > 0:
+            self.state = self._substeps(u0, sol["x_opt"][:, 0], p0, push)
+        else:
+            self.state = self.solver.ddp_solver.model_step(self.state[None], u0[None], p0[None], 0)[0]   # :159 Euler step (same HIP model)
+            if self.model != "lip30":
+                self.state[3:7] /= np.linalg.norm(self.state[3:7])                     # :160 (the LIP state has no quaternion)
         if self.warm_start == "shift":
             x, u = sol["x_opt"], sol["u_opt"]
             self.solver.set_x_warmstart(np.concatenate([x[:, 1:], x[:, -1:]], axis=1))

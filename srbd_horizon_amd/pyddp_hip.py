@@ -117,3 +117,12 @@ class DdpSolver:
 
     def is_converged(self) -> bool:
         return bool(self._eng.is_converged()[0])
+
+    def get_feedback_gains(self):
+        """The local feedback policy of the last solve, u = u_k + K_k (x - x_k): a list of N matrices K_k [nu, nx] (rows: inputs,
+        columns: states -- the transpose-free orientation of the [dim, nodes] arrays solve() returns: K_k @ (x[:, k] deviation)),
+        from one backward sweep at the RETURNED iterate (sddp_policy_range_device)."""
+        self._eng.enable_policy(self.N)
+        self._eng.policy_range_device(0, 1)
+        _, K, _ = self._eng.policy(0, 1)
+        return [K[0, k] for k in range(self.N)]
