@@ -36,17 +36,9 @@ __host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
 // Whether the sweep of model M runs WITHOUT the dense (Vxx F)^T tile ("W-free"): the SRBD models, whose
 // [fx fu] has dense rows (ND > 0).  srbd61's tiles would not fit a CU's 160 KB with the tile; srbd37 drops from 63.8 to 50.9 KB (52.0 with the Gauss-Jordan's multiplier block) and
 // gains 14 % at two workgroups per CU (the W phase becomes a compact 111 x 7 product).  lip30 (no dense rows: the tile IS the
-// product) keeps it: measured neutral to - 1 % without.  -DSDDP_WFREE_ALL / -DSDDP_WFREE_NONE: diagnostic builds.
+// product) keeps it: measured neutral to - 1 % without (profiles/r05/experiments/wfree_switch.diff).
 template <class M>
-constexpr bool mw_wfree() {
-#if defined(SDDP_WFREE_ALL)
-    return true;
-#elif defined(SDDP_WFREE_NONE)
-    return M::NX > 40;
-#else
-    return M::ND > 0;
-#endif
-}
+constexpr bool mw_wfree() { return M::ND > 0; }
 
 // Whether a build of the kernel recomputes per knot what derives from the thread index (row / column decodes, LDS and HBM addresses)
 // instead of carrying it across the knot loops: the thread index passes through an opaque register copy at the top of every knot, so
@@ -56,10 +48,6 @@ constexpr bool mw_wfree() {
 // builds of srbd37 / lip30 lose 4.5 % with it (profiles/r04/experiments/README.md).
 template <class M>
 constexpr bool mw_sink(bool half_register_file) { return half_register_file || M::NX > 40; }
-
-#ifndef SDDP_MW_W2_WAVES
-#define SDDP_MW_W2_WAVES 2      // diagnostic: 3 = the half-register-file build capped at a third of the register file instead
-#endif
 
 template <class M>
 struct LdsMW {
@@ -628,58 +616,7 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
             __syncthreads();
         }
         SDDP_TICK(4)
-#ifdef SDDP_GJ_REDUNDANT
-        constexpr bool kGjRedundant = NU <= 24 && NU + (NX + 1 + kWavesMW - 1) / kWavesMW <= kWave;
-#else
-        constexpr bool kGjRedundant = false;
-#endif
-        if constexpr (kGjRedundant) {
-            // Experiment (profiles/r05/experiments): NO hand-off inside the solve.  Every wave eliminates the
-            // whole [Quu + mu I] block REDUNDANTLY (lanes 0..NU-1: one column each, all NU rows in registers) together with ITS
-            // quarter of the right-hand sides [Qu | Qux] (lanes NU..NU+CW-1); pivot columns by v_readlane inside the wave.  The four
-            // waves compute the same pivots bit for bit, so the positive-definiteness decision needs no exchange.
-            constexpr int CW = (NX + 1 + kWavesMW - 1) / kWavesMW;
-            const int rc = wave * CW + (lane - NU);                       // right-hand side this lane holds: 0 = Qu, c + 1 = Qux column c
-            const bool is_rhs = lane >= NU && lane < NU + CW && rc <= NX;
-            const int qc = lane < NU ? NX + lane : (is_rhs && rc > 0 ? rc - 1 : 0);
-            double a[NU];
-#pragma unroll
-            for (int i = 0; i < NU; ++i) {
-                double v = s[L::QU + i * SQ + qc];
-                v = (is_rhs && rc == 0) ? s[L::QV + NX + i] : v;
-                v += (i == lane) ? mu : 0.0;
-                a[i] = (lane < NU || is_rhs) ? v : 0.0;
-            }
-            if (is_rhs && rc == 0) {
-#pragma unroll
-                for (int i = 0; i < NU; ++i) qu_acc = fmax(qu_acc, fabs(a[i]));
-            }
-            SDDP_TICK(16)
-            bool okp = true;
-#pragma unroll
-            for (int p = 0; p < NU; ++p) {
-                double pv[NU];
-#pragma unroll
-                for (int i = 0; i < NU; ++i) pv[i] = readlane_d(a[i], p);
-                if (!(pv[p] > 0.0) || !(pv[p] < 1e300)) okp = false;
-                const double t = a[p] * fast_rcp(pv[p]);
-#pragma unroll
-                for (int i = 0; i < NU; ++i) a[i] = (i == p) ? t : fma(-pv[i], t, a[i]);
-            }
-            if (!okp) return false;                                       // the same in every wave
-            SDDP_TICK(19)
-            if (is_rhs) {
-                double* dst = rc == 0 ? s + L::KF : s + L::KT + (rc - 1) * SK;
-                double dv = 0.0;
-#pragma unroll
-                for (int i = 0; i < NU; ++i) {
-                    dst[i] = -a[i];
-                    if (rc == 0) dv += -a[i] * s[L::QV + NX + i];
-                }
-                // dv_acc / qu_acc are read from lane NU of every wave at the end of the sweep: the Qu column is lane NU of wave 0
-                if (rc == 0) dv_acc += dv;
-            }
-        } else {
+        {
             double a[RPW][CPL], qu_save[RPW];
             // column of Q a slot reads (any valid one for the slot of column NU, which takes q instead; columns >= NCOL are zeroed): branch-free
             int qcol[CPL];
@@ -710,41 +647,10 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
                 double* gt = s + L::GT + (blk & 1) * RPW * GTS;
                 if (wave == blk) {
                     bool ok = true;
-#ifdef SDDP_GJ_PAIR
-                    // Experiment (profiles/r05/experiments #11): the owner's pivots two at a time -- the 2 x 2 diagonal block is
-                    // inverted with ONE reciprocal (of its determinant) and both pivot columns are fetched before either is used, so
-                    // the serial chain readlane -> reciprocal -> scale -> update runs RPW / 2 times per block instead of RPW times.
-                    // Positive definite <=> a00 > 0 and det > 0 (the second pivot of the one-at-a-time order is det / a00).
-#pragma unroll
-                    for (int r = 0; r + 1 < RPW; r += 2) {
-                        const int p = blk * RPW + r;
-                        if (p + 1 < NU) {
-                            double p0[RPW], p1[RPW];
-#pragma unroll
-                            for (int rr = 0; rr < RPW; ++rr) { p0[rr] = readlane_d(a[rr][0], p); p1[rr] = readlane_d(a[rr][0], p + 1); }
-                            const double det = fma(p0[r], p1[r + 1], -p1[r] * p0[r + 1]);
-                            if (!(p0[r] > 0.0) || !(det > 0.0) || !(det < 1e300)) ok = false;
-                            const double id = fast_rcp(det);
-                            const double i00 = p1[r + 1] * id, i01 = -p1[r] * id, i10 = -p0[r + 1] * id, i11 = p0[r] * id;
-#pragma unroll
-                            for (int cc = 0; cc < CPL; ++cc) {
-                                const double t0 = fma(i00, a[r][cc], i01 * a[r + 1][cc]);
-                                const double t1 = fma(i10, a[r][cc], i11 * a[r + 1][cc]);
-#pragma unroll
-                                for (int rr = 0; rr < RPW; ++rr)
-                                    a[rr][cc] = (rr == r) ? t0 : (rr == r + 1) ? t1 : fma(-p1[rr], t1, fma(-p0[rr], t0, a[rr][cc]));
-                            }
-                        }
-                    }
-                    // an odd last row of the block, or a last pivot without a partner, goes alone (always behind the pairs)
-                    auto paired = [&](int r) { return (r & ~1) + 1 < RPW && blk * RPW + (r & ~1) + 1 < NU; };
-#else
-                    auto paired = [](int) { return false; };
-#endif
 #pragma unroll
                     for (int r = 0; r < RPW; ++r) {
                         const int p = blk * RPW + r;
-                        if (p < NU && !paired(r)) {
+                        if (p < NU) {
                             double pv[RPW];
 #pragma unroll
                             for (int rr = 0; rr < RPW; ++rr) pv[rr] = readlane_d(a[rr][0], p);
@@ -1403,7 +1309,7 @@ __global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A) {
 // the same body capped at half the register file: two workgroups per CU where the tiles of two instances fit its LDS;
 // sddp_options.waves_per_simd = 2 picks it, results are identical
 template <class M>
-__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(SDDP_MW_W2_WAVES))) void solve_kernel_mw_w2(SolveArgs A) {
+__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     solve_queue_mw<M, mw_sink<M>(true)>(A, s);
 }

@@ -13,13 +13,7 @@ namespace sddp {
 
 // large models (> 48 KB of LDS per instance: srbd37, srbd61, lip30) run on 4 waves per instance (sddp_kernels_mw.hpp)
 template <class M>
-constexpr bool use_mw() {
-#ifdef SDDP_MW_ALL
-    return true;
-#else
-    return Lds<M>::BYTES > 48 * 1024;
-#endif
-}
+constexpr bool use_mw() { return Lds<M>::BYTES > 48 * 1024; }
 template <class M>
 constexpr size_t lds_bytes() {
     if constexpr (use_mw<M>()) return LdsMW<M>::BYTES; else return Lds<M>::BYTES;

@@ -1,6 +1,7 @@
 #!/bin/bash
-# A/B of library variants on the driver-shaped run (build/variants/libsddp_<name>.so, built with SDDP_LIB / SDDP_CXXFLAGS):
-#   bash tools/ab_variants.sh base dma base dma        (bench lines and stderr under $OUT, default build/ab)
+# A/B of library variants on the driver-shaped run (build/variants/libsddp_<name>.so, built with SDDP_LIB / SDDP_CXXFLAGS, e.g. from
+# a tree with profiles/r05/experiments/lds_dma.diff applied and the diff's flag in SDDP_CXXFLAGS):
+#   bash tools/ab_variants.sh base lds_dma base lds_dma        (bench lines and stderr under $OUT, default build/ab)
 O=${OUT:-build/ab}
 mkdir -p $O
 for v in "$@"; do
