@@ -241,6 +241,22 @@ int  sddp_apply_policy_device(sddp_handle* h, int first, int count, const double
 int  sddp_set_instance_classes(sddp_handle* h, const int* classes /*[B]*/, int n_classes);
 int  sddp_set_instance_classes_range_device(sddp_handle* h, int first, int count, const int* d_classes, int n_classes);
 int  sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* solves);
+/* ---- heterogeneous fleets: per-instance robot constants (opt-in; a handle that never calls these runs exactly as before) ---------
+ * sddp_set_instance_consts: instance first + i gets consts[i] (host pointer [count]; ordered on the handle's stream like
+ *   sddp_set_params).  The first call allocates a device table with one row per instance, every row the handle's own constants;
+ *   rows outside [first, first + count) keep what they hold.  While the table is active EVERY kernel the handle launches reads
+ *   instance b's row instead of the handle's constants: the solve kernels on every entry point, the queue_order 2 / 3 key pre-pass,
+ *   the policy export, sddp_model_step, sddp_backward / sddp_forward.  The result of an instance still does not depend on the range,
+ *   order or slot it ran in, and a table whose rows all equal the handle's constants gives bit-identical results.
+ *   What may differ per instance: m, I, com, feet, dt, force_scaling, every gain, lip_height, inertia_mode, lever_sign,
+ *   relative_velocity_constraints.  What may not: anything that selects a build or a device side table -- in every entry
+ *   friction_barrier_weight and bound_barrier_weight must be 0 and n_extra 0.  Plain builds of the four models only (both
+ *   waves_per_simd builds): a handle with user rows (n_extra > 0), a barrier, second_order = 2 or a user build returns SDDP_ERR_ARG.
+ * sddp_clear_instance_consts: back to the handle's own constants for every instance (the table is freed).
+ * sddp_instance_consts_active: *on = 1 while the table is active. */
+int  sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_model_consts* consts /*[count]*/);
+int  sddp_clear_instance_consts(sddp_handle* h);
+int  sddp_instance_consts_active(sddp_handle* h, int* on);
 /* slots: resident workgroups the work buffers exist for; grid and queue length (0: no queue) of the last solve launch */
 int  sddp_queue_info(sddp_handle* h, int* slots, int* last_grid, int* last_queued);
 /* which kernel a handle runs: wavefronts per instance (1: solve_kernel, 4: solve_kernel_mw), the build the LAST solve launch used

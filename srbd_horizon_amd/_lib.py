@@ -99,6 +99,9 @@ SYMBOLS = {
     "sddp_set_instance_classes": (C.c_int, [_vp, _vp, C.c_int]),
     "sddp_set_instance_classes_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
     "sddp_class_history": (C.c_int, [_vp, C.c_int, _P(C.c_double), _P(C.c_longlong)]),
+    "sddp_set_instance_consts": (C.c_int, [_vp, C.c_int, C.c_int, _P(SddpModelConsts)]),
+    "sddp_clear_instance_consts": (C.c_int, [_vp]),
+    "sddp_instance_consts_active": (C.c_int, [_vp, _P(C.c_int)]),
     "sddp_queue_info": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
     "sddp_fetch": (C.c_int, [_vp, _vp, _vp, _vp]),
     "sddp_synchronize": (C.c_int, [_vp]),
@@ -327,6 +330,56 @@ def set_consts(c: SddpModelConsts, **over):
         else:
             raise KeyError(f"unknown model constant {k!r}")
     return c
+
+
+# what sddp_set_instance_consts lets differ from one instance to the next (include/sddp.h): field -> trailing shape of its override
+INSTANCE_CONST_FIELDS = {"m": (), "I": (9,), "com": (3,), "feet": (12,), "dt": (), "force_scaling": (), "r_tracking_gain": (),
+                         "rdot_tracking_gain": (), "w_tracking_gain": (), "rel_pos_gain": (), "force_switch_weight": (),
+                         "min_qddot_gain": (), "min_f_gain": (), "zmp_tracking_gain": (), "lip_height": (), "inertia_mode": (),
+                         "lever_sign": (), "relative_velocity_constraints": ()}
+_INT_CONST_FIELDS = ("inertia_mode", "relative_velocity_constraints")
+
+
+def pack_instance_consts(base: SddpModelConsts, overrides: dict, count: int | None = None):
+    """overrides: field -> array [count, ...] (I as [count, 3, 3] or [count, 9], feet as [count, 4, 3] or [count, 12], scalars as
+    [count]) -> a ctypes array SddpModelConsts[count], every entry a copy of `base` with the named fields replaced.  Fields that
+    select a kernel build or a device side table (barrier weights, bounds, user rows) cannot differ per instance: ValueError, like
+    an unknown field or a shape that does not fit.  Needs no device."""
+    if base.n_extra != 0 or base.friction_barrier_weight != 0.0 or base.bound_barrier_weight != 0.0:
+        raise ValueError("per-instance constants exist for plain builds only (no user rows, no barrier)")
+    cols = {}
+    for k, v in overrides.items():
+        if k not in INSTANCE_CONST_FIELDS:
+            known = hasattr(base, k) or k == "extra_rows"
+            raise ValueError(f"{k!r} cannot differ per instance (it selects a kernel build or a device side table)" if known
+                             else f"unknown model constant {k!r}")
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim < 1:
+            raise ValueError(f"{k}: expected one value per instance, shape [count, ...]")
+        n = a.shape[0]
+        width = int(np.prod(INSTANCE_CONST_FIELDS[k], dtype=int))
+        if a.size != n * width:
+            raise ValueError(f"{k}: expected shape [count{''.join(', %d' % d for d in INSTANCE_CONST_FIELDS[k])}], got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{k}: non-finite value")
+        if count is None:
+            count = n
+        if n != count:
+            raise ValueError(f"{k}: {n} instances, expected {count}")
+        cols[k] = a.reshape(n, width)
+    if count is None or count < 1:
+        raise ValueError("no instances: give at least one override or a count >= 1")
+    out = (SddpModelConsts * count)()
+    for i in range(count):
+        C.memmove(C.byref(out[i]), C.byref(base), C.sizeof(SddpModelConsts))
+        for k, a in cols.items():
+            if INSTANCE_CONST_FIELDS[k]:
+                field = getattr(out[i], k)
+                for j in range(a.shape[1]):
+                    field[j] = a[i, j]
+            else:
+                setattr(out[i], k, int(a[i, 0]) if k in _INT_CONST_FIELDS else float(a[i, 0]))
+    return out
 
 
 def check(rc: int, handle=None):

@@ -466,6 +466,7 @@ void sddp_destroy(sddp_handle* h) {
     if (h->xr_dev) (void)hipFree(h->xr_dev);
     if (h->cls) (void)hipFree(h->cls);
     if (h->cls_stat) (void)hipFree(h->cls_stat);
+    if (h->ctab) (void)hipFree(h->ctab);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -824,6 +825,55 @@ int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* s
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (solves) *solves = (long long)st[1];
     if (mean_iters) *mean_iters = st[1] ? double(st[0]) / double(st[1]) : 0.0;
+    return SDDP_OK;
+}
+
+// ---- heterogeneous fleets: per-instance constants ---------------------------------------------------------------------------
+int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_model_consts* consts) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!consts) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: consts is NULL");
+    if (h->model_id >= kUserId0 || h->bar || h->so2 || h->consts.n_extra != 0)
+        return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: per-instance constants exist for the plain builds only (no user rows, no barrier, "
+                                     "no second_order = 2, no user build)");
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    for (int i = 0; i < count; ++i) {   // nothing that selects another build or a device side table may differ per instance
+        const sddp_model_consts& c = consts[i];
+        if (c.n_extra != 0) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: n_extra must be 0 in every entry");
+        if (c.friction_barrier_weight != 0.0 || c.bound_barrier_weight != 0.0)
+            return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: friction_barrier_weight and bound_barrier_weight must be 0 in every entry");
+    }
+    const size_t B = size_t(h->B), n = size_t(count);
+    host_buf rows(std::max(h->ctab ? n : B, n) * sizeof(DevConsts));
+    if (!rows.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
+    DevConsts* r = rows.as<DevConsts>();
+    if (!h->ctab) {   // first call: every row starts as the handle's own constants
+        DevConsts* t = nullptr;
+        if (hipMalloc((void**)&t, B * sizeof(DevConsts)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, SDDP_ERR_NOMEM, "sddp_set_instance_consts: out of device memory");
+        }
+        for (size_t b = 0; b < B; ++b) r[b] = h->dc;
+        const int rc = upload(h, t, r, B * sizeof(DevConsts));
+        if (rc != SDDP_OK) { (void)hipFree(t); return rc; }
+        h->ctab = t;
+    }
+    for (size_t i = 0; i < n; ++i) r[i] = make_dev_consts(consts[i]);
+    return upload(h, h->ctab + first, r, n * sizeof(DevConsts));
+}
+
+int sddp_clear_instance_consts(sddp_handle* h) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->ctab) return SDDP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still read the table
+    h->up_off = 0;
+    (void)hipFree(h->ctab);
+    h->ctab = nullptr;
+    return SDDP_OK;
+}
+
+int sddp_instance_consts_active(sddp_handle* h, int* on) {
+    if (!h || !on) return SDDP_ERR_ARG;
+    *on = h->ctab ? 1 : 0;
     return SDDP_OK;
 }
 

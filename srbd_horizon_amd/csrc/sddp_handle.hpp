@@ -88,7 +88,10 @@ struct sddp_handle {
     unsigned long long* cls_stat = nullptr;   // [n_cls][2]
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
     struct KInfo { const void* fn = nullptr; int slots = 0; };
-    KInfo kinfo[2];                 // per kernel build: dynamic-LDS attribute set, resident workgroups on this device
+    KInfo kinfo[4];                 // per kernel build (and its `_h` twin): dynamic-LDS attribute set, resident workgroups on this device
+    // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; non-null = active, and every kernel of the
+    // handle is launched as its `_h` twin, which reads instance b's row instead of the kernel-argument copy of `dc`
+    sddp::DevConsts* ctab = nullptr;   // [B]
     int last_grid = 0, last_queued = 0;
     int last_build = 0;             // waves_per_simd of the kernel build the last solve launch ran (sddp_kernel_info)
     const void* last_kernel = nullptr;   // ... and that kernel, its dynamic LDS bytes and its workgroups per CU (sddp_kernel_resources)

@@ -969,6 +969,63 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void
 }
 
 // -----------------------------------------------------------------------------------------------------------------
+// Heterogeneous fleets (sddp_set_instance_consts): the `_h` twin of a kernel takes, beside the arguments of the kernel it stands
+// for, a table with one DevConsts row per instance and runs the SAME per-instance body on a copy of the arguments whose `c` is
+// instance b's row.  The body rebuilds everything it derives from `c` (LDS tables, constant blocks) at the start of every
+// instance, so nothing of one robot outlives its solve.  b is wave-uniform (blockIdx, readfirstlane, the LDS queue word) and the
+// table is read-only for the whole launch: the row is read through the constant address space, i.e. by scalar loads into the
+// registers the kernel-argument copy occupies in the homogeneous kernels.  Those kernels are not touched.
+// -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ DevConsts row_of(const DevConsts* __restrict__ ctab, const int b) {
+    static_assert(sizeof(DevConsts) % sizeof(unsigned long long) == 0, "a row is copied in 64-bit words");
+    constexpr int W = int(sizeof(DevConsts) / sizeof(unsigned long long));
+    typedef const unsigned long long __attribute__((address_space(4))) * WordPtr;
+    const WordPtr src = (WordPtr)(ctab + b);
+    unsigned long long w[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) w[i] = src[i];
+    DevConsts c;
+    __builtin_memcpy(&c, w, sizeof(c));
+    return c;
+}
+__device__ __forceinline__ SolveArgs with_row(const SolveArgs& A, const DevConsts* __restrict__ ctab, const int b) {
+    SolveArgs R = A;
+    R.c = row_of(ctab, b);
+    return R;
+}
+
+// solve_queue with the instance's own constants
+template <class M>
+__device__ __forceinline__ void solve_queue_h(const SolveArgs& A, const DevConsts* __restrict__ ctab, double* s) {
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    int i = slot;
+    if (threadIdx.x == 0) A.slot_clock(slot)[0] = wall_clock64();
+    if (queued) {
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
+    while (i < A.count) {
+        const int b = __builtin_amdgcn_readfirstlane((queued && A.order) ? A.order[i] : A.first + i);
+        solve_instance<M>(with_row(A, ctab, b), s, b, slot);
+        if (!queued) break;
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
+    if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
+}
+template <class M>
+__global__ __launch_bounds__(kWave) void solve_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    solve_queue_h<M>(A, ctab, s);
+}
+template <class M>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    solve_queue_h<M>(A, ctab, s);
+}
+
+// -----------------------------------------------------------------------------------------------------------------
 // Policy export (sddp_policy_range_device): ONE backward sweep per instance at the RETURNED iterate, behind the solve launch; the
 // gains of the first `keep` knots of every instance go to a compact per-instance record
 //     pol [B][keep * NU * (NX + 1) + kPolicyTail]:  knot 0 .. keep - 1: kff (NU) then K (NU x NX) row-major  |  mu_used | theta_used |
@@ -1043,6 +1100,24 @@ __global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __re
         i = __builtin_amdgcn_readfirstlane(i);
     }
 }
+template <class M>
+__global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __restrict__ pol, int keep, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    int i = slot;
+    if (queued) {
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
+    while (i < A.count) {
+        const int b = __builtin_amdgcn_readfirstlane(A.first + i);
+        policy_instance<M>(with_row(A, ctab, b), s, b, slot, pol, keep);
+        if (!queued) break;
+        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+    }
+}
 
 // Queue order for a COLD queue (sddp_options.queue_order = 2): the key of an instance is the total cost of its warm start
 // (x_0 := x0 as the solve does; multiple-shooting cost of the given xs / us), evaluated here by one wavefront per instance, one
@@ -1081,6 +1156,47 @@ __global__ __launch_bounds__(kWave) void queue_cost_key_kernel(DevConsts c, int 
         idx[i] = b;
     }
 }
+// the same key for the `_h` twin below (a copy: sharing one body with the kernel above moved that kernel's register allocation)
+template <class M>
+__device__ __forceinline__ void queue_cost_key(const DevConsts& c, const int N, const int i, const int b, const double* __restrict__ x0,
+                                               const double* __restrict__ P, const double* __restrict__ xs,
+                                               const double* __restrict__ us, double* __restrict__ key, int* __restrict__ idx) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    const int lane = threadIdx.x;
+    const double* xb = xs + size_t(b) * (N + 1) * NX;
+    const double* ub = us + size_t(b) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    double Jl = 0.0;
+    for (int k = lane; k <= N; k += kWave) {
+        double x[NX];
+        const double* xk = k == 0 ? x0 + size_t(b) * NX : xb + k * NX;
+#pragma unroll
+        for (int j = 0; j < NX; ++j) x[j] = xk[j];
+        if (k < N) {
+            double u[NU], xn[NX];
+#pragma unroll
+            for (int j = 0; j < NU; ++j) u[j] = ub[k * NU + j];
+            Jl += M::step(c, x, u, Pb + k * NP, k, xn);
+        } else {
+            Jl += M::term_cost(c, x, Pb + k * NP);
+        }
+    }
+    const double J = wave_sum(Jl);
+    if (lane == 0) {
+        key[i] = (J == J) ? J : __builtin_huge_val();      // a non-finite start sorts first (it ends at once with status 3)
+        idx[i] = b;
+    }
+}
+// ... of a heterogeneous fleet: every instance's warm start is priced with its own robot
+template <class M>
+__global__ __launch_bounds__(kWave) void queue_cost_key_kernel_h(const DevConsts* __restrict__ ctab, int N, int first, int count,
+                                                                 const double* __restrict__ x0, const double* __restrict__ P,
+                                                                 const double* __restrict__ xs, const double* __restrict__ us,
+                                                                 double* __restrict__ key, int* __restrict__ idx) {
+    const int i = blockIdx.x;
+    if (i >= count) return;
+    queue_cost_key<M>(row_of(ctab, first + i), N, i, first + i, x0, P, xs, us, key, idx);
+}
 
 // -----------------------------------------------------------------------------------------------------------------
 // single-phase kernels for the parity tests (same device code as the fused kernel)
@@ -1088,6 +1204,22 @@ __global__ __launch_bounds__(kWave) void queue_cost_key_kernel(DevConsts c, int 
 // one model step per instance, x+ = f(x, u, p_k) (ddp.py:228-230): the closed-loop simulator step of the examples
 // (dsrbd_example.py:158-159) through the same device model code as the solver.  One thread per instance.
 // -----------------------------------------------------------------------------------------------------------------
+// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
+template <class M>
+__device__ __forceinline__ void model_step_one(const DevConsts& c, const int b, const int k, const double* __restrict__ x,
+                                               const double* __restrict__ u, const double* __restrict__ p, double* __restrict__ xn) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    double xv[NX], uv[NU], pv[NP], xo[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xv[i] = x[size_t(b) * NX + i];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) uv[i] = u[size_t(b) * NU + i];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) pv[i] = p[size_t(b) * NP + i];
+    (void)M::step(c, xv, uv, pv, k, xo);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xn[size_t(b) * NX + i] = xo[i];
+}
 template <class M>
 __global__ __launch_bounds__(kWave) void model_step_kernel(DevConsts c, int B, int k, const double* __restrict__ x,
                                                            const double* __restrict__ u, const double* __restrict__ p,
@@ -1105,6 +1237,16 @@ __global__ __launch_bounds__(kWave) void model_step_kernel(DevConsts c, int B, i
     (void)M::step(c, xv, uv, pv, k, xo);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[size_t(b) * NX + i] = xo[i];
+}
+// ... of a heterogeneous fleet: one thread per instance, so every lane reads its own row (vector loads)
+template <class M>
+__global__ __launch_bounds__(kWave) void model_step_kernel_h(const DevConsts* __restrict__ ctab, int B, int k, const double* __restrict__ x,
+                                                             const double* __restrict__ u, const double* __restrict__ p,
+                                                             double* __restrict__ xn) {
+    const int b = blockIdx.x * kWave + threadIdx.x;
+    if (b >= B) return;
+    const DevConsts c = ctab[b];
+    model_step_one<M>(c, b, k, x, u, p, xn);
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1148,6 +1290,31 @@ __global__ __launch_bounds__(kWave) void eval_knots_kernel(DevConsts c, int N, i
     for (int e = lane; e < NZ; e += kWave) g_out[t * NZ + e] = r[M::REC_G + e];
 }
 
+// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
+template <class M>
+__device__ __forceinline__ void backward_one(const SolveArgs& A, double* s, const int b) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
+    const int lane = threadIdx.x;
+    const int N = A.N;
+    const double* P = A.P + size_t(b) * (N + 1) * NP;
+    double* xs = A.xs + size_t(b) * (N + 1) * NX;
+    double* us = A.us + size_t(b) * N * NU;
+    double* dft = A.dft + size_t(b) * N * NX;
+    double* gains = A.gains + size_t(b) * N * (NU * (NX + 1));
+    double* rec = A.rec + size_t(b) * (N + 1) * NREC;
+    double J, gap;
+    sweep_tables<M>(A.c, s, lane);
+    phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
+    phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
+    wave_sync();
+    double dV1, G1, G2, qu_inf;
+    SDDP_T_DECL
+    const bool ok = backward_sweep<M>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, lane, dV1, G1, G2, qu_inf, true SDDP_T_PASS);
+    if (lane == 0) {
+        double* sc = A.scal + size_t(b) * kScal;
+        sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
+    }
+}
 template <class M>
 __global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1174,7 +1341,26 @@ __global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs A) {
         sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
     }
 }
+template <class M>
+__global__ __launch_bounds__(kWave) void backward_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int b = blockIdx.x;
+    if (b >= A.B) return;
+    backward_one<M>(with_row(A, ctab, b), s, b);
+}
 
+// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
+template <class M>
+__device__ __forceinline__ void forward_one(const SolveArgs& A, double* s, const int b) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    const int lane = threadIdx.x;
+    const int N = A.N;
+    const double J = rollout<M, false>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
+                                       A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
+                                       A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
+                                       A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s);
+    if (lane == 0) A.scal[size_t(b) * kScal] = J;
+}
 template <class M>
 __global__ __launch_bounds__(kWave) void forward_kernel(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1187,6 +1373,13 @@ __global__ __launch_bounds__(kWave) void forward_kernel(SolveArgs A) {
                                        A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
                                        A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s);
     if (lane == 0) A.scal[size_t(b) * kScal] = J;
+}
+template <class M>
+__global__ __launch_bounds__(kWave) void forward_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int b = blockIdx.x;
+    if (b >= A.B) return;
+    forward_one<M>(with_row(A, ctab, b), s, b);
 }
 
 }  // namespace sddp

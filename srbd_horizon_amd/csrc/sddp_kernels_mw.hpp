@@ -1314,6 +1314,40 @@ __global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2)))
     solve_queue_mw<M, mw_sink<M>(true)>(A, s);
 }
 
+// heterogeneous fleets (with_row in sddp_kernels.hpp): the same queue, every instance on its own row of the constants table.  b comes
+// out of the LDS queue word the kernel has anyway, made wave-uniform for the scalar loads of the row
+template <class M, bool SINK>
+__device__ __forceinline__ void solve_queue_mw_h(const SolveArgs& A, const DevConsts* __restrict__ ctab, double* s) {
+    int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    if (threadIdx.x == 0) A.slot_clock(slot)[0] = wall_clock64();
+    if (queued && threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+    __syncthreads();
+    int i = queued ? *q_pos : slot;
+    __syncthreads();
+    while (i < A.count) {
+        const int b = __builtin_amdgcn_readfirstlane((queued && A.order) ? A.order[i] : A.first + i);
+        solve_instance_mw<M, SINK>(with_row(A, ctab, b), s, b, slot);
+        if (!queued) break;
+        if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+        __syncthreads();
+        i = *q_pos;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
+}
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    solve_queue_mw_h<M, mw_sink<M>(false)>(A, ctab, s);
+}
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    solve_queue_mw_h<M, mw_sink<M>(true)>(A, ctab, s);
+}
+
 // policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread
 template <class M, bool SINK>
 __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, double* __restrict__ pol,
@@ -1381,7 +1415,56 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, doub
         __syncthreads();
     }
 }
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, double* __restrict__ pol, int keep, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
+    const int slot = blockIdx.x;
+    const bool queued = A.qhead != nullptr;
+    if (queued && threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+    __syncthreads();
+    int i = queued ? *q_pos : slot;
+    __syncthreads();
+    while (i < A.count) {
+        const int b = __builtin_amdgcn_readfirstlane(A.first + i);
+        policy_instance_mw<M, mw_sink<M>(false)>(with_row(A, ctab, b), s, b, slot, pol, keep);
+        if (!queued) break;
+        if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
+        __syncthreads();
+        i = *q_pos;
+        __syncthreads();
+    }
+}
 
+// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
+template <class M>
+__device__ __forceinline__ void backward_one_mw(const SolveArgs& A, double* s, const int b) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const int N = A.N;
+    const double* P = A.P + size_t(b) * (N + 1) * NP;
+    double* xs = A.xs + size_t(b) * (N + 1) * NX;
+    double* us = A.us + size_t(b) * N * NU;
+    double* dft = A.dft + size_t(b) * N * NX;
+    double* gains = A.gains + size_t(b) * N * (NU * (NX + 1));
+    double* rec = A.rec + size_t(b) * (N + 1) * NREC;
+    double J = 0.0, gap = 0.0;
+    SDDP_T_DECL
+    sweep_tables_mw<M>(A.c, s, tid);
+    if (wave == 0) {
+        phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
+        phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
+    }
+    __syncthreads();
+    double dV1, G1, G2, qu_inf;
+    double qconst[LdsMW<M>::TQ][3][3];
+    mw_const_block<M>(A.c, tid, qconst);
+    const bool ok = backward_sweep_mw<M, mw_sink<M>(false)>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS);
+    if (tid == 0) {
+        double* sc = A.scal + size_t(b) * kScal;
+        sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
+    }
+}
 template <class M>
 __global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1412,7 +1495,27 @@ __global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw(SolveArgs A) {
         sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
     }
 }
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int b = blockIdx.x;
+    if (b >= A.B) return;
+    backward_one_mw<M>(with_row(A, ctab, b), s, b);
+}
 
+// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
+template <class M>
+__device__ __forceinline__ void forward_one_mw(const SolveArgs& A, double* s, const int b) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    const int tid = threadIdx.x;
+    const int N = A.N;
+    SDDP_T_DECL
+    const double J = rollout_mw<M, false, mw_sink<M>(false)>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
+                                          A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
+                                          A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
+                                          A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, tid, s SDDP_T_PASS);
+    if (tid == 0) A.scal[size_t(b) * kScal] = J;
+}
 template <class M>
 __global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw(SolveArgs A) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1426,6 +1529,13 @@ __global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw(SolveArgs A) {
                                           A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
                                           A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, tid, s SDDP_T_PASS);
     if (tid == 0) A.scal[size_t(b) * kScal] = J;
+}
+template <class M>
+__global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    const int b = blockIdx.x;
+    if (b >= A.B) return;
+    forward_one_mw<M>(with_row(A, ctab, b), s, b);
 }
 
 }  // namespace sddp

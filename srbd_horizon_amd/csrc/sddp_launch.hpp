@@ -35,9 +35,24 @@ template <class M> KernelFn pick_solve(int waves_per_simd) {
 template <class M> KernelFn pick_backward() { if constexpr (use_mw<M>()) return backward_kernel_mw<M>; else return backward_kernel<M>; }
 template <class M> KernelFn pick_forward() { if constexpr (use_mw<M>()) return forward_kernel_mw<M>; else return forward_kernel<M>; }
 
-// resident workgroups of `kern` on this device (the queue's slot count) and its dynamic-LDS attribute, once per handle and build
+// Heterogeneous fleets (sddp_set_instance_consts): the plain builds carry an `_h` twin of every kernel, which reads instance b's
+// row of the handle's constants table (sddp_kernels.hpp with_row).  sddp_api.hip refuses the table on every other build, so
+// h->ctab != nullptr implies has_hetero<M>().
 template <class M>
-int kernel_slots(sddp_handle* h, KernelFn kern, int wps, int* slots) {
+constexpr bool has_hetero() { return !M::BAR && !M::SO2 && M::NXR == 0; }
+using KernelFnH = void (*)(SolveArgs, const DevConsts*);
+template <class M> KernelFnH pick_solve_h(int waves_per_simd) {
+    if constexpr (use_mw<M>()) {
+        if constexpr (has_w2<M>()) return waves_per_simd >= 2 ? solve_kernel_mw_w2_h<M> : solve_kernel_mw_h<M>;
+        else return solve_kernel_mw_h<M>;
+    } else return waves_per_simd >= 2 ? solve_kernel_w2_h<M> : solve_kernel_h<M>;
+}
+template <class M> KernelFnH pick_backward_h() { if constexpr (use_mw<M>()) return backward_kernel_mw_h<M>; else return backward_kernel_h<M>; }
+template <class M> KernelFnH pick_forward_h() { if constexpr (use_mw<M>()) return forward_kernel_mw_h<M>; else return forward_kernel_h<M>; }
+
+// resident workgroups of `kern` on this device (the queue's slot count) and its dynamic-LDS attribute, once per handle and build
+template <class M, class Fn>
+int kernel_slots(sddp_handle* h, Fn kern, int wps, int* slots) {
     constexpr bool MW = use_mw<M>();
     constexpr size_t lds = lds_bytes<M>();
     constexpr int threads = MW ? kThreadsMW : kWave;
@@ -48,7 +63,10 @@ int kernel_slots(sddp_handle* h, KernelFn kern, int wps, int* slots) {
     HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
     if (!MW) per_cu = std::min(per_cu, 4 * (wps >= 2 ? 2 : 1));   // the two builds: 1 or 2 wavefronts per SIMD
     per_cu = std::max(1, std::min(per_cu, 32));
-    auto& k = h->kinfo[h->kinfo[0].fn ? 1 : 0];
+    constexpr int nk = int(sizeof(h->kinfo) / sizeof(h->kinfo[0]));      // two builds and their `_h` twins: never more kernels than entries
+    int free_k = 0;
+    while (free_k < nk - 1 && h->kinfo[free_k].fn) ++free_k;
+    auto& k = h->kinfo[free_k];
     k.fn = reinterpret_cast<const void*>(kern);
     k.slots = per_cu * std::max(1, h->cus);
     *slots = k.slots;
@@ -57,11 +75,12 @@ int kernel_slots(sddp_handle* h, KernelFn kern, int wps, int* slots) {
 
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M>
-int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
+template <class M, bool HET>
+int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
     constexpr bool MW = use_mw<M>();
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    KernelFn kern = pick_solve<M>(wps);
+    auto pick = [](int w) { if constexpr (HET) return pick_solve_h<M>(w); else return pick_solve<M>(w); };
+    auto kern = pick(wps);
     constexpr size_t lds = lds_bytes<M>();
     constexpr int threads = MW ? kThreadsMW : kWave;
     int slots = 0;
@@ -69,7 +88,7 @@ int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
     if (rc != SDDP_OK) return rc;
     if constexpr (MW) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
         if (wps >= 2) {
-            KernelFn k1 = pick_solve<M>(1);
+            auto k1 = pick(1);
             int s1 = 0;
             rc = kernel_slots<M>(h, k1, 1, &s1);
             if (rc != SDDP_OK) return rc;
@@ -101,8 +120,12 @@ int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
         } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
             rc = alloc_cold_queue(h);
             if (rc != SDDP_OK) return rc;
-            hipLaunchKernelGGL(queue_cost_key_kernel<M>, dim3(count), dim3(kWave), 0, h->stream, a.c, a.N, first, count, a.x0, a.P, a.xs,
-                               a.us, h->qkey, h->order_in);
+            if constexpr (HET)
+                hipLaunchKernelGGL(queue_cost_key_kernel_h<M>, dim3(count), dim3(kWave), 0, h->stream, (const DevConsts*)h->ctab, a.N, first, count,
+                                   a.x0, a.P, a.xs, a.us, h->qkey, h->order_in);
+            else
+                hipLaunchKernelGGL(queue_cost_key_kernel<M>, dim3(count), dim3(kWave), 0, h->stream, a.c, a.N, first, count, a.x0, a.P, a.xs,
+                                   a.us, h->qkey, h->order_in);
             HIP_TRY(h, hipGetLastError());
             if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
                 rc = launch_class_keys(h, count);
@@ -118,7 +141,8 @@ int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
     h->last_lds = int(lds);
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a);
+    if constexpr (HET) hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, (const DevConsts*)h->ctab);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a);
     HIP_TRY(h, hipGetLastError());
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
         rc = launch_class_update(h, first, count);
@@ -129,6 +153,13 @@ int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
         ++h->pending;
     }
     return SDDP_OK;
+}
+template <class M>
+int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) return launch_solve_on<M, true>(h, a, first, count);
+    }
+    return launch_solve_on<M, false>(h, a, first, count);
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
@@ -145,8 +176,17 @@ int max_slots(sddp_handle* h, int* slots) {
 template <class M>
 int launch_backward(sddp_handle* h, const SolveArgs& a) {
     constexpr bool MW = use_mw<M>();
-    KernelFn kern = pick_backward<M>();
     constexpr size_t lds = lds_bytes<M>();
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) {
+            KernelFnH kh = pick_backward_h<M>();
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kh, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a, (const DevConsts*)h->ctab);
+            HIP_TRY(h, hipGetLastError());
+            return SDDP_OK;
+        }
+    }
+    KernelFn kern = pick_backward<M>();
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a);
     HIP_TRY(h, hipGetLastError());
@@ -155,8 +195,17 @@ int launch_backward(sddp_handle* h, const SolveArgs& a) {
 template <class M>
 int launch_forward(sddp_handle* h, const SolveArgs& a) {
     constexpr bool MW = use_mw<M>();
-    KernelFn kern = pick_forward<M>();
     constexpr size_t lds = lds_bytes<M>();
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) {
+            KernelFnH kh = pick_forward_h<M>();
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kh, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a, (const DevConsts*)h->ctab);
+            HIP_TRY(h, hipGetLastError());
+            return SDDP_OK;
+        }
+    }
+    KernelFn kern = pick_forward<M>();
     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a);
     HIP_TRY(h, hipGetLastError());
@@ -166,13 +215,16 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
 // policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
 // policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel; the work buffers dft / rec are the solve's,
 // per slot.  Plain builds only (no barrier, no second_order = 2): make_ops leaves the entry null elsewhere.
-template <class M>
-int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
+template <class M, bool HET>
+int launch_policy_on(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
     constexpr bool MW = use_mw<M>();
     constexpr size_t lds = lds_bytes<M>();
     constexpr int threads = MW ? kThreadsMW : kWave;
-    auto kern = []() { if constexpr (MW) return policy_kernel_mw<M>; else return policy_kernel<M>; }();
-    if (h->policy_slots == 0) {
+    auto kern = []() {
+        if constexpr (HET) { if constexpr (MW) return policy_kernel_mw_h<M>; else return policy_kernel_h<M>; }
+        else { if constexpr (MW) return policy_kernel_mw<M>; else return policy_kernel<M>; }
+    }();
+    if (h->policy_slots == 0 || h->policy_kernel != reinterpret_cast<const void*>(kern)) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int per_cu = 0;
         HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
@@ -186,14 +238,30 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
         HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
         a.qhead = h->qhead;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep);
+    if constexpr (HET) hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep, (const DevConsts*)h->ctab);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep);
     HIP_TRY(h, hipGetLastError());
     h->policy_kernel = reinterpret_cast<const void*>(kern);
     return SDDP_OK;
 }
+template <class M>
+int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) return launch_policy_on<M, true>(h, a, first, count, pol, keep);
+    }
+    return launch_policy_on<M, false>(h, a, first, count, pol, keep);
+}
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) {
+            hipLaunchKernelGGL(model_step_kernel_h<M>, dim3((h->B + kWave - 1) / kWave), dim3(kWave), 0, h->stream, (const DevConsts*)h->ctab, h->B, k,
+                               dx, du, dp, dxn);
+            HIP_TRY(h, hipGetLastError());
+            return SDDP_OK;
+        }
+    }
     hipLaunchKernelGGL(model_step_kernel<M>, dim3((h->B + kWave - 1) / kWave), dim3(kWave), 0, h->stream, h->dc, h->B, k, dx, du, dp, dxn);
     HIP_TRY(h, hipGetLastError());
     return SDDP_OK;

@@ -284,6 +284,26 @@ class DdpEngine:
         """One asynchronous launch over the instances [first, first + count); `params` is the whole [B, N+1, np] tensor."""
         self._chk(self.lib.sddp_solve_range_device(self.h, self._dev(params, (self.B, self.N + 1, self.np_)), int(first), int(count)))
 
+    # ---- heterogeneous fleets: per-instance robot constants (include/sddp.h) ------------------------------------------------
+    def set_instance_consts(self, overrides: dict, first: int = 0):
+        """Instances [first, first + count) get their own robot: `overrides` maps a field of the model constants (m, I, com, feet,
+        dt, force_scaling, the gains, lip_height, inertia_mode, lever_sign, relative_velocity_constraints) to an array
+        [count, ...]; fields not named keep the handle's value.  From then on every kernel of the handle reads instance b's
+        constants (solve on every entry point, queue keys, policy export, model_step, backward / forward); the other instances
+        keep what they had -- the handle's constants, or an earlier override.  Unknown fields and fields that select a kernel
+        build (barrier weights, bounds, user rows) raise ValueError before any GPU call."""
+        rows = _lib.pack_instance_consts(self.consts, overrides)
+        self._chk(self.lib.sddp_set_instance_consts(self.h, int(first), len(rows), rows))
+
+    def clear_instance_consts(self):
+        """Back to the handle's own constants for every instance."""
+        self._chk(self.lib.sddp_clear_instance_consts(self.h))
+
+    def instance_consts_active(self) -> bool:
+        on = C.c_int()
+        self._chk(self.lib.sddp_instance_consts_active(self.h, C.byref(on)))
+        return bool(on.value)
+
     # ---- class history (queue_order = 3) -------------------------------------------------------------------------------------
     def set_instance_classes(self, classes, n_classes: int):
         """classes [B] int (host): what kind of problem each instance is (-1: unlabelled); sddp.h queue_order 3"""

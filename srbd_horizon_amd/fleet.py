@@ -87,6 +87,15 @@ class FleetQueue:
         self.eng.load_range_device(lo, self.batch, x0, xs, us)
         self.pending += 1
 
+    def set_instance_consts(self, overrides: dict, first: int = 0):
+        """Per-instance robot constants of this shard's handle (DdpEngine.set_instance_consts): `first` counts within the handle,
+        i.e. instance `first` of block 0 is the first instance of the first submitted batch.  Ordered on the engine's stream, so
+        it may be called between a flush and the next submit."""
+        self.eng.set_instance_consts(overrides, first)
+
+    def clear_instance_consts(self):
+        self.eng.clear_instance_consts()
+
     def flush(self):
         """Solve the pending batches in one launch (asynchronous); with a process group, start the all-gather of their solution
         records (asynchronous too: `wait()` before reading `gathered`)."""
