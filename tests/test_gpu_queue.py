@@ -95,6 +95,23 @@ def test_non_finite_options_are_rejected():
                  ("mu_max", 1e-7), ("queue_order", 4), ("max_slots", -1), ("line_search_decrease_factor", 0.9999999), ("second_order", 3)):
         with pytest.raises(RuntimeError):
             DdpEngine("srbd13", 30, 1, opts=dict(OPTS, **{k: v}))
+    # ... and a ladder of more than 4096 rungs (0.999^j down to 1e-12: 27617), a zero first step, a zero regularisation increment;
+    # on a live handle too, which keeps its options and still solves
+    bad = (dict(alpha_0=0.0), dict(mu_min=0.0), dict(line_search_decrease_factor=0.999, alpha_converge_threshold=1e-12))
+    for over in bad:
+        with pytest.raises(RuntimeError):
+            DdpEngine("srbd13", 30, 1, opts=dict(OPTS, **over))
+    batch = workload.make_batch("srbd13", 30, [0, 1])
+    eng = _engine("srbd13", 30, 2)
+    x0, u0, s0 = _solve(eng, batch)
+    for over in bad:
+        with pytest.raises(RuntimeError):
+            eng.set_options(**over)
+        x, u, s = _solve(eng, batch)
+        np.testing.assert_array_equal(x, x0); np.testing.assert_array_equal(u, u0)
+        for f in s0.dtype.names:
+            np.testing.assert_array_equal(s[f], s0[f], err_msg=f)
+    assert s0["converged"].all()
 
 
 def test_configs3_all_eight_rank_shards_match_the_c_oracle(record_property):
