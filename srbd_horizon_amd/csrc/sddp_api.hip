@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -48,42 +49,62 @@ std::string& create_error() {
 }
 
 int launch_queue_order(sddp_handle* h, int first, int count) {
-    hipLaunchKernelGGL(queue_order_kernel, dim3(1), dim3(1024), 0, h->stream, first, count, h->hist, h->order);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch(h, queue_order_kernel, 1, 1024, 0, first, count, h->hist, h->order);
 }
-
 int launch_class_keys(sddp_handle* h, int count) {
-    hipLaunchKernelGGL(class_key_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, count, h->order_in, h->cls, h->n_cls, h->cls_stat,
-                       h->qkey);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch(h, class_key_kernel, (count + 255) / 256, 256, 0, count, h->order_in, h->cls, h->n_cls, h->cls_stat, h->qkey);
 }
 int launch_class_update(sddp_handle* h, int first, int count) {
-    hipLaunchKernelGGL(class_update_kernel, dim3((count + 255) / 256), dim3(256), 0, h->stream, first, count, h->cls, h->n_cls, h->stats,
-                       h->cls_stat);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat);
 }
+
+namespace {
+// Buffer ownership: every device and pinned allocation of a handle is made by acquire(), which registers it in h->owned.
+// sddp_destroy frees what is registered; release() frees what a handle gives up earlier, and nulls the pointer.
+// sddp_create reserves kOwnedReserve entries (host out-of-memory is SDDP_ERR_NOMEM there), more than a handle has buffers, so the
+// registry does not grow afterwards; the reserve below is for a handle that one day has more.
+constexpr size_t kOwnedReserve = 48;
+template <class T>
+hipError_t acquire(sddp_handle* h, T*& p, size_t bytes, bool pinned = false) {
+    void* q = nullptr;
+    if (h->owned.size() == h->owned.capacity()) {
+        try { h->owned.reserve(h->owned.size() + kOwnedReserve); } catch (...) { return hipErrorOutOfMemory; }
+    }
+    const hipError_t e = pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) return e;
+    h->owned.push_back({q, pinned});
+    p = static_cast<T*>(q);
+    return hipSuccess;
+}
+void free_owned(const sddp_handle::Owned& o) { (void)(o.pinned ? hipHostFree(o.p) : hipFree(o.p)); }
+template <class T>
+void release(sddp_handle* h, T*& p) {
+    for (size_t i = 0; p && i < h->owned.size(); ++i)
+        if (h->owned[i].p == p) { free_owned(h->owned[i]); h->owned.erase(h->owned.begin() + i); break; }
+    p = nullptr;
+}
+// a device buffer made on first use; the message names the allocation as the call sites always did
+#define ACQUIRE_TRY(h, field, bytes)                                                                                          \
+    do {                                                                                                                      \
+        hipError_t e_ = acquire(h, field, bytes);                                                                             \
+        if (e_ != hipSuccess)                                                                                                 \
+            return fail(h, SDDP_ERR_HIP, std::string("hipMalloc((void**)&" #field ", " #bytes "): ") + hipGetErrorString(e_)); \
+    } while (0)
+}  // namespace
 
 int alloc_cold_queue(sddp_handle* h) {
     if (h->sort_tmp) return SDDP_OK;               // the last pointer of the group: set only when all of it exists
-    double *k1 = nullptr, *k2 = nullptr;
-    int* oi = nullptr;
-    void* tmp = nullptr;
     size_t tb = 0;
-    hipError_t e = hipMalloc((void**)&k1, size_t(h->B) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&k2, size_t(h->B) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&oi, size_t(h->B) * sizeof(int));
+    hipError_t e = acquire(h, h->qkey, size_t(h->B) * sizeof(double));
+    if (e == hipSuccess) e = acquire(h, h->qkey2, size_t(h->B) * sizeof(double));
+    if (e == hipSuccess) e = acquire(h, h->order_in, size_t(h->B) * sizeof(int));
     if (e == hipSuccess) e = sort_pairs_desc_temp_bytes(h->B, &tb);
-    if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = acquire(h, h->sort_tmp, std::max<size_t>(tb, 16));
     if (e != hipSuccess) {
-        if (k1) (void)hipFree(k1);
-        if (k2) (void)hipFree(k2);
-        if (oi) (void)hipFree(oi);
+        release(h, h->qkey); release(h, h->qkey2); release(h, h->order_in);
         return fail(h, SDDP_ERR_HIP, std::string("cold-queue buffers: ") + hipGetErrorString(e));
     }
-    h->qkey = k1; h->qkey2 = k2; h->order_in = oi; h->sort_tmp_bytes = tb; h->sort_tmp = tmp;
+    h->sort_tmp_bytes = tb;
     return SDDP_OK;
 }
 }  // namespace sddp
@@ -189,7 +210,59 @@ SolveArgs make_args(sddp_handle* h, const double* d_params) {
     return a;
 }
 
-constexpr size_t kUpRing = size_t(256) << 10;
+int check_range(sddp_handle* h, int first, int count) {
+    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    return SDDP_OK;
+}
+
+// Pinned host staging of a small payload, `images` copies of it: allocated on first use where the payload is at most `limit`
+// bytes.  -> the buffer, or null (payload too large, or no pinned memory to be had: the error is dropped) and the caller takes
+// its pageable path.
+constexpr size_t kPinLimit = size_t(256) << 10;
+template <class T>
+T* staging(sddp_handle* h, T*& p, size_t payload, size_t images = 1, size_t limit = kPinLimit) {
+    if (!p && payload <= limit && acquire(h, p, payload * images, true) != hipSuccess) (void)hipGetLastError();
+    return p;
+}
+
+// The device side tables of a constants struct, into caller-supplied device memory (null: the build has none): the bound barrier's
+// lower[64] | upper[64] (DevConsts::box, barrier builds) and the user rows' coefficients | weights | constants (DevConsts::xr,
+// "_x" builds).  *in_xr: which of the two copies an error came from.
+constexpr int kBoxWords = 128;
+hipError_t upload_side_tables(const sddp_model_consts& c, DevConsts& dc, double* box, double* xr, bool* in_xr = nullptr) {
+    if (box) {
+        double hb[kBoxWords];
+        for (int i = 0; i < 64; ++i) { hb[i] = c.lower[i]; hb[64 + i] = c.upper[i]; }
+        const hipError_t e = hipMemcpy(box, hb, sizeof(hb), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+        dc.box = box;
+    }
+    if (xr) {
+        double t[kXrWords];
+        fill_extra_table(c, t);
+        const hipError_t e = hipMemcpy(xr, t, sizeof(t), hipMemcpyHostToDevice);
+        if (in_xr) *in_xr = true;
+        if (e != hipSuccess) return e;
+        dc.xr = xr;
+        dc.xr_n = c.n_extra;
+    }
+    return hipSuccess;
+}
+
+// the first `words` doubles of every instance's scratch record [B][kScal] into out [B][words]; the caller has waited for the stream
+int read_scal(sddp_handle* h, double* out, int words) {
+    if (words == kScal) {      // the whole record: straight into the caller's array
+        HIP_TRY(h, hipMemcpy(out, h->scal, size_t(h->B) * kScal * sizeof(double), hipMemcpyDeviceToHost));
+        return SDDP_OK;
+    }
+    host_buf buf(size_t(h->B) * kScal * sizeof(double));
+    if (!buf.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
+    const double* sc = buf.as<double>();
+    HIP_TRY(h, hipMemcpy(buf.p, h->scal, size_t(h->B) * kScal * sizeof(double), hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->B; ++b)
+        for (int i = 0; i < words; ++i) out[size_t(b) * words + i] = sc[size_t(b) * kScal + i];
+    return SDDP_OK;
+}
 
 int check_ready(sddp_handle* h) {
     if (!h) return SDDP_ERR_ARG;
@@ -374,23 +447,13 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     int rc = validate_options(h, h->opts);
     if (rc != SDDP_OK) { create_error() = h->err; delete h; return rc; }
     h->dc = make_dev_consts(h->consts);
-    auto alloc = [&](void** p, size_t bytes) { return hipMalloc(p, bytes); };
+    try { h->owned.reserve(kOwnedReserve); } catch (...) { delete h; return fail(nullptr, SDDP_ERR_NOMEM, "out of host memory"); }
+    auto alloc = [&](auto*& p, size_t bytes) { return acquire(h, p, bytes); };
     hipError_t e = hipSuccess;
-    if (bar) {   // the bounds of the bound barrier live in device memory (DevConsts::box)
-        double hb[128];
-        for (int i = 0; i < 64; ++i) { hb[i] = h->consts.lower[i]; hb[64 + i] = h->consts.upper[i]; }
-        e = alloc((void**)&h->box_dev, sizeof(hb));
-        if (e == hipSuccess) e = hipMemcpy(h->box_dev, hb, sizeof(hb), hipMemcpyHostToDevice);
-        h->dc.box = h->box_dev;
-    }
-    if (xr) {    // the user rows' coefficients, weights and constants live in device memory (DevConsts::xr)
-        double t[kXrWords];
-        fill_extra_table(h->consts, t);
-        if (e == hipSuccess) e = alloc((void**)&h->xr_dev, sizeof(t));
-        if (e == hipSuccess) e = hipMemcpy(h->xr_dev, t, sizeof(t), hipMemcpyHostToDevice);
-        h->dc.xr = h->xr_dev;
-        h->dc.xr_n = h->consts.n_extra;
-    }
+    // the bounds of the bound barrier and the user rows' table live in device memory (DevConsts::box, DevConsts::xr)
+    if (bar) e = alloc(h->box_dev, kBoxWords * sizeof(double));
+    if (xr && e == hipSuccess) e = alloc(h->xr_dev, kXrWords * sizeof(double));
+    if (e == hipSuccess) e = upload_side_tables(h->consts, h->dc, h->box_dev, h->xr_dev);
     const size_t D = sizeof(double);
     {
         int dev = 0;
@@ -407,26 +470,26 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     const size_t W = size_t(h->wslots);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     h->own_stream = (e == hipSuccess);
-    if (e == hipSuccess) e = alloc((void**)&h->x0, size_t(batch) * d.nx * D);
-    if (e == hipSuccess) e = alloc((void**)&h->P, h->n_p() * D);
+    if (e == hipSuccess) e = alloc(h->x0, size_t(batch) * d.nx * D);
+    if (e == hipSuccess) e = alloc(h->P, h->n_p() * D);
     // xs | us | stats in ONE allocation: the results of a solve leave the device in one copy (a tick of one robot is three API
     // calls shorter)
-    if (e == hipSuccess) e = alloc((void**)&h->xs, (h->n_x() + h->n_u()) * D + size_t(batch) * sizeof(sddp_stats));
+    if (e == hipSuccess) e = alloc(h->xs, (h->n_x() + h->n_u()) * D + size_t(batch) * sizeof(sddp_stats));
     if (e == hipSuccess) { h->us = h->xs + h->n_x(); h->stats = reinterpret_cast<sddp_stats*>(h->us + h->n_u()); }
-    if (e == hipSuccess) e = alloc((void**)&h->xn, W * (N + 1) * d.nx * D);
-    if (e == hipSuccess) e = alloc((void**)&h->un, W * N * d.nu * D);
+    if (e == hipSuccess) e = alloc(h->xn, W * (N + 1) * d.nx * D);
+    if (e == hipSuccess) e = alloc(h->un, W * N * d.nu * D);
     if (!ops->uses_mw) {   // one-wave kernel: two sets of kSlots line-search candidates per slot
-        if (e == hipSuccess) e = alloc((void**)&h->xc, W * (N + 1) * d.nx * 2 * kSlots * D);
-        if (e == hipSuccess) e = alloc((void**)&h->uc, W * N * d.nu * 2 * kSlots * D);
+        if (e == hipSuccess) e = alloc(h->xc, W * (N + 1) * d.nx * 2 * kSlots * D);
+        if (e == hipSuccess) e = alloc(h->uc, W * N * d.nu * 2 * kSlots * D);
     }
-    if (e == hipSuccess) e = alloc((void**)&h->dft, W * N * d.nx * D);
-    if (e == hipSuccess) e = alloc((void**)&h->gains, W * N * d.nu * (d.nx + 1) * D);
-    if (e == hipSuccess) e = alloc((void**)&h->rec, W * (N + 1) * d.nrec * D);
-    if (e == hipSuccess) e = alloc((void**)&h->scal, size_t(batch) * kScal * D);
-    if (e == hipSuccess) e = alloc((void**)&h->qhead, sizeof(int));
-    if (e == hipSuccess) e = alloc((void**)&h->order, size_t(batch) * sizeof(int));
+    if (e == hipSuccess) e = alloc(h->dft, W * N * d.nx * D);
+    if (e == hipSuccess) e = alloc(h->gains, W * N * d.nu * (d.nx + 1) * D);
+    if (e == hipSuccess) e = alloc(h->rec, W * (N + 1) * d.nrec * D);
+    if (e == hipSuccess) e = alloc(h->scal, size_t(batch) * kScal * D);
+    if (e == hipSuccess) e = alloc(h->qhead, sizeof(int));
+    if (e == hipSuccess) e = alloc(h->order, size_t(batch) * sizeof(int));
     // hist [B] (padded to a multiple of two ints), then the slot clocks [W][2] uint64 (SolveArgs::slot_clock)
-    if (e == hipSuccess) e = alloc((void**)&h->hist, size_t((batch + 1) & ~1) * sizeof(int) + std::max<size_t>(W, 1) * 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = alloc(h->hist, size_t((batch + 1) & ~1) * sizeof(int) + std::max<size_t>(W, 1) * 2 * sizeof(unsigned long long));
     // on the handle's own stream, and complete before sddp_create returns: a null-stream hipMemset is asynchronous to the host
     // and is NOT ordered with a non-blocking stream, so it could land in the middle of the first solve (seen once as a
     // different iteration count on a 1-knot problem)
@@ -452,21 +515,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
 void sddp_destroy(sddp_handle* h) {
     if (!h) return;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* bufs[] = {h->x0, h->P, h->xs /* | us | stats */, h->xn, h->un, h->xc, h->uc, h->tick_in, h->step_buf, h->dft, h->gains, h->rec, h->scal,
-                    h->qhead, h->order, h->hist, h->qkey, h->qkey2, h->order_in, h->sort_tmp, h->policy};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->step_pin) (void)hipHostFree(h->step_pin);
-    if (h->tick_pin) (void)hipHostFree(h->tick_pin);
-    if (h->up_pin) (void)hipHostFree(h->up_pin);
-    if (h->first_pin) (void)hipHostFree(h->first_pin);
-    if (h->first_dev) (void)hipFree(h->first_dev);
-    if (h->box_dev) (void)hipFree(h->box_dev);
-    if (h->xr_dev) (void)hipFree(h->xr_dev);
-    if (h->cls) (void)hipFree(h->cls);
-    if (h->cls_stat) (void)hipFree(h->cls_stat);
-    if (h->ctab) (void)hipFree(h->ctab);
+    for (const auto& o : h->owned) free_owned(o);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -496,22 +545,16 @@ int sddp_set_stream(sddp_handle* h, void* s) {
 // stream (a copy from pageable memory would have to be waited for before the caller may reuse its buffer).  The ring is reused
 // from the start after a stream synchronisation; large uploads go directly and are waited for.
 static int upload(sddp_handle* h, void* dst, const void* src, size_t bytes) {
-    if (bytes <= kUpRing / 4) {
-        if (!h->up_pin && hipHostMalloc((void**)&h->up_pin, kUpRing, hipHostMallocDefault) != hipSuccess) {
-            h->up_pin = nullptr;
-            (void)hipGetLastError();
+    if (bytes <= kPinLimit / 4 && staging(h, h->up_pin, kPinLimit)) {
+        const size_t need = (bytes + 63) & ~size_t(63);
+        if (h->up_off + need > kPinLimit) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            h->up_off = 0;
         }
-        if (h->up_pin) {
-            const size_t need = (bytes + 63) & ~size_t(63);
-            if (h->up_off + need > kUpRing) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                h->up_off = 0;
-            }
-            std::memcpy(h->up_pin + h->up_off, src, bytes);
-            HIP_TRY(h, hipMemcpyAsync(dst, h->up_pin + h->up_off, bytes, hipMemcpyHostToDevice, h->stream));
-            h->up_off += need;
-            return SDDP_OK;
-        }
+        std::memcpy(h->up_pin + h->up_off, src, bytes);
+        HIP_TRY(h, hipMemcpyAsync(dst, h->up_pin + h->up_off, bytes, hipMemcpyHostToDevice, h->stream));
+        h->up_off += need;
+        return SDDP_OK;
     }
     HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -541,7 +584,7 @@ int sddp_set_u_warmstart(sddp_handle* h, const double* u) {
 // ---- device-pointer setters -----------------------------------------------------------------------------------------
 int sddp_load_range_device(sddp_handle* h, int first, int count, const double* d_x0, const double* d_x, const double* d_u) {
     if (!h) return SDDP_ERR_ARG;
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const size_t D = sizeof(double), nx = h->d.nx, nu = h->d.nu, N = h->N;
     if (d_x0) {
         HIP_TRY(h, hipMemcpyAsync(h->x0 + size_t(first) * nx, d_x0, size_t(count) * nx * D, hipMemcpyDeviceToDevice, h->stream));
@@ -574,7 +617,7 @@ int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, i
     int rc = check_ready(h);
     if (rc != SDDP_OK) return rc;
     if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
     rc = h->ops->launch_solve(h, a, first, count);
     if (rc == SDDP_OK) h->last_params = d_params;      // what sddp_policy_range_device differentiates against
@@ -650,12 +693,7 @@ int sddp_synchronize(sddp_handle* h) {
 static int fetch_results(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats) {
     if (!x_out || !u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     const size_t bx = h->n_x() * sizeof(double), bu = h->n_u() * sizeof(double), bs = size_t(h->B) * sizeof(sddp_stats);
-    if (!h->pinned && bx + bu + bs <= (size_t(256) << 10)) {
-        if (hipHostMalloc(&h->pinned, bx + bu + bs, hipHostMallocDefault) == hipSuccess) h->pinned_bytes = bx + bu + bs;
-        else { h->pinned = nullptr; (void)hipGetLastError(); }
-    }
-    if (h->pinned && h->pinned_bytes >= bx + bu + bs) {
-        char* st = static_cast<char*>(h->pinned);
+    if (char* st = staging(h, h->pinned, bx + bu + bs)) {
         HIP_TRY(h, hipMemcpyAsync(st, h->xs, bx + bu + (stats ? bs : 0), hipMemcpyDeviceToHost, h->stream));   // xs | us | stats are contiguous
         const int rc = sddp_synchronize(h);
         if (rc != SDDP_OK) return rc;
@@ -702,15 +740,11 @@ int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
     if (!h->have_params) return fail(h, SDDP_ERR_ARG, "sddp_set_params has not been called");
     if (!h->have_xws || !h->have_uws) return fail(h, SDDP_ERR_ARG, "sddp_advance needs a previous solution or warm start");
     if ((h->N + 1) * std::max(h->d.np, h->d.nx) > kAdvanceWords) return fail(h, SDDP_ERR_ARG, "horizon too long for sddp_advance");
-    if (!h->tick_in) HIP_TRY(h, hipMalloc((void**)&h->tick_in, size_t(h->B) * (h->d.np + h->d.nx) * sizeof(double)));
+    if (!h->tick_in) ACQUIRE_TRY(h, h->tick_in, size_t(h->B) * (h->d.np + h->d.nx) * sizeof(double));
     double* d_pl = h->tick_in;
     double* d_x0 = h->tick_in + size_t(h->B) * h->d.np;
     const size_t bp = size_t(h->B) * h->d.np * sizeof(double), bx0 = size_t(h->B) * h->d.nx * sizeof(double);
-    if (!h->tick_pin && bp + bx0 <= (size_t(256) << 10) && hipHostMalloc((void**)&h->tick_pin, 2 * (bp + bx0), hipHostMallocDefault) != hipSuccess) {
-        h->tick_pin = nullptr;
-        (void)hipGetLastError();
-    }
-    if (h->tick_pin) {   // one enqueued upload from pinned memory; two alternating images, so that the call need not wait for it
+    if (staging(h, h->tick_pin, bp + bx0, 2)) {   // one enqueued upload from pinned memory; two alternating images, so that the call need not wait for it
         if (h->tick_unsynced >= 2) {   // both images may still be read by earlier uploads: wait (a solve in between does it anyway)
             HIP_TRY(h, hipStreamSynchronize(h->stream));
             h->tick_unsynced = 0;
@@ -724,11 +758,9 @@ int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
         HIP_TRY(h, hipMemcpyAsync(d_pl, p_last, bp, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(d_x0, x0, bx0, hipMemcpyHostToDevice, h->stream));
     }
-    hipLaunchKernelGGL(advance_kernel, dim3(h->B), dim3(256), 0, h->stream, h->N, h->d.nx, h->d.nu, h->d.np, h->P, h->xs, h->us,
-                       h->x0, d_pl, d_x0);
-    HIP_TRY(h, hipGetLastError());
-    h->have_x0 = true;
-    return SDDP_OK;
+    const int rc = launch(h, advance_kernel, h->B, 256, 0, h->N, h->d.nx, h->d.nu, h->d.np, h->P, h->xs, h->us, h->x0, d_pl, d_x0);
+    if (rc == SDDP_OK) h->have_x0 = true;
+    return rc;
 }
 
 int sddp_solve_resident(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats) {
@@ -752,16 +784,17 @@ int sddp_solve_resident_first(sddp_handle* h, double* u0_out, double* x1_out, do
     if (rc != SDDP_OK) return rc;
     const int w = h->d.nu + h->d.nx + 3;
     const size_t bytes = size_t(h->B) * w * sizeof(double);
-    if (!h->first_dev) {
-        HIP_TRY(h, hipMalloc((void**)&h->first_dev, bytes));
-        if (hipHostMalloc((void**)&h->first_pin, bytes, hipHostMallocDefault) != hipSuccess) { h->first_pin = nullptr; (void)hipGetLastError(); }
+    if (!h->first_dev) {      // with its pinned host image, of any size (one copy per tick) and asked for this once
+        ACQUIRE_TRY(h, h->first_dev, bytes);
+        staging(h, h->first_pin, bytes, 1, SIZE_MAX);
     }
+    double* host = h->first_pin;
     const int grid = int(std::min<size_t>((size_t(h->B) * w + 255) / 256, 1024));
-    hipLaunchKernelGGL(first_knot_kernel, dim3(grid), dim3(256), 0, h->stream, h->N, h->B, h->d.nx, h->d.nu, h->xs, h->us, h->stats, h->first_dev);
-    HIP_TRY(h, hipGetLastError());
-    host_buf tmp(h->first_pin ? 0 : bytes);
+    rc = launch(h, first_knot_kernel, grid, 256, 0, h->N, h->B, h->d.nx, h->d.nu, h->xs, h->us, h->stats, h->first_dev);
+    if (rc != SDDP_OK) return rc;
+    host_buf tmp(host ? 0 : bytes);
     if (!tmp.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
-    double* host = h->first_pin ? h->first_pin : tmp.as<double>();
+    if (!host) host = tmp.as<double>();
     HIP_TRY(h, hipMemcpyAsync(host, h->first_dev, bytes, hipMemcpyDeviceToHost, h->stream));
     rc = sddp_synchronize(h);
     if (rc != SDDP_OK) return rc;
@@ -784,18 +817,15 @@ static int class_buffers(sddp_handle* h, int n_classes) {
         if (n_classes != h->n_cls) return fail(h, SDDP_ERR_ARG, "n_classes differs from the first call's");
         return SDDP_OK;
     }
-    int* c = nullptr;
-    unsigned long long* st = nullptr;
-    hipError_t e = hipMalloc((void**)&c, size_t(h->B) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void**)&st, size_t(n_classes) * 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(c, 0xFF, size_t(h->B) * sizeof(int), h->stream);       // -1: unlabelled
-    if (e == hipSuccess) e = hipMemsetAsync(st, 0, size_t(n_classes) * 2 * sizeof(unsigned long long), h->stream);
-    if (e != hipSuccess) {
-        if (c) (void)hipFree(c);
-        if (st) (void)hipFree(st);
+    hipError_t e = acquire(h, h->cls, size_t(h->B) * sizeof(int));
+    if (e == hipSuccess) e = acquire(h, h->cls_stat, size_t(n_classes) * 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(h->cls, 0xFF, size_t(h->B) * sizeof(int), h->stream);       // -1: unlabelled
+    if (e == hipSuccess) e = hipMemsetAsync(h->cls_stat, 0, size_t(n_classes) * 2 * sizeof(unsigned long long), h->stream);
+    if (e != hipSuccess) {      // all or nothing
+        release(h, h->cls); release(h, h->cls_stat);
         return fail(h, SDDP_ERR_HIP, std::string("class buffers: ") + hipGetErrorString(e));
     }
-    h->cls = c; h->cls_stat = st; h->n_cls = n_classes;
+    h->n_cls = n_classes;
     return SDDP_OK;
 }
 
@@ -810,7 +840,7 @@ int sddp_set_instance_classes(sddp_handle* h, const int* classes, int n_classes)
 
 int sddp_set_instance_classes_range_device(sddp_handle* h, int first, int count, const int* d_classes, int n_classes) {
     if (!h || !d_classes) return SDDP_ERR_ARG;
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     int rc = class_buffers(h, n_classes);
     if (rc != SDDP_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->cls + first, d_classes, size_t(count) * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
@@ -835,7 +865,7 @@ int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_mo
     if (h->model_id >= kUserId0 || h->bar || h->so2 || h->consts.n_extra != 0)
         return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: per-instance constants exist for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build)");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     for (int i = 0; i < count; ++i) {   // nothing that selects another build or a device side table may differ per instance
         const sddp_model_consts& c = consts[i];
         if (c.n_extra != 0) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: n_extra must be 0 in every entry");
@@ -848,13 +878,13 @@ int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_mo
     DevConsts* r = rows.as<DevConsts>();
     if (!h->ctab) {   // first call: every row starts as the handle's own constants
         DevConsts* t = nullptr;
-        if (hipMalloc((void**)&t, B * sizeof(DevConsts)) != hipSuccess) {
+        if (acquire(h, t, B * sizeof(DevConsts)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(h, SDDP_ERR_NOMEM, "sddp_set_instance_consts: out of device memory");
         }
         for (size_t b = 0; b < B; ++b) r[b] = h->dc;
         const int rc = upload(h, t, r, B * sizeof(DevConsts));
-        if (rc != SDDP_OK) { (void)hipFree(t); return rc; }
+        if (rc != SDDP_OK) { release(h, t); return rc; }
         h->ctab = t;
     }
     for (size_t i = 0; i < n; ++i) r[i] = make_dev_consts(consts[i]);
@@ -866,8 +896,7 @@ int sddp_clear_instance_consts(sddp_handle* h) {
     if (!h->ctab) return SDDP_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still read the table
     h->up_off = 0;
-    (void)hipFree(h->ctab);
-    h->ctab = nullptr;
+    release(h, h->ctab);
     return SDDP_OK;
 }
 
@@ -890,12 +919,10 @@ int sddp_pack_records_device(sddp_handle* h, int first, int count, int mode, dou
     int w = 0;
     const int rc = sddp_record_words(h, mode, &w);
     if (rc != SDDP_OK) return rc;
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const int grid = int(std::min<size_t>((size_t(count) * w + 255) / 256, 2048));
-    hipLaunchKernelGGL(pack_records_kernel, dim3(grid), dim3(256), 0, h->stream, h->N, h->d.nx, h->d.nu, first, count, mode, h->xs, h->us,
-                       h->stats, d_out, h->policy, h->policy ? h->policy_words() : 0);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch(h, pack_records_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, mode, h->xs, h->us, h->stats, d_out, h->policy,
+                  h->policy ? h->policy_words() : 0);
 }
 
 // ---- policy export ------------------------------------------------------------------------------------------------------
@@ -906,12 +933,11 @@ int sddp_enable_policy(sddp_handle* h, int knots) {
         return fail(h, SDDP_ERR_ARG, "sddp_enable_policy: no policy kernel for this build (barrier and second_order = 2 builds have none)");
     if (knots == h->policy_knots) return SDDP_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still write the old buffer
-    if (h->policy) { (void)hipFree(h->policy); h->policy = nullptr; }
+    release(h, h->policy);
     h->policy_knots = 0;
     if (knots == 0) return SDDP_OK;
     const size_t bytes = size_t(h->B) * (size_t(knots) * h->d.nu * (h->d.nx + 1) + 4) * sizeof(double);
-    if (hipMalloc((void**)&h->policy, bytes) != hipSuccess) {
-        h->policy = nullptr;
+    if (acquire(h, h->policy, bytes) != hipSuccess) {
         (void)hipGetLastError();
         return fail(h, SDDP_ERR_NOMEM, "sddp_enable_policy: out of device memory");
     }
@@ -932,7 +958,7 @@ int sddp_policy_range_device(sddp_handle* h, int first, int count) {
     if (!h) return SDDP_ERR_ARG;
     if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_range_device: no solve has run on this handle");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, h->last_params);
     return h->ops->launch_policy(h, a, first, count, h->policy, h->policy_knots);
 }
@@ -941,7 +967,7 @@ int sddp_fetch_policy(sddp_handle* h, int first, int count, double* out) {
     if (!h) return SDDP_ERR_ARG;
     if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const size_t w = size_t(h->policy_words());
     HIP_TRY(h, hipMemcpyAsync(out, h->policy + size_t(first) * w, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     return sddp_synchronize(h);
@@ -951,12 +977,10 @@ int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double*
     if (!h) return SDDP_ERR_ARG;
     if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!d_x_meas || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const int grid = int(std::min<size_t>((size_t(count) * h->d.nu + 255) / 256, 2048));
-    hipLaunchKernelGGL(apply_policy_kernel, dim3(grid), dim3(256), 0, h->stream, h->N, h->d.nx, h->d.nu, first, count, h->xs, h->us, h->policy,
-                       h->policy_words(), d_x_meas, d_u_out);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch(h, apply_policy_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, h->xs, h->us, h->policy, h->policy_words(),
+                  d_x_meas, d_u_out);
 }
 
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {
@@ -964,15 +988,10 @@ int sddp_model_step(sddp_handle* h, const double* x, const double* u, const doub
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");
     const size_t B = size_t(h->B), nx = h->d.nx, nu = h->d.nu, np = h->d.np, D = sizeof(double);
     const size_t words = B * (2 * nx + nu + np);
-    if (!h->step_buf) HIP_TRY(h, hipMalloc((void**)&h->step_buf, words * D));
-    if (!h->step_pin && words * D <= (size_t(256) << 10) && hipHostMalloc((void**)&h->step_pin, words * D, hipHostMallocDefault) != hipSuccess) {
-        h->step_pin = nullptr;
-        (void)hipGetLastError();
-    }
+    if (!h->step_buf) ACQUIRE_TRY(h, h->step_buf, words * D);
     double *dx = h->step_buf, *du = dx + B * nx, *dp = du + B * nu, *dxn = dp + B * np;
     int rc = SDDP_OK;
-    if (h->step_pin) {   // x | u | p packed in pinned memory: one enqueued upload, one enqueued download, one wait
-        double* hp = h->step_pin;
+    if (double* hp = staging(h, h->step_pin, words * D)) {   // x | u | p packed in pinned memory: one enqueued upload and download, one wait
         std::memcpy(hp, x, B * nx * D);
         std::memcpy(hp + B * nx, u, B * nu * D);
         std::memcpy(hp + B * (nx + nu), p, B * np * D);
@@ -1071,32 +1090,27 @@ int sddp_eval_knots(int model_id, const sddp_model_consts* consts, int N, int nk
     // every device buffer of the call in one table, freed on every return path
     enum { B_XR, B_BOX, B_K, B_X, B_U, B_P, B_REC, B_F, B_FF, B_H, B_G, B_L, B_N };
     void* buf[B_N] = {};
-    const size_t bytes[B_N] = {xr ? kXrWords * D : 0, bar ? 128 * D : 0, nk * sizeof(int), size_t(nk) * d.nx * D, size_t(nk) * d.nu * D, size_t(nk) * d.np * D,
+    const size_t bytes[B_N] = {xr ? kXrWords * D : 0, bar ? kBoxWords * D : 0, nk * sizeof(int), size_t(nk) * d.nx * D, size_t(nk) * d.nu * D, size_t(nk) * d.np * D,
                                size_t(nk) * d.nrec * D, size_t(nk) * d.nx * D, size_t(nk) * d.nx * nz * D, size_t(nk) * nz * nz * D,
                                size_t(nk) * nz * D, size_t(nk) * D};
-    auto release = [&]() { for (void* b : buf) if (b) (void)hipFree(b); };
-#define TRY0(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return fail(nullptr, SDDP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    auto free_all = [&]() { for (void* b : buf) if (b) (void)hipFree(b); };
+#define TRY0(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { free_all(); return fail(nullptr, SDDP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
     for (int i = 0; i < B_N; ++i)
         if (bytes[i]) TRY0(hipMalloc(&buf[i], bytes[i]));
-    if (bar) {
-        double hb[128];
-        for (int i = 0; i < 64; ++i) { hb[i] = cc.lower[i]; hb[64 + i] = cc.upper[i]; }
-        TRY0(hipMemcpy(buf[B_BOX], hb, sizeof(hb), hipMemcpyHostToDevice));
-        dc.box = static_cast<double*>(buf[B_BOX]);
-    }
-    if (xr) {
-        double t[kXrWords];
-        fill_extra_table(cc, t);
-        TRY0(hipMemcpy(buf[B_XR], t, sizeof(t), hipMemcpyHostToDevice));
-        dc.xr = static_cast<double*>(buf[B_XR]);
-        dc.xr_n = cc.n_extra;
+    auto dd = [&](int i) { return static_cast<double*>(buf[i]); };
+    bool in_xr = false;
+    // The two strings below are kept verbatim on purpose: they are the messages this call gave when it made the two copies itself
+    // (hb, t: the host images that upload_side_tables now builds).  Do not "correct" them.
+    if (hipError_t e = upload_side_tables(cc, dc, dd(B_BOX), dd(B_XR), &in_xr); e != hipSuccess) {
+        free_all();
+        return fail(nullptr, SDDP_ERR_HIP, std::string(in_xr ? "hipMemcpy(buf[B_XR], t, sizeof(t), hipMemcpyHostToDevice): "
+                                                             : "hipMemcpy(buf[B_BOX], hb, sizeof(hb), hipMemcpyHostToDevice): ") + hipGetErrorString(e));
     }
     TRY0(hipMemcpy(buf[B_K], k, bytes[B_K], hipMemcpyHostToDevice));
     TRY0(hipMemcpy(buf[B_X], x, bytes[B_X], hipMemcpyHostToDevice));
     TRY0(hipMemcpy(buf[B_U], u, bytes[B_U], hipMemcpyHostToDevice));
     TRY0(hipMemcpy(buf[B_P], p, bytes[B_P], hipMemcpyHostToDevice));
     TRY0(hipMemset(buf[B_REC], 0, bytes[B_REC]));
-    auto dd = [&](int i) { return static_cast<double*>(buf[i]); };
     ops->launch_eval_knots(dc, N, nk, static_cast<const int*>(buf[B_K]), dd(B_X), dd(B_U), dd(B_P), dd(B_REC), dd(B_F), dd(B_FF), dd(B_H),
                            dd(B_G), dd(B_L));
     TRY0(hipGetLastError());
@@ -1107,7 +1121,7 @@ int sddp_eval_knots(int model_id, const sddp_model_consts* consts, int N, int nk
     if (g_out) TRY0(hipMemcpy(g_out, buf[B_G], bytes[B_G], hipMemcpyDeviceToHost));
     if (L_out) TRY0(hipMemcpy(L_out, buf[B_L], bytes[B_L], hipMemcpyDeviceToHost));
 #undef TRY0
-    release();
+    free_all();
     return SDDP_OK;
 }
 
@@ -1124,15 +1138,7 @@ int sddp_backward(sddp_handle* h, const double* params, double mu, double* gains
     h->gains_by_instance = true;
     if (gains_out) HIP_TRY(h, hipMemcpyAsync(gains_out, h->gains, h->n_g() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (scal_out) {
-        host_buf buf(size_t(h->B) * kScal * sizeof(double));
-        if (!buf.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
-        const double* sc = buf.as<double>();
-        HIP_TRY(h, hipMemcpy(buf.p, h->scal, size_t(h->B) * kScal * sizeof(double), hipMemcpyDeviceToHost));
-        for (int b = 0; b < h->B; ++b)
-            for (int i = 0; i < 8; ++i) scal_out[size_t(b) * 8 + i] = sc[size_t(b) * kScal + i];
-    }
-    return SDDP_OK;
+    return scal_out ? read_scal(h, scal_out, 8) : SDDP_OK;
 }
 
 int sddp_forward(sddp_handle* h, const double* params, double alpha, double* x_out, double* u_out, double* cost_out) {
@@ -1148,22 +1154,14 @@ int sddp_forward(sddp_handle* h, const double* params, double alpha, double* x_o
     if (x_out) HIP_TRY(h, hipMemcpyAsync(x_out, h->xn, h->n_x() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (u_out) HIP_TRY(h, hipMemcpyAsync(u_out, h->un, h->n_u() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (cost_out) {
-        host_buf buf(size_t(h->B) * kScal * sizeof(double));
-        if (!buf.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
-        const double* sc = buf.as<double>();
-        HIP_TRY(h, hipMemcpy(buf.p, h->scal, size_t(h->B) * kScal * sizeof(double), hipMemcpyDeviceToHost));
-        for (int b = 0; b < h->B; ++b) cost_out[b] = sc[size_t(b) * kScal];
-    }
-    return SDDP_OK;
+    return cost_out ? read_scal(h, cost_out, 1) : SDDP_OK;
 }
 
 // diagnostic (not part of include/sddp.h): raw [B][16] scratch record; holds per-phase cycle sums in a -DSDDP_STAMPS build
 int sddp_debug_read_scal(sddp_handle* h, double* out) {
     if (!h || !out) return SDDP_ERR_ARG;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(out, h->scal, size_t(h->B) * kScal * sizeof(double), hipMemcpyDeviceToHost));
-    return SDDP_OK;
+    return read_scal(h, out, kScal);
 }
 
 }  // extern "C"

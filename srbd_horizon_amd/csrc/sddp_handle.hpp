@@ -67,8 +67,7 @@ struct sddp_handle {
     char* tick_pin = nullptr;       // two pinned images of tick_in (small batches)
     int tick_flip = 0, tick_unsynced = 0;
     double* step_pin = nullptr;     // pinned host image of step_buf (small batches)
-    void* pinned = nullptr;         // small batches: pinned host staging of x | u | stats, so the three result copies are truly asynchronous
-    size_t pinned_bytes = 0;
+    char* pinned = nullptr;         // small batches: pinned host staging of x | u | stats, so the three result copies are truly asynchronous
     // work queue: the solve launch runs on `slots` resident workgroups that pull instances from a queue
     int wslots = 0;                 // slots the work buffers (xn un xc uc dft gains rec) are allocated for = min(B, resident capacity)
     int cus = 0;
@@ -87,8 +86,11 @@ struct sddp_handle {
     int n_cls = 0;
     unsigned long long* cls_stat = nullptr;   // [n_cls][2]
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
-    struct KInfo { const void* fn = nullptr; int slots = 0; };
-    KInfo kinfo[4];                 // per kernel build (and its `_h` twin): dynamic-LDS attribute set, resident workgroups on this device
+    // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward and their `_h`
+    // twins), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.  An entry is
+    // made by the first launch of the kernel and kept for the handle's life (sddp_launch.hpp kernel_slots)
+    struct KInfo { const void* fn; int slots; };
+    std::vector<KInfo> kernels;
     // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; non-null = active, and every kernel of the
     // handle is launched as its `_h` twin, which reads instance b's row instead of the kernel-argument copy of `dc`
     sddp::DevConsts* ctab = nullptr;   // [B]
@@ -100,14 +102,15 @@ struct sddp_handle {
     double* xr_dev = nullptr;       // user rows: coefficients | weights | constants (DevConsts::xr, "_x" builds)
     double* first_dev = nullptr;    // [B][nu + nx + 3] packed first knots of sddp_solve_resident_first, and its pinned host image
     double* first_pin = nullptr;
-    // policy export (sddp_enable_policy): [B][policy_knots * nu * (nx + 1) + 4], the parameter tensor of the last solve launch,
-    // resident workgroups of the policy kernel on this device (0: not asked yet) and that kernel
+    // policy export (sddp_enable_policy): [B][policy_knots * nu * (nx + 1) + 4], and the parameter tensor of the last solve launch
     double* policy = nullptr;
-    int policy_knots = 0, policy_slots = 0;
+    int policy_knots = 0;
     const double* last_params = nullptr;
-    const void* policy_kernel = nullptr;
     char* up_pin = nullptr;         // pinned ring for small host->device uploads of the setters (no wait per call)
     size_t up_off = 0;
+    // every device and pinned allocation above, registered where it is made (sddp_api.hip acquire / release): what sddp_destroy frees
+    struct Owned { void* p; bool pinned; };
+    std::vector<Owned> owned;
 
     size_t n_x() const { return size_t(B) * (N + 1) * d.nx; }
     size_t n_u() const { return size_t(B) * N * d.nu; }
@@ -132,6 +135,14 @@ inline int fail(sddp_handle* h, int code, const std::string& msg) {
         if (e_ != hipSuccess)                                                                          \
             return sddp::fail(h, SDDP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
     } while (0)
+
+// one kernel launch on the handle's stream
+template <class Fn, class... A>
+int launch(sddp_handle* h, Fn kern, int grid, int threads, size_t lds, const A&... args) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, args...);
+    HIP_TRY(h, hipGetLastError());
+    return SDDP_OK;
+}
 
 // the cold-queue buffers of a handle, all or nothing (a partial failure leaves every pointer null)
 int alloc_cold_queue(sddp_handle* h);

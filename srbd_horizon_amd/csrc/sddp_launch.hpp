@@ -2,6 +2,7 @@
 // Included by sddp_inst.hip only: one translation unit per model build.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "sddp_handle.hpp"
 #include "sddp_kernels.hpp"
@@ -24,73 +25,98 @@ constexpr bool has_w2() {
     if constexpr (use_mw<M>()) return 2 * LdsMW<M>::BYTES <= size_t(160) * 1024; else return true;
 }
 
-// only the kernel a model actually uses is instantiated
-using KernelFn = void (*)(SolveArgs);
-template <class M> KernelFn pick_solve(int waves_per_simd) {
-    if constexpr (use_mw<M>()) {
-        if constexpr (has_w2<M>()) return waves_per_simd >= 2 ? solve_kernel_mw_w2<M> : solve_kernel_mw<M>;
-        else return solve_kernel_mw<M>;
-    } else return waves_per_simd >= 2 ? solve_kernel_w2<M> : solve_kernel<M>;
-}
-template <class M> KernelFn pick_backward() { if constexpr (use_mw<M>()) return backward_kernel_mw<M>; else return backward_kernel<M>; }
-template <class M> KernelFn pick_forward() { if constexpr (use_mw<M>()) return forward_kernel_mw<M>; else return forward_kernel<M>; }
+template <class M>
+constexpr int threads_of() { return use_mw<M>() ? kThreadsMW : kWave; }
 
 // Heterogeneous fleets (sddp_set_instance_consts): the plain builds carry an `_h` twin of every kernel, which reads instance b's
 // row of the handle's constants table (sddp_kernels.hpp with_row).  sddp_api.hip refuses the table on every other build, so
 // h->ctab != nullptr implies has_hetero<M>().
 template <class M>
 constexpr bool has_hetero() { return !M::BAR && !M::SO2 && M::NXR == 0; }
-using KernelFnH = void (*)(SolveArgs, const DevConsts*);
-template <class M> KernelFnH pick_solve_h(int waves_per_simd) {
-    if constexpr (use_mw<M>()) {
-        if constexpr (has_w2<M>()) return waves_per_simd >= 2 ? solve_kernel_mw_w2_h<M> : solve_kernel_mw_h<M>;
-        else return solve_kernel_mw_h<M>;
-    } else return waves_per_simd >= 2 ? solve_kernel_w2_h<M> : solve_kernel_h<M>;
+// f(std::bool_constant<HET>): the HET instantiation of a launcher, HET = the handle's table is active.  A build without `_h` twins
+// never instantiates f(true_type), and so none of their kernels.
+template <class M, class F>
+int with_table(sddp_handle* h, F f) {
+    if constexpr (has_hetero<M>()) {
+        if (h->ctab) return f(std::true_type{});
+    }
+    return f(std::false_type{});
 }
-template <class M> KernelFnH pick_backward_h() { if constexpr (use_mw<M>()) return backward_kernel_mw_h<M>; else return backward_kernel_h<M>; }
-template <class M> KernelFnH pick_forward_h() { if constexpr (use_mw<M>()) return forward_kernel_mw_h<M>; else return forward_kernel_h<M>; }
+// the constants argument of the kernels that take it first: the table (`_h` twins) or the handle's own constants
+template <bool HET>
+auto consts_arg(sddp_handle* h) { if constexpr (HET) return (const DevConsts*)h->ctab; else return h->dc; }
+// launch of a kernel whose `_h` twin takes the table behind the common arguments
+template <bool HET, class Fn, class... A>
+int launch_model(sddp_handle* h, Fn kern, int grid, int threads, size_t lds, const A&... args) {
+    if constexpr (HET) return launch(h, kern, grid, threads, lds, args..., (const DevConsts*)h->ctab);
+    else return launch(h, kern, grid, threads, lds, args...);
+}
 
-// resident workgroups of `kern` on this device (the queue's slot count) and its dynamic-LDS attribute, once per handle and build
+// only the kernel a model actually uses is instantiated
+using KernelFn = void (*)(SolveArgs);
+using KernelFnH = void (*)(SolveArgs, const DevConsts*);
+template <bool HET> using KernelOf = std::conditional_t<HET, KernelFnH, KernelFn>;
+template <class M, bool HET> KernelOf<HET> pick_solve(int waves_per_simd) {
+    [[maybe_unused]] const bool w2 = waves_per_simd >= 2;
+    if constexpr (HET) {
+        if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2_h<M> : solve_kernel_h<M>;
+        else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2_h<M> : solve_kernel_mw_h<M>;
+        else return solve_kernel_mw_h<M>;
+    } else {
+        if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M> : solve_kernel<M>;
+        else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M> : solve_kernel_mw<M>;
+        else return solve_kernel_mw<M>;
+    }
+}
+template <class M, bool HET> KernelOf<HET> pick_backward() {
+    if constexpr (HET) { if constexpr (use_mw<M>()) return backward_kernel_mw_h<M>; else return backward_kernel_h<M>; }
+    else { if constexpr (use_mw<M>()) return backward_kernel_mw<M>; else return backward_kernel<M>; }
+}
+template <class M, bool HET> KernelOf<HET> pick_forward() {
+    if constexpr (HET) { if constexpr (use_mw<M>()) return forward_kernel_mw_h<M>; else return forward_kernel_h<M>; }
+    else { if constexpr (use_mw<M>()) return forward_kernel_mw<M>; else return forward_kernel<M>; }
+}
+template <class M, bool HET> auto pick_policy() {
+    if constexpr (HET) { if constexpr (use_mw<M>()) return policy_kernel_mw_h<M>; else return policy_kernel_h<M>; }
+    else { if constexpr (use_mw<M>()) return policy_kernel_mw<M>; else return policy_kernel<M>; }
+}
+
+// The handle's entry for `kern` (sddp_handle::kernels), made the first time the handle meets the kernel: its dynamic-LDS attribute
+// is set, and its resident workgroups on this device (the queue's slot count) are what the occupancy query gives per CU, at most
+// `cap` (0: no cap) and within [1, 32], times the CUs.  slots may be null: a launch that needs the attribute only.
 template <class M, class Fn>
-int kernel_slots(sddp_handle* h, Fn kern, int wps, int* slots) {
-    constexpr bool MW = use_mw<M>();
-    constexpr size_t lds = lds_bytes<M>();
-    constexpr int threads = MW ? kThreadsMW : kWave;
-    for (auto& k : h->kinfo)
-        if (k.fn == reinterpret_cast<const void*>(kern)) { *slots = k.slots; return SDDP_OK; }
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+int kernel_slots(sddp_handle* h, Fn kern, int cap, int* slots) {
+    const void* fn = reinterpret_cast<const void*>(kern);
+    for (const auto& k : h->kernels)
+        if (k.fn == fn) { if (slots) *slots = k.slots; return SDDP_OK; }
+    try { h->kernels.reserve(h->kernels.size() + 1); } catch (...) { return fail(h, SDDP_ERR_NOMEM, "out of host memory"); }
+    HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<M>()));
     int per_cu = 0;
-    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
-    if (!MW) per_cu = std::min(per_cu, 4 * (wps >= 2 ? 2 : 1));   // the two builds: 1 or 2 wavefronts per SIMD
+    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads_of<M>(), lds_bytes<M>()));
+    if (cap > 0) per_cu = std::min(per_cu, cap);
     per_cu = std::max(1, std::min(per_cu, 32));
-    constexpr int nk = int(sizeof(h->kinfo) / sizeof(h->kinfo[0]));      // two builds and their `_h` twins: never more kernels than entries
-    int free_k = 0;
-    while (free_k < nk - 1 && h->kinfo[free_k].fn) ++free_k;
-    auto& k = h->kinfo[free_k];
-    k.fn = reinterpret_cast<const void*>(kern);
-    k.slots = per_cu * std::max(1, h->cus);
-    *slots = k.slots;
+    h->kernels.push_back({fn, per_cu * std::max(1, h->cus)});
+    if (slots) *slots = h->kernels.back().slots;
     return SDDP_OK;
 }
+// the one-wave solve kernel's two builds run 1 or 2 wavefronts per SIMD; the four-wave kernels take what fits
+template <class M>
+constexpr int solve_cap(int wps) { return use_mw<M>() ? 0 : 4 * (wps >= 2 ? 2 : 1); }
 
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
 template <class M, bool HET>
 int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
-    constexpr bool MW = use_mw<M>();
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    auto pick = [](int w) { if constexpr (HET) return pick_solve_h<M>(w); else return pick_solve<M>(w); };
-    auto kern = pick(wps);
-    constexpr size_t lds = lds_bytes<M>();
-    constexpr int threads = MW ? kThreadsMW : kWave;
+    auto kern = pick_solve<M, HET>(wps);
     int slots = 0;
-    int rc = kernel_slots<M>(h, kern, wps, &slots);
+    int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
     if (rc != SDDP_OK) return rc;
-    if constexpr (MW) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
+    if constexpr (use_mw<M>()) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
         if (wps >= 2) {
-            auto k1 = pick(1);
+            auto k1 = pick_solve<M, HET>(1);
             int s1 = 0;
-            rc = kernel_slots<M>(h, k1, 1, &s1);
+            rc = kernel_slots<M>(h, k1, solve_cap<M>(1), &s1);
             if (rc != SDDP_OK) return rc;
             if (s1 >= slots) { kern = k1; slots = s1; wps = 1; }
         }
@@ -120,13 +146,9 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
         } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
             rc = alloc_cold_queue(h);
             if (rc != SDDP_OK) return rc;
-            if constexpr (HET)
-                hipLaunchKernelGGL(queue_cost_key_kernel_h<M>, dim3(count), dim3(kWave), 0, h->stream, (const DevConsts*)h->ctab, a.N, first, count,
-                                   a.x0, a.P, a.xs, a.us, h->qkey, h->order_in);
-            else
-                hipLaunchKernelGGL(queue_cost_key_kernel<M>, dim3(count), dim3(kWave), 0, h->stream, a.c, a.N, first, count, a.x0, a.P, a.xs,
-                                   a.us, h->qkey, h->order_in);
-            HIP_TRY(h, hipGetLastError());
+            auto key = [] { if constexpr (HET) return queue_cost_key_kernel_h<M>; else return queue_cost_key_kernel<M>; }();
+            rc = launch(h, key, count, kWave, 0, consts_arg<HET>(h), a.N, first, count, a.x0, a.P, a.xs, a.us, h->qkey, h->order_in);
+            if (rc != SDDP_OK) return rc;
             if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
                 rc = launch_class_keys(h, count);
                 if (rc != SDDP_OK) return rc;
@@ -138,12 +160,11 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
     h->last_grid = grid; h->last_queued = count > grid ? count : 0;
     h->last_build = wps;
     h->last_kernel = reinterpret_cast<const void*>(kern);
-    h->last_lds = int(lds);
+    h->last_lds = int(lds_bytes<M>());
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    if constexpr (HET) hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, (const DevConsts*)h->ctab);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
+    rc = launch_model<HET>(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a);
+    if (rc != SDDP_OK) return rc;
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
         rc = launch_class_update(h, first, count);
         if (rc != SDDP_OK) return rc;
@@ -156,115 +177,66 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
 }
 template <class M>
 int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
-    if constexpr (has_hetero<M>()) {
-        if (h->ctab) return launch_solve_on<M, true>(h, a, first, count);
-    }
-    return launch_solve_on<M, false>(h, a, first, count);
+    return with_table<M>(h, [&](auto het) { return launch_solve_on<M, decltype(het)::value>(h, a, first, count); });
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
 int max_slots(sddp_handle* h, int* slots) {
-    if constexpr (!has_w2<M>()) return kernel_slots<M>(h, pick_solve<M>(1), 1, slots);
-    else {
-        int s1 = 0, s2 = 0;
-        int rc = kernel_slots<M>(h, pick_solve<M>(1), 1, &s1);
-        if (rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M>(2), 2, &s2);
-        *slots = std::max(s1, s2);
-        return rc;
-    }
+    int s1 = 0, s2 = 0;
+    int rc = kernel_slots<M>(h, pick_solve<M, false>(1), solve_cap<M>(1), &s1);
+    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M, false>(2), solve_cap<M>(2), &s2);
+    *slots = std::max(s1, s2);
+    return rc;
+}
+// the phase-level entry points: one backward sweep / one forward rollout of every instance, instance b on workgroup b.  They go
+// through kernel_slots for the dynamic-LDS attribute alone: the grid is h->B, the slot count of the entry is not read
+template <class M, class Pick>
+int launch_phase(sddp_handle* h, const SolveArgs& a, Pick pick) {
+    return with_table<M>(h, [&](auto het) {
+        auto kern = pick(het);
+        const int rc = kernel_slots<M>(h, kern, 0, nullptr);
+        if (rc != SDDP_OK) return rc;
+        return launch_model<decltype(het)::value>(h, kern, h->B, threads_of<M>(), lds_bytes<M>(), a);
+    });
 }
 template <class M>
 int launch_backward(sddp_handle* h, const SolveArgs& a) {
-    constexpr bool MW = use_mw<M>();
-    constexpr size_t lds = lds_bytes<M>();
-    if constexpr (has_hetero<M>()) {
-        if (h->ctab) {
-            KernelFnH kh = pick_backward_h<M>();
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kh, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a, (const DevConsts*)h->ctab);
-            HIP_TRY(h, hipGetLastError());
-            return SDDP_OK;
-        }
-    }
-    KernelFn kern = pick_backward<M>();
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch_phase<M>(h, a, [](auto het) { return pick_backward<M, decltype(het)::value>(); });
 }
 template <class M>
 int launch_forward(sddp_handle* h, const SolveArgs& a) {
-    constexpr bool MW = use_mw<M>();
-    constexpr size_t lds = lds_bytes<M>();
-    if constexpr (has_hetero<M>()) {
-        if (h->ctab) {
-            KernelFnH kh = pick_forward_h<M>();
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kh, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a, (const DevConsts*)h->ctab);
-            HIP_TRY(h, hipGetLastError());
-            return SDDP_OK;
-        }
-    }
-    KernelFn kern = pick_forward<M>();
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(h->B), dim3(MW ? kThreadsMW : kWave), lds, h->stream, a);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return launch_phase<M>(h, a, [](auto het) { return pick_forward<M, decltype(het)::value>(); });
 }
 
 // policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
-// policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel; the work buffers dft / rec are the solve's,
-// per slot.  Plain builds only (no barrier, no second_order = 2): make_ops leaves the entry null elsewhere.
-template <class M, bool HET>
-int launch_policy_on(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
-    constexpr bool MW = use_mw<M>();
-    constexpr size_t lds = lds_bytes<M>();
-    constexpr int threads = MW ? kThreadsMW : kWave;
-    auto kern = []() {
-        if constexpr (HET) { if constexpr (MW) return policy_kernel_mw_h<M>; else return policy_kernel_h<M>; }
-        else { if constexpr (MW) return policy_kernel_mw<M>; else return policy_kernel<M>; }
-    }();
-    if (h->policy_slots == 0 || h->policy_kernel != reinterpret_cast<const void*>(kern)) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
-        if (!MW) per_cu = std::min(per_cu, 8);
-        h->policy_slots = std::max(1, std::min(per_cu, 32)) * std::max(1, h->cus);
-    }
-    int grid = std::min(count, std::min(h->policy_slots, h->wslots));
-    if (h->opts.max_slots > 0) grid = std::min(grid, h->opts.max_slots);
-    a.first = first; a.count = count; a.order = nullptr; a.qhead = nullptr;
-    if (count > grid) {
-        HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
-        a.qhead = h->qhead;
-    }
-    if constexpr (HET) hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep, (const DevConsts*)h->ctab);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, h->stream, a, pol, keep);
-    HIP_TRY(h, hipGetLastError());
-    h->policy_kernel = reinterpret_cast<const void*>(kern);
-    return SDDP_OK;
-}
+// policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel (the one-wave kernel: at most 8 per CU); the work
+// buffers dft / rec are the solve's, per slot.  Plain builds only (no barrier, no second_order = 2): make_ops leaves the entry null
+// elsewhere.
 template <class M>
 int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
-    if constexpr (has_hetero<M>()) {
-        if (h->ctab) return launch_policy_on<M, true>(h, a, first, count, pol, keep);
-    }
-    return launch_policy_on<M, false>(h, a, first, count, pol, keep);
+    return with_table<M>(h, [&](auto het) {
+        auto kern = pick_policy<M, decltype(het)::value>();
+        int slots = 0;
+        int rc = kernel_slots<M>(h, kern, use_mw<M>() ? 0 : 8, &slots);
+        if (rc != SDDP_OK) return rc;
+        int grid = std::min(count, std::min(slots, h->wslots));
+        if (h->opts.max_slots > 0) grid = std::min(grid, h->opts.max_slots);
+        a.first = first; a.count = count; a.order = nullptr; a.qhead = nullptr;
+        if (count > grid) {
+            HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
+            a.qhead = h->qhead;
+        }
+        return launch_model<decltype(het)::value>(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep);
+    });
 }
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
-    if constexpr (has_hetero<M>()) {
-        if (h->ctab) {
-            hipLaunchKernelGGL(model_step_kernel_h<M>, dim3((h->B + kWave - 1) / kWave), dim3(kWave), 0, h->stream, (const DevConsts*)h->ctab, h->B, k,
-                               dx, du, dp, dxn);
-            HIP_TRY(h, hipGetLastError());
-            return SDDP_OK;
-        }
-    }
-    hipLaunchKernelGGL(model_step_kernel<M>, dim3((h->B + kWave - 1) / kWave), dim3(kWave), 0, h->stream, h->dc, h->B, k, dx, du, dp, dxn);
-    HIP_TRY(h, hipGetLastError());
-    return SDDP_OK;
+    return with_table<M>(h, [&](auto het) {
+        constexpr bool HET = decltype(het)::value;
+        auto kern = [] { if constexpr (HET) return model_step_kernel_h<M>; else return model_step_kernel<M>; }();
+        return launch(h, kern, (h->B + kWave - 1) / kWave, kWave, 0, consts_arg<HET>(h), h->B, k, dx, du, dp, dxn);
+    });
 }
 
 template <class M>
