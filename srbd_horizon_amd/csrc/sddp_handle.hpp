@@ -86,13 +86,13 @@ struct sddp_handle {
     int n_cls = 0;
     unsigned long long* cls_stat = nullptr;   // [n_cls][2]
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
-    // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward and their `_h`
-    // twins), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.  An entry is
-    // made by the first launch of the kernel and kept for the handle's life (sddp_launch.hpp kernel_slots)
+    // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward, without and with
+    // the constants table), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.
+    // An entry is made by the first launch of the kernel and kept for the handle's life (sddp_launch.hpp kernel_slots)
     struct KInfo { const void* fn; int slots; };
     std::vector<KInfo> kernels;
     // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; non-null = active, and every kernel of the
-    // handle is launched as its `_h` twin, which reads instance b's row instead of the kernel-argument copy of `dc`
+    // handle is launched in its table instantiation, which reads instance b's row instead of the kernel-argument copy of `dc`
     sddp::DevConsts* ctab = nullptr;   // [B]
     int last_grid = 0, last_queued = 0;
     int last_build = 0;             // waves_per_simd of the kernel build the last solve launch ran (sddp_kernel_info)

@@ -19,6 +19,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "sddp_models.hpp"
 
 namespace sddp {
@@ -931,50 +933,17 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
     wave_sync();
 }
 
-// The launch as a work queue: one resident wavefront (slot) per workgroup, each solving instances until the queue is empty.
-// No workgroup ever waits for another one, so any grid size terminates; a slot's work buffers are private to its wavefront
-// (its own loads and stores are seen in program order), the per-instance inputs were written before the launch.
-// Every instance starts from freshly built LDS tables, so a result does not depend on which slot solved it or on what that
-// slot solved before: bit-identical to one launch per instance.
-template <class M>
-__device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s) {
-    const int slot = blockIdx.x;
-    const bool queued = A.qhead != nullptr;
-    int i = slot;                                      // no queue: workgroup w solves instance first + w
-    if (threadIdx.x == 0) A.slot_clock(slot)[0] = wall_clock64();
-    if (queued) {
-        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
-        i = __builtin_amdgcn_readfirstlane(i);
-    }
-    while (i < A.count) {                              // every wavefront reaches the exit: the head only grows
-        const int b = (queued && A.order) ? A.order[i] : A.first + i;
-        solve_instance<M>(A, s, b, slot);              // one call site: the body is compiled once
-        if (!queued) break;
-        if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
-        i = __builtin_amdgcn_readfirstlane(i);
-    }
-    if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
-}
-
-// two builds of the same body: the register allocation is the only difference (sddp_options.waves_per_simd)
-template <class M>
-__global__ __launch_bounds__(kWave) void solve_kernel(SolveArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M>(A, s);
-}
-template <class M>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M>(A, s);
-}
-
 // -----------------------------------------------------------------------------------------------------------------
-// Heterogeneous fleets (sddp_set_instance_consts): the `_h` twin of a kernel takes, beside the arguments of the kernel it stands
-// for, a table with one DevConsts row per instance and runs the SAME per-instance body on a copy of the arguments whose `c` is
-// instance b's row.  The body rebuilds everything it derives from `c` (LDS tables, constant blocks) at the start of every
-// instance, so nothing of one robot outlives its solve.  b is wave-uniform (blockIdx, readfirstlane, the LDS queue word) and the
-// table is read-only for the whole launch: the row is read through the constant address space, i.e. by scalar loads into the
-// registers the kernel-argument copy occupies in the homogeneous kernels.  Those kernels are not touched.
+// Heterogeneous fleets (sddp_set_instance_consts): a kernel that runs the model is ONE template with two instantiations.
+// `Tab...` is empty (the homogeneous kernel: its argument list is the one it always had, the constants are the kernel-argument
+// copy `A.c` / `c`) or holds one `const DevConsts*`, a table with one DevConsts row per instance, passed behind the common
+// arguments; the per-instance body then runs on a copy of the arguments whose `c` is instance b's row.  The body rebuilds
+// everything it derives from `c` (LDS tables, constant blocks) at the start of every instance, so nothing of one robot outlives
+// its solve.  b is wave-uniform (blockIdx, readfirstlane, the LDS queue word) and the table is read-only for the whole launch:
+// the row is read through the constant address space, i.e. by scalar loads into the registers the kernel-argument copy occupies
+// in the homogeneous instantiation.  The overloads of consts_of / args_of / index_of are all that tells the instantiations apart:
+// the ones without a table hand their argument back, so the homogeneous kernel contains nothing it did not contain before there
+// was a table.  (The policy kernels are the exception: policy_kernel_h below.)
 // -----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ DevConsts row_of(const DevConsts* __restrict__ ctab, const int b) {
     static_assert(sizeof(DevConsts) % sizeof(unsigned long long) == 0, "a row is copied in 64-bit words");
@@ -988,41 +957,57 @@ __device__ __forceinline__ DevConsts row_of(const DevConsts* __restrict__ ctab, 
     __builtin_memcpy(&c, w, sizeof(c));
     return c;
 }
-__device__ __forceinline__ SolveArgs with_row(const SolveArgs& A, const DevConsts* __restrict__ ctab, const int b) {
+// the constants / the arguments of instance b: the kernel's own, or a copy whose `c` is row b of the table
+__device__ __forceinline__ const DevConsts& consts_of(const DevConsts& c, const int) { return c; }
+__device__ __forceinline__ DevConsts consts_of(const DevConsts* __restrict__ ctab, const int b) { return row_of(ctab, b); }
+__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int) { return A; }
+__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const DevConsts* __restrict__ ctab) {
     SolveArgs R = A;
     R.c = row_of(ctab, b);
     return R;
 }
+// a queue position's instance index: with a table made wave-uniform, for the scalar loads of the row
+__device__ __forceinline__ int index_of(const int b) { return b; }
+__device__ __forceinline__ int index_of(const int b, const DevConsts*) { return __builtin_amdgcn_readfirstlane(b); }
+// first argument of the kernels that take their constants by value: the table stands in its place
+template <class... Tab>
+using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevConsts*>;
 
-// solve_queue with the instance's own constants
-template <class M>
-__device__ __forceinline__ void solve_queue_h(const SolveArgs& A, const DevConsts* __restrict__ ctab, double* s) {
+// The launch as a work queue: one resident wavefront (slot) per workgroup, each solving instances until the queue is empty.
+// No workgroup ever waits for another one, so any grid size terminates; a slot's work buffers are private to its wavefront
+// (its own loads and stores are seen in program order), the per-instance inputs were written before the launch.
+// Every instance starts from freshly built LDS tables, so a result does not depend on which slot solved it or on what that
+// slot solved before: bit-identical to one launch per instance.
+template <class M, class... Tab>
+__device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, Tab __restrict__... ctab) {
     const int slot = blockIdx.x;
     const bool queued = A.qhead != nullptr;
-    int i = slot;
+    int i = slot;                                      // no queue: workgroup w solves instance first + w
     if (threadIdx.x == 0) A.slot_clock(slot)[0] = wall_clock64();
     if (queued) {
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
     }
-    while (i < A.count) {
-        const int b = __builtin_amdgcn_readfirstlane((queued && A.order) ? A.order[i] : A.first + i);
-        solve_instance<M>(with_row(A, ctab, b), s, b, slot);
+    while (i < A.count) {                              // every wavefront reaches the exit: the head only grows
+        const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
+        solve_instance<M>(args_of(A, b, ctab...), s, b, slot);   // one call site: the body is compiled once
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
     }
     if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
 }
-template <class M>
-__global__ __launch_bounds__(kWave) void solve_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+
+// two builds of the same body: the register allocation is the only difference (sddp_options.waves_per_simd)
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void solve_kernel(SolveArgs A, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_h<M>(A, ctab, s);
+    solve_queue<M>(A, s, ctab...);
 }
-template <class M>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_h<M>(A, ctab, s);
+    solve_queue<M>(A, s, ctab...);
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1082,7 +1067,9 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     wave_sync();
 }
 
-// a work queue like the solve launch (solve_queue), in index order: every instance costs one sweep
+// a work queue like the solve launch (solve_queue), in index order: every instance costs one sweep.  The table kernel is written
+// out beside the plain one: every form that folded the two into one template moved the register allocation of one of them
+// (profiles/hetero_merge/README.md).
 template <class M>
 __global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __restrict__ pol, int keep) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1111,8 +1098,8 @@ __global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __
         i = __builtin_amdgcn_readfirstlane(i);
     }
     while (i < A.count) {
-        const int b = __builtin_amdgcn_readfirstlane(A.first + i);
-        policy_instance<M>(with_row(A, ctab, b), s, b, slot, pol, keep);
+        const int b = index_of(A.first + i, ctab);
+        policy_instance<M>(args_of(A, b, ctab), s, b, slot, pol, keep);
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
@@ -1123,15 +1110,17 @@ __global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __
 // (x_0 := x0 as the solve does; multiple-shooting cost of the given xs / us), evaluated here by one wavefront per instance, one
 // lane per knot -- the same model code and the same sum the solve itself starts from.  The keys are then sorted in descending
 // order (sddp_sort.hip): the instances farthest from their optimum start first.  Nothing here depends on an earlier solve.
-template <class M>
-__global__ __launch_bounds__(kWave) void queue_cost_key_kernel(DevConsts c, int N, int first, int count, const double* __restrict__ x0,
-                                                               const double* __restrict__ P, const double* __restrict__ xs,
-                                                               const double* __restrict__ us, double* __restrict__ key,
-                                                               int* __restrict__ idx) {
+// With a table (a heterogeneous fleet) every instance's warm start is priced with its own robot.
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void queue_cost_key_kernel(ConstsArg<Tab...> consts, int N, int first, int count,
+                                                               const double* __restrict__ x0, const double* __restrict__ P,
+                                                               const double* __restrict__ xs, const double* __restrict__ us,
+                                                               double* __restrict__ key, int* __restrict__ idx) {
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
     const int i = blockIdx.x, lane = threadIdx.x;
     if (i >= count) return;
     const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
     const double* xb = xs + size_t(b) * (N + 1) * NX;
     const double* ub = us + size_t(b) * N * NU;
     const double* Pb = P + size_t(b) * (N + 1) * NP;
@@ -1155,47 +1144,6 @@ __global__ __launch_bounds__(kWave) void queue_cost_key_kernel(DevConsts c, int 
         key[i] = (J == J) ? J : __builtin_huge_val();      // a non-finite start sorts first (it ends at once with status 3)
         idx[i] = b;
     }
-}
-// the same key for the `_h` twin below (a copy: sharing one body with the kernel above moved that kernel's register allocation)
-template <class M>
-__device__ __forceinline__ void queue_cost_key(const DevConsts& c, const int N, const int i, const int b, const double* __restrict__ x0,
-                                               const double* __restrict__ P, const double* __restrict__ xs,
-                                               const double* __restrict__ us, double* __restrict__ key, int* __restrict__ idx) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    const int lane = threadIdx.x;
-    const double* xb = xs + size_t(b) * (N + 1) * NX;
-    const double* ub = us + size_t(b) * N * NU;
-    const double* Pb = P + size_t(b) * (N + 1) * NP;
-    double Jl = 0.0;
-    for (int k = lane; k <= N; k += kWave) {
-        double x[NX];
-        const double* xk = k == 0 ? x0 + size_t(b) * NX : xb + k * NX;
-#pragma unroll
-        for (int j = 0; j < NX; ++j) x[j] = xk[j];
-        if (k < N) {
-            double u[NU], xn[NX];
-#pragma unroll
-            for (int j = 0; j < NU; ++j) u[j] = ub[k * NU + j];
-            Jl += M::step(c, x, u, Pb + k * NP, k, xn);
-        } else {
-            Jl += M::term_cost(c, x, Pb + k * NP);
-        }
-    }
-    const double J = wave_sum(Jl);
-    if (lane == 0) {
-        key[i] = (J == J) ? J : __builtin_huge_val();      // a non-finite start sorts first (it ends at once with status 3)
-        idx[i] = b;
-    }
-}
-// ... of a heterogeneous fleet: every instance's warm start is priced with its own robot
-template <class M>
-__global__ __launch_bounds__(kWave) void queue_cost_key_kernel_h(const DevConsts* __restrict__ ctab, int N, int first, int count,
-                                                                 const double* __restrict__ x0, const double* __restrict__ P,
-                                                                 const double* __restrict__ xs, const double* __restrict__ us,
-                                                                 double* __restrict__ key, int* __restrict__ idx) {
-    const int i = blockIdx.x;
-    if (i >= count) return;
-    queue_cost_key<M>(row_of(ctab, first + i), N, i, first + i, x0, P, xs, us, key, idx);
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1204,29 +1152,17 @@ __global__ __launch_bounds__(kWave) void queue_cost_key_kernel_h(const DevConsts
 // one model step per instance, x+ = f(x, u, p_k) (ddp.py:228-230): the closed-loop simulator step of the examples
 // (dsrbd_example.py:158-159) through the same device model code as the solver.  One thread per instance.
 // -----------------------------------------------------------------------------------------------------------------
-// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
-template <class M>
-__device__ __forceinline__ void model_step_one(const DevConsts& c, const int b, const int k, const double* __restrict__ x,
-                                               const double* __restrict__ u, const double* __restrict__ p, double* __restrict__ xn) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    double xv[NX], uv[NU], pv[NP], xo[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xv[i] = x[size_t(b) * NX + i];
-#pragma unroll
-    for (int i = 0; i < NU; ++i) uv[i] = u[size_t(b) * NU + i];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) pv[i] = p[size_t(b) * NP + i];
-    (void)M::step(c, xv, uv, pv, k, xo);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xn[size_t(b) * NX + i] = xo[i];
-}
-template <class M>
-__global__ __launch_bounds__(kWave) void model_step_kernel(DevConsts c, int B, int k, const double* __restrict__ x,
+// One thread per instance: b is not wave-uniform, so with a table every lane loads its own row (vector loads), not consts_of's.
+__device__ __forceinline__ const DevConsts& lane_consts_of(const DevConsts& c, const int) { return c; }
+__device__ __forceinline__ DevConsts lane_consts_of(const DevConsts* __restrict__ ctab, const int b) { return ctab[b]; }
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void model_step_kernel(ConstsArg<Tab...> consts, int B, int k, const double* __restrict__ x,
                                                            const double* __restrict__ u, const double* __restrict__ p,
                                                            double* __restrict__ xn) {
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
     const int b = blockIdx.x * kWave + threadIdx.x;
     if (b >= B) return;
+    const DevConsts& c = lane_consts_of(consts, b);
     double xv[NX], uv[NU], pv[NP], xo[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) xv[i] = x[size_t(b) * NX + i];
@@ -1237,16 +1173,6 @@ __global__ __launch_bounds__(kWave) void model_step_kernel(DevConsts c, int B, i
     (void)M::step(c, xv, uv, pv, k, xo);
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[size_t(b) * NX + i] = xo[i];
-}
-// ... of a heterogeneous fleet: one thread per instance, so every lane reads its own row (vector loads)
-template <class M>
-__global__ __launch_bounds__(kWave) void model_step_kernel_h(const DevConsts* __restrict__ ctab, int B, int k, const double* __restrict__ x,
-                                                             const double* __restrict__ u, const double* __restrict__ p,
-                                                             double* __restrict__ xn) {
-    const int b = blockIdx.x * kWave + threadIdx.x;
-    if (b >= B) return;
-    const DevConsts c = ctab[b];
-    model_step_one<M>(c, b, k, x, u, p, xn);
 }
 
 // -----------------------------------------------------------------------------------------------------------------
@@ -1290,37 +1216,13 @@ __global__ __launch_bounds__(kWave) void eval_knots_kernel(DevConsts c, int N, i
     for (int e = lane; e < NZ; e += kWave) g_out[t * NZ + e] = r[M::REC_G + e];
 }
 
-// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
-template <class M>
-__device__ __forceinline__ void backward_one(const SolveArgs& A, double* s, const int b) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
-    const int lane = threadIdx.x;
-    const int N = A.N;
-    const double* P = A.P + size_t(b) * (N + 1) * NP;
-    double* xs = A.xs + size_t(b) * (N + 1) * NX;
-    double* us = A.us + size_t(b) * N * NU;
-    double* dft = A.dft + size_t(b) * N * NX;
-    double* gains = A.gains + size_t(b) * N * (NU * (NX + 1));
-    double* rec = A.rec + size_t(b) * (N + 1) * NREC;
-    double J, gap;
-    sweep_tables<M>(A.c, s, lane);
-    phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
-    phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
-    wave_sync();
-    double dV1, G1, G2, qu_inf;
-    SDDP_T_DECL
-    const bool ok = backward_sweep<M>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, lane, dV1, G1, G2, qu_inf, true SDDP_T_PASS);
-    if (lane == 0) {
-        double* sc = A.scal + size_t(b) * kScal;
-        sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
-    }
-}
-template <class M>
-__global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs K, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= A.B) return;
+    if (b >= K.B) return;
+    const SolveArgs& A = args_of(K, b, ctab...);
     const int N = A.N;
     const double* P = A.P + size_t(b) * (N + 1) * NP;
     double* xs = A.xs + size_t(b) * (N + 1) * NX;
@@ -1340,46 +1242,21 @@ __global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs A) {
         double* sc = A.scal + size_t(b) * kScal;
         sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
     }
-}
-template <class M>
-__global__ __launch_bounds__(kWave) void backward_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    const int b = blockIdx.x;
-    if (b >= A.B) return;
-    backward_one<M>(with_row(A, ctab, b), s, b);
 }
 
-// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
-template <class M>
-__device__ __forceinline__ void forward_one(const SolveArgs& A, double* s, const int b) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    const int lane = threadIdx.x;
-    const int N = A.N;
-    const double J = rollout<M, false>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
-                                       A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
-                                       A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
-                                       A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s);
-    if (lane == 0) A.scal[size_t(b) * kScal] = J;
-}
-template <class M>
-__global__ __launch_bounds__(kWave) void forward_kernel(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void forward_kernel(SolveArgs K, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
     const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= A.B) return;
+    if (b >= K.B) return;
+    const SolveArgs& A = args_of(K, b, ctab...);
     const int N = A.N;
     const double J = rollout<M, false>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
                                        A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
                                        A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
                                        A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s);
     if (lane == 0) A.scal[size_t(b) * kScal] = J;
-}
-template <class M>
-__global__ __launch_bounds__(kWave) void forward_kernel_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    const int b = blockIdx.x;
-    if (b >= A.B) return;
-    forward_one<M>(with_row(A, ctab, b), s, b);
 }
 
 }  // namespace sddp

@@ -1276,9 +1276,10 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
     __syncthreads();
 }
 
-// work queue over the resident workgroups (see solve_queue in sddp_kernels.hpp); the queue position travels through LDS
-template <class M, bool SINK>
-__device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s) {
+// work queue over the resident workgroups (see solve_queue in sddp_kernels.hpp); the queue position travels through LDS.  With a
+// table (args_of) b comes out of the LDS queue word the kernel has anyway.
+template <class M, bool SINK, class... Tab>
+__device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, Tab __restrict__... ctab) {
     // the queue position lives in a control word of the dynamic LDS block (CTL + 15), so that the occupancy query and the
     // dynamic-LDS attribute cover every byte of LDS the kernel uses
     int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
@@ -1290,8 +1291,8 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s) {
     int i = queued ? *q_pos : slot;
     __syncthreads();                                   // every thread has read it before the solve re-zeroes the LDS block
     while (i < A.count) {
-        const int b = (queued && A.order) ? A.order[i] : A.first + i;
-        solve_instance_mw<M, SINK>(A, s, b, slot);           // ends with a barrier: q_pos may be rewritten
+        const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
+        solve_instance_mw<M, SINK>(args_of(A, b, ctab...), s, b, slot);   // ends with a barrier: q_pos may be rewritten
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1300,52 +1301,18 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s) {
     }
     if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
 }
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(false)>(A, s);
+    solve_queue_mw<M, mw_sink<M>(false)>(A, s, ctab...);
 }
 
 // the same body capped at half the register file: two workgroups per CU where the tiles of two instances fit its LDS;
 // sddp_options.waves_per_simd = 2 picks it, results are identical
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(true)>(A, s);
-}
-
-// heterogeneous fleets (with_row in sddp_kernels.hpp): the same queue, every instance on its own row of the constants table.  b comes
-// out of the LDS queue word the kernel has anyway, made wave-uniform for the scalar loads of the row
-template <class M, bool SINK>
-__device__ __forceinline__ void solve_queue_mw_h(const SolveArgs& A, const DevConsts* __restrict__ ctab, double* s) {
-    int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
-    const int slot = blockIdx.x;
-    const bool queued = A.qhead != nullptr;
-    if (threadIdx.x == 0) A.slot_clock(slot)[0] = wall_clock64();
-    if (queued && threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
-    __syncthreads();
-    int i = queued ? *q_pos : slot;
-    __syncthreads();
-    while (i < A.count) {
-        const int b = __builtin_amdgcn_readfirstlane((queued && A.order) ? A.order[i] : A.first + i);
-        solve_instance_mw<M, SINK>(with_row(A, ctab, b), s, b, slot);
-        if (!queued) break;
-        if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
-        __syncthreads();
-        i = *q_pos;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
-}
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw_h<M, mw_sink<M>(false)>(A, ctab, s);
-}
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw_h<M, mw_sink<M>(true)>(A, ctab, s);
+    solve_queue_mw<M, mw_sink<M>(true)>(A, s, ctab...);
 }
 
 // policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread
@@ -1396,6 +1363,7 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
     __syncthreads();
 }
 
+// (two kernels, like policy_kernel / policy_kernel_h in sddp_kernels.hpp)
 template <class M>
 __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, double* __restrict__ pol, int keep) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1426,8 +1394,8 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, do
     int i = queued ? *q_pos : slot;
     __syncthreads();
     while (i < A.count) {
-        const int b = __builtin_amdgcn_readfirstlane(A.first + i);
-        policy_instance_mw<M, mw_sink<M>(false)>(with_row(A, ctab, b), s, b, slot, pol, keep);
+        const int b = index_of(A.first + i, ctab);
+        policy_instance_mw<M, mw_sink<M>(false)>(args_of(A, b, ctab), s, b, slot, pol, keep);
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1436,41 +1404,13 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, do
     }
 }
 
-// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
-template <class M>
-__device__ __forceinline__ void backward_one_mw(const SolveArgs& A, double* s, const int b) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const int N = A.N;
-    const double* P = A.P + size_t(b) * (N + 1) * NP;
-    double* xs = A.xs + size_t(b) * (N + 1) * NX;
-    double* us = A.us + size_t(b) * N * NU;
-    double* dft = A.dft + size_t(b) * N * NX;
-    double* gains = A.gains + size_t(b) * N * (NU * (NX + 1));
-    double* rec = A.rec + size_t(b) * (N + 1) * NREC;
-    double J = 0.0, gap = 0.0;
-    SDDP_T_DECL
-    sweep_tables_mw<M>(A.c, s, tid);
-    if (wave == 0) {
-        phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
-        phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
-    }
-    __syncthreads();
-    double dV1, G1, G2, qu_inf;
-    double qconst[LdsMW<M>::TQ][3][3];
-    mw_const_block<M>(A.c, tid, qconst);
-    const bool ok = backward_sweep_mw<M, mw_sink<M>(false)>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS);
-    if (tid == 0) {
-        double* sc = A.scal + size_t(b) * kScal;
-        sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
-    }
-}
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw(SolveArgs K, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    if (b >= A.B) return;
+    if (b >= K.B) return;
+    const SolveArgs& A = args_of(K, b, ctab...);
     const int N = A.N;
     const double* P = A.P + size_t(b) * (N + 1) * NP;
     double* xs = A.xs + size_t(b) * (N + 1) * NX;
@@ -1495,33 +1435,14 @@ __global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw(SolveArgs A) {
         sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
     }
 }
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void backward_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    const int b = blockIdx.x;
-    if (b >= A.B) return;
-    backward_one_mw<M>(with_row(A, ctab, b), s, b);
-}
 
-// (body of the `_h` twin below: a copy of the kernel's, because sharing one body moved the register allocation of existing kernels)
-template <class M>
-__device__ __forceinline__ void forward_one_mw(const SolveArgs& A, double* s, const int b) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    const int tid = threadIdx.x;
-    const int N = A.N;
-    SDDP_T_DECL
-    const double J = rollout_mw<M, false, mw_sink<M>(false)>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
-                                          A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
-                                          A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
-                                          A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, tid, s SDDP_T_PASS);
-    if (tid == 0) A.scal[size_t(b) * kScal] = J;
-}
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw(SolveArgs A) {
+template <class M, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw(SolveArgs K, Tab __restrict__... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (b >= A.B) return;
+    if (b >= K.B) return;
+    const SolveArgs& A = args_of(K, b, ctab...);
     const int N = A.N;
     SDDP_T_DECL
     const double J = rollout_mw<M, false, mw_sink<M>(false)>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
@@ -1529,13 +1450,6 @@ __global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw(SolveArgs A) {
                                           A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
                                           A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, tid, s SDDP_T_PASS);
     if (tid == 0) A.scal[size_t(b) * kScal] = J;
-}
-template <class M>
-__global__ __launch_bounds__(kThreadsMW) void forward_kernel_mw_h(SolveArgs A, const DevConsts* __restrict__ ctab) {
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    const int b = blockIdx.x;
-    if (b >= A.B) return;
-    forward_one_mw<M>(with_row(A, ctab, b), s, b);
 }
 
 }  // namespace sddp

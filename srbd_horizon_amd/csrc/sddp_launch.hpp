@@ -2,7 +2,6 @@
 // Included by sddp_inst.hip only: one translation unit per model build.
 #pragma once
 #include <algorithm>
-#include <type_traits>
 
 #include "sddp_handle.hpp"
 #include "sddp_kernels.hpp"
@@ -28,56 +27,40 @@ constexpr bool has_w2() {
 template <class M>
 constexpr int threads_of() { return use_mw<M>() ? kThreadsMW : kWave; }
 
-// Heterogeneous fleets (sddp_set_instance_consts): the plain builds carry an `_h` twin of every kernel, which reads instance b's
-// row of the handle's constants table (sddp_kernels.hpp with_row).  sddp_api.hip refuses the table on every other build, so
-// h->ctab != nullptr implies has_hetero<M>().
+// Heterogeneous fleets (sddp_set_instance_consts): on the plain builds every kernel has a table form that takes the handle's
+// constants table behind its arguments and reads instance b's row of it (sddp_kernels.hpp args_of): a second instantiation of
+// the same template, except for the policy export, whose table form is a kernel of its own (policy_kernel[_mw]_h).  sddp_api.hip
+// refuses the table on every other build, so h->ctab != nullptr implies has_hetero<M>().
 template <class M>
 constexpr bool has_hetero() { return !M::BAR && !M::SO2 && M::NXR == 0; }
-// f(std::bool_constant<HET>): the HET instantiation of a launcher, HET = the handle's table is active.  A build without `_h` twins
-// never instantiates f(true_type), and so none of their kernels.
+// f(tab...): a launcher with the kernels' trailing argument pack, the handle's table when it is active and nothing otherwise.  A
+// build without has_hetero never instantiates f(table), and so none of the table kernels.
 template <class M, class F>
 int with_table(sddp_handle* h, F f) {
     if constexpr (has_hetero<M>()) {
-        if (h->ctab) return f(std::true_type{});
+        if (h->ctab) return f((const DevConsts*)h->ctab);
     }
-    return f(std::false_type{});
+    return f();
 }
-// the constants argument of the kernels that take it first: the table (`_h` twins) or the handle's own constants
-template <bool HET>
-auto consts_arg(sddp_handle* h) { if constexpr (HET) return (const DevConsts*)h->ctab; else return h->dc; }
-// launch of a kernel whose `_h` twin takes the table behind the common arguments
-template <bool HET, class Fn, class... A>
-int launch_model(sddp_handle* h, Fn kern, int grid, int threads, size_t lds, const A&... args) {
-    if constexpr (HET) return launch(h, kern, grid, threads, lds, args..., (const DevConsts*)h->ctab);
-    else return launch(h, kern, grid, threads, lds, args...);
-}
+// the constants argument of the kernels that take it first: the handle's own constants, or the table in their place
+inline const DevConsts& consts_arg(sddp_handle* h) { return h->dc; }
+inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return tab; }
 
 // only the kernel a model actually uses is instantiated
-using KernelFn = void (*)(SolveArgs);
-using KernelFnH = void (*)(SolveArgs, const DevConsts*);
-template <bool HET> using KernelOf = std::conditional_t<HET, KernelFnH, KernelFn>;
-template <class M, bool HET> KernelOf<HET> pick_solve(int waves_per_simd) {
+template <class M, class... Tab> auto pick_solve(int waves_per_simd) {
     [[maybe_unused]] const bool w2 = waves_per_simd >= 2;
-    if constexpr (HET) {
-        if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2_h<M> : solve_kernel_h<M>;
-        else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2_h<M> : solve_kernel_mw_h<M>;
-        else return solve_kernel_mw_h<M>;
-    } else {
-        if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M> : solve_kernel<M>;
-        else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M> : solve_kernel_mw<M>;
-        else return solve_kernel_mw<M>;
-    }
+    if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M, Tab...> : solve_kernel<M, Tab...>;
+    else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M, Tab...> : solve_kernel_mw<M, Tab...>;
+    else return solve_kernel_mw<M, Tab...>;
 }
-template <class M, bool HET> KernelOf<HET> pick_backward() {
-    if constexpr (HET) { if constexpr (use_mw<M>()) return backward_kernel_mw_h<M>; else return backward_kernel_h<M>; }
-    else { if constexpr (use_mw<M>()) return backward_kernel_mw<M>; else return backward_kernel<M>; }
+template <class M, class... Tab> auto pick_backward() {
+    if constexpr (use_mw<M>()) return backward_kernel_mw<M, Tab...>; else return backward_kernel<M, Tab...>;
 }
-template <class M, bool HET> KernelOf<HET> pick_forward() {
-    if constexpr (HET) { if constexpr (use_mw<M>()) return forward_kernel_mw_h<M>; else return forward_kernel_h<M>; }
-    else { if constexpr (use_mw<M>()) return forward_kernel_mw<M>; else return forward_kernel<M>; }
+template <class M, class... Tab> auto pick_forward() {
+    if constexpr (use_mw<M>()) return forward_kernel_mw<M, Tab...>; else return forward_kernel<M, Tab...>;
 }
-template <class M, bool HET> auto pick_policy() {
-    if constexpr (HET) { if constexpr (use_mw<M>()) return policy_kernel_mw_h<M>; else return policy_kernel_h<M>; }
+template <class M, class... Tab> auto pick_policy() {   // the one entry point whose table kernel is a kernel of its own
+    if constexpr (sizeof...(Tab) != 0) { if constexpr (use_mw<M>()) return policy_kernel_mw_h<M>; else return policy_kernel_h<M>; }
     else { if constexpr (use_mw<M>()) return policy_kernel_mw<M>; else return policy_kernel<M>; }
 }
 
@@ -105,16 +88,16 @@ constexpr int solve_cap(int wps) { return use_mw<M>() ? 0 : 4 * (wps >= 2 ? 2 : 
 
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M, bool HET>
-int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
+template <class M, class... Tab>
+int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... tab) {
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    auto kern = pick_solve<M, HET>(wps);
+    auto kern = pick_solve<M, Tab...>(wps);
     int slots = 0;
     int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
     if (rc != SDDP_OK) return rc;
     if constexpr (use_mw<M>()) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
         if (wps >= 2) {
-            auto k1 = pick_solve<M, HET>(1);
+            auto k1 = pick_solve<M, Tab...>(1);
             int s1 = 0;
             rc = kernel_slots<M>(h, k1, solve_cap<M>(1), &s1);
             if (rc != SDDP_OK) return rc;
@@ -146,8 +129,8 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
         } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
             rc = alloc_cold_queue(h);
             if (rc != SDDP_OK) return rc;
-            auto key = [] { if constexpr (HET) return queue_cost_key_kernel_h<M>; else return queue_cost_key_kernel<M>; }();
-            rc = launch(h, key, count, kWave, 0, consts_arg<HET>(h), a.N, first, count, a.x0, a.P, a.xs, a.us, h->qkey, h->order_in);
+            rc = launch(h, queue_cost_key_kernel<M, Tab...>, count, kWave, 0, consts_arg(h, tab...), a.N, first, count, a.x0, a.P, a.xs, a.us,
+                        h->qkey, h->order_in);
             if (rc != SDDP_OK) return rc;
             if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
                 rc = launch_class_keys(h, count);
@@ -163,7 +146,7 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
     h->last_lds = int(lds_bytes<M>());
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    rc = launch_model<HET>(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a);
+    rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, tab...);
     if (rc != SDDP_OK) return rc;
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
         rc = launch_class_update(h, first, count);
@@ -177,14 +160,14 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count) {
 }
 template <class M>
 int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
-    return with_table<M>(h, [&](auto het) { return launch_solve_on<M, decltype(het)::value>(h, a, first, count); });
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M>(h, a, first, count, tab...); });
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
 int max_slots(sddp_handle* h, int* slots) {
     int s1 = 0, s2 = 0;
-    int rc = kernel_slots<M>(h, pick_solve<M, false>(1), solve_cap<M>(1), &s1);
-    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M, false>(2), solve_cap<M>(2), &s2);
+    int rc = kernel_slots<M>(h, pick_solve<M>(1), solve_cap<M>(1), &s1);
+    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M>(2), solve_cap<M>(2), &s2);
     *slots = std::max(s1, s2);
     return rc;
 }
@@ -192,20 +175,20 @@ int max_slots(sddp_handle* h, int* slots) {
 // through kernel_slots for the dynamic-LDS attribute alone: the grid is h->B, the slot count of the entry is not read
 template <class M, class Pick>
 int launch_phase(sddp_handle* h, const SolveArgs& a, Pick pick) {
-    return with_table<M>(h, [&](auto het) {
-        auto kern = pick(het);
+    return with_table<M>(h, [&](auto... tab) {
+        auto kern = pick(tab...);
         const int rc = kernel_slots<M>(h, kern, 0, nullptr);
         if (rc != SDDP_OK) return rc;
-        return launch_model<decltype(het)::value>(h, kern, h->B, threads_of<M>(), lds_bytes<M>(), a);
+        return launch(h, kern, h->B, threads_of<M>(), lds_bytes<M>(), a, tab...);
     });
 }
 template <class M>
 int launch_backward(sddp_handle* h, const SolveArgs& a) {
-    return launch_phase<M>(h, a, [](auto het) { return pick_backward<M, decltype(het)::value>(); });
+    return launch_phase<M>(h, a, [](auto... tab) { return pick_backward<M, decltype(tab)...>(); });
 }
 template <class M>
 int launch_forward(sddp_handle* h, const SolveArgs& a) {
-    return launch_phase<M>(h, a, [](auto het) { return pick_forward<M, decltype(het)::value>(); });
+    return launch_phase<M>(h, a, [](auto... tab) { return pick_forward<M, decltype(tab)...>(); });
 }
 
 // policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
@@ -214,8 +197,8 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
 // elsewhere.
 template <class M>
 int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
-    return with_table<M>(h, [&](auto het) {
-        auto kern = pick_policy<M, decltype(het)::value>();
+    return with_table<M>(h, [&](auto... tab) {
+        auto kern = pick_policy<M, decltype(tab)...>();
         int slots = 0;
         int rc = kernel_slots<M>(h, kern, use_mw<M>() ? 0 : 8, &slots);
         if (rc != SDDP_OK) return rc;
@@ -226,16 +209,14 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
             HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
             a.qhead = h->qhead;
         }
-        return launch_model<decltype(het)::value>(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep);
+        return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep, tab...);
     });
 }
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
-    return with_table<M>(h, [&](auto het) {
-        constexpr bool HET = decltype(het)::value;
-        auto kern = [] { if constexpr (HET) return model_step_kernel_h<M>; else return model_step_kernel<M>; }();
-        return launch(h, kern, (h->B + kWave - 1) / kWave, kWave, 0, consts_arg<HET>(h), h->B, k, dx, du, dp, dxn);
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, model_step_kernel<M, decltype(tab)...>, (h->B + kWave - 1) / kWave, kWave, 0, consts_arg(h, tab...), h->B, k, dx, du, dp, dxn);
     });
 }
 

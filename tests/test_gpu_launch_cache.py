@@ -1,5 +1,6 @@
 """Every launcher of a model build through ONE handle (sddp_launch.hpp: solve in both register-file builds, policy export, backward
-sweep, forward rollout, each as the plain kernel and as its `_h` twin), checked bit for bit against fresh handles.
+sweep, forward rollout, each without and with the constants table, the two instantiations of a kernel), checked bit for bit
+against fresh handles.
 
 A handle keeps per-kernel launch state (dynamic-LDS attribute, resident workgroups) from the first launch of each kernel on.  The
 other tests drive one or two launchers per handle; here one handle meets every kernel of its build in turn, switches the constants
