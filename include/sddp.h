@@ -233,6 +233,47 @@ int  sddp_policy_words(sddp_handle* h, int* words, int* knots);
 int  sddp_policy_range_device(sddp_handle* h, int first, int count);
 int  sddp_fetch_policy(sddp_handle* h, int first, int count, double* out /*[count][words]*/);
 int  sddp_apply_policy_device(sddp_handle* h, int first, int count, const double* d_x_meas, double* d_u_out);
+/* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
+ * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
+ * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),
+ * hands out the ones that are finished, raises max_iters and finishes the stragglers in a second launch -- and every robot gets
+ * exactly the result of the uncut solve: xs, us and every field of sddp_stats, iters and rollouts cumulative, are the bytes a
+ * single solve at the final max_iters returns.  That is what tells a SLICE from a per-tick BUDGET (max_iters = 6, restart from the
+ * iterate next tick): the restart is a fresh solve that throws mu, rho, theta and the exact defects away.
+ * What is carried is the state the iteration keeps from one accepted step to the next: the sddp_stats record -- cost, alpha, gap, mu,
+ * expected, rho, iters, rollouts; theta = 1 iff second_order != 0 and alpha == alpha_0 --, the iterate in xs / us, and the defects of the cut
+ * iterate, kept per instance in a carry buffer [B][N][nx].  Nothing is recomputed from the trajectory: recomputed defects equal
+ * (1 - alpha) d only up to rounding, and the cost would be summed in another order.
+ * sddp_enable_resume: on = 1 allocates the carry buffer and one flag per instance (all 0), and makes every later solve launch of
+ *   the handle use the resumable instantiation of its kernel (same arithmetic; at its end an instance with status 1 stores its
+ *   defects and sets its flag, any other clears it).  on = 0 frees them: back to the ordinary kernels.  Plain builds of the four
+ *   models only (both waves_per_simd builds, with or without an instance-constants table): a handle with user rows (n_extra > 0),
+ *   a barrier, second_order = 2 or a user build returns SDDP_ERR_ARG, like sddp_set_instance_consts.
+ * sddp_continue_range_device: one launch over the instances [first, first + count), a work queue over the slots like
+ *   sddp_solve_range_device, asynchronous on the handle's stream.  An instance whose flag is 1 takes up its solve where it stopped
+ *   and runs while iters < options.max_iters: max_iters is the TOTAL cap, not a budget of this launch -- raise it with
+ *   sddp_set_options between the slices (changing any other option between slices is allowed and guarantees nothing).  An instance
+ *   whose flag is 0 -- finished, never solved, or invalidated -- is left untouched, bit for bit.  The result of an instance does
+ *   not depend on the range, order or slot it ran in, nor on how many slices its solve was cut into.  SDDP_ERR_ARG without
+ *   sddp_enable_resume, or if no solve has run on the handle.  d_params is the tensor the cut solve ran on; a caller-owned tensor
+ *   that the caller changes between the slices is the caller's business (the identity above then does not hold).
+ *   sddp_continue_device: the whole batch.  sddp_continue_resident: the whole batch on the resident parameters (sddp_set_params, or
+ *   the tensor sddp_solve uploaded).
+ * sddp_unfinished_count: *n = instances of [first, first + count) whose flag is 1 (one small reduction kernel and a 4-byte copy;
+ *   waits for the stream): whether a second launch is worth it.
+ * Invalidation: every call that rewrites an instance's x0, xs, us, resident params row or constants row clears the flags of the
+ *   instances it touches, on the stream: sddp_set_initial_state*, sddp_set_*_warmstart*, sddp_load_range_device, sddp_advance,
+ *   sddp_set_params, sddp_set_instance_consts, sddp_clear_instance_consts.  A fresh sddp_solve* launch overwrites the flags of its
+ *   range.  The policy export, sddp_pack_records_device, sddp_fetch and sddp_solve_resident_first read xs / us / stats and work
+ *   behind a continue launch as behind a solve.
+ * Class history (queue_order = 3): an instance is counted once, with its total iteration count, by the launch in which it leaves
+ *   status 1 -- a cut launch does not count the instances it leaves resumable, the continue launch counts the ones it ran and
+ *   finished.  (v9) */
+int  sddp_enable_resume(sddp_handle* h, int on);
+int  sddp_continue_range_device(sddp_handle* h, const double* d_params, int first, int count);
+int  sddp_continue_device(sddp_handle* h, const double* d_params);
+int  sddp_continue_resident(sddp_handle* h);
+int  sddp_unfinished_count(sddp_handle* h, int first, int count, int* n);
 /* Class labels for queue_order = 3: classes[b] in [0, n_classes) (or -1: unlabelled) says what kind of problem instance b is --
  * anything the caller knows BEFORE the solve that correlates with its length.  The handle keeps, per class, the iterations and the
  * number of solves of every labelled instance it has solved (under any queue order) and orders a queued launch by the class

@@ -96,6 +96,11 @@ SYMBOLS = {
     "sddp_policy_range_device": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sddp_fetch_policy": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sddp_apply_policy_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
+    "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
+    "sddp_continue_device": (C.c_int, [_vp, _vp]),
+    "sddp_continue_resident": (C.c_int, [_vp]),
+    "sddp_unfinished_count": (C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_int)]),
     "sddp_set_instance_classes": (C.c_int, [_vp, _vp, C.c_int]),
     "sddp_set_instance_classes_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
     "sddp_class_history": (C.c_int, [_vp, C.c_int, _P(C.c_double), _P(C.c_longlong)]),
@@ -133,6 +138,8 @@ INSTANCES = [
 # -sink-insts-to-avoid-spills moves hoisted loop-invariant address arithmetic back into the loops instead of spilling it:
 # 25.8 -> 27.3 k solves/s when it went in, 31.8 -> 32.3 k on the round's final kernel (profiles/r04/experiments/README.md).  Measured and NOT applied elsewhere: srbd13 -1 % (scratch 524 -> 288 B
 # but slower), srbd37 +2.3 % in the two-per-SIMD build and -3 % in the other, which share a translation unit.
+# the plain builds have resumable solve kernels (sddp_enable_resume), compiled in a translation unit of their own (csrc/sddp_inst.hip)
+RESUME_INSTANCES = ("srbd13", "srbd37", "lip30", "srbd61")
 INSTANCE_FLAGS = {k: ["-mllvm", "-sink-insts-to-avoid-spills"] for k in ("srbd61", "srbd61_x", "srbd61_b")}
 HEADERS = ["sddp_kernels.hpp", "sddp_kernels_mw.hpp", "sddp_models.hpp", "sddp_sort.hpp", "sddp_handle.hpp", "sddp_launch.hpp", "sddp_kernels_host.hpp"]
 
@@ -194,6 +201,10 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
     for fn, model, mname in INSTANCES:
         obj = os.path.join(objdir, "inst_" + fn + ".o")
         defs = ["-DSDDP_INST_MODEL=" + model, "-DSDDP_INST_FN=ops_" + fn, '-DSDDP_INST_NAME="' + mname + '"', *INSTANCE_FLAGS.get(fn, [])]
+        if fn in RESUME_INSTANCES:
+            robj = os.path.join(objdir, "inst_" + fn + "_resume.o")
+            jobs.append((robj, inst, base + defs + ["-DSDDP_INST_RESUME", inst, "-o", robj]))
+            defs.append("-DSDDP_INST_HAS_RESUME")
         jobs.append((obj, inst, base + defs + [inst, "-o", obj]))
     todo, left_stale = [], []
     for obj, src, cmd in jobs:

@@ -55,6 +55,9 @@ int launch_class_keys(sddp_handle* h, int count) {
     return launch(h, class_key_kernel, (count + 255) / 256, 256, 0, count, h->order_in, h->cls, h->n_cls, h->cls_stat, h->qkey);
 }
 int launch_class_update(sddp_handle* h, int first, int count) {
+    if (h->resumable)   // resumable solves: an instance is counted by the launch in which it leaves status 1
+        return launch(h, class_update_resume_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat,
+                      h->resumable, h->resumable + 2 * size_t(h->B), h->continuing ? 1 : 0);
     return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat);
 }
 
@@ -212,6 +215,13 @@ SolveArgs make_args(sddp_handle* h, const double* d_params) {
 
 int check_range(sddp_handle* h, int first, int count) {
     if (first < 0 || count < 1 || first > h->B - count) return fail(h, SDDP_ERR_ARG, "instance range outside the batch");
+    return SDDP_OK;
+}
+
+// Resumable solves: a call that rewrites x0, xs, us, the resident params row or the constants row of the instances
+// [first, first + count) makes what their cut solve carried meaningless; their flags are cleared, on the stream, behind the rewrite.
+int invalidate_resume(sddp_handle* h, int first, int count) {
+    if (h->resumable) HIP_TRY(h, hipMemsetAsync(h->resumable + first, 0, size_t(count) * sizeof(int), h->stream));
     return SDDP_OK;
 }
 
@@ -527,6 +537,8 @@ int sddp_set_options(sddp_handle* h, const sddp_options* opts) {
     if (rc != SDDP_OK) return rc;
     if ((opts->second_order == 2) != (h->opts.second_order == 2) && h->model_id != SDDP_MODEL_LIP30)
         return fail(h, SDDP_ERR_ARG, "second_order = 2 selects another kernel build and record size: choose it at sddp_create");
+    if (opts->second_order == 2 && h->carry)
+        return fail(h, SDDP_ERR_ARG, "second_order = 2 on a handle with resumable solves: call sddp_enable_resume(h, 0) first");
     h->opts = *opts;
     return SDDP_OK;
 }
@@ -567,19 +579,19 @@ int sddp_set_initial_state(sddp_handle* h, const double* x0) {
     if (!h || !x0) return SDDP_ERR_ARG;
     const int rc = upload(h, h->x0, x0, size_t(h->B) * h->d.nx * sizeof(double));
     if (rc == SDDP_OK) h->have_x0 = true;
-    return rc;
+    return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
 }
 int sddp_set_x_warmstart(sddp_handle* h, const double* x) {
     if (!h || !x) return SDDP_ERR_ARG;
     const int rc = upload(h, h->xs, x, h->n_x() * sizeof(double));
     if (rc == SDDP_OK) h->have_xws = true;
-    return rc;
+    return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
 }
 int sddp_set_u_warmstart(sddp_handle* h, const double* u) {
     if (!h || !u) return SDDP_ERR_ARG;
     const int rc = upload(h, h->us, u, h->n_u() * sizeof(double));
     if (rc == SDDP_OK) h->have_uws = true;
-    return rc;
+    return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
 }
 // ---- device-pointer setters -----------------------------------------------------------------------------------------
 int sddp_load_range_device(sddp_handle* h, int first, int count, const double* d_x0, const double* d_x, const double* d_u) {
@@ -598,7 +610,7 @@ int sddp_load_range_device(sddp_handle* h, int first, int count, const double* d
         HIP_TRY(h, hipMemcpyAsync(h->us + size_t(first) * N * nu, d_u, size_t(count) * N * nu * D, hipMemcpyDeviceToDevice, h->stream));
         h->have_uws = true;
     }
-    return SDDP_OK;
+    return (d_x0 || d_x || d_u) ? invalidate_resume(h, first, count) : SDDP_OK;
 }
 int sddp_set_initial_state_device(sddp_handle* h, const double* d) {
     if (!h || !d) return SDDP_ERR_ARG;
@@ -627,6 +639,79 @@ int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, i
 int sddp_solve_device(sddp_handle* h, const double* d_params) {
     if (!h) return SDDP_ERR_ARG;
     return sddp_solve_range_device(h, d_params, 0, h->B);
+}
+
+// ---- resumable solves -----------------------------------------------------------------------------------------------
+int sddp_enable_resume(sddp_handle* h, int on) {
+    if (!h) return SDDP_ERR_ARG;
+    if (on && (h->model_id >= kUserId0 || h->bar || h->so2 || h->consts.n_extra != 0))
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no user rows, no barrier, "
+                                     "no second_order = 2, no user build)");
+    if (on && !h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no resumable kernels");
+    if (on && h->opts.second_order == 2)      // (lip30, whose one build takes the option: the resumable kernels are not tested with it)
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no second_order = 2)");
+    if ((on != 0) == (h->carry != nullptr)) return SDDP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still use the buffers
+    h->up_off = 0;
+    release(h, h->carry);
+    release(h, h->resumable);
+    if (!on) return SDDP_OK;
+    const size_t flag_bytes = (3 * size_t(h->B) + 1) * sizeof(int);
+    int* flags = nullptr;
+    double* carry = nullptr;
+    hipError_t e = acquire(h, carry, size_t(h->B) * h->N * h->d.nx * sizeof(double));
+    if (e == hipSuccess) e = acquire(h, flags, flag_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, flag_bytes, h->stream);
+    if (e != hipSuccess) {      // all or nothing
+        (void)hipGetLastError();
+        release(h, carry); release(h, flags);
+        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_resume: out of device memory");
+    }
+    h->carry = carry;
+    h->resumable = flags;
+    return SDDP_OK;
+}
+
+int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first, int count) {
+    int rc = check_ready(h);
+    if (rc != SDDP_OK) return rc;
+    if (!h->carry) return fail(h, SDDP_ERR_ARG, "sddp_continue: sddp_enable_resume has not been called (plain builds only: no barrier, no "
+                                                "second_order = 2, no user rows)");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_continue: no solve has run on this handle");
+    if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    SolveArgs a = make_args(h, d_params);
+    if (h->cls)   // which instances this launch resumes: the class statistics count those that it also finishes
+        HIP_TRY(h, hipMemsetAsync(h->resumable + 2 * size_t(h->B) + first, 0, size_t(count) * sizeof(int), h->stream));
+    h->continuing = true;
+    rc = h->ops->launch_solve(h, a, first, count);
+    h->continuing = false;
+    if (rc == SDDP_OK) h->last_params = d_params;
+    return rc;
+}
+
+int sddp_continue_device(sddp_handle* h, const double* d_params) {
+    if (!h) return SDDP_ERR_ARG;
+    return sddp_continue_range_device(h, d_params, 0, h->B);
+}
+
+int sddp_continue_resident(sddp_handle* h) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->have_params && h->last_params != h->P)      // resident: sddp_set_params, or the tensor sddp_solve uploaded
+        return fail(h, SDDP_ERR_ARG, h->carry ? "sddp_continue_resident: no resident parameters (sddp_set_params or sddp_solve)"
+                                              : "sddp_continue: sddp_enable_resume has not been called");
+    return sddp_continue_range_device(h, h->P, 0, h->B);
+}
+
+int sddp_unfinished_count(sddp_handle* h, int first, int count, int* n) {
+    if (!h || !n) return SDDP_ERR_ARG;
+    if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_unfinished_count: sddp_enable_resume has not been called");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    int* d_n = h->resumable + 3 * size_t(h->B);
+    const int rc = launch(h, unfinished_count_kernel, 1, 256, 0, first, count, (const int*)h->resumable, d_n);
+    if (rc != SDDP_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(n, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
 }
 
 int sddp_queue_info(sddp_handle* h, int* slots, int* last_grid, int* last_queued) {
@@ -732,7 +817,7 @@ int sddp_set_params(sddp_handle* h, const double* params) {
     if (!h || !params) return SDDP_ERR_ARG;
     const int rc = upload(h, h->P, params, h->n_p() * sizeof(double));
     if (rc == SDDP_OK) h->have_params = true;
-    return rc;
+    return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
 }
 
 int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
@@ -760,7 +845,7 @@ int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
     }
     const int rc = launch(h, advance_kernel, h->B, 256, 0, h->N, h->d.nx, h->d.nu, h->d.np, h->P, h->xs, h->us, h->x0, d_pl, d_x0);
     if (rc == SDDP_OK) h->have_x0 = true;
-    return rc;
+    return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
 }
 
 int sddp_solve_resident(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats) {
@@ -888,7 +973,8 @@ int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_mo
         h->ctab = t;
     }
     for (size_t i = 0; i < n; ++i) r[i] = make_dev_consts(consts[i]);
-    return upload(h, h->ctab + first, r, n * sizeof(DevConsts));
+    const int rc = upload(h, h->ctab + first, r, n * sizeof(DevConsts));
+    return rc == SDDP_OK ? invalidate_resume(h, first, count) : rc;
 }
 
 int sddp_clear_instance_consts(sddp_handle* h) {
@@ -897,7 +983,7 @@ int sddp_clear_instance_consts(sddp_handle* h) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still read the table
     h->up_off = 0;
     release(h, h->ctab);
-    return SDDP_OK;
+    return invalidate_resume(h, 0, h->B);
 }
 
 int sddp_instance_consts_active(sddp_handle* h, int* on) {

@@ -29,6 +29,11 @@ struct ModelOps {
     const char* name;      // kernel-facing model name (bench / profiles)
     int (*max_slots)(sddp_handle*, int*);
     int (*launch_solve)(sddp_handle*, SolveArgs, int, int);
+    // resumable solves: the launcher of the kernels' RESUME instantiations, compiled in a translation unit of its own (sddp_inst.hip
+    // with -DSDDP_INST_RESUME); null: the build has none.  launch_cost_keys: the queue_order 2 / 3 key pre-pass, which that unit calls
+    // through this table instead of instantiating the key kernel a second time
+    int (*launch_solve_resume)(sddp_handle*, SolveArgs, int, int) = nullptr;
+    int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
@@ -106,6 +111,11 @@ struct sddp_handle {
     double* policy = nullptr;
     int policy_knots = 0;
     const double* last_params = nullptr;
+    // resumable solves (sddp_enable_resume): non-null = on, and every solve launch runs the kernels' RESUME instantiation
+    double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
+    int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
+                                    // then one word: the result of sddp_unfinished_count
+    bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
     char* up_pin = nullptr;         // pinned ring for small host->device uploads of the setters (no wait per call)
     size_t up_off = 0;
     // every device and pinned allocation above, registered where it is made (sddp_api.hip acquire / release): what sddp_destroy frees

@@ -2,15 +2,33 @@
 //   -DSDDP_INST_MODEL=<device model type>  -DSDDP_INST_FN=<name of the accessor>  -DSDDP_INST_NAME="<model name>"
 // (in parallel: the solve kernels of one model build are 10-30 s of device code generation each).  The accessor returns the
 // build's table of launchers (sddp_handle.hpp ModelOps); sddp_api.hip picks a table by (model_id, barrier, second_order).
+// The plain builds (_lib.py RESUME_INSTANCES) are compiled a second time with -DSDDP_INST_RESUME: that unit holds nothing but the
+// RESUME instantiations of the solve kernels and their launcher, which the main unit (-DSDDP_INST_HAS_RESUME) enters in its table.
 #include "sddp_launch.hpp"
 
 #if !defined(SDDP_INST_MODEL) || !defined(SDDP_INST_FN) || !defined(SDDP_INST_NAME)
 #error "compile with -DSDDP_INST_MODEL=... -DSDDP_INST_FN=... -DSDDP_INST_NAME=..."
 #endif
+#define SDDP_CAT2(a, b) a##b
+#define SDDP_CAT(a, b) SDDP_CAT2(a, b)
+#define SDDP_INST_RESUME_FN SDDP_CAT(SDDP_INST_FN, _resume_solve)
 
 namespace sddp {
+#ifdef SDDP_INST_RESUME
+int SDDP_INST_RESUME_FN(sddp_handle* h, SolveArgs a, int first, int count) { return launch_solve_resume<SDDP_INST_MODEL>(h, a, first, count); }
+#else
+#ifdef SDDP_INST_HAS_RESUME
+int SDDP_INST_RESUME_FN(sddp_handle* h, SolveArgs a, int first, int count);
+#endif
 const ModelOps* SDDP_INST_FN() {
-    static const ModelOps ops = make_ops<SDDP_INST_MODEL>(SDDP_INST_NAME);
+    static const ModelOps ops = [] {
+        ModelOps o = make_ops<SDDP_INST_MODEL>(SDDP_INST_NAME);
+#ifdef SDDP_INST_HAS_RESUME
+        o.launch_solve_resume = SDDP_INST_RESUME_FN;
+#endif
+        return o;
+    }();
     return &ops;
 }
+#endif
 }  // namespace sddp

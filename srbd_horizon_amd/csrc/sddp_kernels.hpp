@@ -85,6 +85,23 @@ struct SolveArgs {
     }
 };
 
+// Resumable solves (sddp_enable_resume): what the RESUME instantiations of the solve kernels take beside SolveArgs, as a kernel
+// argument of their own behind it.  (Not fields of SolveArgs: the size of the kernel-argument segment decides how the compiler
+// widens the scalar loads of the arguments, and 24 bytes more moved the register allocation of the ordinary one-wave kernels.)
+// Both buffers are per INSTANCE: slots are reused within a launch and differ from one launch to the next.
+struct ResumeArgs {
+    double* carry;      // [B][N][NX]  the defects (the slot's dft) of an instance whose solve was cut at max_iters (status 1)
+    int* resumable;     // [3][B]  1: instance b can be continued (its last solve ended with status 1 and nothing of it was rewritten
+                        //         since) | the lane whose trajectory the 4-wave kernel's next pass stores (its `guess`) | 1: the
+                        //         continue launch in flight resumed instance b (class history, sddp_api.hip launch_class_update)
+    int cont;           // 1: a continue launch (sddp_continue_*): resumable instances are taken up where they stopped, every other
+                        // instance is left as it is
+};
+struct NoResume {};    // stands in its place in the ordinary instantiations: nothing is passed, nothing is read
+// a trailing kernel argument as the kernel declares it: the table pointer __restrict__ as it always was, ResumeArgs by value
+template <class T> struct KernelArg { using type = T; };
+template <class T> struct KernelArg<T*> { using type = T* __restrict__; };
+
 // Hand-off between phases of a ONE-WAVEFRONT workgroup.  LDS (and global) accesses of one wave are performed in issue order, so a
 // later ds_read of any lane sees an earlier ds_write of any lane without waiting; what must not happen is the COMPILER moving
 // accesses across the hand-off.  A wavefront-scope fence does exactly that and costs no instruction, where __syncthreads()
@@ -789,12 +806,28 @@ __device__ double rollout(const DevConsts& c, int N, const double* __restrict__ 
 // -----------------------------------------------------------------------------------------------------------------
 // fused persistent solve: one wavefront per MPC instance, all iterations in one launch (replaces ddp.py:101)
 // -----------------------------------------------------------------------------------------------------------------
-template <class M>
-__device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, const int b, const int slot) {
+// RESUME (sddp_enable_resume): the instantiation that can stop at max_iters and be taken up again.  It differs in three places --
+// entry (a continue launch skips the starting point of a resumable instance and loads what the iteration carries from one accepted
+// step to the next: stats and the carried defects; it returns at once for any other instance), and exit (the defects go to the
+// instance's carry row when status == 1; the flag is set).  Nothing is recomputed from the trajectory: recomputed defects equal
+// (1 - alpha) d only up to rounding (and are noise where the engine carries exact zeros), and phase_defects sums the cost in
+// another order than the rollout that produced J -- either would break the bit identity with the uncut solve.  With RESUME false
+// every such line is behind `if constexpr`: the ordinary instantiation is the code it was.
+template <class M, bool RESUME = false, class Res = NoResume>
+__device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res()) {
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int lane = threadIdx.x;
     const int N = A.N;
     const sddp_options& o = A.o;
+    // `resumed`: a run-time flag in the RESUME instantiation, a compile-time false in the ordinary one (the conditions on it fold in
+    // the front end: the ordinary instantiation is compiled from the statements it always had)
+    std::conditional_t<RESUME, bool, const std::false_type> resumed{};
+    if constexpr (RESUME) {
+        if (R.cont) {   // wave-uniform: a kernel argument and instance b's flag
+            if (R.resumable[b] != 1) return;
+            resumed = true;
+        }
+    }
     const double* x0 = A.x0 + size_t(b) * NX;
     const double* P = A.P + size_t(b) * (N + 1) * NP;
     double* xs = A.xs + size_t(b) * (N + 1) * NX;
@@ -813,7 +846,13 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
     SDDP_T_DECL
     sweep_tables<M>(A.c, s, lane);
     // ---- starting point
-    if (o.initial_rollout) {
+    if (resumed) {   // the iterate is in A.xs / A.us; its defects as the cut solve left them
+        if constexpr (RESUME) {
+            const double* cr = R.carry + size_t(b) * N * NX;
+            for (int e = lane; e < N * NX; e += kWave) dft[e] = cr[e];
+            wave_sync();
+        }
+    } else if (o.initial_rollout) {
         J = rollout<M, true>(A.c, N, x0, P, xs, us, dft, gains, xc, uc, 0.0, 0, lane, s);
         wave_sync();
         for (int e = lane; e < (N + 1) * NX; e += kWave) xs[e] = xc[e];
@@ -827,6 +866,15 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
     }
     double mu = o.mu0, rho = 0.0, alpha = 0.0, expected = 0.0, theta = 0.0;
     int iters = 0, converged = 0, status = 1, rollouts = 0, win = 0;
+    if constexpr (RESUME) {
+        if (resumed) {
+            const sddp_stats st = A.stats[b];
+            J = st.cost; gap = st.gap; mu = st.mu; rho = st.rho; alpha = st.alpha; expected = st.expected;
+            theta = (o.second_order && alpha == o.alpha_0) ? 1.0 : 0.0;
+            iters = st.iters; rollouts = st.rollouts;
+            if (lane == 0) R.resumable[2 * A.B + b] = 1;
+        }
+    }
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
@@ -930,6 +978,13 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
         A.stats[b] = st;
         A.hist[b] = iters;
     }
+    if constexpr (RESUME) {
+        if (status == 1) {
+            double* cr = R.carry + size_t(b) * N * NX;
+            for (int e = lane; e < N * NX; e += kWave) cr[e] = dft[e];
+        }
+        if (lane == 0) R.resumable[b] = status == 1 ? 1 : 0;
+    }
     wave_sync();
 }
 
@@ -969,6 +1024,16 @@ __device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, co
 // a queue position's instance index: with a table made wave-uniform, for the scalar loads of the row
 __device__ __forceinline__ int index_of(const int b) { return b; }
 __device__ __forceinline__ int index_of(const int b, const DevConsts*) { return __builtin_amdgcn_readfirstlane(b); }
+// The trailing arguments of a solve kernel: nothing, the table, ResumeArgs, or ResumeArgs and the table (in this order).  The
+// overloads below skip the ResumeArgs for what concerns the table, and resume_of picks them out (NoResume where there are none).
+__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int, const ResumeArgs&) { return A; }
+__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const ResumeArgs&, const DevConsts* __restrict__ ctab) { return args_of(A, b, ctab); }
+__device__ __forceinline__ int index_of(const int b, const ResumeArgs&) { return b; }
+__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const DevConsts* ctab) { return index_of(b, ctab); }
+__device__ __forceinline__ NoResume resume_of() { return NoResume(); }
+__device__ __forceinline__ NoResume resume_of(const DevConsts*) { return NoResume(); }
+__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r) { return r; }
+__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const DevConsts*) { return r; }
 // first argument of the kernels that take their constants by value: the table stands in its place
 template <class... Tab>
 using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevConsts*>;
@@ -978,8 +1043,8 @@ using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevCo
 // (its own loads and stores are seen in program order), the per-instance inputs were written before the launch.
 // Every instance starts from freshly built LDS tables, so a result does not depend on which slot solved it or on what that
 // slot solved before: bit-identical to one launch per instance.
-template <class M, class... Tab>
-__device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, Tab __restrict__... ctab) {
+template <class M, bool RESUME, class... Tab>
+__device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, typename KernelArg<Tab>::type... ctab) {
     const int slot = blockIdx.x;
     const bool queued = A.qhead != nullptr;
     int i = slot;                                      // no queue: workgroup w solves instance first + w
@@ -990,7 +1055,8 @@ __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, Tab _
     }
     while (i < A.count) {                              // every wavefront reaches the exit: the head only grows
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
-        solve_instance<M>(args_of(A, b, ctab...), s, b, slot);   // one call site: the body is compiled once
+        if constexpr (RESUME) solve_instance<M, true>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
+        else solve_instance<M>(args_of(A, b, ctab...), s, b, slot);   // one call site per instantiation: the body is compiled once
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
@@ -999,15 +1065,15 @@ __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, Tab _
 }
 
 // two builds of the same body: the register allocation is the only difference (sddp_options.waves_per_simd)
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void solve_kernel(SolveArgs A, Tab __restrict__... ctab) {
+template <class M, bool RESUME, class... Tab>
+__global__ __launch_bounds__(kWave) void solve_kernel(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M>(A, s, ctab...);
+    solve_queue<M, RESUME, Tab...>(A, s, ctab...);
 }
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A, Tab __restrict__... ctab) {
+template <class M, bool RESUME, class... Tab>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M>(A, s, ctab...);
+    solve_queue<M, RESUME, Tab...>(A, s, ctab...);
 }
 
 // -----------------------------------------------------------------------------------------------------------------

@@ -59,6 +59,35 @@ __global__ __launch_bounds__(256) void class_update_kernel(int first, int count,
     atomicAdd(&cls_stat[2 * c + 1], 1ull);
 }
 
+// The class statistics of a handle with resumable solves (sddp_enable_resume): an instance is counted once, with its total iteration
+// count, by the launch in which it leaves status 1.  A fresh solve launch (cont = 0) skips the instances it leaves resumable; a
+// continue launch counts the instances it resumed (`ran`, zeroed before the launch) and finished.
+__global__ __launch_bounds__(256) void class_update_resume_kernel(int first, int count, const int* __restrict__ cls, int n_cls,
+                                                                  const sddp_stats* __restrict__ st, unsigned long long* __restrict__ cls_stat,
+                                                                  const int* __restrict__ resumable, const int* __restrict__ ran, int cont) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i, c = cls[b];
+    if (c < 0 || c >= n_cls) return;
+    if (resumable[b] == 1 || (cont && ran[b] != 1)) return;
+    atomicAdd(&cls_stat[2 * c], (unsigned long long)st[b].iters);
+    atomicAdd(&cls_stat[2 * c + 1], 1ull);
+}
+
+// sddp_unfinished_count: how many instances of [first, first + count) can be continued (flag 1).  One workgroup.
+__global__ __launch_bounds__(256) void unfinished_count_kernel(int first, int count, const int* __restrict__ resumable, int* __restrict__ out) {
+    __shared__ int part[256];
+    int n = 0;
+    for (int i = threadIdx.x; i < count; i += 256) n += resumable[first + i] == 1 ? 1 : 0;
+    part[threadIdx.x] = n;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = part[0];
+}
+
 // what an MPC tick applies: the first input u_0 and the state the plan expects next, x_1, of every instance, packed
 // [B][nu + nx] (+ cost, iterations, status as three more doubles) for one small copy to the host instead of the whole trajectories
 __global__ __launch_bounds__(256) void first_knot_kernel(int N, int B, int nx, int nu, const double* __restrict__ xs,

@@ -1100,14 +1100,23 @@ __device__ __forceinline__ double rollout_mw(const DevConsts& c, int N, const do
     return J;
 }
 
-// fused persistent solve, 4 waves per instance
-template <class M, bool SINK>
-__device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s, const int b, const int slot) {
+// fused persistent solve, 4 waves per instance.  RESUME: see solve_instance (sddp_kernels.hpp); this kernel carries one word more,
+// the lane whose trajectory its next pass stores (`guess`: it decides whether an accepted step costs a second rollout, and so the
+// rollout count).
+template <class M, bool SINK, bool RESUME = false, class Res = NoResume>
+__device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res()) {
     using L = LdsMW<M>;
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     const int N = A.N;
     const sddp_options& o = A.o;
+    std::conditional_t<RESUME, bool, const std::false_type> resumed{};      // (see solve_instance)
+    if constexpr (RESUME) {
+        if (R.cont) {   // the same for every thread of the workgroup: a kernel argument and instance b's flag
+            if (R.resumable[b] != 1) return;
+            resumed = true;
+        }
+    }
     const double* x0 = A.x0 + size_t(b) * NX;
     const double* P = A.P + size_t(b) * (N + 1) * NP;
     double* xs = A.xs + size_t(b) * (N + 1) * NX;
@@ -1124,7 +1133,12 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
     double qconst[LdsMW<M>::TQ][3][3];
     mw_const_block<M>(A.c, tid, qconst);
     // ---- starting point (cost and defect norm computed by wave 0, shared through CTL)
-    if (o.initial_rollout) {
+    if (resumed) {   // the iterate is in A.xs / A.us; its defects as the cut solve left them
+        if constexpr (RESUME) {
+            const double* cr = R.carry + size_t(b) * N * NX;
+            for (int e = tid; e < N * NX; e += kThreadsMW) dft[e] = cr[e];
+        }
+    } else if (o.initial_rollout) {
         J = rollout_mw<M, true, SINK>(A.c, N, x0, P, xs, us, dft, gains, xn, un, 0.0, 0, tid, s SDDP_T_PASS);
         __syncthreads();
         for (int e = tid; e < (N + 1) * NX; e += kThreadsMW) xs[e] = xn[e];
@@ -1141,6 +1155,16 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
     __syncthreads();
     double mu = o.mu0, rho = 0.0, alpha = 0.0, expected = 0.0, theta = 0.0;
     int iters = 0, converged = 0, status = 1, rollouts = 0, guess = 0;
+    if constexpr (RESUME) {
+        if (resumed) {
+            const sddp_stats st = A.stats[b];
+            J = st.cost; gap = st.gap; mu = st.mu; rho = st.rho; alpha = st.alpha; expected = st.expected;
+            theta = (o.second_order && alpha == o.alpha_0) ? 1.0 : 0.0;
+            iters = st.iters; rollouts = st.rollouts;
+            guess = R.resumable[A.B + b];
+            if (tid == 0) R.resumable[2 * A.B + b] = 1;
+        }
+    }
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
@@ -1273,13 +1297,20 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
         A.stats[b] = st;
         A.hist[b] = iters;
     }
+    if constexpr (RESUME) {
+        if (status == 1) {
+            double* cr = R.carry + size_t(b) * N * NX;
+            for (int e = tid; e < N * NX; e += kThreadsMW) cr[e] = dft[e];
+        }
+        if (tid == 0) { R.resumable[b] = status == 1 ? 1 : 0; R.resumable[A.B + b] = guess; }
+    }
     __syncthreads();
 }
 
 // work queue over the resident workgroups (see solve_queue in sddp_kernels.hpp); the queue position travels through LDS.  With a
 // table (args_of) b comes out of the LDS queue word the kernel has anyway.
-template <class M, bool SINK, class... Tab>
-__device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, Tab __restrict__... ctab) {
+template <class M, bool SINK, bool RESUME, class... Tab>
+__device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, typename KernelArg<Tab>::type... ctab) {
     // the queue position lives in a control word of the dynamic LDS block (CTL + 15), so that the occupancy query and the
     // dynamic-LDS attribute cover every byte of LDS the kernel uses
     int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
@@ -1292,7 +1323,7 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, Ta
     __syncthreads();                                   // every thread has read it before the solve re-zeroes the LDS block
     while (i < A.count) {
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
-        solve_instance_mw<M, SINK>(args_of(A, b, ctab...), s, b, slot);   // ends with a barrier: q_pos may be rewritten
+        solve_instance_mw<M, SINK, RESUME>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));   // ends with a barrier: q_pos may be rewritten
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1301,18 +1332,18 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, Ta
     }
     if (threadIdx.x == 0) A.slot_clock(slot)[1] = wall_clock64();
 }
-template <class M, class... Tab>
-__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A, Tab __restrict__... ctab) {
+template <class M, bool RESUME, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(false)>(A, s, ctab...);
+    solve_queue_mw<M, mw_sink<M>(false), RESUME, Tab...>(A, s, ctab...);
 }
 
 // the same body capped at half the register file: two workgroups per CU where the tiles of two instances fit its LDS;
 // sddp_options.waves_per_simd = 2 picks it, results are identical
-template <class M, class... Tab>
-__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A, Tab __restrict__... ctab) {
+template <class M, bool RESUME, class... Tab>
+__global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(true)>(A, s, ctab...);
+    solve_queue_mw<M, mw_sink<M>(true), RESUME, Tab...>(A, s, ctab...);
 }
 
 // policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread

@@ -46,12 +46,21 @@ int with_table(sddp_handle* h, F f) {
 inline const DevConsts& consts_arg(sddp_handle* h) { return h->dc; }
 inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return tab; }
 
+// Resumable solves (sddp_enable_resume): on the plain builds the solve kernels have a third and fourth instantiation, RES = true
+// (sddp_kernels.hpp solve_instance), which every solve launch of a handle with a carry buffer uses.  sddp_api.hip refuses the
+// buffer on every other build, so h->carry != nullptr implies has_resume<M>().  They are compiled in a translation unit of their
+// own (sddp_inst.hip with -DSDDP_INST_RESUME; launch_solve_resume below is instantiated nowhere else): with them in the same
+// device module the ordinary one-wave kernels come out with another register allocation and 4 bytes less or more scratch, though
+// not a statement of theirs differs (profiles/resume/README.md).
+template <class M>
+constexpr bool has_resume() { return has_hetero<M>(); }
+
 // only the kernel a model actually uses is instantiated
-template <class M, class... Tab> auto pick_solve(int waves_per_simd) {
+template <class M, bool RES, class... Tab> auto pick_solve(int waves_per_simd) {
     [[maybe_unused]] const bool w2 = waves_per_simd >= 2;
-    if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M, Tab...> : solve_kernel<M, Tab...>;
-    else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M, Tab...> : solve_kernel_mw<M, Tab...>;
-    else return solve_kernel_mw<M, Tab...>;
+    if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M, RES, Tab...> : solve_kernel<M, RES, Tab...>;
+    else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M, RES, Tab...> : solve_kernel_mw<M, RES, Tab...>;
+    else return solve_kernel_mw<M, RES, Tab...>;
 }
 template <class M, class... Tab> auto pick_backward() {
     if constexpr (use_mw<M>()) return backward_kernel_mw<M, Tab...>; else return backward_kernel<M, Tab...>;
@@ -86,18 +95,31 @@ int kernel_slots(sddp_handle* h, Fn kern, int cap, int* slots) {
 template <class M>
 constexpr int solve_cap(int wps) { return use_mw<M>() ? 0 : 4 * (wps >= 2 ? 2 : 1); }
 
+// the queue_order 2 / 3 pre-pass: the initial cost of every instance of the launch, into h->qkey / h->order_in
+template <class M>
+int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, queue_cost_key_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), a.N, first, count, a.x0, a.P, a.xs, a.us,
+                      h->qkey, h->order_in);
+    });
+}
+
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M, class... Tab>
+template <class M, bool RES, class... Tab>
 int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... tab) {
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    auto kern = pick_solve<M, Tab...>(wps);
+    // the kernels' trailing arguments: [ResumeArgs] [table]
+    auto pick = [](int w) {
+        if constexpr (RES) return pick_solve<M, true, ResumeArgs, Tab...>(w); else return pick_solve<M, false, Tab...>(w);
+    };
+    auto kern = pick(wps);
     int slots = 0;
     int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
     if (rc != SDDP_OK) return rc;
     if constexpr (use_mw<M>()) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
         if (wps >= 2) {
-            auto k1 = pick_solve<M, Tab...>(1);
+            auto k1 = pick(1);
             int s1 = 0;
             rc = kernel_slots<M>(h, k1, solve_cap<M>(1), &s1);
             if (rc != SDDP_OK) return rc;
@@ -129,8 +151,8 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
         } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
             rc = alloc_cold_queue(h);
             if (rc != SDDP_OK) return rc;
-            rc = launch(h, queue_cost_key_kernel<M, Tab...>, count, kWave, 0, consts_arg(h, tab...), a.N, first, count, a.x0, a.P, a.xs, a.us,
-                        h->qkey, h->order_in);
+            if constexpr (RES) rc = h->ops->launch_cost_keys(h, a, first, count);      // (the key kernel lives in the build's main unit)
+            else rc = launch_cost_keys<M>(h, a, first, count);
             if (rc != SDDP_OK) return rc;
             if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
                 rc = launch_class_keys(h, count);
@@ -146,7 +168,8 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
     h->last_lds = int(lds_bytes<M>());
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, tab...);
+    if constexpr (RES) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0}, tab...);
+    else rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, tab...);
     if (rc != SDDP_OK) return rc;
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
         rc = launch_class_update(h, first, count);
@@ -160,14 +183,23 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
 }
 template <class M>
 int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M>(h, a, first, count, tab...); });
+    if (h->carry) {   // resumable solves: the RESUME instantiations, in their own translation unit
+        if (!h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "this build has no resumable kernels");
+        return h->ops->launch_solve_resume(h, a, first, count);
+    }
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, false>(h, a, first, count, tab...); });
+}
+template <class M>
+int launch_solve_resume(sddp_handle* h, SolveArgs a, int first, int count) {
+    static_assert(has_resume<M>(), "resumable solves exist for the plain builds only");
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true>(h, a, first, count, tab...); });
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
 int max_slots(sddp_handle* h, int* slots) {
     int s1 = 0, s2 = 0;
-    int rc = kernel_slots<M>(h, pick_solve<M>(1), solve_cap<M>(1), &s1);
-    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M>(2), solve_cap<M>(2), &s2);
+    int rc = kernel_slots<M>(h, pick_solve<M, false>(1), solve_cap<M>(1), &s1);
+    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M, false>(2), solve_cap<M>(2), &s2);
     *slots = std::max(s1, s2);
     return rc;
 }
@@ -235,6 +267,7 @@ ModelOps make_ops(const char* name) {
     o.name = name;
     o.max_slots = max_slots<M>;
     o.launch_solve = launch_solve<M>;
+    o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
     if constexpr (!M::BAR && !M::SO2) o.launch_policy = launch_policy<M>;

@@ -115,6 +115,29 @@ class DDPSolver:
             raise ValueError("engine / problem parameter widths disagree")
         self.var_solution = None
         self._have_x0 = self._have_x = self._have_u = False
+        self.slices = None
+
+    def set_slices(self, slices):
+        """slices = (k, total): every solve runs as a first slice of at most k iterations and, if it is unfinished then, a
+        continue launch up to `total` (resumable solves, include/sddp.h) -- the result is the one of a single solve with
+        max_iters = total, bit for bit.  None: back to one launch per solve."""
+        self.slices = None if slices is None else (int(slices[0]), int(slices[1]))
+        self.ddp_solver.enable_resume(self.slices is not None)
+        if self.slices is not None:
+            self.ddp_solver.set_options(max_iters=self.slices[1])
+
+    def _launch(self, solve):
+        """solve() -> (x, u) on the engine, in slices when set_slices asked for them"""
+        if self.slices is None:
+            return solve()
+        eng, (k, total) = self.ddp_solver, self.slices
+        eng.set_options(max_iters=k)
+        x, u = solve()
+        eng.set_options(max_iters=total)
+        if eng.unfinished() > 0:
+            eng.continue_solve()
+            x, u, _ = eng.fetch()
+        return x, u
 
     # ---- reference surface -----------------------------------------------------------------------------------------
     def setInitialState(self, x0):
@@ -145,7 +168,7 @@ class DDPSolver:
             self.ddp_solver.set_x_warmstart(np.repeat(self._x0[:, None, :], self.prb.nodes, axis=1))
             self._have_x = True
         params = self._parameter_matrix()[None]                             # ddp.py:98-99, vectorised
-        x, u = self.ddp_solver.solve(params)                                # ddp.py:101
+        x, u = self._launch(lambda: self.ddp_solver.solve(params))          # ddp.py:101
         x, u = np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)   # reference layout [dim, nodes]
         self.var_solution = self._createVarSolDict(x, u)
         self.var_solution["x_opt"] = x                                      # ddp.py:103
@@ -189,7 +212,7 @@ class DDPSolver:
                 self._shadow = pm.copy()
                 self.ddp_solver.advance(pm[-1][None], x0)             # warm start and state advance as usual ...
                 self.ddp_solver.set_params(pm[None])                  # ... then the parameters as the host has them
-        x, u = self.ddp_solver.solve_resident()
+        x, u = self._launch(self.ddp_solver.solve_resident)
         x, u = np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)
         self.var_solution = self._createVarSolDict(x, u)
         self.var_solution["x_opt"] = x

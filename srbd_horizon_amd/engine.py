@@ -32,6 +32,7 @@ class DdpEngine:
         self._chk(self.lib.sddp_handle_dims(h, None, None, C.byref(npar)))
         self.np_ = npar.value
         self._keep = []
+        self.resume_enabled = False
 
     # ---- lifetime ------------------------------------------------------------------------------------------------
     def close(self):
@@ -283,6 +284,30 @@ class DdpEngine:
     def solve_range_device(self, params, first: int, count: int):
         """One asynchronous launch over the instances [first, first + count); `params` is the whole [B, N+1, np] tensor."""
         self._chk(self.lib.sddp_solve_range_device(self.h, self._dev(params, (self.B, self.N + 1, self.np_)), int(first), int(count)))
+
+    # ---- resumable solves: continue a solve cut at max_iters, bit for bit (include/sddp.h) -------------------------------------
+    def enable_resume(self, on: bool = True):
+        """Every later solve launch of the handle can be continued: an instance that ends with status 1 (max_iters) keeps what the
+        iteration carries.  Plain builds only (no barrier, no second_order = 2, no user rows)."""
+        self._chk(self.lib.sddp_enable_resume(self.h, int(bool(on))))
+        self.resume_enabled = bool(on)
+
+    def continue_solve(self, params=None, first: int = 0, count: int | None = None):
+        """One asynchronous launch that takes up the unfinished instances (status 1) of [first, first + count) where they stopped and
+        runs them while iters < max_iters -- the TOTAL cap: raise it with set_options(max_iters=...) first.  Every other instance
+        is left untouched.  params: the device tensor [B, N+1, np] the cut solve ran on; None = the resident tensor."""
+        n = int(self.B - first if count is None else count)
+        if params is None and first == 0 and n == self.B:
+            self._chk(self.lib.sddp_continue_resident(self.h))
+            return
+        p = C.c_void_p(self.device_buffer(5)[0]) if params is None else self._dev(params, (self.B, self.N + 1, self.np_))
+        self._chk(self.lib.sddp_continue_range_device(self.h, p, int(first), n))
+
+    def unfinished(self, first: int = 0, count: int | None = None) -> int:
+        """How many instances of [first, first + count) can be continued (waits for the stream)."""
+        n = C.c_int()
+        self._chk(self.lib.sddp_unfinished_count(self.h, int(first), int(self.B - first if count is None else count), C.byref(n)))
+        return n.value
 
     # ---- heterogeneous fleets: per-instance robot constants (include/sddp.h) ------------------------------------------------
     def set_instance_consts(self, overrides: dict, first: int = 0):

@@ -124,6 +124,47 @@ class FleetQueue:
         self.pending = 0
         return n
 
+    def solve_sliced(self, first_slice: int, max_iters: int):
+        """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
+        `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the
+        finished instances are final and can be handed out at once; if any instance is unfinished, max_iters is raised and a
+        second launch finishes the stragglers alone (a finished instance costs it one queue pull).  Every instance ends with
+        exactly the bytes of one uncut solve at `max_iters`.
+        -> (finished [n] bool device tensor: which instances the first slice finished; records [n, words] of all of them after the
+        last slice).  `first_records` keeps the records packed behind the first slice.
+        The records are always the "first_knot" ones and there is no collective and no policy launch, whatever `gather` / `policy`
+        the queue was made with: the caller owns the two record tensors.  The engine is left as it was found: resumable solves are
+        switched on for this call only when they were off (so later flush() calls run the ordinary kernels and the carry buffer is
+        freed; a caller that slices every tick calls `engine.enable_resume()` once itself and saves the allocation per call), and
+        `max_iters` is restored."""
+        import torch
+        n = self.pending * self.batch
+        if n == 0:
+            return None, None
+        eng = self.eng
+        was_on, was_iters = eng.resume_enabled, int(eng.opts.max_iters)
+        eng.enable_resume(True)
+        words = eng.record_words("first_knot")
+        if getattr(self, "_sliced", None) is None or self._sliced[0].shape != (self.batch * self.depth, words):
+            mk = lambda: torch.empty((self.batch * self.depth, words), dtype=torch.float64, device=self.x.device)
+            self._sliced = [mk(), mk()]
+        eng.set_options(max_iters=int(first_slice))
+        eng.solve_range_device(self.P, 0, n)
+        self.first_records = eng.pack_records_device(self._sliced[0][:n], 0, n, "first_knot")
+        finished = self.si[:n, _lib.STATS_I32_STATUS] != 1
+        self.launches += 1
+        eng.set_options(max_iters=int(max_iters))
+        records = self.first_records
+        if eng.unfinished(0, n) > 0:
+            eng.continue_solve(self.P, 0, n)
+            records = eng.pack_records_device(self._sliced[1][:n], 0, n, "first_knot")
+            self.launches += 1
+        if not was_on:
+            eng.enable_resume(False)                                         # (waits for the stream: the records are complete)
+        eng.set_options(max_iters=was_iters)
+        self.pending = 0
+        return finished, records
+
     def _wait(self, k):
         if self._work[k] is not None:
             self._work[k].wait()

@@ -118,6 +118,19 @@ class DdpSolver:
     def is_converged(self) -> bool:
         return bool(self._eng.is_converged()[0])
 
+    # ---- beyond pyddp: a solve cut at max_iters can be continued (include/sddp.h, resumable solves) ----------------------------
+    def enable_resume(self, on: bool = True):
+        self._eng.enable_resume(on)
+
+    def continue_solve(self, max_iters: int):
+        """Take the last solve up where max_iters stopped it and run it up to `max_iters` iterations in total: the result is the
+        one solve() gives with that max_iters from the start, bit for bit.  -> (x [nx, N+1], u [nu, N]) like solve()."""
+        self._eng.set_options(max_iters=int(max_iters))
+        self._eng.continue_solve()
+        x, u, st = self._eng.fetch()
+        self.stats = st[0]
+        return np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)
+
     def get_feedback_gains(self):
         """The local feedback policy of the last solve, u = u_k + K_k (x - x_k): a list of N matrices K_k [nu, nx] (rows: inputs,
         columns: states -- the transpose-free orientation of the [dim, nodes] arrays solve() returns: K_k @ (x[:, k] deviation)),
