@@ -373,7 +373,7 @@ int  sddp_eval_knots(int model_id, const sddp_model_consts* consts, int N, int n
                      const double* x, const double* u, const double* p,
                      double* f_out, double* F_out, double* H_out, double* g_out, double* L_out);
 /* one backward sweep on the handle's current trajectory: gains [B][N][nu*(nx+1)] (kff then K row-major),
- * scal [B][8] = dV1, dV2, G1, G2, ok, mu, qu_inf, Vx0[0] */
+ * scal [B][8] = dV1, dV2, G1, G2, ok, mu, qu_inf, J (the total cost of the trajectory) */
 int  sddp_backward(sddp_handle* h, const double* params, double mu, double* gains_out, double* scal_out);
 /* one forward pass at step `alpha` from the handle's trajectory and the gains of the last sddp_backward */
 int  sddp_forward(sddp_handle* h, const double* params, double alpha, double* x_out, double* u_out, double* cost_out);

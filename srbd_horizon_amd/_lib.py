@@ -122,6 +122,10 @@ SYMBOLS = {
     "sddp_backward": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp]),
     "sddp_forward": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp, _vp]),
 }
+# diagnostics the library exports beside include/sddp.h (not part of the ABI)
+DEBUG_SYMBOLS = {
+    "sddp_debug_set_phase_mode": (C.c_int, [_vp, C.c_double, C.c_int]),      # theta, closed: how sddp_backward / sddp_forward run
+}
 
 _lib = None
 
@@ -256,7 +260,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **DEBUG_SYMBOLS}.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1219,6 +1219,8 @@ int sddp_backward(sddp_handle* h, const double* params, double mu, double* gains
     HIP_TRY(h, hipMemcpyAsync(h->P, params, h->n_p() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     SolveArgs a = make_args(h, h->P);
     a.mu = mu;
+    a.alpha = h->phase_theta;                // the backward test kernels pass it on as the sweep's theta
+    a.first = h->phase_closed ? 1 : 0;       // SolveArgs::first: the one-wave test kernels' "closed gaps" flag
     rc = h->ops->launch_backward(h, a);
     if (rc != SDDP_OK) return rc;
     h->gains_by_instance = true;
@@ -1235,12 +1237,31 @@ int sddp_forward(sddp_handle* h, const double* params, double alpha, double* x_o
     HIP_TRY(h, hipMemcpyAsync(h->P, params, h->n_p() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     SolveArgs a = make_args(h, h->P);
     a.alpha = alpha;
+    a.first = h->phase_closed ? 1 : 0;       // SolveArgs::first: the one-wave test kernels' "closed gaps" flag
     rc = h->ops->launch_forward(h, a);
     if (rc != SDDP_OK) return rc;
     if (x_out) HIP_TRY(h, hipMemcpyAsync(x_out, h->xn, h->n_x() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (u_out) HIP_TRY(h, hipMemcpyAsync(u_out, h->un, h->n_u() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return cost_out ? read_scal(h, cost_out, 1) : SDDP_OK;
+}
+
+// diagnostic (not part of include/sddp.h): how the NEXT sddp_backward / sddp_forward calls of the handle run.  theta: the weight of
+// the sweep's second-order term (what a solve sets to 1 after a full step; second_order = 2 handles add the whole v'.f_zz tensor,
+// the others the bilinear-torque term).  closed = 1: the sweep and the rollout take the path of an iterate whose gaps count as
+// closed (v' = Vx, no Vxx d product, no (1 - alpha) d correction) whatever the defects of the trajectory are -- one-wave kernels
+// only: the 4-wavefront kernels have no such branch, SDDP_ERR_ARG there.  (0.0, 0) is the default and what the entry points
+// always did.  A refused call leaves the mode as it was.
+int sddp_debug_set_phase_mode(sddp_handle* h, double theta, int closed) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!std::isfinite(theta)) return fail(h, SDDP_ERR_ARG, "sddp_debug_set_phase_mode: theta must be finite");
+    if (closed != 0 && closed != 1) return fail(h, SDDP_ERR_ARG, "sddp_debug_set_phase_mode: closed must be 0 or 1");
+    if (closed && h->ops->uses_mw)
+        return fail(h, SDDP_ERR_ARG, "sddp_debug_set_phase_mode: closed = 1 exists on the one-wavefront kernels only (the 4-wavefront "
+                                     "sweep and rollout have no closed-gap path)");
+    h->phase_theta = theta;
+    h->phase_closed = closed;
+    return SDDP_OK;
 }
 
 // diagnostic (not part of include/sddp.h): raw [B][16] scratch record; holds per-phase cycle sums in a -DSDDP_STAMPS build

@@ -116,6 +116,10 @@ struct sddp_handle {
     int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
                                     // then one word: the result of sddp_unfinished_count
     bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
+    // phase-level mode (sddp_debug_set_phase_mode, diagnostics): what sddp_backward / sddp_forward launch with.  Default (0, 0): the
+    // Gauss-Newton sweep on open gaps, as those entry points always ran
+    double phase_theta = 0.0;       // weight of the second-order term of the sweep (the solve's theta: 0 or 1)
+    int phase_closed = 0;           // 1: the one-wave kernels take their closed-gap path (has_gap = false: all defects count as zero)
     char* up_pin = nullptr;         // pinned ring for small host->device uploads of the setters (no wait per call)
     size_t up_off = 0;
     // every device and pinned allocation above, registered where it is made (sddp_api.hip acquire / release): what sddp_destroy frees

@@ -73,6 +73,9 @@ struct SolveArgs {
     // takes queue positions i = atomicAdd(qhead, 1) until i >= count and solves instance order[i] (order == nullptr:
     // first + i).  The work buffers xn/un/xc/uc/dft/gains/rec are per SLOT (indexed by blockIdx.x), x0/P/xs/us/stats/scal/hist
     // per instance.
+    // The one-wave test kernels (backward_kernel, forward_kernel) index by blockIdx.x and B and never read `first` as a range: to
+    // them first != 0 says "closed gaps" (sddp_debug_set_phase_mode: the sweep and the rollout run their has_gap = false path).
+    // The flag rides here because the struct must not grow (static_assert below); no other kernel is launched with it set.
     int first, count;
     int* qhead;
     const int* order;   // [count] absolute instance indices, or nullptr
@@ -84,6 +87,8 @@ struct SolveArgs {
         return reinterpret_cast<unsigned long long*>(hist + ((B + 1) & ~1)) + 2 * slot;
     }
 };
+// the size of the kernel-argument segment is part of the solve kernels' code (see ResumeArgs): a new field goes elsewhere
+static_assert(sizeof(SolveArgs) == 584, "SolveArgs must not grow or shrink: it changes the register allocation of the solve kernels");
 
 // Resumable solves (sddp_enable_resume): what the RESUME instantiations of the solve kernels take beside SolveArgs, as a kernel
 // argument of their own behind it.  (Not fields of SolveArgs: the size of the kernel-argument segment decides how the compiler
@@ -1303,7 +1308,8 @@ __global__ __launch_bounds__(kWave) void backward_kernel(SolveArgs K, Tab __rest
     wave_sync();
     double dV1, G1, G2, qu_inf;
     SDDP_T_DECL
-    const bool ok = backward_sweep<M>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, lane, dV1, G1, G2, qu_inf, true SDDP_T_PASS);
+    const bool has_gap = K.first == 0;      // (SolveArgs::first: closed gaps of sddp_debug_set_phase_mode; A.alpha: its theta)
+    const bool ok = backward_sweep<M>(A.c, N, P, dft, rec, gains, A.mu, A.alpha, s, lane, dV1, G1, G2, qu_inf, has_gap SDDP_T_PASS);
     if (lane == 0) {
         double* sc = A.scal + size_t(b) * kScal;
         sc[0] = dV1; sc[1] = -0.5 * dV1; sc[2] = G1; sc[3] = G2; sc[4] = ok ? 1.0 : 0.0; sc[5] = A.mu; sc[6] = qu_inf; sc[7] = J;
@@ -1321,7 +1327,8 @@ __global__ __launch_bounds__(kWave) void forward_kernel(SolveArgs K, Tab __restr
     const double J = rollout<M, false>(A.c, N, A.x0 + size_t(b) * NX, A.P + size_t(b) * (N + 1) * NP,
                                        A.xs + size_t(b) * (N + 1) * NX, A.us + size_t(b) * N * NU,
                                        A.dft + size_t(b) * N * NX, A.gains + size_t(b) * N * (NU * (NX + 1)),
-                                       A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s);
+                                       A.xn + size_t(b) * (N + 1) * NX, A.un + size_t(b) * N * NU, A.alpha, 0, lane, s,
+                                       K.first == 0);      // (SolveArgs::first: closed gaps of sddp_debug_set_phase_mode)
     if (lane == 0) A.scal[size_t(b) * kScal] = J;
 }
 

@@ -176,21 +176,35 @@ class DdpEngine:
         return f.astype(bool)
 
     # ---- phase-level entry points (parity tests) ---------------------------------------------------------------------------
-    def backward(self, params, mu=0.0):
+    def _phase_mode(self, theta=0.0, closed=False):
+        self._chk(self.lib.sddp_debug_set_phase_mode(self.h, float(theta), int(bool(closed))))
+
+    def backward(self, params, mu=0.0, theta=0.0, closed=False):
+        """One sweep at the handle's trajectory.  theta: weight of the second-order term (a solve's sweep after a full step runs
+        theta = 1); closed: the closed-gap path, all defects taken as zero (one-wave kernels only).  The mode holds for this call."""
         p = self._c(params, (self.B, self.N + 1, self.np_))
         gains = np.empty((self.B, self.N, self.nu * (self.nx + 1)))
         scal = np.empty((self.B, 8))
-        self._chk(self.lib.sddp_backward(self.h, _lib.ptr(p), float(mu), _lib.ptr(gains), _lib.ptr(scal)))
+        self._phase_mode(theta, closed)
+        try:
+            self._chk(self.lib.sddp_backward(self.h, _lib.ptr(p), float(mu), _lib.ptr(gains), _lib.ptr(scal)))
+        finally:
+            self._phase_mode()
         kff = gains[:, :, :self.nu]
         K = gains[:, :, self.nu:].reshape(self.B, self.N, self.nu, self.nx)
         return kff, K, scal
 
-    def forward(self, params, alpha):
+    def forward(self, params, alpha, closed=False):
+        """One rollout with the gains of the last backward(); closed: without the (1 - alpha) d correction (one-wave kernels only)."""
         p = self._c(params, (self.B, self.N + 1, self.np_))
         x = np.empty((self.B, self.N + 1, self.nx))
         u = np.empty((self.B, self.N, self.nu))
         cost = np.empty(self.B)
-        self._chk(self.lib.sddp_forward(self.h, _lib.ptr(p), float(alpha), _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost)))
+        self._phase_mode(0.0, closed)
+        try:
+            self._chk(self.lib.sddp_forward(self.h, _lib.ptr(p), float(alpha), _lib.ptr(x), _lib.ptr(u), _lib.ptr(cost)))
+        finally:
+            self._phase_mode()
         return x, u, cost
 
     # ---- HBM-resident path (torch tensors on the GPU; PyTorch is plumbing for device memory and streams) ------------------

@@ -9,6 +9,7 @@ import pytest
 
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
+from tests import sweep_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -46,6 +47,37 @@ def test_results_do_not_depend_on_what_the_lds_held(model, N, wps):
                     consts=batch.get("consts"))
     clean = _run(eng, batch, xs, us, poison=False)
     dirty = _run(eng, batch, xs, us, poison=True)
+    for a, b in zip(clean, dirty):
+        assert np.all(np.isfinite(b)), "a NaN out of the poisoned LDS reached the result"
+        assert np.array_equal(a, b)
+
+
+def _run_modes(eng, case, P, poison):
+    closed = case.gaps == "closed"
+    out = []
+    for phase in ("backward", "forward"):
+        if phase == "forward":
+            eng.backward(P, case.mu, case.theta, closed)
+        if poison:
+            eng.poison_lds()
+        if phase == "backward":
+            kff, K, scal = eng.backward(P, case.mu, case.theta, closed)
+            out += [kff.copy(), K.copy(), scal.copy()]
+        else:
+            out += list(eng.forward(P, 0.25, closed))
+    return out
+
+
+@pytest.mark.parametrize("name", sweep_cases.POISON_CASES)
+def test_second_order_and_closed_gap_paths_do_not_depend_on_what_the_lds_held(name):
+    """the sweep with its second-order term on (theta = 1: the v'.f_ux term on the one-wave kernel with closed gaps, the v'.f_zz
+    tensor of the 4-wavefront second_order = 2 build) and the closed-gap rollout reuse tiles the Gauss-Newton sweep leaves alone"""
+    case = sweep_cases.CASES[name]
+    P = sweep_cases.start(case)["params"]
+    eng = sweep_cases.make_engine(case)
+    clean = _run_modes(eng, case, P, poison=False)
+    dirty = _run_modes(eng, case, P, poison=True)
+    assert clean[2][:, 4].all()                                   # the sweeps pass: the gains compared are gains
     for a, b in zip(clean, dirty):
         assert np.all(np.isfinite(b)), "a NaN out of the poisoned LDS reached the result"
         assert np.array_equal(a, b)

@@ -458,7 +458,7 @@ def test_friction_cone_barrier_solve_matches_oracle_and_tightens_the_cone(name, 
             DdpEngine(name, N, 1, consts=dict(bound_barrier_weight=1.0))
 
 
-@pytest.mark.parametrize("name,N,seeds", [("srbd13", 30, [0, 1, 2, 4, 6]), ("srbd37", 20, [3, 5])])
+@pytest.mark.parametrize("name,N,seeds", [("srbd13", 30, [0, 1, 2, 4, 6]), ("srbd37", 20, [3, 5, 12])])
 def test_full_second_order_mode_matches_oracle(name, N, seeds):
     """second_order = 2 ("full DDP": v'.f_zz for the wdot and quaternion rows + exact Hessian of the wdot residual, after full
     steps, Gauss-Newton fallback): the SO2 kernel builds against the numpy oracle, iteration by iteration."""
@@ -476,7 +476,9 @@ def test_full_second_order_mode_matches_oracle(name, N, seeds):
         assert np.max(np.abs(x[b] - r.xs)) <= 1e-6 and np.max(np.abs(u[b] - r.us)) <= 1e-6
         assert abs(st["cost"][b] - r.cost) <= 1e-9 * abs(r.cost)
         differs += int(r.iters != r1.iters)
-    assert differs > 0 or name == "srbd37"               # the mode does take another path than the default one
+    # the mode does take another path than the default one.  (srbd37: of the seeds 0..31 only 12 takes another number of iterations,
+    # 7 against 6; term by term the second_order = 2 builds are compared in tests/test_gpu_sweep_modes.py)
+    assert differs > 0
     with pytest.raises(RuntimeError):
         eng.set_options(second_order=1)                   # another kernel build and record size: create-time choice
 
