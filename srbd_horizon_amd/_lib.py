@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 import numpy as np
 
@@ -130,21 +131,33 @@ DEBUG_SYMBOLS = {
 _lib = None
 
 
-# model builds of the library: (accessor suffix, device model type, model name).  One translation unit each (csrc/sddp_inst.hip).
+class Build(NamedTuple):
+    """One model build of the library: one translation unit (csrc/sddp_inst.hip) that defines the accessor sddp::ops_<fn>()."""
+    fn: str                 # accessor suffix
+    type: str               # device model type (csrc/sddp_models.hpp)
+    model: str              # model name, a key of MODEL_IDS
+    traits: tuple = ()      # of "bar" (barrier build), "so2" (full second order), "xr" (user rows): the type's BAR, SO2, NXR > 0
+    flags: tuple = ()       # compiler options of this build alone
+
+
+# srbd61 (one workgroup per CU, 512 registers a lane, still 1.8 KB of scratch): LLVM's -sink-insts-to-avoid-spills moves hoisted
+# loop-invariant address arithmetic back into the loops instead of spilling it: 25.8 -> 27.3 k solves/s when it went in, 31.8 -> 32.3 k
+# on the round's final kernel (profiles/r04/experiments/README.md).  Measured and NOT applied elsewhere: srbd13 -1 % (scratch
+# 524 -> 288 B but slower), srbd37 +2.3 % in the two-per-SIMD build and -3 % in the other, which share a translation unit.
+_SINK = ("-mllvm", "-sink-insts-to-avoid-spills")
+# THE list of model builds: what build() compiles and hands to csrc/sddp_api.hip, which finds a handle's build in it by
+# (model, traits); no two entries share that key (build() checks).  The builds without traits are the plain builds: they alone have
+# table kernels (sddp_set_instance_consts) and resumable solve kernels (sddp_enable_resume), the latter compiled in a translation
+# unit of their own (inst_units).  A new build: its alias in csrc/sddp_models.hpp and one entry here.
 INSTANCES = [
-    ("srbd13", "Srbd13", "srbd13"), ("srbd13_b", "Srbd13B", "srbd13"), ("srbd13_s", "Srbd13S", "srbd13"), ("srbd13_bs", "Srbd13BS", "srbd13"),
-    ("srbd37", "Srbd37", "srbd37"), ("srbd37_b", "Srbd37B", "srbd37"), ("srbd37_s", "Srbd37S", "srbd37"), ("srbd37_bs", "Srbd37BS", "srbd37"),
-    ("lip30", "Lip30", "lip30"), ("srbd61", "Srbd61", "srbd61"),
-    ("srbd13_x", "Srbd13X", "srbd13"), ("srbd37_x", "Srbd37X", "srbd37"), ("lip30_x", "Lip30X", "lip30"),    # user rows (n_extra > 0)
-    ("srbd61_x", "Srbd61X", "srbd61"), ("srbd61_b", "Srbd61B", "srbd61"),    # srbd61: user rows; friction-cone barrier
+    Build("srbd13", "Srbd13", "srbd13"), Build("srbd13_b", "Srbd13B", "srbd13", ("bar",)),
+    Build("srbd13_s", "Srbd13S", "srbd13", ("so2",)), Build("srbd13_bs", "Srbd13BS", "srbd13", ("bar", "so2")),
+    Build("srbd37", "Srbd37", "srbd37"), Build("srbd37_b", "Srbd37B", "srbd37", ("bar",)),
+    Build("srbd37_s", "Srbd37S", "srbd37", ("so2",)), Build("srbd37_bs", "Srbd37BS", "srbd37", ("bar", "so2")),
+    Build("lip30", "Lip30", "lip30"), Build("srbd61", "Srbd61", "srbd61", (), _SINK),
+    Build("srbd13_x", "Srbd13X", "srbd13", ("xr",)), Build("srbd37_x", "Srbd37X", "srbd37", ("xr",)), Build("lip30_x", "Lip30X", "lip30", ("xr",)),
+    Build("srbd61_x", "Srbd61X", "srbd61", ("xr",), _SINK), Build("srbd61_b", "Srbd61B", "srbd61", ("bar",), _SINK),
 ]
-# Per-build compiler options.  srbd61 (one workgroup per CU, 512 registers a lane, still 1.8 KB of scratch): LLVM's
-# -sink-insts-to-avoid-spills moves hoisted loop-invariant address arithmetic back into the loops instead of spilling it:
-# 25.8 -> 27.3 k solves/s when it went in, 31.8 -> 32.3 k on the round's final kernel (profiles/r04/experiments/README.md).  Measured and NOT applied elsewhere: srbd13 -1 % (scratch 524 -> 288 B
-# but slower), srbd37 +2.3 % in the two-per-SIMD build and -3 % in the other, which share a translation unit.
-# the plain builds have resumable solve kernels (sddp_enable_resume), compiled in a translation unit of their own (csrc/sddp_inst.hip)
-RESUME_INSTANCES = ("srbd13", "srbd37", "lip30", "srbd61")
-INSTANCE_FLAGS = {k: ["-mllvm", "-sink-insts-to-avoid-spills"] for k in ("srbd61", "srbd61_x", "srbd61_b")}
 HEADERS = ["sddp_kernels.hpp", "sddp_kernels_mw.hpp", "sddp_models.hpp", "sddp_sort.hpp", "sddp_handle.hpp", "sddp_launch.hpp", "sddp_kernels_host.hpp"]
 
 
@@ -156,6 +169,29 @@ def header_stamp(root: str = ROOT) -> str:
     for p in [os.path.join(root, "srbd_horizon_amd", "csrc", n) for n in HEADERS] + [os.path.join(root, "include", "sddp.h")]:
         h.update(open(p, "rb").read())
     return "0x" + h.hexdigest()[:15]
+
+
+def inst_units():
+    """The translation units of csrc/sddp_inst.hip as (unit name, definitions and options): one per entry of INSTANCES, named by
+    its accessor suffix, and for every build without traits the unit <suffix>_resume of its resumable solve kernels, whose
+    launcher the build's main unit declares (-DSDDP_INST_HAS_RESUME).  A build with traits that asked for one would not compile
+    (csrc/sddp_launch.hpp launch_solve_resume)."""
+    units = []
+    for b in INSTANCES:
+        defs = ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
+        if not b.traits:
+            units.append((b.fn + "_resume", defs + ["-DSDDP_INST_RESUME"]))
+            defs = defs + ["-DSDDP_INST_HAS_RESUME"]
+        units.append((b.fn, defs))
+    return units
+
+
+def compile_command(unit: str | None = None, root: str = ROOT) -> list:
+    """The head of every compile command of the library's HIP sources: the compiler, its flags, the include paths of the tree at
+    `root` and, for a unit of inst_units(), that unit's definitions.  The tail is the caller's: -c or -shared, source, output."""
+    head = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
+            "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "srbd_horizon_amd", "csrc")]
+    return head + (dict(inst_units())[unit] if unit is not None else [])
 
 
 def _newer(target: str, deps) -> bool:
@@ -184,7 +220,9 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
     only: recompile just these model builds (development); refuses to link while another object is stale."""
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    keys = [(b.model, frozenset(b.traits)) for b in INSTANCES]
+    if len(set(keys)) != len(keys) or any(b.model not in MODEL_IDS for b in INSTANCES):
+        raise RuntimeError("INSTANCES: two builds of one model with the same traits, or a model name that MODEL_IDS does not know")
     extra = os.environ.get("SDDP_CXXFLAGS", "").split()      # diagnostic builds only (-DSDDP_STAMPS), with SDDP_LIB
     default = LIB_PATH.endswith("libsddp_hip.so") and not extra
     tag = "" if default else "_" + hashlib.sha1(repr((LIB_PATH, tuple(extra))).encode()).hexdigest()[:10]
@@ -194,22 +232,18 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
     if not force and only is None and not os.path.isdir(objdir) and _newer(LIB_PATH, srcs + hdrs):
         return LIB_PATH                                      # a shipped library newer than every source: nothing to do
     os.makedirs(objdir, exist_ok=True)
-    base = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC, *extra, "-c"]
+    # sddp_api.hip names no build: it gets the accessors of INSTANCES as an X-macro list, and the stamp of the headers (user builds:
+    # userterms.py)
+    api_defs = [f"-DSDDP_HEADER_STAMP={header_stamp()}ULL", "-DSDDP_BUILDS=" + " ".join(f"X(ops_{b.fn})" for b in INSTANCES)]
     jobs = []
-    for name in ("sddp_api", "sddp_sort"):
+    for name, defs in (("sddp_api", api_defs), ("sddp_sort", [])):
         src = os.path.join(CSRC, name + ".hip")
         obj = os.path.join(objdir, name + ".o")
-        stamp = [f"-DSDDP_HEADER_STAMP={header_stamp()}ULL"] if name == "sddp_api" else []   # (user builds: userterms.py)
-        jobs.append((obj, src, base + stamp + [src, "-o", obj]))
+        jobs.append((obj, src, compile_command() + extra + defs + ["-c", src, "-o", obj]))
     inst = os.path.join(CSRC, "sddp_inst.hip")
-    for fn, model, mname in INSTANCES:
-        obj = os.path.join(objdir, "inst_" + fn + ".o")
-        defs = ["-DSDDP_INST_MODEL=" + model, "-DSDDP_INST_FN=ops_" + fn, '-DSDDP_INST_NAME="' + mname + '"', *INSTANCE_FLAGS.get(fn, [])]
-        if fn in RESUME_INSTANCES:
-            robj = os.path.join(objdir, "inst_" + fn + "_resume.o")
-            jobs.append((robj, inst, base + defs + ["-DSDDP_INST_RESUME", inst, "-o", robj]))
-            defs.append("-DSDDP_INST_HAS_RESUME")
-        jobs.append((obj, inst, base + defs + [inst, "-o", obj]))
+    for unit, _ in inst_units():
+        obj = os.path.join(objdir, "inst_" + unit + ".o")
+        jobs.append((obj, inst, compile_command(unit) + extra + ["-c", inst, "-o", obj]))
     todo, left_stale = [], []
     for obj, src, cmd in jobs:
         picked = only is not None and any(obj.endswith("inst_" + o + ".o") for o in only)
@@ -237,7 +271,7 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
     if todo:
         with ThreadPoolExecutor(max_workers=workers) as ex:
             list(ex.map(compile_one, todo))
-    link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *[j[0] for j in jobs], "-o", LIB_PATH]
+    link = [compile_command()[0], "--offload-arch=gfx950", "-shared", "-fPIC", *[j[0] for j in jobs], "-o", LIB_PATH]
     if verbose:
         print(" ".join(link), flush=True)
     subprocess.run(link, check=True)

@@ -25,23 +25,16 @@
 
 using namespace sddp;
 
-// the model builds of the library (sddp_inst.hip, one translation unit each; srbd_horizon_amd/_lib.py INSTANCES)
+// The model builds of the library (sddp_inst.hip, one translation unit each).  This file names none of them: it is compiled with
+// -DSDDP_BUILDS="X(ops_a) X(ops_b) ...", the accessors of srbd_horizon_amd/_lib.py INSTANCES, and expands the list twice: here into
+// their declarations, below into the table that model_ops searches.  An entry without its translation unit does not link.
+#ifndef SDDP_BUILDS
+#error "compile with -DSDDP_BUILDS=\"X(ops_...) X(ops_...) ...\": the accessors of the model builds (srbd_horizon_amd/_lib.py INSTANCES)"
+#endif
 namespace sddp {
-const ModelOps* ops_srbd13();
-const ModelOps* ops_srbd13_b();
-const ModelOps* ops_srbd13_s();
-const ModelOps* ops_srbd13_bs();
-const ModelOps* ops_srbd37();
-const ModelOps* ops_srbd37_b();
-const ModelOps* ops_srbd37_s();
-const ModelOps* ops_srbd37_bs();
-const ModelOps* ops_lip30();
-const ModelOps* ops_srbd61();
-const ModelOps* ops_srbd13_x();
-const ModelOps* ops_srbd37_x();
-const ModelOps* ops_srbd61_x();
-const ModelOps* ops_srbd61_b();
-const ModelOps* ops_lip30_x();
+#define X(fn) const ModelOps* fn();
+SDDP_BUILDS
+#undef X
 
 std::string& create_error() {
     thread_local std::string e;
@@ -135,32 +128,28 @@ int base_model(int id) {
     return u ? u->base : id;
 }
 
-// bar: the barrier build of the SRBD models (friction cone and / or variable bounds), so2: the full second-order build
+#define X(fn) fn,
+const ModelOps* (*const kBuilds[])() = {SDDP_BUILDS};
+#undef X
+
+// The build of model `id` with exactly these traits, or null.  bar: the barrier build (friction cone and / or variable bounds), so2:
+// the full second-order build, xr: user rows.  What the list has no build for finds nothing: user rows together with a barrier or
+// second_order = 2, srbd61 with second_order = 2 (LDS is full).  A user build is its plain build only, with its user rows.
 const ModelOps* model_ops(int id, bool bar = false, bool so2 = false, bool xr = false) {
-    if (id >= kUserId0) {   // a user build: its plain build only, with its user rows
+    if (id >= kUserId0) {
         const UserBuild* u = user_build(id);
         return (u && !bar && !so2) ? u->ops : nullptr;
     }
-    if (xr) {     // user rows: plain builds only
-        if (bar || so2) return nullptr;
-        switch (id) {
-            case SDDP_MODEL_SRBD13: return ops_srbd13_x();
-            case SDDP_MODEL_SRBD37: return ops_srbd37_x();
-            case SDDP_MODEL_LIP30: return ops_lip30_x();
-            case SDDP_MODEL_SRBD61: return ops_srbd61_x();
-            default: return nullptr;
-        }
+    for (auto build : kBuilds) {
+        const ModelOps* o = build();
+        if (o->model == id && o->bar == bar && o->so2 == so2 && o->xr == xr) return o;
     }
-    switch (id) {
-        case SDDP_MODEL_SRBD13: return so2 ? (bar ? ops_srbd13_bs() : ops_srbd13_s()) : (bar ? ops_srbd13_b() : ops_srbd13());
-        case SDDP_MODEL_SRBD37: return so2 ? (bar ? ops_srbd37_bs() : ops_srbd37_s()) : (bar ? ops_srbd37_b() : ops_srbd37());
-        case SDDP_MODEL_LIP30: return ops_lip30();
-        case SDDP_MODEL_SRBD61: return so2 ? nullptr : (bar ? ops_srbd61_b() : ops_srbd61());   // no second_order = 2 build: LDS is full
-        default: return nullptr;
-    }
+    return nullptr;
 }
-// models whose only build is the default one: linear-quadratic (lip30), or no barrier / second_order = 2 build instantiated (srbd61)
+// lip30 is linear-quadratic: its barrier weight and second_order = 2 select nothing (and are not an error), whatever builds exist
 bool single_build(int id) { return id == SDDP_MODEL_LIP30; }
+// the plain builds: no barrier, no second_order = 2, no user rows and so no user build.  What exists for them only asks here
+bool plain_build(const sddp_handle* h) { return h->ops->table_kernels; }
 
 // a user build's handles carry exactly its rows (weights / kinds / constant parts in the extra_* table)
 const char* check_user_rows(int id, const sddp_model_consts* c) {
@@ -451,7 +440,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
         return fail(nullptr, SDDP_ERR_HIP, "no HIP device visible: the SDDP engine has no CPU fallback");
     sddp_handle* h = new (std::nothrow) sddp_handle();
     if (!h) return fail(nullptr, SDDP_ERR_NOMEM, "out of host memory");
-    h->model_id = model_id; h->N = N; h->B = batch; h->d = d; h->ops = ops; h->bar = bar; h->so2 = so2;
+    h->model_id = model_id; h->N = N; h->B = batch; h->d = d; h->ops = ops;
     if (opts) h->opts = *opts; else sddp_default_options(&h->opts);
     if (consts) h->consts = *consts; else sddp_default_consts_for(model_id, &h->consts);
     int rc = validate_options(h, h->opts);
@@ -461,8 +450,8 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     auto alloc = [&](auto*& p, size_t bytes) { return acquire(h, p, bytes); };
     hipError_t e = hipSuccess;
     // the bounds of the bound barrier and the user rows' table live in device memory (DevConsts::box, DevConsts::xr)
-    if (bar) e = alloc(h->box_dev, kBoxWords * sizeof(double));
-    if (xr && e == hipSuccess) e = alloc(h->xr_dev, kXrWords * sizeof(double));
+    if (ops->bar) e = alloc(h->box_dev, kBoxWords * sizeof(double));
+    if (ops->xr && e == hipSuccess) e = alloc(h->xr_dev, kXrWords * sizeof(double));
     if (e == hipSuccess) e = upload_side_tables(h->consts, h->dc, h->box_dev, h->xr_dev);
     const size_t D = sizeof(double);
     {
@@ -644,7 +633,7 @@ int sddp_solve_device(sddp_handle* h, const double* d_params) {
 // ---- resumable solves -----------------------------------------------------------------------------------------------
 int sddp_enable_resume(sddp_handle* h, int on) {
     if (!h) return SDDP_ERR_ARG;
-    if (on && (h->model_id >= kUserId0 || h->bar || h->so2 || h->consts.n_extra != 0))
+    if (on && !plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build)");
     if (on && !h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no resumable kernels");
@@ -947,7 +936,7 @@ int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* s
 int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_model_consts* consts) {
     if (!h) return SDDP_ERR_ARG;
     if (!consts) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: consts is NULL");
-    if (h->model_id >= kUserId0 || h->bar || h->so2 || h->consts.n_extra != 0)
+    if (!plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: per-instance constants exist for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build)");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;

@@ -2,11 +2,13 @@
 //
 // The library is built from one translation unit per model build (sddp_inst.hip, compiled once per entry of
 // srbd_horizon_amd/_lib.py INSTANCES, in parallel) plus the model-independent host code (sddp_api.hip).  A model build reaches
-// the API through a ModelOps table of plain function pointers: nothing templated crosses a translation unit.
+// the API through a ModelOps table: what the build is (model, traits), and plain function pointers to what it can do.  Nothing
+// templated crosses a translation unit, and sddp_api.hip asks the table instead of knowing the builds.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -21,8 +23,21 @@ struct Dims {
     int nx, nu, np, nrec;
 };
 
-// what a model build provides (sddp_launch.hpp: make_ops<M>)
+// the built-in model (SDDP_MODEL_*) of a model name, -1: none
+inline int model_of_name(const char* name) {
+    static const char* const names[] = {"srbd13", "srbd37", "lip30", "srbd61"};      // in the order of sddp.h's SDDP_MODEL_* values
+    static_assert(SDDP_MODEL_SRBD13 == 0 && SDDP_MODEL_SRBD37 == 1 && SDDP_MODEL_LIP30 == 2 && SDDP_MODEL_SRBD61 == 3, "order of names");
+    for (int i = 0; i < 4; ++i)
+        if (std::strcmp(name, names[i]) == 0) return i;
+    return -1;
+}
+
+// what a model build is and provides (sddp_launch.hpp: make_ops<M>)
 struct ModelOps {
+    // the build's key: a handle's build is the one whose model and traits are the ones asked for (sddp_api.hip model_ops)
+    int model;             // the built-in model it is a build of (a user build: the model it was generated for)
+    bool bar, so2, xr;     // barrier build; full second-order build (second_order = 2); user rows.  None of them: a plain build
+    bool table_kernels;    // every kernel has a table form (per-instance constants, sddp_set_instance_consts): the plain builds
     Dims dims;
     bool uses_mw;          // 4 wavefronts per instance (sddp_kernels_mw.hpp); else one
     bool w2_build;         // a half-register-file build exists (two instances per SIMD / two workgroups per CU)
@@ -65,8 +80,6 @@ struct sddp_handle {
     long long n_ms = 0;
     std::string err;
     bool have_x0 = false, have_xws = false, have_uws = false, have_params = false;
-    bool bar = false;               // friction-cone barrier build (consts.friction_barrier_weight > 0)
-    bool so2 = false;               // full second-order build (opts.second_order == 2 at sddp_create)
     double* tick_in = nullptr;      // [B][np + nx] staging of sddp_advance
     double* step_buf = nullptr;     // [B][2 nx + nu + np] operands and result of sddp_model_step
     char* tick_pin = nullptr;       // two pinned images of tick_in (small batches)

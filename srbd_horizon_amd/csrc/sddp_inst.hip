@@ -1,9 +1,11 @@
 // sddp_inst.hip -- one model build of the library: compiled once per entry of srbd_horizon_amd/_lib.py INSTANCES with
 //   -DSDDP_INST_MODEL=<device model type>  -DSDDP_INST_FN=<name of the accessor>  -DSDDP_INST_NAME="<model name>"
 // (in parallel: the solve kernels of one model build are 10-30 s of device code generation each).  The accessor returns the
-// build's table of launchers (sddp_handle.hpp ModelOps); sddp_api.hip picks a table by (model_id, barrier, second_order).
-// The plain builds (_lib.py RESUME_INSTANCES) are compiled a second time with -DSDDP_INST_RESUME: that unit holds nothing but the
-// RESUME instantiations of the solve kernels and their launcher, which the main unit (-DSDDP_INST_HAS_RESUME) enters in its table.
+// build's table (sddp_handle.hpp ModelOps): which model it is a build of, its traits and its launchers.  sddp_api.hip receives
+// the accessors' names from the same list and finds a handle's build among them by (model, traits).
+// The plain builds (the entries without traits) are compiled a second time with -DSDDP_INST_RESUME: that unit holds nothing but
+// the RESUME instantiations of the solve kernels and their launcher, which the main unit (-DSDDP_INST_HAS_RESUME) enters in its
+// table.  Either flag on a build with traits does not compile (sddp_launch.hpp launch_solve_resume) or does not link.
 #include "sddp_launch.hpp"
 
 #if !defined(SDDP_INST_MODEL) || !defined(SDDP_INST_FN) || !defined(SDDP_INST_NAME)

@@ -27,12 +27,18 @@ constexpr bool has_w2() {
 template <class M>
 constexpr int threads_of() { return use_mw<M>() ? kThreadsMW : kWave; }
 
+// A build's traits are M::BAR (barrier build), M::SO2 (full second order) and M::NXR > 0 (user rows; the user builds too).  A
+// PLAIN build has none of them.  This is the one statement of the rule: what only the plain builds have refers to it, and
+// sddp_api.hip reads the outcome from the build's table (ModelOps::table_kernels, launch_solve_resume) instead of deriving it.
+template <class M>
+constexpr bool is_plain() { return !M::BAR && !M::SO2 && M::NXR == 0; }
+
 // Heterogeneous fleets (sddp_set_instance_consts): on the plain builds every kernel has a table form that takes the handle's
 // constants table behind its arguments and reads instance b's row of it (sddp_kernels.hpp args_of): a second instantiation of
 // the same template, except for the policy export, whose table form is a kernel of its own (policy_kernel[_mw]_h).  sddp_api.hip
 // refuses the table on every other build, so h->ctab != nullptr implies has_hetero<M>().
 template <class M>
-constexpr bool has_hetero() { return !M::BAR && !M::SO2 && M::NXR == 0; }
+constexpr bool has_hetero() { return is_plain<M>(); }
 // f(tab...): a launcher with the kernels' trailing argument pack, the handle's table when it is active and nothing otherwise.  A
 // build without has_hetero never instantiates f(table), and so none of the table kernels.
 template <class M, class F>
@@ -53,7 +59,11 @@ inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return 
 // device module the ordinary one-wave kernels come out with another register allocation and 4 bytes less or more scratch, though
 // not a statement of theirs differs (profiles/resume/README.md).
 template <class M>
-constexpr bool has_resume() { return has_hetero<M>(); }
+constexpr bool has_resume() { return is_plain<M>(); }
+// Policy export: the plain builds and their user-row forms, which are plain builds but for the rows (sddp_models.hpp: NXR > 0
+// excludes BAR and SO2).  The barrier and second_order = 2 builds have no policy kernel.
+template <class M>
+constexpr bool has_policy() { return is_plain<M>() || M::NXR > 0; }
 
 // only the kernel a model actually uses is instantiated
 template <class M, bool RES, class... Tab> auto pick_solve(int waves_per_simd) {
@@ -225,8 +235,7 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
 
 // policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
 // policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel (the one-wave kernel: at most 8 per CU); the work
-// buffers dft / rec are the solve's, per slot.  Plain builds only (no barrier, no second_order = 2): make_ops leaves the entry null
-// elsewhere.
+// buffers dft / rec are the solve's, per slot.  has_policy<M>() builds only: make_ops leaves the entry null elsewhere.
 template <class M>
 int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
     return with_table<M>(h, [&](auto... tab) {
@@ -261,6 +270,9 @@ void launch_eval_knots(const DevConsts& dc, int N, int nk, const int* dk, const 
 template <class M>
 ModelOps make_ops(const char* name) {
     ModelOps o;
+    o.model = model_of_name(name);
+    o.bar = M::BAR; o.so2 = M::SO2; o.xr = M::NXR > 0;
+    o.table_kernels = has_hetero<M>();
     o.dims = {M::NX, M::NU, M::NP, M::NREC};
     o.uses_mw = use_mw<M>();
     o.w2_build = has_w2<M>();
@@ -270,7 +282,7 @@ ModelOps make_ops(const char* name) {
     o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
-    if constexpr (!M::BAR && !M::SO2) o.launch_policy = launch_policy<M>;
+    if constexpr (has_policy<M>()) o.launch_policy = launch_policy<M>;
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

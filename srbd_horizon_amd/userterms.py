@@ -337,10 +337,10 @@ SDDP_USER_EXPORT int sddp_user_rows() {{ return {len(spec.rows)}; }}
 
 # ---- compilation ------------------------------------------------------------------------------------------------------------
 def _command(src_path: str, out_path: str, root: str = _lib.ROOT):
-    csrc, inc = os.path.join(root, "srbd_horizon_amd", "csrc"), os.path.join(root, "include")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    return [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-I" + inc, "-I" + csrc,
-            f"-DSDDP_HEADER_STAMP={_lib.header_stamp(root)}ULL", "-shared", src_path, os.path.join(csrc, "sddp_sort.hip"), "-o", out_path]
+    """A user build is compiled like a model build of the library (_lib.compile_command); the tail is its own: one shared object of
+    the generated unit and the queue sort, which exports the accessors alone."""
+    return _lib.compile_command(root=root) + ["-fvisibility=hidden", f"-DSDDP_HEADER_STAMP={_lib.header_stamp(root)}ULL", "-shared", src_path,
+                                              os.path.join(root, "srbd_horizon_amd", "csrc", "sddp_sort.hip"), "-o", out_path]
 
 
 def build_key(src: str, root: str = _lib.ROOT) -> str:

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Instruction mix per PHASE of the one-wavefront solve kernel, from a listing with phase markers:
 
-    hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -Isrbd_horizon_amd/csrc -DSDDP_MARKS -DSDDP_INST_MODEL=Srbd13 \
-          -DSDDP_INST_FN=ops_srbd13 '-DSDDP_INST_NAME="srbd13"' -S --cuda-device-only srbd_horizon_amd/csrc/sddp_inst.hip -o srbd13_marks.s
+    $(python -c "from srbd_horizon_amd import _lib; print(*_lib.compile_command('srbd13'))") -DSDDP_MARKS \
+          -S --cuda-device-only srbd_horizon_amd/csrc/sddp_inst.hip -o srbd13_marks.s
     python tools/isa_phase_mix.py srbd13_marks.s solve_kernel_w2
 
--DSDDP_MARKS turns the SDDP_TICK(i) phase boundaries of csrc/sddp_kernels.hpp into assembler comments.  Every instruction of the
+(_lib.compile_command: build()'s own command for that unit of the library.)  -DSDDP_MARKS turns the SDDP_TICK(i) phase boundaries of csrc/sddp_kernels.hpp into assembler comments.  Every instruction of the
 kernel is attributed to the last marker in STATIC order; blocks are split by loop depth, so that the body of a knot loop (executed
 once per knot: its inner loops are fully unrolled or run one trip) is counted apart from the code around it.  The counts are
 wave-instructions per knot and phase -- what the SIMD has to issue -- beside the FMAs the algorithm needs at wave level."""

@@ -1,12 +1,13 @@
-"""Code-object resources of every kernel of every model build (srbd_horizon_amd/_lib.py INSTANCES): SGPRs, VGPRs, AGPRs, scratch
-bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports them for gfx950.
+"""Code-object resources of every kernel of every translation unit of the model builds (srbd_horizon_amd/_lib.py inst_units: one
+unit per entry of INSTANCES, and the units `<build>_resume` of the plain builds' resumable solve kernels): SGPRs, VGPRs, AGPRs,
+scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports them for gfx950.
 
-    python tools/kernel_resources.py [-j JOBS] [--only srbd13,srbd37] > resources.txt
+    python tools/kernel_resources.py [-j JOBS] [--only srbd13,srbd13_resume] [--root OTHER_TREE] > resources.txt
 
-Each build is compiled device-only with build()'s own flags plus -Rpass-analysis=kernel-resource-usage; nothing is linked or
-written beside the table.  Two trees compile to the same kernels exactly when their tables are equal line by line: what a change
-that must leave the existing kernels alone is checked with (profiles/iteration_refactor, profiles/hetero).  The LDS column is 0
-for every kernel that uses dynamic LDS only."""
+Each unit is compiled device-only with build()'s own command (_lib.compile_command) plus -Rpass-analysis=kernel-resource-usage;
+nothing is linked or written beside the table.  Two trees compile to the same kernels exactly when their tables are equal line by
+line: what a change that must leave the existing kernels alone is checked with (profiles/iteration_refactor, profiles/hetero,
+profiles/build_table).  The LDS column is 0 for every kernel that uses dynamic LDS only."""
 import argparse
 import os
 import re
@@ -32,12 +33,9 @@ def demangle(names):
     return out.stdout.splitlines()
 
 
-def compile_one(job):
-    fn, model, mname = job
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + _lib.INCLUDE, "-I" + _lib.CSRC,
-           "-DSDDP_INST_MODEL=" + model, "-DSDDP_INST_FN=ops_" + fn, '-DSDDP_INST_NAME="' + mname + '"', *_lib.INSTANCE_FLAGS.get(fn, []),
-           "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(_lib.CSRC, "sddp_inst.hip"), "-o", os.devnull]
+def compile_one(fn, root=ROOT):
+    cmd = _lib.compile_command(fn, root) + ["--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                                            os.path.join(root, "srbd_horizon_amd", "csrc", "sddp_inst.hip"), "-o", os.devnull]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"{fn}: {r.stderr[-2000:]}")
@@ -61,12 +59,13 @@ def compile_one(job):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
-    ap.add_argument("--only", default="", help="comma-separated accessor suffixes of _lib.INSTANCES")
+    ap.add_argument("--only", default="", help="comma-separated unit names of _lib.inst_units()")
+    ap.add_argument("--root", default=ROOT, help="the tree whose csrc is compiled, with this tree's unit list and command (default: this tree)")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
-    jobs = [j for j in _lib.INSTANCES if not only or j[0] in only]
+    jobs = [name for name, _ in _lib.inst_units() if not only or name in only]
     with ThreadPoolExecutor(max_workers=max(1, args.j)) as ex:
-        done = dict(ex.map(compile_one, jobs))
+        done = dict(ex.map(lambda fn: compile_one(fn, args.root), jobs))
     print(f"{'build':<10} {'kernel':<72} {'SGPR':>5} {'VGPR':>5} {'AGPR':>5} {'Scratch':>8} {'Occ':>4} {'LDS':>7}")
     for fn in sorted(done):
         for r in done[fn]:
