@@ -53,6 +53,10 @@ class SddpStats(C.Structure):
 STATS_DTYPE = np.dtype([("cost", "f8"), ("alpha", "f8"), ("gap", "f8"), ("mu", "f8"), ("expected", "f8"), ("rho", "f8"),
                         ("iters", "i4"), ("converged", "i4"), ("status", "i4"), ("rollouts", "i4")])
 assert STATS_DTYPE.itemsize == C.sizeof(SddpStats) == 64
+LOG_WORDS, LOG_MAX_ROWS = 16, 4096      # one record of the iteration log (include/sddp.h); the largest `rows`
+# the words of a record, by name
+LOG_FIELDS = ("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", "theta", "mu", "tried", "slack", "iters", "rollouts",
+              "mu_bumps", "reserved")
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = 8, 16
 STATS_F64_COST, STATS_I32_ITERS, STATS_I32_STATUS, STATS_I32_ROLLOUTS = 0, 12, 14, 15
@@ -102,6 +106,9 @@ SYMBOLS = {
     "sddp_continue_device": (C.c_int, [_vp, _vp]),
     "sddp_continue_resident": (C.c_int, [_vp]),
     "sddp_unfinished_count": (C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_int)]),
+    "sddp_enable_iteration_log": (C.c_int, [_vp, C.c_int]),
+    "sddp_iteration_log_info": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_fetch_iteration_log": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sddp_set_instance_classes": (C.c_int, [_vp, _vp, C.c_int]),
     "sddp_set_instance_classes_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
     "sddp_class_history": (C.c_int, [_vp, C.c_int, _P(C.c_double), _P(C.c_longlong)]),
@@ -148,7 +155,7 @@ _SINK = ("-mllvm", "-sink-insts-to-avoid-spills")
 # THE list of model builds: what build() compiles and hands to csrc/sddp_api.hip, which finds a handle's build in it by
 # (model, traits); no two entries share that key (build() checks).  The builds without traits are the plain builds: they alone have
 # table kernels (sddp_set_instance_consts) and resumable solve kernels (sddp_enable_resume), the latter compiled in a translation
-# unit of their own (inst_units).  A new build: its alias in csrc/sddp_models.hpp and one entry here.
+# unit of their own (inst_units), and the iteration-log form of those in another (log_units).  A new build: its alias in csrc/sddp_models.hpp and one entry here.
 INSTANCES = [
     Build("srbd13", "Srbd13", "srbd13"), Build("srbd13_b", "Srbd13B", "srbd13", ("bar",)),
     Build("srbd13_s", "Srbd13S", "srbd13", ("so2",)), Build("srbd13_bs", "Srbd13BS", "srbd13", ("bar", "so2")),
@@ -175,23 +182,37 @@ def inst_units():
     """The translation units of csrc/sddp_inst.hip as (unit name, definitions and options): one per entry of INSTANCES, named by
     its accessor suffix, and for every build without traits the unit <suffix>_resume of its resumable solve kernels, whose
     launcher the build's main unit declares (-DSDDP_INST_HAS_RESUME).  A build with traits that asked for one would not compile
-    (csrc/sddp_launch.hpp launch_solve_resume)."""
+    (csrc/sddp_launch.hpp launch_solve_resume).  The main unit of such a build also declares (-DSDDP_INST_HAS_LOG) the launcher of
+    its iteration-log kernels, which log_units() lists: translation_units() is what links."""
     units = []
     for b in INSTANCES:
         defs = ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
         if not b.traits:
             units.append((b.fn + "_resume", defs + ["-DSDDP_INST_RESUME"]))
-            defs = defs + ["-DSDDP_INST_HAS_RESUME"]
+            defs = defs + ["-DSDDP_INST_HAS_RESUME", "-DSDDP_INST_HAS_LOG"]
         units.append((b.fn, defs))
     return units
 
 
+def log_units():
+    """For every build without traits the unit <suffix>_log: the solve kernels' instantiations that keep an iteration log
+    (sddp_enable_iteration_log; they are resumable instantiations as well) and their launcher, a translation unit of their own
+    like <suffix>_resume and for the same reason."""
+    return [(b.fn + "_log", ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags,
+                             "-DSDDP_INST_LOG"]) for b in INSTANCES if not b.traits]
+
+
+def translation_units():
+    """Every translation unit of csrc/sddp_inst.hip that build() compiles and links: inst_units() and log_units()."""
+    return inst_units() + log_units()
+
+
 def compile_command(unit: str | None = None, root: str = ROOT) -> list:
     """The head of every compile command of the library's HIP sources: the compiler, its flags, the include paths of the tree at
-    `root` and, for a unit of inst_units(), that unit's definitions.  The tail is the caller's: -c or -shared, source, output."""
+    `root` and, for a unit of translation_units(), that unit's definitions.  The tail is the caller's: -c or -shared, source, output."""
     head = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC",
             "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "srbd_horizon_amd", "csrc")]
-    return head + (dict(inst_units())[unit] if unit is not None else [])
+    return head + (dict(translation_units())[unit] if unit is not None else [])
 
 
 def _newer(target: str, deps) -> bool:
@@ -241,7 +262,7 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
         obj = os.path.join(objdir, name + ".o")
         jobs.append((obj, src, compile_command() + extra + defs + ["-c", src, "-o", obj]))
     inst = os.path.join(CSRC, "sddp_inst.hip")
-    for unit, _ in inst_units():
+    for unit, _ in translation_units():
         obj = os.path.join(objdir, "inst_" + unit + ".o")
         jobs.append((obj, inst, compile_command(unit) + extra + ["-c", inst, "-o", obj]))
     todo, left_stale = [], []

@@ -644,7 +644,12 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     h->up_off = 0;
     release(h, h->carry);
     release(h, h->resumable);
-    if (!on) return SDDP_OK;
+    if (!on) {   // the iteration log rides on the resumable kernels: it goes with them
+        release(h, h->ilog);
+        release(h, h->ilog_n);
+        h->ilog_rows = 0;
+        return SDDP_OK;
+    }
     const size_t flag_bytes = (3 * size_t(h->B) + 1) * sizeof(int);
     int* flags = nullptr;
     double* carry = nullptr;
@@ -700,6 +705,60 @@ int sddp_unfinished_count(sddp_handle* h, int first, int count, int* n) {
     const int rc = launch(h, unfinished_count_kernel, 1, 256, 0, first, count, (const int*)h->resumable, d_n);
     if (rc != SDDP_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(n, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
+}
+
+// ---- iteration log ------------------------------------------------------------------------------------------------------
+int sddp_enable_iteration_log(sddp_handle* h, int rows) {
+    if (!h) return SDDP_ERR_ARG;
+    if (rows < 0 || rows > SDDP_LOG_MAX_ROWS) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: rows must be 1 .. 4096 (0: off)");
+    if (rows > 0 && !plain_build(h))
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: the iteration log exists for the plain builds only (no user rows, no barrier, "
+                                     "no second_order = 2, no user build), like sddp_enable_resume");
+    if (rows > 0 && !h->ops->launch_solve_log) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no iteration-log kernels");
+    if (rows > 0 && !h->carry)
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: call sddp_enable_resume first (the log is kept by the resumable kernels; plain "
+                                     "builds only)");
+    if (rows == h->ilog_rows) return SDDP_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still write the buffers
+    h->up_off = 0;
+    release(h, h->ilog);
+    release(h, h->ilog_n);
+    h->ilog_rows = 0;
+    if (rows == 0) return SDDP_OK;
+    double* log = nullptr;
+    int* n = nullptr;
+    const size_t log_bytes = size_t(h->B) * rows * kLogWords * sizeof(double);
+    hipError_t e = acquire(h, log, log_bytes);
+    if (e == hipSuccess) e = acquire(h, n, size_t(h->B) * sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(log, 0, log_bytes, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(n, 0, size_t(h->B) * sizeof(int), h->stream);
+    if (e != hipSuccess) {      // all or nothing
+        (void)hipGetLastError();
+        release(h, log); release(h, n);
+        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_iteration_log: out of device memory");
+    }
+    h->ilog = log;
+    h->ilog_n = n;
+    h->ilog_rows = rows;
+    return SDDP_OK;
+}
+
+int sddp_iteration_log_info(sddp_handle* h, int* rows, int* words) {
+    if (!h) return SDDP_ERR_ARG;
+    if (rows) *rows = h->ilog_rows;
+    if (words) *words = kLogWords;
+    return SDDP_OK;
+}
+
+int sddp_fetch_iteration_log(sddp_handle* h, int first, int count, double* out, int* n_out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->ilog) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
+    if (!out && !n_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t w = size_t(h->ilog_rows) * kLogWords;
+    if (out) HIP_TRY(h, hipMemcpyAsync(out, h->ilog + size_t(first) * w, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (n_out) HIP_TRY(h, hipMemcpyAsync(n_out, h->ilog_n + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return sddp_synchronize(h);
 }
 
@@ -1121,6 +1180,12 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
         case 8:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
             if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
             *ptr = h->policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
+        case 9:   // the iteration log [B][rows][16] and (10) its record counts [B] of sddp_enable_iteration_log
+        case 10:
+            if (!h->ilog) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
+            if (which == 9) { *ptr = h->ilog; n = (long long)(size_t(h->B) * h->ilog_rows * kLogWords * sizeof(double)); }
+            else { *ptr = h->ilog_n; n = (long long)(size_t(h->B) * sizeof(int)); }
+            break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");
     }
     if (bytes) *bytes = n;

@@ -49,6 +49,9 @@ struct ModelOps {
     // through this table instead of instantiating the key kernel a second time
     int (*launch_solve_resume)(sddp_handle*, SolveArgs, int, int) = nullptr;
     int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
+    // iteration log: the launcher of the LOG instantiations (RESUME as well), in a unit of their own again (-DSDDP_INST_LOG); null:
+    // the build has none
+    int (*launch_solve_log)(sddp_handle*, SolveArgs, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
@@ -129,6 +132,10 @@ struct sddp_handle {
     int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
                                     // then one word: the result of sddp_unfinished_count
     bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
+    // iteration log (sddp_enable_iteration_log; needs `carry`): non-null = on, and every solve launch runs the LOG instantiation
+    double* ilog = nullptr;         // [B][ilog_rows][kLogWords] one record per line search of an instance's last solve (LogArgs::log)
+    int* ilog_n = nullptr;          // [B] records written (LogArgs::count)
+    int ilog_rows = 0;
     // phase-level mode (sddp_debug_set_phase_mode, diagnostics): what sddp_backward / sddp_forward launch with.  Default (0, 0): the
     // Gauss-Newton sweep on open gaps, as those entry points always ran
     double phase_theta = 0.0;       // weight of the second-order term of the sweep (the solve's theta: 0 or 1)

@@ -103,6 +103,35 @@ struct ResumeArgs {
                         // instance is left as it is
 };
 struct NoResume {};    // stands in its place in the ordinary instantiations: nothing is passed, nothing is read
+// Iteration log (sddp_enable_iteration_log): one record of kLogWords doubles per line search an instance ran, in the layout of the
+// first 12 words of the C oracle's trace record (oracle/c/ddp_engine.inc) and four words more:
+//   0 J of the iterate the search starts from | 1 A1 | 2 B2 | 3 rho | 4 gap | 5 expected | 6 accepted alpha (0: none) |
+//   7 accepted J (0: none) | 8 theta of this sweep | 9 mu of this sweep (after any bump) | 10 candidates tried (index of the accepted
+//   step length in the ladder + 1, or the ladder's length) | 11 slack | 12 iters after this search | 13 rollouts after this search
+//   (cumulative, as sddp_stats.rollouts) | 14 mu bumps in this sweep | 15 reserved, 0
+// The LOG instantiations of the solve kernels (always RESUME instantiations as well: a continue launch appends to the records of
+// the cut solve) take it as a kernel argument of their own behind ResumeArgs.  Both buffers are per INSTANCE.
+constexpr int kLogWords = SDDP_LOG_WORDS;
+static_assert(kLogWords == 16, "log_record writes 16 words");
+struct LogArgs {
+    double* log;        // [B][rows][kLogWords]
+    int* count;         // [B]  records written; saturates at rows (later searches are not logged)
+    int rows;
+};
+struct NoLog {};
+// what an instance's solve keeps for its records: the records written so far, the mu bumps of the sweep, the step lengths tried
+template <bool LOG> struct LogState {};
+template <> struct LogState<true> { int n = 0, bumps = 0, tried = 0; };
+// one record, by the calling lane alone: 16 contiguous doubles
+__device__ __forceinline__ void log_record(const LogArgs& G, const int b, const int row, const double J, const double A1, const double B2,
+                                           const double rho, const double gap, const double expected, const double a_acc, const double J_acc,
+                                           const double theta, const double mu, const int tried, const double slack, const int iters,
+                                           const int rollouts, const int bumps) {
+    double* r = G.log + (size_t(b) * G.rows + row) * kLogWords;
+    r[0] = J; r[1] = A1; r[2] = B2; r[3] = rho; r[4] = gap; r[5] = expected; r[6] = a_acc; r[7] = J_acc;
+    r[8] = theta; r[9] = mu; r[10] = double(tried); r[11] = slack; r[12] = double(iters); r[13] = double(rollouts);
+    r[14] = double(bumps); r[15] = 0.0;
+}
 // a trailing kernel argument as the kernel declares it: the table pointer __restrict__ as it always was, ResumeArgs by value
 template <class T> struct KernelArg { using type = T; };
 template <class T> struct KernelArg<T*> { using type = T* __restrict__; };
@@ -818,8 +847,12 @@ __device__ double rollout(const DevConsts& c, int N, const double* __restrict__ 
 // (1 - alpha) d only up to rounding (and are noise where the engine carries exact zeros), and phase_defects sums the cost in
 // another order than the rollout that produced J -- either would break the bit identity with the uncut solve.  With RESUME false
 // every such line is behind `if constexpr`: the ordinary instantiation is the code it was.
-template <class M, bool RESUME = false, class Res = NoResume>
-__device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res()) {
+// LOG (sddp_enable_iteration_log; RESUME instantiations only): one record per line search goes to the instance's rows of the log, written
+// by lane 0 behind the search, where the accepted trajectory's pointers flip -- after the rollout's stores and before the next loads.
+// Every value of a record is wave-uniform as the iteration has it.  Every such line is behind `if constexpr (LOG)`.
+template <class M, bool RESUME = false, class Res = NoResume, bool LOG = false, class Lg = NoLog>
+__device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res(), const Lg& G = Lg()) {
+    static_assert(!LOG || RESUME, "the iteration log rides on the resumable instantiation");
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int lane = threadIdx.x;
     const int N = A.N;
@@ -880,6 +913,10 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
             if (lane == 0) R.resumable[2 * A.B + b] = 1;
         }
     }
+    LogState<LOG> lg;
+    if constexpr (LOG) {
+        if (resumed) lg.n = __builtin_amdgcn_readfirstlane(G.count[b]);      // a continue launch appends
+    }
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
@@ -890,11 +927,13 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
             double dV1, G1, G2, qu_inf, a_win = 0.0, J_win = 0.0;
             bool ok = true, stop = false, accepted = false;
             do {   // at most twice: a failed sweep / line search with the second-order term is redone without it
+                if constexpr (LOG) { lg.bumps = 0; lg.tried = 0; }
                 while (true) {
                     ok = backward_sweep<M>(A.c, N, P, dft, rec, gains, mu, theta, s, lane, dV1, G1, G2, qu_inf, gap > 0.0 SDDP_T_PASS);
                     if (ok) break;
                     if (theta != 0.0) { theta = 0.0; continue; }
                     mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
+                    if constexpr (LOG) ++lg.bumps;
                     if (mu > o.mu_max) break;
                 }
                 if (!ok) { status = 2; stop = true; break; }
@@ -923,6 +962,7 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
                     const unsigned long long mask = __ballot(good);
                     if (mask) {
                         win = __ffsll((long long)mask) - 1;
+                        if constexpr (LOG) lg.tried += win + 1;
                         a_win = __shfl(a, win, kWave);
                         J_win = __shfl(Jl, win, kWave);
                         if (win >= kSlots) {   // the winner is not one of the kept candidates: roll it again into slot 0
@@ -934,7 +974,16 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
                         accepted = true;
                         break;
                     }
+                    if constexpr (LOG) lg.tried += __popcll(__ballot(valid));
                     a_base = __shfl(a, kWave - 1, kWave) * o.line_search_decrease_factor;
+                }
+                if constexpr (LOG) {
+                    if (lg.n < G.rows) {
+                        if (lane == 0)
+                            log_record(G, b, lg.n, J, A1, B2, rho, gap, expected, accepted ? a_win : 0.0, accepted ? J_win : 0.0, theta, mu,
+                                       lg.tried, slack, iters + (accepted ? 1 : 0), rollouts, lg.bumps);
+                        ++lg.n;
+                    }
                 }
                 if (accepted) break;
                 if (theta != 0.0) { theta = 0.0; continue; }                       // redo with the plain Gauss-Newton step
@@ -990,6 +1039,9 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
         }
         if (lane == 0) R.resumable[b] = status == 1 ? 1 : 0;
     }
+    if constexpr (LOG) {
+        if (lane == 0) G.count[b] = lg.n;      // (a fresh solve that wrote nothing: 0)
+    }
     wave_sync();
 }
 
@@ -1039,6 +1091,21 @@ __device__ __forceinline__ NoResume resume_of() { return NoResume(); }
 __device__ __forceinline__ NoResume resume_of(const DevConsts*) { return NoResume(); }
 __device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r) { return r; }
 __device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const DevConsts*) { return r; }
+// ... and with an iteration log: ResumeArgs, LogArgs, [table]
+__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int, const ResumeArgs&, const LogArgs&) { return A; }
+__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const ResumeArgs&, const LogArgs&, const DevConsts* __restrict__ ctab) { return args_of(A, b, ctab); }
+__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const LogArgs&) { return b; }
+__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const LogArgs&, const DevConsts* ctab) { return index_of(b, ctab); }
+__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const LogArgs&) { return r; }
+__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const LogArgs&, const DevConsts*) { return r; }
+__device__ __forceinline__ NoLog log_of(const ResumeArgs&) { return NoLog(); }
+__device__ __forceinline__ NoLog log_of(const ResumeArgs&, const DevConsts*) { return NoLog(); }
+__device__ __forceinline__ const LogArgs& log_of(const ResumeArgs&, const LogArgs& g) { return g; }
+__device__ __forceinline__ const LogArgs& log_of(const ResumeArgs&, const LogArgs& g, const DevConsts*) { return g; }
+// whether a kernel's trailing arguments hold LogArgs: the LOG instantiation.  (Read from the pack, not a template parameter of the
+// kernels: the ordinary and the RESUME kernels keep their names.)
+template <class... Tab>
+constexpr bool has_log_arg() { return (std::is_same_v<Tab, LogArgs> || ...); }
 // first argument of the kernels that take their constants by value: the table stands in its place
 template <class... Tab>
 using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevConsts*>;
@@ -1060,7 +1127,8 @@ __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, typen
     }
     while (i < A.count) {                              // every wavefront reaches the exit: the head only grows
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
-        if constexpr (RESUME) solve_instance<M, true>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
+        if constexpr (has_log_arg<Tab...>()) solve_instance<M, true, ResumeArgs, true, LogArgs>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...), log_of(ctab...));
+        else if constexpr (RESUME) solve_instance<M, true>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
         else solve_instance<M>(args_of(A, b, ctab...), s, b, slot);   // one call site per instantiation: the body is compiled once
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);

@@ -1103,8 +1103,11 @@ __device__ __forceinline__ double rollout_mw(const DevConsts& c, int N, const do
 // fused persistent solve, 4 waves per instance.  RESUME: see solve_instance (sddp_kernels.hpp); this kernel carries one word more,
 // the lane whose trajectory its next pass stores (`guess`: it decides whether an accepted step costs a second rollout, and so the
 // rollout count).
-template <class M, bool SINK, bool RESUME = false, class Res = NoResume>
-__device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res()) {
+// LOG: see solve_instance; thread 0 writes the record behind the search, from values every thread of the workgroup holds or wave 0
+// used for the decision (A1, B2, slack).
+template <class M, bool SINK, bool RESUME = false, class Res = NoResume, bool LOG = false, class Lg = NoLog>
+__device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, const Res& R = Res(), const Lg& G = Lg()) {
+    static_assert(!LOG || RESUME, "the iteration log rides on the resumable instantiation");
     using L = LdsMW<M>;
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
@@ -1165,6 +1168,10 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
             if (tid == 0) R.resumable[2 * A.B + b] = 1;
         }
     }
+    LogState<LOG> lg;
+    if constexpr (LOG) {
+        if (resumed) lg.n = __builtin_amdgcn_readfirstlane(G.count[b]);      // a continue launch appends
+    }
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
@@ -1181,11 +1188,13 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
             double dV1, G1, G2, qu_inf, a_win = 0.0, J_win = 0.0;
             bool ok = true, stop = false, accepted = false;
             do {   // at most twice: a failed sweep / line search with the second-order term is redone without it
+                if constexpr (LOG) { lg.bumps = 0; lg.tried = 0; }
                 while (true) {
                     ok = backward_sweep_mw<M, SINK>(A.c, N, P, dft, rec, gains, mu, theta, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS);
                     if (ok) break;
                     if (theta != 0.0) { theta = 0.0; continue; }
                     mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
+                    if constexpr (LOG) ++lg.bumps;
                     if (mu > o.mu_max) break;
                 }
                 if (!ok) { status = 2; stop = true; break; }
@@ -1228,6 +1237,7 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
                     __syncthreads();
                     const int win = int(s[L::CTL + 12]);
                     if (win >= 0) {
+                        if constexpr (LOG) lg.tried += win + 1;
                         a_win = __shfl(a, win, kWave);
                         J_win = s[L::CTL + 13];
                         if (win != guess) {   // the accepted lane's trajectory was not the one stored: roll it again
@@ -1241,8 +1251,17 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
                         accepted = true;
                         break;
                     }
+                    if constexpr (LOG) lg.tried += __popcll(__ballot(valid));
                     a_base = __shfl(a, kWave - 1, kWave) * o.line_search_decrease_factor;
                     guess = 0;
+                }
+                if constexpr (LOG) {
+                    if (lg.n < G.rows) {
+                        if (tid == 0)
+                            log_record(G, b, lg.n, J, A1, B2, rho, gap, expected, accepted ? a_win : 0.0, accepted ? J_win : 0.0, theta, mu,
+                                       lg.tried, slack, iters + (accepted ? 1 : 0), rollouts, lg.bumps);
+                        ++lg.n;
+                    }
                 }
                 if (!accepted && theta != 0.0) {   // fall back to the plain Gauss-Newton sweep once
                     theta = 0.0;
@@ -1304,6 +1323,9 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
         }
         if (tid == 0) { R.resumable[b] = status == 1 ? 1 : 0; R.resumable[A.B + b] = guess; }
     }
+    if constexpr (LOG) {
+        if (tid == 0) G.count[b] = lg.n;
+    }
     __syncthreads();
 }
 
@@ -1323,7 +1345,9 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, ty
     __syncthreads();                                   // every thread has read it before the solve re-zeroes the LDS block
     while (i < A.count) {
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
-        solve_instance_mw<M, SINK, RESUME>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));   // ends with a barrier: q_pos may be rewritten
+        // ends with a barrier: q_pos may be rewritten
+        if constexpr (has_log_arg<Tab...>()) solve_instance_mw<M, SINK, true, ResumeArgs, true, LogArgs>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...), log_of(ctab...));
+        else solve_instance_mw<M, SINK, RESUME>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();

@@ -60,6 +60,11 @@ inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return 
 // not a statement of theirs differs (profiles/resume/README.md).
 template <class M>
 constexpr bool has_resume() { return is_plain<M>(); }
+// Iteration log (sddp_enable_iteration_log): a fifth and sixth instantiation, RES and LOG = true, which every solve launch of a
+// handle with a log buffer uses; sddp_api.hip grants the buffer only to a handle with a carry buffer.  Compiled in a third
+// translation unit (sddp_inst.hip with -DSDDP_INST_LOG), for the reason above (profiles/iteration_log/README.md).
+template <class M>
+constexpr bool has_log() { return has_resume<M>(); }
 // Policy export: the plain builds and their user-row forms, which are plain builds but for the rows (sddp_models.hpp: NXR > 0
 // excludes BAR and SO2).  The barrier and second_order = 2 builds have no policy kernel.
 template <class M>
@@ -116,12 +121,14 @@ int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
 
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M, bool RES, class... Tab>
+template <class M, bool RES, bool LOG, class... Tab>
 int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... tab) {
+    static_assert(RES || !LOG, "the iteration log rides on the resumable instantiation");
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    // the kernels' trailing arguments: [ResumeArgs] [table]
+    // the kernels' trailing arguments: [ResumeArgs [LogArgs]] [table]
     auto pick = [](int w) {
-        if constexpr (RES) return pick_solve<M, true, ResumeArgs, Tab...>(w); else return pick_solve<M, false, Tab...>(w);
+        if constexpr (LOG) return pick_solve<M, true, ResumeArgs, LogArgs, Tab...>(w);
+        else if constexpr (RES) return pick_solve<M, true, ResumeArgs, Tab...>(w); else return pick_solve<M, false, Tab...>(w);
     };
     auto kern = pick(wps);
     int slots = 0;
@@ -178,7 +185,9 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
     h->last_lds = int(lds_bytes<M>());
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    if constexpr (RES) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0}, tab...);
+    if constexpr (LOG) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0},
+                                   LogArgs{h->ilog, h->ilog_n, h->ilog_rows}, tab...);
+    else if constexpr (RES) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0}, tab...);
     else rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, tab...);
     if (rc != SDDP_OK) return rc;
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
@@ -193,16 +202,25 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
 }
 template <class M>
 int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
+    if (h->carry && h->ilog) {   // ... with an iteration log: the LOG instantiations, in theirs
+        if (!h->ops->launch_solve_log) return fail(h, SDDP_ERR_ARG, "this build has no iteration-log kernels");
+        return h->ops->launch_solve_log(h, a, first, count);
+    }
     if (h->carry) {   // resumable solves: the RESUME instantiations, in their own translation unit
         if (!h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "this build has no resumable kernels");
         return h->ops->launch_solve_resume(h, a, first, count);
     }
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, false>(h, a, first, count, tab...); });
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, false, false>(h, a, first, count, tab...); });
 }
 template <class M>
 int launch_solve_resume(sddp_handle* h, SolveArgs a, int first, int count) {
     static_assert(has_resume<M>(), "resumable solves exist for the plain builds only");
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true>(h, a, first, count, tab...); });
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true, false>(h, a, first, count, tab...); });
+}
+template <class M>
+int launch_solve_log(sddp_handle* h, SolveArgs a, int first, int count) {
+    static_assert(has_log<M>(), "the iteration log exists for the plain builds only");
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true, true>(h, a, first, count, tab...); });
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>

@@ -323,6 +323,43 @@ class DdpEngine:
         self._chk(self.lib.sddp_unfinished_count(self.h, int(first), int(self.B - first if count is None else count), C.byref(n)))
         return n.value
 
+    # ---- iteration log: one record per line search of every solve, kept on the device (include/sddp.h) ----------------------
+    def enable_iteration_log(self, rows: int):
+        """Every later solve launch keeps, per instance, one record of 16 doubles (_lib.LOG_FIELDS) per line search it ran, at most
+        `rows` (1 .. 4096) of them; 0 frees the buffers.  Needs enable_resume() first (plain builds only)."""
+        self._chk(self.lib.sddp_enable_iteration_log(self.h, int(rows)))
+
+    def iteration_log_rows(self) -> int:
+        """The rows per instance the log was enabled with (0: off)."""
+        rows = C.c_int()
+        self._chk(self.lib.sddp_iteration_log_info(self.h, C.byref(rows), None))
+        return rows.value
+
+    def iteration_log(self, first: int = 0, count: int | None = None):
+        """-> (records [count, rows, 16], n [count] int32) of the instances [first, first + count) as numpy (waits for the stream):
+        the rows [0, n[i]) of instance first + i are the line searches of its last solve, continue launches included."""
+        n = int(self.B - first if count is None else count)
+        rec = np.empty((max(n, 0), self.iteration_log_rows(), _lib.LOG_WORDS))
+        cnt = np.empty(max(n, 0), dtype=np.int32)
+        self._chk(self.lib.sddp_fetch_iteration_log(self.h, int(first), n, _lib.ptr(rec), _lib.ptr(cnt)))
+        return rec, cnt
+
+    def iteration_log_device(self):
+        """Zero-copy torch views of the log in HBM: (records [B, rows, 16] float64, n [B] int32) -- device_buffer(9) and (10);
+        ordered behind the handle's stream like fetch_device_views."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        class _Dev:
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+        pl, nb = self.device_buffer(9)
+        pn, _ = self.device_buffer(10)
+        rows = nb // (self.B * _lib.LOG_WORDS * 8)
+        return (torch.as_tensor(_Dev(pl, (self.B, rows, _lib.LOG_WORDS), "<f8"), device=dev),
+                torch.as_tensor(_Dev(pn, (self.B,), "<i4"), device=dev))
+
     # ---- heterogeneous fleets: per-instance robot constants (include/sddp.h) ------------------------------------------------
     def set_instance_consts(self, overrides: dict, first: int = 0):
         """Instances [first, first + count) get their own robot: `overrides` maps a field of the model constants (m, I, com, feet,

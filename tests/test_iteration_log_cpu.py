@@ -1,0 +1,112 @@
+"""Iteration log without a GPU: the ABI surface and the build list, the refusals that need no device, and -- on the C oracle alone --
+that the settings of tests/iteration_log_cases.py show every kind of record the GPU test compares, and on which instances the
+oracle is a stable reference."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+from srbd_horizon_amd import _lib
+from tests import iteration_log_cases as lc, options_cases as oc, resume_cases as rc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {"sddp_enable_iteration_log": 2, "sddp_iteration_log_info": 3, "sddp_fetch_iteration_log": 5}
+F = lc.F
+
+
+def test_header_declares_the_log_functions_and_ctypes_binds_them_with_matching_argument_counts():
+    hdr = open(os.path.join(ROOT, "include", "sddp.h")).read()
+    for name, nargs in NEW.items():
+        m = re.search(r"^int\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr, re.M)
+        assert m, f"{name} is not declared in include/sddp.h"
+        assert len(re.sub(r"/\*.*?\*/", "", m.group(1)).split(",")) == nargs, (name, m.group(1))
+        res, args = _lib.SYMBOLS[name]
+        assert len(args) == nargs and res is not None, (name, args)
+    assert re.search(r"#define SDDP_ABI_VERSION 9\b", hdr)              # functions only: no layout changed
+    assert re.search(r"#define SDDP_LOG_WORDS 16\b", hdr) and _lib.LOG_WORDS == 16 == len(_lib.LOG_FIELDS)
+    assert re.search(r"#define SDDP_LOG_MAX_ROWS 4096\b", hdr) and _lib.LOG_MAX_ROWS == 4096
+    assert list(_lib.LOG_FIELDS[:12]) == ["J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", "theta", "mu", "tried", "slack"]
+
+
+def test_the_log_units_are_exactly_the_builds_without_traits():
+    units = _lib.translation_units()
+    names = [n for n, _ in units]
+    assert len(set(names)) == len(names) == len(_lib.inst_units()) + 4
+    log = sorted(n[:-len("_log")] for n in names if n.endswith("_log"))
+    assert log == sorted(b.fn for b in _lib.INSTANCES if not b.traits) == ["lip30", "srbd13", "srbd37", "srbd61"]
+    by_name = dict(units)
+    for name, defs in units:
+        # a log unit is compiled with its build's own flags, and the build's main unit declares the launcher it defines
+        assert ("-DSDDP_INST_LOG" in defs) == name.endswith("_log") and ("-DSDDP_INST_HAS_LOG" in defs) == (name in log), name
+        if name.endswith("_log"):
+            main = [d for d in by_name[name[:-len("_log")]] if not d.startswith("-DSDDP_INST_HAS_")]
+            assert [d for d in defs if d != "-DSDDP_INST_LOG"] == main and "-DSDDP_INST_RESUME" not in defs, name
+    assert _lib.compile_command("srbd61_log")[-3:] == ["-mllvm", "-sink-insts-to-avoid-spills", "-DSDDP_INST_LOG"]
+
+
+def test_calls_without_a_handle_are_argument_errors():
+    _lib.build()
+    lib = _lib.load()
+    rows, words = C.c_int(-1), C.c_int(-1)
+    ERR_ARG = -1                                                         # SDDP_ERR_ARG
+    assert lib.sddp_enable_iteration_log(None, 8) == ERR_ARG
+    assert lib.sddp_iteration_log_info(None, C.byref(rows), C.byref(words)) == ERR_ARG
+    assert lib.sddp_fetch_iteration_log(None, 0, 1, None, None) == ERR_ARG
+    assert (rows.value, words.value) == (-1, -1)
+
+
+def _retry_pairs(tr):
+    """indices i of a search that failed with theta = 1 and was redone from the same iterate with theta = 0"""
+    return [i for i in range(len(tr) - 1) if tr[i, F["alpha"]] == 0.0 and tr[i, F["theta"]] == 1.0 and tr[i + 1, F["theta"]] == 0.0
+            and tr[i + 1, F["J"]] == tr[i, F["J"]]]
+
+
+def test_the_settings_show_every_kind_of_record_on_the_c_oracle():
+    """a GPU test of a field nobody exercises proves nothing: (1) a theta-retry pair (setting "T": srbd13 seeds 8, 23, 44 -- not to be
+    had from seeds under the five settings of resume_cases, see iteration_log_cases), (2) mu bumped in a sweep (set E), (3) open gaps
+    with rho > 0 (set A), (4) a solve that converges with zero records ("Z"), and ladders longer than one step (base: up to 9)."""
+    t = lc.traces("srbd13", "T")[0]
+    pairs = {b: _retry_pairs(t[b]) for b in range(len(t)) if _retry_pairs(t[b])}
+    assert set(pairs) >= {8, 23, 44}, pairs
+    for b, idx in pairs.items():      # the redone search is what the iteration goes on with
+        assert all(t[b][i + 1, F["alpha"]] > 0.0 for i in idx), b
+    assert not any(_retry_pairs(tr) for case in ("base", "A", "E", "so0", "ir1") for tr in lc.traces("srbd13", case)[0])
+    for model in rc.SHAPES:
+        e = lc.traces(model, "E")[0]
+        mu0 = lc.options("E")["mu0"]
+        assert all(len(tr) and tr[0, F["mu"]] > max(mu0, 0.0) for tr in e), model             # (2) the first sweep bumps, every instance
+        z = lc.traces(model, "Z")
+        assert all(len(tr) == 0 for tr in z[0]) and (oc.stat(z[1], "status") == 0).all(), model      # (4)
+    for model in ("srbd13", "srbd37", "lip30"):
+        a = lc.traces(model, "A")[0]
+        assert any(((tr[:, F["gap"]] > 0.0) & (tr[:, F["rho"]] > 0.0)).any() for tr in a), model     # (3)
+    grow = [b for b, tr in enumerate(lc.traces("srbd13", "A")[0]) if (np.diff(tr[:, F["rho"]]) > 0.0).any()]
+    assert grow, "no srbd13 instance of set A raises rho after its first search"
+    assert max(tr[:, F["tried"]].max() for tr in lc.traces("srbd13", "base")[0]) >= 4
+    # saturation (rows = 5 in the GPU test: some instances fill their rows, some leave pattern rows) and the cuts have something to cut
+    for model in ("srbd13", "srbd37"):
+        counts = [len(tr) for tr in lc.traces(model, "base")[0]]
+        assert min(counts) < 5 < max(counts), (model, counts)
+    assert min(len(tr) for tr in lc.traces("srbd13", "base")[0]) >= 3 and max(len(tr) for tr in lc.traces("srbd13", "base")[0]) > rc.CUT["srbd13"]
+    assert max(len(tr) for case in lc.SETTINGS for m in rc.SHAPES for tr in lc.traces(m, case)[0]) < lc.ROWS
+
+
+def test_the_oracle_is_a_stable_reference_on_all_but_one_instance_in_48():
+    """Which instances the GPU test leaves out of the oracle comparison: those on which the oracle's two builds (-ffp-contract=off /
+    fast) disagree in the record count or an accepted step length.  At most 1 in 48 for srbd13, none for the other models.  (srbd13
+    "ir1" does not meet that on seeds 0..47 -- thirteen instances -- and is compared on iteration_log_cases.IR1_SEEDS.)"""
+    worst = {}
+    for model, (N, B) in rc.SHAPES.items():
+        for case in lc.SETTINGS:
+            ex = lc.excluded(model, case)
+            assert len(ex) <= (1 if model == "srbd13" else 0), (model, case, ex)
+            # the reference's own scatter in the fields compared with a tolerance, in the GPU test's metric (see there)
+            a, c = lc.traces(model, case, "off")[0], lc.traces(model, case, "fast")[0]
+            for b in set(range(B)) - set(ex):
+                for f in ("expected", "A1", "B2"):
+                    d = np.abs(a[b][:, F[f]] - c[b][:, F[f]]) / (lc.MODEL_RTOL * np.abs(a[b][:, F[f]]) + lc.COST_RTOL * np.abs(a[b][:, F["J"]]))
+                    worst[f] = max(worst.get(f, 0.0), float(d.max()) if d.size else 0.0)
+    print("largest off/fast difference of the oracle, as a fraction of the GPU test's bound:", worst)
+    assert max(worst.values()) <= 0.1
+    assert len(set(lc.IR1_SEEDS)) == 48 and [s for s in range(48) if s not in lc.IR1_SEEDS] == [3, 4, 8, 9, 13, 14, 23, 24, 29, 33, 34, 39, 44]

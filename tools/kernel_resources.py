@@ -1,5 +1,6 @@
-"""Code-object resources of every kernel of every translation unit of the model builds (srbd_horizon_amd/_lib.py inst_units: one
-unit per entry of INSTANCES, and the units `<build>_resume` of the plain builds' resumable solve kernels): SGPRs, VGPRs, AGPRs,
+"""Code-object resources of every kernel of every translation unit of the model builds (srbd_horizon_amd/_lib.py translation_units:
+one unit per entry of INSTANCES, and the units `<build>_resume` and `<build>_log` of the plain builds' resumable solve kernels and
+their iteration-log form): SGPRs, VGPRs, AGPRs,
 scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports them for gfx950.
 
     python tools/kernel_resources.py [-j JOBS] [--only srbd13,srbd13_resume] [--root OTHER_TREE] > resources.txt
@@ -59,11 +60,11 @@ def compile_one(fn, root=ROOT):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
-    ap.add_argument("--only", default="", help="comma-separated unit names of _lib.inst_units()")
+    ap.add_argument("--only", default="", help="comma-separated unit names of _lib.translation_units()")
     ap.add_argument("--root", default=ROOT, help="the tree whose csrc is compiled, with this tree's unit list and command (default: this tree)")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
-    jobs = [name for name, _ in _lib.inst_units() if not only or name in only]
+    jobs = [name for name, _ in _lib.translation_units() if not only or name in only]
     with ThreadPoolExecutor(max_workers=max(1, args.j)) as ex:
         done = dict(ex.map(lambda fn: compile_one(fn, args.root), jobs))
     print(f"{'build':<10} {'kernel':<72} {'SGPR':>5} {'VGPR':>5} {'AGPR':>5} {'Scratch':>8} {'Occ':>4} {'LDS':>7}")
