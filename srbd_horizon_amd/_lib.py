@@ -154,8 +154,9 @@ class Build(NamedTuple):
 _SINK = ("-mllvm", "-sink-insts-to-avoid-spills")
 # THE list of model builds: what build() compiles and hands to csrc/sddp_api.hip, which finds a handle's build in it by
 # (model, traits); no two entries share that key (build() checks).  The builds without traits are the plain builds: they alone have
-# table kernels (sddp_set_instance_consts) and resumable solve kernels (sddp_enable_resume), the latter compiled in a translation
-# unit of their own (inst_units), and the iteration-log form of those in another (log_units).  A new build: its alias in csrc/sddp_models.hpp and one entry here.
+# table kernels (sddp_set_instance_consts) and the solve kernels' further variants (VARIANTS: sddp_enable_resume,
+# sddp_enable_iteration_log), each compiled in a translation unit of its own (translation_units).  A new build: its alias in
+# csrc/sddp_models.hpp and one entry here.
 INSTANCES = [
     Build("srbd13", "Srbd13", "srbd13"), Build("srbd13_b", "Srbd13B", "srbd13", ("bar",)),
     Build("srbd13_s", "Srbd13S", "srbd13", ("so2",)), Build("srbd13_bs", "Srbd13BS", "srbd13", ("bar", "so2")),
@@ -178,33 +179,20 @@ def header_stamp(root: str = ROOT) -> str:
     return "0x" + h.hexdigest()[:15]
 
 
-def inst_units():
-    """The translation units of csrc/sddp_inst.hip as (unit name, definitions and options): one per entry of INSTANCES, named by
-    its accessor suffix, and for every build without traits the unit <suffix>_resume of its resumable solve kernels, whose
-    launcher the build's main unit declares (-DSDDP_INST_HAS_RESUME).  A build with traits that asked for one would not compile
-    (csrc/sddp_launch.hpp launch_solve_resume).  The main unit of such a build also declares (-DSDDP_INST_HAS_LOG) the launcher of
-    its iteration-log kernels, which log_units() lists: translation_units() is what links."""
-    units = []
-    for b in INSTANCES:
-        defs = ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
-        if not b.traits:
-            units.append((b.fn + "_resume", defs + ["-DSDDP_INST_RESUME"]))
-            defs = defs + ["-DSDDP_INST_HAS_RESUME", "-DSDDP_INST_HAS_LOG"]
-        units.append((b.fn, defs))
-    return units
-
-
-def log_units():
-    """For every build without traits the unit <suffix>_log: the solve kernels' instantiations that keep an iteration log
-    (sddp_enable_iteration_log; they are resumable instantiations as well) and their launcher, a translation unit of their own
-    like <suffix>_resume and for the same reason."""
-    return [(b.fn + "_log", ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags,
-                             "-DSDDP_INST_LOG"]) for b in INSTANCES if not b.traits]
+# the solve variants, in the order of csrc/sddp_handle.hpp SolveVariant: the suffix of a variant's translation units
+VARIANTS = ("", "resume", "log")
 
 
 def translation_units():
-    """Every translation unit of csrc/sddp_inst.hip that build() compiles and links: inst_units() and log_units()."""
-    return inst_units() + log_units()
+    """Every translation unit of csrc/sddp_inst.hip that build() compiles and links, as (unit name, definitions and options): the main
+    unit of every entry of INSTANCES, named by its accessor suffix, and for every build without traits one side unit
+    <suffix>_<variant> per further entry of VARIANTS: that variant's solve kernels and their launcher (-DSDDP_INST_VARIANT=<index>),
+    which the main unit enters in its table.  A side unit is its main unit's command line plus that one definition; a build with
+    traits that asked for one would not compile (csrc/sddp_launch.hpp launch_solve_variant)."""
+    return [(b.fn + ("_" + suffix if v else ""),
+             ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
+             + (["-DSDDP_INST_VARIANT=%d" % v] if v else []))
+            for b in INSTANCES for v, suffix in enumerate(VARIANTS) if v == 0 or not b.traits]
 
 
 def compile_command(unit: str | None = None, root: str = ROOT) -> list:

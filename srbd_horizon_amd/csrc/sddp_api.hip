@@ -636,7 +636,7 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     if (on && !plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build)");
-    if (on && !h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no resumable kernels");
+    if (on && !h->ops->launch_solve_variant[kSolveResume]) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no kernels of that solve variant");
     if (on && h->opts.second_order == 2)      // (lip30, whose one build takes the option: the resumable kernels are not tested with it)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no second_order = 2)");
     if ((on != 0) == (h->carry != nullptr)) return SDDP_OK;
@@ -715,7 +715,7 @@ int sddp_enable_iteration_log(sddp_handle* h, int rows) {
     if (rows > 0 && !plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: the iteration log exists for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build), like sddp_enable_resume");
-    if (rows > 0 && !h->ops->launch_solve_log) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no iteration-log kernels");
+    if (rows > 0 && !h->ops->launch_solve_variant[kSolveLog]) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no kernels of that solve variant");
     if (rows > 0 && !h->carry)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: call sddp_enable_resume first (the log is kept by the resumable kernels; plain "
                                      "builds only)");

@@ -32,6 +32,12 @@ inline int model_of_name(const char* name) {
     return -1;
 }
 
+// The variants of the solve kernels: what a solve launch passes behind SolveArgs, and so which instantiation it runs: nothing,
+// ResumeArgs (a handle with a carry buffer, sddp_enable_resume), ResumeArgs and LogArgs (... and a log buffer,
+// sddp_enable_iteration_log).  THE list: a variant is a value here, its arguments in sddp_launch.hpp variant_args and its units'
+// suffix in srbd_horizon_amd/_lib.py VARIANTS, in the same order.
+enum SolveVariant { kSolvePlain = 0, kSolveResume, kSolveLog, kSolveVariants };
+
 // what a model build is and provides (sddp_launch.hpp: make_ops<M>)
 struct ModelOps {
     // the build's key: a handle's build is the one whose model and traits are the ones asked for (sddp_api.hip model_ops)
@@ -43,15 +49,13 @@ struct ModelOps {
     bool w2_build;         // a half-register-file build exists (two instances per SIMD / two workgroups per CU)
     const char* name;      // kernel-facing model name (bench / profiles)
     int (*max_slots)(sddp_handle*, int*);
-    int (*launch_solve)(sddp_handle*, SolveArgs, int, int);
-    // resumable solves: the launcher of the kernels' RESUME instantiations, compiled in a translation unit of its own (sddp_inst.hip
-    // with -DSDDP_INST_RESUME); null: the build has none.  launch_cost_keys: the queue_order 2 / 3 key pre-pass, which that unit calls
-    // through this table instead of instantiating the key kernel a second time
-    int (*launch_solve_resume)(sddp_handle*, SolveArgs, int, int) = nullptr;
+    int (*launch_solve)(sddp_handle*, SolveArgs, int, int);      // picks the variant the handle's state asks for
+    // one launcher per variant of the solve kernels.  [kSolvePlain] is always set; the others are null where the build has none (every
+    // build with traits), and are compiled in a translation unit of their own each (sddp_inst.hip with -DSDDP_INST_VARIANT=<variant>).
+    // launch_cost_keys: the queue_order 2 / 3 key pre-pass, which those units call through this table instead of instantiating the key
+    // kernel a second time
+    int (*launch_solve_variant[kSolveVariants])(sddp_handle*, SolveArgs, int, int) = {};
     int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
-    // iteration log: the launcher of the LOG instantiations (RESUME as well), in a unit of their own again (-DSDDP_INST_LOG); null:
-    // the build has none
-    int (*launch_solve_log)(sddp_handle*, SolveArgs, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
@@ -127,12 +131,12 @@ struct sddp_handle {
     double* policy = nullptr;
     int policy_knots = 0;
     const double* last_params = nullptr;
-    // resumable solves (sddp_enable_resume): non-null = on, and every solve launch runs the kernels' RESUME instantiation
+    // resumable solves (sddp_enable_resume): non-null = on, and every solve launch runs the kernels' kSolveResume variant
     double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
     int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
                                     // then one word: the result of sddp_unfinished_count
     bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
-    // iteration log (sddp_enable_iteration_log; needs `carry`): non-null = on, and every solve launch runs the LOG instantiation
+    // iteration log (sddp_enable_iteration_log; needs `carry`): non-null = on, and every solve launch runs the kSolveLog variant
     double* ilog = nullptr;         // [B][ilog_rows][kLogWords] one record per line search of an instance's last solve (LogArgs::log)
     int* ilog_n = nullptr;          // [B] records written (LogArgs::count)
     int ilog_rows = 0;

@@ -1053,9 +1053,9 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
 // everything it derives from `c` (LDS tables, constant blocks) at the start of every instance, so nothing of one robot outlives
 // its solve.  b is wave-uniform (blockIdx, readfirstlane, the LDS queue word) and the table is read-only for the whole launch:
 // the row is read through the constant address space, i.e. by scalar loads into the registers the kernel-argument copy occupies
-// in the homogeneous instantiation.  The overloads of consts_of / args_of / index_of are all that tells the instantiations apart:
-// the ones without a table hand their argument back, so the homogeneous kernel contains nothing it did not contain before there
-// was a table.  (The policy kernels are the exception: policy_kernel_h below.)
+// in the homogeneous instantiation.  consts_of / args_of / index_of are all that tells the instantiations apart: without a table
+// they hand their argument back, so the homogeneous kernel contains nothing it did not contain before there was a table.  (The
+// policy kernels are the exception: policy_kernel_h below.)
 // -----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ DevConsts row_of(const DevConsts* __restrict__ ctab, const int b) {
     static_assert(sizeof(DevConsts) % sizeof(unsigned long long) == 0, "a row is copied in 64-bit words");
@@ -1069,43 +1069,54 @@ __device__ __forceinline__ DevConsts row_of(const DevConsts* __restrict__ ctab, 
     __builtin_memcpy(&c, w, sizeof(c));
     return c;
 }
-// the constants / the arguments of instance b: the kernel's own, or a copy whose `c` is row b of the table
+// the constants of instance b for the kernels that take them first (ConstsArg): the kernel's own, or row b of the table
 __device__ __forceinline__ const DevConsts& consts_of(const DevConsts& c, const int) { return c; }
 __device__ __forceinline__ DevConsts consts_of(const DevConsts* __restrict__ ctab, const int b) { return row_of(ctab, b); }
-__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int) { return A; }
-__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const DevConsts* __restrict__ ctab) {
+// The trailing arguments of a kernel that takes SolveArgs first are a subset of (ResumeArgs, LogArgs, const DevConsts* table), in
+// this order, and are picked out of the pack BY TYPE: the types of the pack are all that tells a kernel's instantiations apart.
+// Types are compared as the kernels declare them (KernelArg: a pointer is __restrict__ there, and is deduced so).
+template <class T, class... Pack>
+constexpr bool has_arg() { return (std::is_same_v<typename KernelArg<T>::type, typename KernelArg<Pack>::type> || ...); }
+// the argument of type T out of a..., or the stand-in `none` where there is no such argument; by reference either way
+template <class T, class None>
+__device__ __forceinline__ const None& arg_of(const None& none) { return none; }
+template <class T, class None, class Head, class... Rest>
+__device__ __forceinline__ decltype(auto) arg_of(const None& none, const Head& head, const Rest&... rest) {
+    if constexpr (has_arg<T, Head>()) return (head); else return arg_of<T>(none, rest...);
+}
+// ... and its type: T, or None
+template <class T, class None, class... Pack>
+using ArgOr = std::conditional_t<has_arg<T, Pack...>(), T, None>;
+// the lookup on the six packs in use: the argument asked for where the pack holds it, the stand-in where it does not
+template <class T, class None, class... Pack>
+using ArgOfResult = decltype(arg_of<T>(std::declval<const None&>(), std::declval<const typename KernelArg<Pack>::type&>()...));
+template <bool RES, bool LOG, bool TAB, class... Pack>
+constexpr bool arg_lookup_is =
+    std::is_same_v<ArgOfResult<ResumeArgs, NoResume, Pack...>, std::conditional_t<RES, const ResumeArgs&, const NoResume&>> &&
+    std::is_same_v<ArgOfResult<LogArgs, NoLog, Pack...>, std::conditional_t<LOG, const LogArgs&, const NoLog&>> &&
+    std::is_same_v<ArgOfResult<const DevConsts*, NoLog, Pack...>, std::conditional_t<TAB, const DevConsts* __restrict__ const&, const NoLog&>> &&
+    has_arg<ResumeArgs, Pack...>() == RES && has_arg<LogArgs, Pack...>() == LOG && has_arg<const DevConsts*, Pack...>() == TAB;
+static_assert(arg_lookup_is<false, false, false> && arg_lookup_is<false, false, true, const DevConsts*>, "the ordinary kernels");
+static_assert(arg_lookup_is<true, false, false, ResumeArgs> && arg_lookup_is<true, false, true, ResumeArgs, const DevConsts*>, "the RESUME kernels");
+static_assert(arg_lookup_is<true, true, false, ResumeArgs, LogArgs> && arg_lookup_is<true, true, true, ResumeArgs, LogArgs, const DevConsts*>, "the LOG kernels");
+// the arguments of instance b: the kernel's own, or with a table a copy whose `c` is row b of it.  The copy is made behind a
+// __restrict__ parameter of its own: with the table handed to row_of straight out of the pack, every table kernel of the srbd
+// models came out with another schedule and register allocation.
+__device__ __forceinline__ SolveArgs args_with_row(const SolveArgs& A, const int b, const DevConsts* __restrict__ ctab) {
     SolveArgs R = A;
     R.c = row_of(ctab, b);
     return R;
 }
+template <class... Extra>
+__device__ __forceinline__ decltype(auto) args_of(const SolveArgs& A, const int b, const Extra&... extra) {
+    if constexpr (has_arg<const DevConsts*, Extra...>()) return args_with_row(A, b, arg_of<const DevConsts*>(nullptr, extra...));
+    else return (A);
+}
 // a queue position's instance index: with a table made wave-uniform, for the scalar loads of the row
-__device__ __forceinline__ int index_of(const int b) { return b; }
-__device__ __forceinline__ int index_of(const int b, const DevConsts*) { return __builtin_amdgcn_readfirstlane(b); }
-// The trailing arguments of a solve kernel: nothing, the table, ResumeArgs, or ResumeArgs and the table (in this order).  The
-// overloads below skip the ResumeArgs for what concerns the table, and resume_of picks them out (NoResume where there are none).
-__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int, const ResumeArgs&) { return A; }
-__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const ResumeArgs&, const DevConsts* __restrict__ ctab) { return args_of(A, b, ctab); }
-__device__ __forceinline__ int index_of(const int b, const ResumeArgs&) { return b; }
-__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const DevConsts* ctab) { return index_of(b, ctab); }
-__device__ __forceinline__ NoResume resume_of() { return NoResume(); }
-__device__ __forceinline__ NoResume resume_of(const DevConsts*) { return NoResume(); }
-__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r) { return r; }
-__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const DevConsts*) { return r; }
-// ... and with an iteration log: ResumeArgs, LogArgs, [table]
-__device__ __forceinline__ const SolveArgs& args_of(const SolveArgs& A, const int, const ResumeArgs&, const LogArgs&) { return A; }
-__device__ __forceinline__ SolveArgs args_of(const SolveArgs& A, const int b, const ResumeArgs&, const LogArgs&, const DevConsts* __restrict__ ctab) { return args_of(A, b, ctab); }
-__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const LogArgs&) { return b; }
-__device__ __forceinline__ int index_of(const int b, const ResumeArgs&, const LogArgs&, const DevConsts* ctab) { return index_of(b, ctab); }
-__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const LogArgs&) { return r; }
-__device__ __forceinline__ const ResumeArgs& resume_of(const ResumeArgs& r, const LogArgs&, const DevConsts*) { return r; }
-__device__ __forceinline__ NoLog log_of(const ResumeArgs&) { return NoLog(); }
-__device__ __forceinline__ NoLog log_of(const ResumeArgs&, const DevConsts*) { return NoLog(); }
-__device__ __forceinline__ const LogArgs& log_of(const ResumeArgs&, const LogArgs& g) { return g; }
-__device__ __forceinline__ const LogArgs& log_of(const ResumeArgs&, const LogArgs& g, const DevConsts*) { return g; }
-// whether a kernel's trailing arguments hold LogArgs: the LOG instantiation.  (Read from the pack, not a template parameter of the
-// kernels: the ordinary and the RESUME kernels keep their names.)
-template <class... Tab>
-constexpr bool has_log_arg() { return (std::is_same_v<Tab, LogArgs> || ...); }
+template <class... Extra>
+__device__ __forceinline__ int index_of(const int b, const Extra&...) {
+    if constexpr (has_arg<const DevConsts*, Extra...>()) return __builtin_amdgcn_readfirstlane(b); else return b;
+}
 // first argument of the kernels that take their constants by value: the table stands in its place
 template <class... Tab>
 using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevConsts*>;
@@ -1115,8 +1126,12 @@ using ConstsArg = std::conditional_t<sizeof...(Tab) == 0, DevConsts, const DevCo
 // (its own loads and stores are seen in program order), the per-instance inputs were written before the launch.
 // Every instance starts from freshly built LDS tables, so a result does not depend on which slot solved it or on what that
 // slot solved before: bit-identical to one launch per instance.
-template <class M, bool RESUME, class... Tab>
+// Which instantiation of the instance body runs is read off the pack: RESUME with ResumeArgs in it, LOG with LogArgs.
+template <class M, class... Tab>
 __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, typename KernelArg<Tab>::type... ctab) {
+    constexpr bool RESUME = has_arg<ResumeArgs, Tab...>(), LOG = has_arg<LogArgs, Tab...>();
+    using Res = ArgOr<ResumeArgs, NoResume, Tab...>;
+    using Lg = ArgOr<LogArgs, NoLog, Tab...>;
     const int slot = blockIdx.x;
     const bool queued = A.qhead != nullptr;
     int i = slot;                                      // no queue: workgroup w solves instance first + w
@@ -1127,9 +1142,8 @@ __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, typen
     }
     while (i < A.count) {                              // every wavefront reaches the exit: the head only grows
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
-        if constexpr (has_log_arg<Tab...>()) solve_instance<M, true, ResumeArgs, true, LogArgs>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...), log_of(ctab...));
-        else if constexpr (RESUME) solve_instance<M, true>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
-        else solve_instance<M>(args_of(A, b, ctab...), s, b, slot);   // one call site per instantiation: the body is compiled once
+        // one call site: the body is compiled once
+        solve_instance<M, RESUME, Res, LOG, Lg>(args_of(A, b, ctab...), s, b, slot, arg_of<ResumeArgs>(NoResume(), ctab...), arg_of<LogArgs>(NoLog(), ctab...));
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
@@ -1140,13 +1154,15 @@ __device__ __forceinline__ void solve_queue(const SolveArgs& A, double* s, typen
 // two builds of the same body: the register allocation is the only difference (sddp_options.waves_per_simd)
 template <class M, bool RESUME, class... Tab>
 __global__ __launch_bounds__(kWave) void solve_kernel(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
+    static_assert(RESUME == has_arg<ResumeArgs, Tab...>(), "RESUME names the instantiation, the pack decides it");
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M, RESUME, Tab...>(A, s, ctab...);
+    solve_queue<M, Tab...>(A, s, ctab...);
 }
 template <class M, bool RESUME, class... Tab>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_w2(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
+    static_assert(RESUME == has_arg<ResumeArgs, Tab...>(), "RESUME names the instantiation, the pack decides it");
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue<M, RESUME, Tab...>(A, s, ctab...);
+    solve_queue<M, Tab...>(A, s, ctab...);
 }
 
 // -----------------------------------------------------------------------------------------------------------------

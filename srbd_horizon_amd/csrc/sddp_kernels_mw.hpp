@@ -1331,8 +1331,11 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
 
 // work queue over the resident workgroups (see solve_queue in sddp_kernels.hpp); the queue position travels through LDS.  With a
 // table (args_of) b comes out of the LDS queue word the kernel has anyway.
-template <class M, bool SINK, bool RESUME, class... Tab>
+template <class M, bool SINK, class... Tab>
 __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, typename KernelArg<Tab>::type... ctab) {
+    constexpr bool RESUME = has_arg<ResumeArgs, Tab...>(), LOG = has_arg<LogArgs, Tab...>();
+    using Res = ArgOr<ResumeArgs, NoResume, Tab...>;
+    using Lg = ArgOr<LogArgs, NoLog, Tab...>;
     // the queue position lives in a control word of the dynamic LDS block (CTL + 15), so that the occupancy query and the
     // dynamic-LDS attribute cover every byte of LDS the kernel uses
     int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
@@ -1346,8 +1349,7 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, ty
     while (i < A.count) {
         const int b = index_of((queued && A.order) ? A.order[i] : A.first + i, ctab...);
         // ends with a barrier: q_pos may be rewritten
-        if constexpr (has_log_arg<Tab...>()) solve_instance_mw<M, SINK, true, ResumeArgs, true, LogArgs>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...), log_of(ctab...));
-        else solve_instance_mw<M, SINK, RESUME>(args_of(A, b, ctab...), s, b, slot, resume_of(ctab...));
+        solve_instance_mw<M, SINK, RESUME, Res, LOG, Lg>(args_of(A, b, ctab...), s, b, slot, arg_of<ResumeArgs>(NoResume(), ctab...), arg_of<LogArgs>(NoLog(), ctab...));
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1358,16 +1360,18 @@ __device__ __forceinline__ void solve_queue_mw(const SolveArgs& A, double* s, ty
 }
 template <class M, bool RESUME, class... Tab>
 __global__ __launch_bounds__(kThreadsMW) void solve_kernel_mw(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
+    static_assert(RESUME == has_arg<ResumeArgs, Tab...>(), "RESUME names the instantiation, the pack decides it");
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(false), RESUME, Tab...>(A, s, ctab...);
+    solve_queue_mw<M, mw_sink<M>(false), Tab...>(A, s, ctab...);
 }
 
 // the same body capped at half the register file: two workgroups per CU where the tiles of two instances fit its LDS;
 // sddp_options.waves_per_simd = 2 picks it, results are identical
 template <class M, bool RESUME, class... Tab>
 __global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2))) void solve_kernel_mw_w2(SolveArgs A, typename KernelArg<Tab>::type... ctab) {
+    static_assert(RESUME == has_arg<ResumeArgs, Tab...>(), "RESUME names the instantiation, the pack decides it");
     extern __shared__ __attribute__((aligned(16))) double s[];
-    solve_queue_mw<M, mw_sink<M>(true), RESUME, Tab...>(A, s, ctab...);
+    solve_queue_mw<M, mw_sink<M>(true), Tab...>(A, s, ctab...);
 }
 
 // policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread

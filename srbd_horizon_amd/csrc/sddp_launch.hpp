@@ -2,6 +2,8 @@
 // Included by sddp_inst.hip only: one translation unit per model build.
 #pragma once
 #include <algorithm>
+#include <tuple>
+#include <utility>
 
 #include "sddp_handle.hpp"
 #include "sddp_kernels.hpp"
@@ -29,7 +31,7 @@ constexpr int threads_of() { return use_mw<M>() ? kThreadsMW : kWave; }
 
 // A build's traits are M::BAR (barrier build), M::SO2 (full second order) and M::NXR > 0 (user rows; the user builds too).  A
 // PLAIN build has none of them.  This is the one statement of the rule: what only the plain builds have refers to it, and
-// sddp_api.hip reads the outcome from the build's table (ModelOps::table_kernels, launch_solve_resume) instead of deriving it.
+// sddp_api.hip reads the outcome from the build's table (ModelOps::table_kernels, launch_solve_variant) instead of deriving it.
 template <class M>
 constexpr bool is_plain() { return !M::BAR && !M::SO2 && M::NXR == 0; }
 
@@ -52,27 +54,30 @@ int with_table(sddp_handle* h, F f) {
 inline const DevConsts& consts_arg(sddp_handle* h) { return h->dc; }
 inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return tab; }
 
-// Resumable solves (sddp_enable_resume): on the plain builds the solve kernels have a third and fourth instantiation, RES = true
-// (sddp_kernels.hpp solve_instance), which every solve launch of a handle with a carry buffer uses.  sddp_api.hip refuses the
-// buffer on every other build, so h->carry != nullptr implies has_resume<M>().  They are compiled in a translation unit of their
-// own (sddp_inst.hip with -DSDDP_INST_RESUME; launch_solve_resume below is instantiated nowhere else): with them in the same
-// device module the ordinary one-wave kernels come out with another register allocation and 4 bytes less or more scratch, though
-// not a statement of theirs differs (profiles/resume/README.md).
-template <class M>
-constexpr bool has_resume() { return is_plain<M>(); }
-// Iteration log (sddp_enable_iteration_log): a fifth and sixth instantiation, RES and LOG = true, which every solve launch of a
-// handle with a log buffer uses; sddp_api.hip grants the buffer only to a handle with a carry buffer.  Compiled in a third
-// translation unit (sddp_inst.hip with -DSDDP_INST_LOG), for the reason above (profiles/iteration_log/README.md).
-template <class M>
-constexpr bool has_log() { return has_resume<M>(); }
+// Solve variants (sddp_handle.hpp SolveVariant): on the plain builds the solve kernels have two more instantiations per variant
+// beyond kSolvePlain (without and with the table), told apart by what they take behind SolveArgs.  A handle with a carry buffer
+// (sddp_enable_resume) launches kSolveResume, one with a log buffer as well (sddp_enable_iteration_log) kSolveLog; sddp_api.hip
+// refuses either buffer on every other build.  Each variant is compiled in a translation unit of its own (sddp_inst.hip with
+// -DSDDP_INST_VARIANT; launch_solve_variant<M, V> is instantiated nowhere else): with them in the same device module the ordinary
+// one-wave kernels come out with another register allocation and 4 bytes less or more scratch, though not a statement of theirs
+// differs (profiles/resume/README.md, profiles/iteration_log/README.md).
+// What variant V passes behind SolveArgs, in the kernels' order (the table, if any, follows): the one place that says so.
+template <SolveVariant V>
+auto variant_args(const sddp_handle* h) {
+    [[maybe_unused]] const ResumeArgs res{h->carry, h->resumable, h->continuing ? 1 : 0};
+    if constexpr (V == kSolveResume) return std::make_tuple(res);
+    else if constexpr (V == kSolveLog) return std::make_tuple(res, LogArgs{h->ilog, h->ilog_n, h->ilog_rows});
+    else return std::tuple<>();
+}
 // Policy export: the plain builds and their user-row forms, which are plain builds but for the rows (sddp_models.hpp: NXR > 0
 // excludes BAR and SO2).  The barrier and second_order = 2 builds have no policy kernel.
 template <class M>
 constexpr bool has_policy() { return is_plain<M>() || M::NXR > 0; }
 
 // only the kernel a model actually uses is instantiated
-template <class M, bool RES, class... Tab> auto pick_solve(int waves_per_simd) {
+template <class M, class... Tab> auto pick_solve(int waves_per_simd) {      // Tab: the kernel's trailing arguments, a variant's and the table
     [[maybe_unused]] const bool w2 = waves_per_simd >= 2;
+    constexpr bool RES = has_arg<ResumeArgs, Tab...>();
     if constexpr (!use_mw<M>()) return w2 ? solve_kernel_w2<M, RES, Tab...> : solve_kernel<M, RES, Tab...>;
     else if constexpr (has_w2<M>()) return w2 ? solve_kernel_mw_w2<M, RES, Tab...> : solve_kernel_mw<M, RES, Tab...>;
     else return solve_kernel_mw<M, RES, Tab...>;
@@ -121,15 +126,12 @@ int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
 
 // one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
 // buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M, bool RES, bool LOG, class... Tab>
+template <class M, SolveVariant V, class... Tab>
 int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... tab) {
-    static_assert(RES || !LOG, "the iteration log rides on the resumable instantiation");
     int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    // the kernels' trailing arguments: [ResumeArgs [LogArgs]] [table]
-    auto pick = [](int w) {
-        if constexpr (LOG) return pick_solve<M, true, ResumeArgs, LogArgs, Tab...>(w);
-        else if constexpr (RES) return pick_solve<M, true, ResumeArgs, Tab...>(w); else return pick_solve<M, false, Tab...>(w);
-    };
+    // the kernels' trailing arguments: they name the instantiation and are what the launch passes
+    const auto extra = std::tuple_cat(variant_args<V>(h), std::make_tuple(tab...));
+    auto pick = [&](int w) { return std::apply([w](const auto&... x) { return pick_solve<M, std::decay_t<decltype(x)>...>(w); }, extra); };
     auto kern = pick(wps);
     int slots = 0;
     int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
@@ -168,7 +170,7 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
         } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
             rc = alloc_cold_queue(h);
             if (rc != SDDP_OK) return rc;
-            if constexpr (RES) rc = h->ops->launch_cost_keys(h, a, first, count);      // (the key kernel lives in the build's main unit)
+            if constexpr (V != kSolvePlain) rc = h->ops->launch_cost_keys(h, a, first, count);      // (the key kernel lives in the build's main unit)
             else rc = launch_cost_keys<M>(h, a, first, count);
             if (rc != SDDP_OK) return rc;
             if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
@@ -185,10 +187,7 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
     h->last_lds = int(lds_bytes<M>());
     h->last_per_cu = slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
-    if constexpr (LOG) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0},
-                                   LogArgs{h->ilog, h->ilog_n, h->ilog_rows}, tab...);
-    else if constexpr (RES) rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, ResumeArgs{h->carry, h->resumable, h->continuing ? 1 : 0}, tab...);
-    else rc = launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, tab...);
+    rc = std::apply([&](const auto&... x) { return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, x...); }, extra);
     if (rc != SDDP_OK) return rc;
     if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
         rc = launch_class_update(h, first, count);
@@ -200,34 +199,31 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
     }
     return SDDP_OK;
 }
+template <class M, SolveVariant V>
+int launch_solve_variant(sddp_handle* h, SolveArgs a, int first, int count) {
+    static_assert(V == kSolvePlain || is_plain<M>(), "the plain builds alone have solve variants");
+    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, V>(h, a, first, count, tab...); });
+}
+// launch_solve_variant<M, V> for V > 0 as the build's main unit names it without instantiating it: declared here, defined (an
+// explicit specialisation) by the unit compiled with -DSDDP_INST_VARIANT=V alone.  A build whose side unit is missing does not load.
+template <class M, SolveVariant V>
+int side_launcher(sddp_handle* h, SolveArgs a, int first, int count);
+template <class M, int... V>
+void enter_side_launchers(ModelOps& o, std::integer_sequence<int, V...>) {
+    if constexpr (is_plain<M>()) ((o.launch_solve_variant[V + 1] = side_launcher<M, SolveVariant(V + 1)>), ...);
+}
 template <class M>
 int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
-    if (h->carry && h->ilog) {   // ... with an iteration log: the LOG instantiations, in theirs
-        if (!h->ops->launch_solve_log) return fail(h, SDDP_ERR_ARG, "this build has no iteration-log kernels");
-        return h->ops->launch_solve_log(h, a, first, count);
-    }
-    if (h->carry) {   // resumable solves: the RESUME instantiations, in their own translation unit
-        if (!h->ops->launch_solve_resume) return fail(h, SDDP_ERR_ARG, "this build has no resumable kernels");
-        return h->ops->launch_solve_resume(h, a, first, count);
-    }
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, false, false>(h, a, first, count, tab...); });
-}
-template <class M>
-int launch_solve_resume(sddp_handle* h, SolveArgs a, int first, int count) {
-    static_assert(has_resume<M>(), "resumable solves exist for the plain builds only");
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true, false>(h, a, first, count, tab...); });
-}
-template <class M>
-int launch_solve_log(sddp_handle* h, SolveArgs a, int first, int count) {
-    static_assert(has_log<M>(), "the iteration log exists for the plain builds only");
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, true, true>(h, a, first, count, tab...); });
+    const SolveVariant v = h->ilog ? kSolveLog : h->carry ? kSolveResume : kSolvePlain;
+    if (!h->ops->launch_solve_variant[v]) return fail(h, SDDP_ERR_ARG, "this build has no kernels of the solve variant that the handle asks for");
+    return h->ops->launch_solve_variant[v](h, a, first, count);
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
 int max_slots(sddp_handle* h, int* slots) {
     int s1 = 0, s2 = 0;
-    int rc = kernel_slots<M>(h, pick_solve<M, false>(1), solve_cap<M>(1), &s1);
-    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M, false>(2), solve_cap<M>(2), &s2);
+    int rc = kernel_slots<M>(h, pick_solve<M>(1), solve_cap<M>(1), &s1);
+    if (has_w2<M>() && rc == SDDP_OK) rc = kernel_slots<M>(h, pick_solve<M>(2), solve_cap<M>(2), &s2);
     *slots = std::max(s1, s2);
     return rc;
 }
@@ -297,6 +293,8 @@ ModelOps make_ops(const char* name) {
     o.name = name;
     o.max_slots = max_slots<M>;
     o.launch_solve = launch_solve<M>;
+    o.launch_solve_variant[kSolvePlain] = launch_solve_variant<M, kSolvePlain>;
+    enter_side_launchers<M>(o, std::make_integer_sequence<int, kSolveVariants - 1>());
     o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;

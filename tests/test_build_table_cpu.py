@@ -119,11 +119,25 @@ def test_the_combinations_the_library_accepts_are_the_keys_of_the_list_plus_the_
     assert [c for c in COMBINATIONS if listed(*c)] == EXISTING
 
 
+def _variant_defs(defs):
+    return [d for d in defs if d.startswith("-DSDDP_INST_VARIANT")]
+
+
 def test_the_resume_units_are_exactly_the_builds_without_traits():
-    units = [name for name, _ in _lib.inst_units()]
-    assert len(set(units)) == len(units) == 19
-    resume = sorted(u[:-len("_resume")] for u in units if u.endswith("_resume"))
-    assert resume == sorted(b.fn for b in _lib.INSTANCES if not b.traits) == ["lip30", "srbd13", "srbd37", "srbd61"]
-    for name, defs in _lib.inst_units():      # the main unit of a build declares the launcher that its resume unit defines
-        plain = name in resume
-        assert ("-DSDDP_INST_HAS_RESUME" in defs) == plain and ("-DSDDP_INST_RESUME" in defs) == name.endswith("_resume"), name
+    units = _lib.translation_units()
+    names = [name for name, _ in units]
+    plain = sorted(b.fn for b in _lib.INSTANCES if not b.traits)
+    assert _lib.VARIANTS == ("", "resume", "log")                # the order of csrc/sddp_handle.hpp SolveVariant
+    assert len(set(names)) == len(names) == len(_lib.INSTANCES) + 2 * len(plain) == 23
+    assert len([n for n in names if not n.endswith("_log")]) == 19
+    resume = sorted(u[:-len("_resume")] for u in names if u.endswith("_resume"))
+    assert resume == plain == ["lip30", "srbd13", "srbd37", "srbd61"]
+    by_name = dict(units)
+    for name, defs in units:
+        # the one definition that says which variant a unit is: on the side units alone, the main units carry none
+        side = [v for v, suffix in enumerate(_lib.VARIANTS) if v and name.endswith("_" + suffix) and name[:-len(suffix) - 1] in plain]
+        assert _variant_defs(defs) == ["-DSDDP_INST_VARIANT=%d" % v for v in side], name
+        assert (_variant_defs(defs) == ["-DSDDP_INST_VARIANT=1"]) == name.endswith("_resume"), name
+        if name.endswith("_resume"):      # a resume unit is compiled as its build's main unit but for that definition
+            assert [d for d in defs if d not in _variant_defs(defs)] == by_name[name[:-len("_resume")]], name
+    assert sorted(n for n, defs in units if not _variant_defs(defs)) == sorted(b.fn for b in _lib.INSTANCES)

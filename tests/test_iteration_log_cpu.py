@@ -32,17 +32,19 @@ def test_header_declares_the_log_functions_and_ctypes_binds_them_with_matching_a
 def test_the_log_units_are_exactly_the_builds_without_traits():
     units = _lib.translation_units()
     names = [n for n, _ in units]
-    assert len(set(names)) == len(names) == len(_lib.inst_units()) + 4
     log = sorted(n[:-len("_log")] for n in names if n.endswith("_log"))
     assert log == sorted(b.fn for b in _lib.INSTANCES if not b.traits) == ["lip30", "srbd13", "srbd37", "srbd61"]
+    assert len(set(names)) == len(names) == len(_lib.INSTANCES) + 2 * len(log) == len([n for n in names if not n.endswith("_log")]) + 4
     by_name = dict(units)
+    LOG = "-DSDDP_INST_VARIANT=%d" % _lib.VARIANTS.index("log")
     for name, defs in units:
-        # a log unit is compiled with its build's own flags, and the build's main unit declares the launcher it defines
-        assert ("-DSDDP_INST_LOG" in defs) == name.endswith("_log") and ("-DSDDP_INST_HAS_LOG" in defs) == (name in log), name
+        # a log unit is compiled with its build's own flags and the definition that says it is the log variant; no other unit has that
+        assert (LOG in defs) == name.endswith("_log") and len([d for d in defs if d.startswith("-DSDDP_INST_VARIANT")]) <= 1, name
         if name.endswith("_log"):
-            main = [d for d in by_name[name[:-len("_log")]] if not d.startswith("-DSDDP_INST_HAS_")]
-            assert [d for d in defs if d != "-DSDDP_INST_LOG"] == main and "-DSDDP_INST_RESUME" not in defs, name
-    assert _lib.compile_command("srbd61_log")[-3:] == ["-mllvm", "-sink-insts-to-avoid-spills", "-DSDDP_INST_LOG"]
+            assert [d for d in defs if d != LOG] == by_name[name[:-len("_log")]], name
+    for unit in ("srbd61", "srbd61_resume", "srbd61_log"):
+        assert [d for d in by_name[unit] if not d.startswith("-D")] == ["-mllvm", "-sink-insts-to-avoid-spills"], unit
+    assert _lib.compile_command("srbd61_log")[-3:] == ["-mllvm", "-sink-insts-to-avoid-spills", LOG] and LOG == "-DSDDP_INST_VARIANT=2"
 
 
 def test_calls_without_a_handle_are_argument_errors():

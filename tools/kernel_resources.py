@@ -1,14 +1,16 @@
 """Code-object resources of every kernel of every translation unit of the model builds (srbd_horizon_amd/_lib.py translation_units:
-one unit per entry of INSTANCES, and the units `<build>_resume` and `<build>_log` of the plain builds' resumable solve kernels and
-their iteration-log form): SGPRs, VGPRs, AGPRs,
-scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports them for gfx950.
+one unit per entry of INSTANCES, and the side units `<build>_resume` and `<build>_log` of the plain builds' further solve variants,
+_lib.VARIANTS): SGPRs, VGPRs, AGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports
+them for gfx950.
 
     python tools/kernel_resources.py [-j JOBS] [--only srbd13,srbd13_resume] [--root OTHER_TREE] > resources.txt
 
 Each unit is compiled device-only with build()'s own command (_lib.compile_command) plus -Rpass-analysis=kernel-resource-usage;
 nothing is linked or written beside the table.  Two trees compile to the same kernels exactly when their tables are equal line by
 line: what a change that must leave the existing kernels alone is checked with (profiles/iteration_refactor, profiles/hetero,
-profiles/build_table).  The LDS column is 0 for every kernel that uses dynamic LDS only."""
+profiles/build_table, profiles/solve_variants; tools/isa_diff.py compares the instructions).  --root compiles another tree's csrc
+by THIS tree's unit list and definitions: a tree whose unit recipe differs is tabulated by its own copy of this tool.  The LDS
+column is 0 for every kernel that uses dynamic LDS only."""
 import argparse
 import os
 import re
