@@ -106,6 +106,8 @@ SYMBOLS = {
     "sddp_continue_device": (C.c_int, [_vp, _vp]),
     "sddp_continue_resident": (C.c_int, [_vp]),
     "sddp_unfinished_count": (C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_int)]),
+    "sddp_set_time_budget": (C.c_int, [_vp, C.c_double, C.c_int]),
+    "sddp_time_budget_info": (C.c_int, [_vp, _P(C.c_double), _P(C.c_int)]),
     "sddp_enable_iteration_log": (C.c_int, [_vp, C.c_int]),
     "sddp_iteration_log_info": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
     "sddp_fetch_iteration_log": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),

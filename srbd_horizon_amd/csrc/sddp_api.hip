@@ -214,6 +214,22 @@ int invalidate_resume(sddp_handle* h, int first, int count) {
     return SDDP_OK;
 }
 
+// Where the solve and the continue entry points meet: one launch sequence of the handle's build over [first, first + count).  With a
+// time budget armed (sddp_set_time_budget) the deadline stamp leads it on the stream -- in front of the queue_order pre-pass and the
+// sort, which the budget therefore covers.
+unsigned long long* clock_words(sddp_handle* h) {
+    return reinterpret_cast<unsigned long long*>(h->resumable + ResumeArgs::clock_offset(h->B));
+}
+int launch_solve_sequence(sddp_handle* h, const SolveArgs& a, int first, int count) {
+    if (h->budget_us > 0.0 && h->resumable) {
+        // 100 MHz clock: ticks = round(100 * budget_us); capped where deadline = start + ticks could wrap
+        const double t = std::min(std::round(100.0 * h->budget_us), 4.0e18);
+        const int rc = launch(h, deadline_stamp_kernel, 1, 1, 0, clock_words(h), (unsigned long long)t);
+        if (rc != SDDP_OK) return rc;
+    }
+    return h->ops->launch_solve(h, a, first, count);
+}
+
 // Pinned host staging of a small payload, `images` copies of it: allocated on first use where the payload is at most `limit`
 // bytes.  -> the buffer, or null (payload too large, or no pinned memory to be had: the error is dropped) and the caller takes
 // its pageable path.
@@ -620,7 +636,7 @@ int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, i
     if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
-    rc = h->ops->launch_solve(h, a, first, count);
+    rc = launch_solve_sequence(h, a, first, count);
     if (rc == SDDP_OK) h->last_params = d_params;      // what sddp_policy_range_device differentiates against
     return rc;
 }
@@ -644,13 +660,16 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     h->up_off = 0;
     release(h, h->carry);
     release(h, h->resumable);
+    h->budget_us = 0.0;      // the time budget rides on the resumable kernels too: disarmed
+    h->budget_min_iters = 0;
     if (!on) {   // the iteration log rides on the resumable kernels: it goes with them
         release(h, h->ilog);
         release(h, h->ilog_n);
         h->ilog_rows = 0;
         return SDDP_OK;
     }
-    const size_t flag_bytes = (3 * size_t(h->B) + 1) * sizeof(int);
+    // flags [3][B] | the unfinished count | (padding) | the time budget's clock words [2] uint64
+    const size_t flag_bytes = ResumeArgs::clock_offset(h->B) * sizeof(int) + 2 * sizeof(unsigned long long);
     int* flags = nullptr;
     double* carry = nullptr;
     hipError_t e = acquire(h, carry, size_t(h->B) * h->N * h->d.nx * sizeof(double));
@@ -678,7 +697,7 @@ int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first
     if (h->cls)   // which instances this launch resumes: the class statistics count those that it also finishes
         HIP_TRY(h, hipMemsetAsync(h->resumable + 2 * size_t(h->B) + first, 0, size_t(count) * sizeof(int), h->stream));
     h->continuing = true;
-    rc = h->ops->launch_solve(h, a, first, count);
+    rc = launch_solve_sequence(h, a, first, count);
     h->continuing = false;
     if (rc == SDDP_OK) h->last_params = d_params;
     return rc;
@@ -706,6 +725,26 @@ int sddp_unfinished_count(sddp_handle* h, int first, int count, int* n) {
     if (rc != SDDP_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(n, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return sddp_synchronize(h);
+}
+
+// ---- time budget ----------------------------------------------------------------------------------------------------------
+int sddp_set_time_budget(sddp_handle* h, double budget_us, int min_iters) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!std::isfinite(budget_us) || budget_us < 0.0) return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: budget_us must be finite and >= 0 (0: off)");
+    if (min_iters < 0) return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: min_iters must be >= 0");
+    if (budget_us > 0.0 && !h->carry)
+        return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: call sddp_enable_resume first (the budget is kept by the resumable kernels; plain "
+                                     "builds only)");
+    h->budget_us = budget_us;      // host state only: it takes effect with the next launch sequence
+    h->budget_min_iters = budget_us > 0.0 ? min_iters : 0;
+    return SDDP_OK;
+}
+
+int sddp_time_budget_info(sddp_handle* h, double* budget_us, int* min_iters) {
+    if (!h) return SDDP_ERR_ARG;
+    if (budget_us) *budget_us = h->budget_us;
+    if (min_iters) *min_iters = h->budget_min_iters;
+    return SDDP_OK;
 }
 
 // ---- iteration log ------------------------------------------------------------------------------------------------------
@@ -1186,6 +1225,9 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
             if (which == 9) { *ptr = h->ilog; n = (long long)(size_t(h->B) * h->ilog_rows * kLogWords * sizeof(double)); }
             else { *ptr = h->ilog_n; n = (long long)(size_t(h->B) * sizeof(int)); }
             break;
+        case 11:  // the time budget's clock words: start | deadline of the last budgeted launch sequence (zeros before the first)
+            if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume has not been called");
+            *ptr = clock_words(h); n = (long long)(2 * sizeof(unsigned long long)); break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");
     }
     if (bytes) *bytes = n;

@@ -134,7 +134,12 @@ struct sddp_handle {
     // resumable solves (sddp_enable_resume): non-null = on, and every solve launch runs the kernels' kSolveResume variant
     double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
     int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
-                                    // then one word: the result of sddp_unfinished_count
+                                    // then one word: the result of sddp_unfinished_count; then, at ResumeArgs::clock_offset(B), the
+                                    // time budget's clock words [2] uint64 (start | deadline of the last budgeted launch)
+    // time budget (sddp_set_time_budget; needs `carry`): budget_us > 0 = armed, and every solve / continue launch sequence is led
+    // by deadline_stamp_kernel and passes budget_min_iters to the resumable kernels (ResumeArgs::budget_iters; -1 while not armed)
+    double budget_us = 0.0;
+    int budget_min_iters = 0;
     bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
     // iteration log (sddp_enable_iteration_log; needs `carry`): non-null = on, and every solve launch runs the kSolveLog variant
     double* ilog = nullptr;         // [B][ilog_rows][kLogWords] one record per line search of an instance's last solve (LogArgs::log)

@@ -101,8 +101,26 @@ struct ResumeArgs {
                         //         continue launch in flight resumed instance b (class history, sddp_api.hip launch_class_update)
     int cont;           // 1: a continue launch (sddp_continue_*): resumable instances are taken up where they stopped, every other
                         // instance is left as it is
+    int budget_iters;   // time budget (sddp_set_time_budget).  < 0: not armed -- the clock and the clock words are never read.
+                        // >= 0: armed, and the iterations every instance that THIS launch runs is owed before the deadline is
+                        // consulted (min_iters).  It sits in the struct's tail padding: the argument segment keeps its size
+    // the clock words [2] uint64 behind the flags (padded to 8 bytes): the constant-rate clock at the start of the launch sequence
+    // and the deadline, written by deadline_stamp_kernel (sddp_kernels_host.hpp) in front of the launch on the same stream
+    __host__ __device__ static size_t clock_offset(int B) { return (3 * size_t(B) + 2) & ~size_t(1); }      // in ints
+    __device__ __forceinline__ const unsigned long long* clock_words(int B) const {
+        return reinterpret_cast<const unsigned long long*>(resumable + clock_offset(B));
+    }
 };
+static_assert(sizeof(ResumeArgs) == 24, "ResumeArgs must not grow: budget_iters lives in what was padding");
 struct NoResume {};    // stands in its place in the ordinary instantiations: nothing is passed, nothing is read
+// Time budget: has the launch's deadline passed?  Called in the RESUME instantiations only, and only while the budget is armed.  The
+// deadline is constant for the whole launch (an earlier kernel of the stream wrote it) and its address is wave-uniform, so it is
+// read through the constant address space like a table row (row_of): a scalar load, no vector register.  wall_clock64 is the scalar
+// read of the 100 MHz constant-rate clock the slot clocks use.
+__device__ __forceinline__ bool deadline_passed(const ResumeArgs& R, const int B) {
+    typedef const unsigned long long __attribute__((address_space(4))) * WordPtr;
+    return wall_clock64() >= ((WordPtr)R.clock_words(B))[1];
+}
 // Iteration log (sddp_enable_iteration_log): one record of kLogWords doubles per line search an instance ran, in the layout of the
 // first 12 words of the C oracle's trace record (oracle/c/ddp_engine.inc) and four words more:
 //   0 J of the iterate the search starts from | 1 A1 | 2 B2 | 3 rho | 4 gap | 5 expected | 6 accepted alpha (0: none) |
@@ -917,9 +935,18 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
     if constexpr (LOG) {
         if (resumed) lg.n = __builtin_amdgcn_readfirstlane(G.count[b]);      // a continue launch appends
     }
+    std::conditional_t<RESUME, int, const std::false_type> iters_at_entry{};      // what this launch owes an instance counts from here
+    if constexpr (RESUME) iters_at_entry = iters;
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
+            if constexpr (RESUME) {
+                // Time budget: one clock read per accepted iteration, here at the loop head and nowhere inside the iteration.  Leaving
+                // here is leaving at `iters < o.max_iters` turned false: status is still 1, nothing of the iterate is half-made, and
+                // the exit below stores what a solve at max_iters = iters stores.  The decision is wave-uniform by construction:
+                // kernel arguments, `iters` (the same in every lane) and two scalar reads (the clock, the deadline word).
+                if (R.budget_iters >= 0 && iters - iters_at_entry >= R.budget_iters && deadline_passed(R, A.B)) break;
+            }
             SDDP_TICK(9)
             phase_derivs<M>(A.c, N, xs, us, P, rec, lane);
             wave_sync();

@@ -1,5 +1,5 @@
 // sddp_kernels_host.hpp -- the model-independent kernels of the library (queue order by history, receding-horizon shift,
-// first-knot packing).  Included by sddp_api.hip only: they are not templates, so they must live in ONE translation unit.
+// first-knot packing, the time budget's deadline stamp).  Included by sddp_api.hip only: they are not templates, so they must live in ONE translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,6 +86,17 @@ __global__ __launch_bounds__(256) void unfinished_count_kernel(int first, int co
         __syncthreads();
     }
     if (threadIdx.x == 0) *out = part[0];
+}
+
+// Time budget (sddp_set_time_budget): one thread, in front of the first kernel of a solve or continue launch sequence on the handle's
+// stream.  w[0] = the 100 MHz constant-rate clock now, w[1] = the deadline, `ticks` later: what the RESUME solve kernels compare
+// their own clock reads with (sddp_kernels.hpp deadline_passed).  The budget so counts device time from the moment the stream
+// reaches the launch sequence; the host clock plays no part.  Ordinary vector stores.
+__global__ __launch_bounds__(64) void deadline_stamp_kernel(unsigned long long* __restrict__ w, unsigned long long ticks) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long start = wall_clock64();
+    w[0] = start;
+    w[1] = start + ticks;
 }
 
 // what an MPC tick applies: the first input u_0 and the state the plan expects next, x_1, of every instance, packed

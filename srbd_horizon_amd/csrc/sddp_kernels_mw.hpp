@@ -1152,6 +1152,20 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
         if (wave == 0) phase_defects<M>(A.c, N, xs, us, P, dft, lane, J, gap);
     }
     if (tid == 0) { s[L::CTL + 12] = J; s[L::CTL + 13] = gap; }
+    // Time budget (sddp_set_time_budget; RESUME instantiations, armed handles only).  The loop below must end at the same iteration in
+    // all four waves, or the next barrier never completes.  So no wave ever compares a clock read of its own: THREAD 0 ALONE reads
+    // the clock, in front of a barrier the loop has anyway, and writes its verdict to the control word CTL + 0 (which nothing else
+    // uses); every thread reads that word at the loop head, behind the barrier.  Two sites write it: here, for the first test of the
+    // loop head, and at the loop's tail between its two barriers, for the next one.  Uniformity: (1) one writer, and a barrier
+    // between its write and every read; (2) the word is not written again before every thread has passed at least one more barrier
+    // (the unconditional one behind phase_derivs at the earliest), so no thread can read a later verdict than another; (3) everything
+    // else the loop head tests -- budget_iters (a kernel argument), iters and the iteration count at entry -- is the same number in
+    // every thread.  Hence the break is workgroup-uniform.  An unarmed handle (budget_iters < 0) never reads the clock, the clock
+    // words or the control word.  (Nothing of this lives in a register across the iteration: the verdict stays in LDS and the count
+    // at entry is re-read from the instance's stats record, which nothing writes before the instance's exit.)
+    if constexpr (RESUME) {
+        if (R.budget_iters >= 0 && tid == 0) s[L::CTL + 0] = deadline_passed(R, A.B) ? 1.0 : 0.0;
+    }
     __syncthreads();
     J = s[L::CTL + 12];
     gap = s[L::CTL + 13];
@@ -1175,6 +1189,12 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
     if (!(fabs(J) < 1e300)) { status = 3; }
     else
         while (iters < o.max_iters) {
+            if constexpr (RESUME) {
+                // cut by the deadline: the exit of `iters < o.max_iters` turned false -- status 1, the iterate whole, the stores below
+                // those of a solve at max_iters = iters.  Workgroup-uniform (see above): every thread leaves here or none does.
+                // What this launch owes the instance counts from its iteration count at entry: 0, or the resumed solve's.
+                if (R.budget_iters >= 0 && s[L::CTL + 0] != 0.0 && iters - (resumed ? A.stats[b].iters : 0) >= R.budget_iters) break;
+            }
             SDDP_TICK(9)
             const bool work_dirty = iters > 0 || o.initial_rollout;        // a forward pass used the whole work area:
             if (work_dirty) {                                              // zero it, then the constants of F~^T by waves 1..3
@@ -1295,6 +1315,9 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
             ++iters;
             theta = (o.second_order && alpha == o.alpha_0) ? 1.0 : 0.0;
             if (mu > o.mu0) mu = fmax(o.mu0, mu * 0.1);
+            if constexpr (RESUME) {   // thread 0's verdict for the next loop head, between the two barriers the tail has (see above the loop)
+                if (R.budget_iters >= 0 && tid == 0) s[L::CTL + 0] = deadline_passed(R, A.B) ? 1.0 : 0.0;
+            }
             __syncthreads();
             if (fabs(dJ) < o.cost_reduction_ths && gap <= o.gap_tol) { converged = 1; status = 0; break; }
         }

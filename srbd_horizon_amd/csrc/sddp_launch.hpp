@@ -64,7 +64,7 @@ inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return 
 // What variant V passes behind SolveArgs, in the kernels' order (the table, if any, follows): the one place that says so.
 template <SolveVariant V>
 auto variant_args(const sddp_handle* h) {
-    [[maybe_unused]] const ResumeArgs res{h->carry, h->resumable, h->continuing ? 1 : 0};
+    [[maybe_unused]] const ResumeArgs res{h->carry, h->resumable, h->continuing ? 1 : 0, h->budget_us > 0.0 ? h->budget_min_iters : -1};
     if constexpr (V == kSolveResume) return std::make_tuple(res);
     else if constexpr (V == kSolveLog) return std::make_tuple(res, LogArgs{h->ilog, h->ilog_n, h->ilog_rows});
     else return std::tuple<>();

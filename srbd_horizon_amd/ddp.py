@@ -126,6 +126,21 @@ class DDPSolver:
         if self.slices is not None:
             self.ddp_solver.set_options(max_iters=self.slices[1])
 
+    def set_time_budget(self, budget_us, min_iters: int = 1):
+        """budget_us > 0: every solve ends `budget_us` microseconds of device time after its launch started, with at least
+        `min_iters` iterations made, and returns the iterate it has then (time-budgeted launches, include/sddp.h; stats status 1,
+        not converged).  None / 0: off.  Not together with set_slices."""
+        on = budget_us is not None and float(budget_us) > 0.0
+        if on and self.slices is not None:
+            raise ValueError("a time budget and slices are two ways to cut a solve: choose one")
+        if on:
+            self.ddp_solver.enable_resume(True)
+            self.ddp_solver.set_time_budget(float(budget_us), int(min_iters))
+        elif self.ddp_solver.resume_enabled:
+            self.ddp_solver.set_time_budget(0.0)
+            if self.slices is None:
+                self.ddp_solver.enable_resume(False)
+
     def _launch(self, solve):
         """solve() -> (x, u) on the engine, in slices when set_slices asked for them"""
         if self.slices is None:

@@ -323,6 +323,42 @@ class DdpEngine:
         self._chk(self.lib.sddp_unfinished_count(self.h, int(first), int(self.B - first if count is None else count), C.byref(n)))
         return n.value
 
+    # ---- time-budgeted launches: a launch that ends at a device-clock deadline, resumable (include/sddp.h) --------------------
+    def set_time_budget(self, budget_us: float, min_iters: int = 0):
+        """budget_us > 0: every later solve / continue launch of the handle ends `budget_us` microseconds of device time after its
+        launch sequence started -- an instance still iterating then is left as a max_iters cut leaves it (status 1, resumable:
+        continue_solve), the rest of the queue drains without iterating.  min_iters: the iterations every instance the launch runs
+        is owed whatever the clock says (0: none, 1: the real-time-iteration setting).  budget_us = 0 disarms it.  Needs
+        enable_resume() first; enable_resume(False) disarms it."""
+        self._chk(self.lib.sddp_set_time_budget(self.h, float(budget_us), int(min_iters)))
+
+    def time_budget(self):
+        """-> (budget_us, min_iters) as armed; (0.0, 0): no budget."""
+        b, m = C.c_double(), C.c_int()
+        self._chk(self.lib.sddp_time_budget_info(self.h, C.byref(b), C.byref(m)))
+        return b.value, m.value
+
+    def deadline_clock(self):
+        """(start, deadline) of the last launch sequence that ran under a budget, on the 100 MHz clock of slot_times() -- device
+        buffer 11; waits for the stream."""
+        import torch
+        self.synchronize()
+        ptr, _ = self.device_buffer(11)
+
+        class _Dev:
+            __cuda_array_interface__ = {"shape": (2,), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
+
+        t = torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device())).cpu().numpy().copy().view(np.uint64)
+        return int(t[0]), int(t[1])
+
+    def deadline_overrun_us(self) -> float:
+        """How far the last launch ran past its deadline, in microseconds: the latest slot end time (device buffer 7) minus the
+        deadline (device buffer 11).  Negative: the launch was over that long before the deadline.  Meaningful only when the last
+        solve / continue launch ran with a budget armed; waits for the stream."""
+        _, deadline = self.deadline_clock()
+        end = int(self.slot_times()[:, 1].max())
+        return (end - deadline) / 100.0
+
     # ---- iteration log: one record per line search of every solve, kept on the device (include/sddp.h) ----------------------
     def enable_iteration_log(self, rows: int):
         """Every later solve launch keeps, per instance, one record of 16 doubles (_lib.LOG_FIELDS) per line search it ran, at most

@@ -165,6 +165,50 @@ class FleetQueue:
         self.pending = 0
         return finished, records
 
+    def solve_within(self, budget_us: float, total: int, min_iters: int = 0):
+        """The pending batches under a TIME budget (time-budgeted launches, include/sddp.h): solve_sliced with the first slice
+        cut by the device clock instead of an iteration count.  ONE launch at max_iters = `total` ends `budget_us` microseconds
+        of device time after it started (every instance it runs gets at least `min_iters` iterations) and the first-knot records
+        are packed behind it -- those of the finished instances are final; if any instance is unfinished, a second launch with
+        the budget OFF finishes the stragglers alone.  Every instance ends with exactly the bytes of one uncut solve at `total`.
+        -> (finished [n] bool device tensor: which instances the budgeted launch finished; records [n, words] of all of them
+        after the last launch).  `first_records` keeps the records packed behind the first launch, `overrun_us` how far that launch
+        ran past its deadline.  Records, collective and policy as in solve_sliced; the engine is left as it was found: resumable
+        solves, the time budget and max_iters are restored."""
+        import torch
+        n = self.pending * self.batch
+        if n == 0:
+            return None, None
+        eng = self.eng
+        was_on, was_iters = eng.resume_enabled, int(eng.opts.max_iters)
+        was_budget = eng.time_budget() if was_on else (0.0, 0)
+        eng.enable_resume(True)
+        words = eng.record_words("first_knot")
+        if getattr(self, "_sliced", None) is None or self._sliced[0].shape != (self.batch * self.depth, words):
+            mk = lambda: torch.empty((self.batch * self.depth, words), dtype=torch.float64, device=self.x.device)
+            self._sliced = [mk(), mk()]
+        eng.set_options(max_iters=int(total))
+        eng.set_time_budget(budget_us, min_iters)
+        eng.solve_range_device(self.P, 0, n)
+        self.first_records = eng.pack_records_device(self._sliced[0][:n], 0, n, "first_knot")
+        finished = self.si[:n, _lib.STATS_I32_STATUS] != 1
+        self.launches += 1
+        eng.set_time_budget(0.0)
+        records = self.first_records
+        unfinished = eng.unfinished(0, n)                                    # (waits for the stream)
+        self.overrun_us = eng.deadline_overrun_us()                          # before the second launch rewrites the slot times
+        if unfinished > 0:
+            eng.continue_solve(self.P, 0, n)
+            records = eng.pack_records_device(self._sliced[1][:n], 0, n, "first_knot")
+            self.launches += 1
+        if not was_on:
+            eng.enable_resume(False)                                         # (waits for the stream: the records are complete)
+        else:
+            eng.set_time_budget(*was_budget)
+        eng.set_options(max_iters=was_iters)
+        self.pending = 0
+        return finished, records
+
     def _wait(self, k):
         if self._work[k] is not None:
             self._work[k].wait()

@@ -25,8 +25,11 @@ EXAMPLE_OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 class MpcLoop:
     def __init__(self, model: str = "srbd37", ns: int = 20, T: float | None = None, opts: dict | None = None, robot=None,
                  warm_start: str = "shift", number_of_legs: int = 2, contact_model: int | None = None, feedback_substeps: int = 0,
-                 feedback: bool = True, slices=None):
-        """slices = (k, total): every tick's solve is a first slice of at most k iterations and, if unfinished, a continue launch up
+                 feedback: bool = True, slices=None, budget_us: float | None = None, min_iters: int = 1):
+        """budget_us: every tick's solve runs under a device-time budget of that many microseconds, with at least `min_iters`
+        iterations (DDPSolver.set_time_budget), and the tick applies the iterate the solve has then; a budget that never runs out
+        visits the states of the unbudgeted loop.
+        slices = (k, total): every tick's solve is a first slice of at most k iterations and, if unfinished, a continue launch up
         to `total` iterations (DDPSolver.set_slices); the loop visits the same states, tick for tick, as with max_iters = total.
         feedback_substeps: 0 (default) = the reference loop, the first input applied open loop over one Euler step.  n > 0: the
         simulator step of a tick is split into n Euler sub-steps of dt / n and the input applied at each of them is the solver's
@@ -70,6 +73,8 @@ class MpcLoop:
         self.solver = DDPSolver(self.srbd.prb, opts=dict(EXAMPLE_OPTS if opts is None else opts))
         if slices is not None:
             self.solver.set_slices(slices)
+        if budget_us is not None:
+            self.solver.set_time_budget(budget_us, min_iters)
         self.state = self.srbd.getInitialState().astype(float)
         c_init_z = float(self.srbd.initial_foot_position[0][2])
         self.wpg = _wpg.steps_phase(self.srbd.f, self.srbd.c, self.srbd.cdot, c_init_z, self.srbd.c_ref, self.srbd.w_ref,
