@@ -114,6 +114,11 @@ SYMBOLS = {
     "sddp_set_instance_classes": (C.c_int, [_vp, _vp, C.c_int]),
     "sddp_set_instance_classes_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int]),
     "sddp_class_history": (C.c_int, [_vp, C.c_int, _P(C.c_double), _P(C.c_longlong)]),
+    "sddp_enable_auto_classes": (C.c_int, [_vp, C.c_int]),
+    "sddp_auto_classes_info": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_fetch_instance_classes": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_get_class_stats": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_add_class_stats": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sddp_set_instance_consts": (C.c_int, [_vp, C.c_int, C.c_int, _P(SddpModelConsts)]),
     "sddp_clear_instance_consts": (C.c_int, [_vp]),
     "sddp_instance_consts_active": (C.c_int, [_vp, _P(C.c_int)]),

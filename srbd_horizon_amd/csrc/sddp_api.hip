@@ -53,6 +53,11 @@ int launch_class_update(sddp_handle* h, int first, int count) {
                       h->resumable, h->resumable + 2 * size_t(h->B), h->continuing ? 1 : 0);
     return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat);
 }
+int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {      // one wavefront per instance, four per workgroup
+    const ModelOps* o = h->ops;
+    return launch(h, class_label_kernel, (count + 3) / 4, 256, 0, h->N, h->d.np, o->col_cmd[0], o->col_cmd[1], o->col_sw[0], o->col_sw[1], first,
+                  count, P, h->cls);
+}
 
 namespace {
 // Buffer ownership: every device and pinned allocation of a handle is made by acquire(), which registers it in h->owned.
@@ -342,7 +347,8 @@ int sddp_register_user_build(const char* path, int* model_id) {
     else if (base_fn() != SDDP_MODEL_SRBD13 && base_fn() != SDDP_MODEL_SRBD37) err = "user build: base model must be srbd13 or srbd37";
     else if (rows_fn() < 1 || rows_fn() > SDDP_MAX_EXTRA) err = "user build: 1..8 user rows";
     if (err) { dlclose(dl); return fail(nullptr, SDDP_ERR_ARG, err); }
-    static const CoreHooks hooks{&create_error, &alloc_cold_queue, &launch_queue_order, &launch_class_keys, &launch_class_update};
+    static const CoreHooks hooks{&create_error, &alloc_cold_queue, &launch_queue_order, &launch_class_keys, &launch_class_update,
+                                  &launch_class_labels};
     bind_fn(&hooks);
     try {
         v.push_back(UserBuild{std::string(path), ops_fn(), base_fn(), rows_fn()});
@@ -1001,8 +1007,15 @@ static int class_buffers(sddp_handle* h, int n_classes) {
     return SDDP_OK;
 }
 
+// the labels are the handle's own while auto classes are on (sddp_enable_auto_classes)
+static int check_caller_labels(sddp_handle* h) {
+    if (h->auto_cls) return fail(h, SDDP_ERR_ARG, "the handle labels its instances itself (sddp_enable_auto_classes): call sddp_enable_auto_classes(h, 0) first");
+    return SDDP_OK;
+}
+
 int sddp_set_instance_classes(sddp_handle* h, const int* classes, int n_classes) {
     if (!h || !classes) return SDDP_ERR_ARG;
+    if (check_caller_labels(h) != SDDP_OK) return SDDP_ERR_ARG;
     int rc = class_buffers(h, n_classes);
     if (rc != SDDP_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(h->cls, classes, size_t(h->B) * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1012,6 +1025,7 @@ int sddp_set_instance_classes(sddp_handle* h, const int* classes, int n_classes)
 
 int sddp_set_instance_classes_range_device(sddp_handle* h, int first, int count, const int* d_classes, int n_classes) {
     if (!h || !d_classes) return SDDP_ERR_ARG;
+    if (check_caller_labels(h) != SDDP_OK) return SDDP_ERR_ARG;
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     int rc = class_buffers(h, n_classes);
     if (rc != SDDP_OK) return rc;
@@ -1028,6 +1042,65 @@ int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* s
     if (solves) *solves = (long long)st[1];
     if (mean_iters) *mean_iters = st[1] ? double(st[0]) / double(st[1]) : 0.0;
     return SDDP_OK;
+}
+
+// ---- auto classes: the handle labels its instances itself; the history leaves and enters a handle ---------------------------
+int sddp_enable_auto_classes(sddp_handle* h, int on) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!on) { h->auto_cls = false; return SDDP_OK; }      // labels and history stay
+    const long long n = 36LL * (h->N + 2);                 // 4 stance patterns x (N + 2) values of first_change x 3 x 3 commands
+    if (h->cls && h->n_cls != n)
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_auto_classes: the handle has a class table with another n_classes (caller labels were set "
+                                     "first); the library's labels need 36 (N + 2)");
+    if (n > (1 << 20)) return fail(h, SDDP_ERR_ARG, "sddp_enable_auto_classes: horizon too long (36 (N + 2) classes must be <= 2^20)");
+    const int rc = class_buffers(h, int(n));
+    if (rc != SDDP_OK) return rc;
+    h->auto_cls = true;
+    return SDDP_OK;
+}
+
+int sddp_auto_classes_info(sddp_handle* h, int* on, int* n_classes) {
+    if (!h) return SDDP_ERR_ARG;
+    if (on) *on = h->auto_cls ? 1 : 0;
+    if (n_classes) *n_classes = h->cls ? h->n_cls : 0;
+    return SDDP_OK;
+}
+
+int sddp_fetch_instance_classes(sddp_handle* h, int first, int count, int* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    HIP_TRY(h, hipMemcpyAsync(out, h->cls + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
+}
+
+static int check_class_range(sddp_handle* h, int first_class, int count) {
+    if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+    if (first_class < 0 || count < 1 || first_class > h->n_cls - count) return fail(h, SDDP_ERR_ARG, "class range outside the class table");
+    return SDDP_OK;
+}
+
+int sddp_get_class_stats(sddp_handle* h, int first_class, int count, unsigned long long* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (check_class_range(h, first_class, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    HIP_TRY(h, hipMemcpyAsync(out, h->cls_stat + 2 * size_t(first_class), size_t(count) * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              h->stream));
+    return sddp_synchronize(h);
+}
+
+int sddp_add_class_stats(sddp_handle* h, int first_class, int count, const unsigned long long* in) {
+    if (!h) return SDDP_ERR_ARG;
+    if (check_class_range(h, first_class, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!in) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (!h->cls_in) ACQUIRE_TRY(h, h->cls_in, size_t(h->n_cls) * 2 * sizeof(unsigned long long));
+    // staged on the stream (the pinned ring for a small table), then added there: ordered with the launches that read and update the table
+    unsigned long long* d_in = h->cls_in + 2 * size_t(first_class);
+    const int rc = upload(h, d_in, in, size_t(count) * 2 * sizeof(unsigned long long));
+    if (rc != SDDP_OK) return rc;
+    return launch(h, class_stats_add_kernel, (2 * count + 255) / 256, 256, 0, 2 * count, (const unsigned long long*)d_in,
+                  h->cls_stat + 2 * size_t(first_class));
 }
 
 // ---- heterogeneous fleets: per-instance constants ---------------------------------------------------------------------------
@@ -1228,6 +1301,9 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
         case 11:  // the time budget's clock words: start | deadline of the last budgeted launch sequence (zeros before the first)
             if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume has not been called");
             *ptr = clock_words(h); n = (long long)(2 * sizeof(unsigned long long)); break;
+        case 12:  // the class labels [B] (int; -1: unlabelled): the caller's, or the handle's own under sddp_enable_auto_classes
+            if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+            *ptr = h->cls; n = (long long)(size_t(h->B) * sizeof(int)); break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");
     }
     if (bytes) *bytes = n;

@@ -45,6 +45,9 @@ struct ModelOps {
     bool bar, so2, xr;     // barrier build; full second-order build (second_order = 2); user rows.  None of them: a plain build
     bool table_kernels;    // every kernel has a table form (per-instance constants, sddp_set_instance_consts): the plain builds
     Dims dims;
+    // the parameter columns the class label reads (sddp_enable_auto_classes; sddp_models.hpp P_CMD0 / P_CMD1 / P_SW_L / P_SW_R): the
+    // commanded velocity x, y and the switch of the first contact of the left and of the right foot
+    int col_cmd[2] = {0, 0}, col_sw[2] = {0, 0};
     bool uses_mw;          // 4 wavefronts per instance (sddp_kernels_mw.hpp); else one
     bool w2_build;         // a half-register-file build exists (two instances per SIMD / two workgroups per CU)
     const char* name;      // kernel-facing model name (bench / profiles)
@@ -106,10 +109,13 @@ struct sddp_handle {
     int* order_in = nullptr;
     void* sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
-    // class history (queue_order = 3): the caller's class label per instance, and per class the iterations / solves so far
+    // class history (queue_order = 3): the class label per instance -- the caller's, or the handle's own (auto_cls) --, and per class
+    // the iterations / solves so far
     int* cls = nullptr;             // [B], -1: unlabelled
     int n_cls = 0;
     unsigned long long* cls_stat = nullptr;   // [n_cls][2]
+    bool auto_cls = false;          // sddp_enable_auto_classes: every fresh solve launch labels its range first (implies cls != nullptr)
+    unsigned long long* cls_in = nullptr;     // [n_cls][2] device staging of sddp_add_class_stats, made by its first call
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
     // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward, without and with
     // the constants table), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.
@@ -195,6 +201,8 @@ int launch_queue_order(sddp_handle* h, int first, int count);
 // class statistics behind a solve launch
 int launch_class_keys(sddp_handle* h, int count);
 int launch_class_update(sddp_handle* h, int first, int count);
+// auto classes: the labels of [first, first + count) from the launch's parameter tensor into h->cls, in front of a fresh solve launch
+int launch_class_labels(sddp_handle* h, const double* P, int first, int count);
 
 // the services above as a user build reaches them (srbd_horizon_amd/userterms.py): it is loaded RTLD_LOCAL and cannot resolve this
 // library's symbols, so sddp_register_user_build hands it this table and the build's own definitions of them call through it
@@ -204,6 +212,7 @@ struct CoreHooks {
     int (*launch_queue_order)(sddp_handle*, int, int);
     int (*launch_class_keys)(sddp_handle*, int);
     int (*launch_class_update)(sddp_handle*, int, int);
+    int (*launch_class_labels)(sddp_handle*, const double*, int, int);
 };
 
 }  // namespace sddp

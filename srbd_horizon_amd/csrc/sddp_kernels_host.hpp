@@ -1,4 +1,4 @@
-// sddp_kernels_host.hpp -- the model-independent kernels of the library (queue order by history, receding-horizon shift,
+// sddp_kernels_host.hpp -- the model-independent kernels of the library (queue order by history, class labels, receding-horizon shift,
 // first-knot packing, the time budget's deadline stamp).  Included by sddp_api.hip only: they are not templates, so they must live in ONE translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,6 +72,47 @@ __global__ __launch_bounds__(256) void class_update_resume_kernel(int first, int
     if (resumable[b] == 1 || (cont && ran[b] != 1)) return;
     atomicAdd(&cls_stat[2 * c], (unsigned long long)st[b].iters);
     atomicAdd(&cls_stat[2 * c + 1], 1ull);
+}
+
+// Auto classes (sddp_enable_auto_classes): the label of every instance of [first, first + count), computed from the parameter tensor
+// of the launch, in front of its key pre-pass (what workload.schedule_classes states in numpy):
+//   sw[k][j] = P[b][k][col_sw[j]] > 0.5 (a NaN is "not in stance"), stance0 = 2 sw[0][0] + sw[0][1],
+//   first_change = smallest k in 1..N with sw[k] != sw[0], N + 1 if none, cmd(v) = 0 / 1 / 2 for |v| <= 1e-12 / v > 1e-12 / v < -1e-12,
+//   label = ((stance0 (N + 2) + first_change) 3 + cmd(P[b][N][col_cmd0])) 3 + cmd(P[b][N][col_cmd1])      in [0, 36 (N + 2))
+// One wavefront per instance, four per workgroup: lane l looks at node 64 c + l of chunk c and compares its two switches with node 0's,
+// lane 0's of chunk 0; the first set bit of the first non-empty ballot is first_change (node 0 never differs from itself).  np: the
+// handle's parameter row width.  About N + 1 cache lines per instance are touched, two words of each.
+__global__ __launch_bounds__(256) void class_label_kernel(int N, int np, int col_cmd0, int col_cmd1, int col_sw0, int col_sw1, int first, int count,
+                                                          const double* __restrict__ P, int* __restrict__ cls) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= count) return;                                    // (the whole wavefront)
+    const int b = first + i;
+    const double* Pb = P + size_t(b) * (N + 1) * np;
+    int s0 = 0, first_change = N + 1;
+    for (int k0 = 0; k0 <= N; k0 += 64) {
+        const int k = k0 + lane;
+        int s = 0;
+        if (k <= N) {
+            const double* p = Pb + size_t(k) * np;
+            s = (p[col_sw0] > 0.5 ? 2 : 0) + (p[col_sw1] > 0.5 ? 1 : 0);
+        }
+        if (k0 == 0) s0 = __shfl(s, 0);
+        const unsigned long long differs = __ballot(k <= N && s != s0);
+        if (differs) { first_change = k0 + __ffsll(differs) - 1; break; }      // (uniform: every lane sees the same ballot)
+    }
+    if (lane == 0) {
+        const double vx = Pb[size_t(N) * np + col_cmd0], vy = Pb[size_t(N) * np + col_cmd1];
+        const int cx = vx > 1e-12 ? 1 : (vx < -1e-12 ? 2 : 0), cy = vy > 1e-12 ? 1 : (vy < -1e-12 ? 2 : 0);
+        cls[b] = ((s0 * (N + 2) + first_change) * 3 + cx) * 3 + cy;
+    }
+}
+
+// sddp_add_class_stats: another handle's history (sums of iterations, solves; both additive) onto the words [2 first_class, ...) of
+// this one's, on the handle's stream like class_update_kernel
+__global__ __launch_bounds__(256) void class_stats_add_kernel(int words, const unsigned long long* __restrict__ in,
+                                                              unsigned long long* __restrict__ cls_stat) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < words) cls_stat[i] += in[i];
 }
 
 // sddp_unfinished_count: how many instances of [first, first + count) can be continued (flag 1).  One workgroup.

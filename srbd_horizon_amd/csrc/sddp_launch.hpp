@@ -160,6 +160,10 @@ int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... ta
         e1 = h->ev[2 * h->pending + 1];
         HIP_TRY(h, hipEventRecord(e0, h->stream));
     }
+    if (h->auto_cls && !h->continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
+        rc = launch_class_labels(h, a.P, first, count);      // continue launch keeps the labels of the solve that was cut
+        if (rc != SDDP_OK) return rc;
+    }
     if (count > grid) {
         HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
         a.qhead = h->qhead;
@@ -288,6 +292,7 @@ ModelOps make_ops(const char* name) {
     o.bar = M::BAR; o.so2 = M::SO2; o.xr = M::NXR > 0;
     o.table_kernels = has_hetero<M>();
     o.dims = {M::NX, M::NU, M::NP, M::NREC};
+    o.col_cmd[0] = M::P_CMD0; o.col_cmd[1] = M::P_CMD1; o.col_sw[0] = M::P_SW_L; o.col_sw[1] = M::P_SW_R;
     o.uses_mw = use_mw<M>();
     o.w2_build = has_w2<M>();
     o.name = name;

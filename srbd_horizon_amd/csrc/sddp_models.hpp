@@ -342,6 +342,9 @@ struct SrbdModel {
     // parameters in creation order (ddp.py:173-177): rdot_ref(3) w_ref(3) otg(1) (c_ref_i, cdot_switch_i) x NC, oref(4)
     static constexpr int NPB = CS ? 11 + 2 * NC : 19, NP = NPB + NXR;
     static_assert((CS && (NC == 4 || NC == 8)) || (!CS && NC == 2), "srbd37 / srbd61 / srbd13");
+    // what the class label reads (sddp.h sddp_enable_auto_classes; ModelOps::col_cmd / col_sw): the commanded velocity rdot_ref x, y and
+    // the switch of the first contact of the left and of the right foot, p_sw(p, 0) and p_sw(p, CM)
+    static constexpr int P_CMD0 = 0, P_CMD1 = 1, P_SW_L = CS ? 8 : 17, P_SW_R = CS ? 8 + 2 * (NC / 2) : 18;
     // the bound barrier's masks and bound arrays (sddp_model_consts.lower / upper) cover 64 entries of z: models with more
     // (srbd61: 109) take the friction-cone barrier only -- sddp_create refuses bound_barrier_weight > 0 for them, as the oracle does
     static constexpr bool BOX = BAR_ && (CS_ ? 13 + 12 * NC_ : 13 + 3 * NC_) <= 64;
@@ -1421,6 +1424,7 @@ struct LipModel {
     template <class QM> __device__ __forceinline__ static void add_barrier(const double*, QM, int, int, double = 0.0) {}
     template <class QM> __device__ __forceinline__ static void add_const_rows(const DevConsts&, QM, int, int) {}   // (one Q block per thread: unused)
     static constexpr int NX = 30, NU = 15, NZ = 45, NPB = 11, NP = NPB + NXR;
+    static constexpr int P_CMD0 = 0, P_CMD1 = 1, P_SW_L = 4, P_SW_R = 8;      // the class label's columns (see SrbdModel): p_sw(p, 0), p_sw(p, 2)
     static constexpr int XR = 0, XC = 3, XRD = 15, XCD = 18;
     static constexpr int REC_G = 0, NREC = NZ, NSO2T = 0, NSO2L = 0;
     static constexpr bool SO2 = false;

@@ -418,7 +418,8 @@ class DdpEngine:
 
     # ---- class history (queue_order = 3) -------------------------------------------------------------------------------------
     def set_instance_classes(self, classes, n_classes: int):
-        """classes [B] int (host): what kind of problem each instance is (-1: unlabelled); sddp.h queue_order 3"""
+        """classes [B] int (host): what kind of problem each instance is (-1: unlabelled); sddp.h queue_order 3.  Raises on a handle
+        that labels its instances itself (enable_auto_classes)."""
         c = np.ascontiguousarray(classes, dtype=np.int32)
         if c.shape != (self.B,):
             raise ValueError(f"expected {self.B} class labels")
@@ -437,6 +438,44 @@ class DdpEngine:
         m, n = C.c_double(), C.c_longlong()
         self._chk(self.lib.sddp_class_history(self.h, int(cls), C.byref(m), C.byref(n)))
         return m.value, n.value
+
+    # ---- auto classes: queue_order = 3 without caller labels; the history leaves and enters a handle (include/sddp.h) ---------------
+    def enable_auto_classes(self, on: bool = True):
+        """The handle labels its instances itself: every fresh solve launch computes, on the device and in front of everything else
+        it launches, the label workload.schedule_classes(model, params) states -- stance pattern at node 0, nodes to the first
+        contact switch, sign of the commanded velocity -- from the parameter tensor it runs on; n_classes = 36 (N + 2).  Raises if
+        the caller set labels with another n_classes first; while on, set_instance_classes* raise.  on=False: the labelling
+        stops, labels and history stay."""
+        self._chk(self.lib.sddp_enable_auto_classes(self.h, int(bool(on))))
+
+    def auto_classes_info(self):
+        """-> (on, n_classes of the handle's class table whoever made it; 0: none)"""
+        on, n = C.c_int(), C.c_int()
+        self._chk(self.lib.sddp_auto_classes_info(self.h, C.byref(on), C.byref(n)))
+        return bool(on.value), n.value
+
+    def instance_classes(self, first: int = 0, count: int | None = None):
+        """-> the class labels [count] int32 of the instances [first, first + count) (-1: unlabelled); waits for the stream."""
+        n = int(self.B - first if count is None else count)
+        out = np.empty(max(n, 0), dtype=np.int32)
+        self._chk(self.lib.sddp_fetch_instance_classes(self.h, int(first), n, _lib.ptr(out)))
+        return out
+
+    def class_stats(self, first_class: int = 0, count: int | None = None):
+        """-> the learned history [count, 2] uint64 = (sum of iterations, solves) of the classes [first_class, first_class + count),
+        all of them by default; waits for the stream."""
+        n = int(self.auto_classes_info()[1] - first_class if count is None else count)
+        out = np.zeros((max(n, 0), 2), dtype=np.uint64)
+        self._chk(self.lib.sddp_get_class_stats(self.h, int(first_class), n, _lib.ptr(out)))
+        return out
+
+    def add_class_stats(self, stats, first_class: int = 0):
+        """ADD a history [count, 2] (class_stats() of another handle of the same N: a restarted server, another shard) to this
+        handle's, classes [first_class, first_class + count); ordered on the handle's stream."""
+        s = np.ascontiguousarray(stats, dtype=np.uint64)
+        if s.ndim != 2 or s.shape[1] != 2:
+            raise ValueError("expected stats of shape [count, 2]")
+        self._chk(self.lib.sddp_add_class_stats(self.h, int(first_class), int(s.shape[0]), _lib.ptr(s)))
 
     RECORD_MODES = {"full": 0, "first_knot": 1, "first_knot_policy": 2}
 

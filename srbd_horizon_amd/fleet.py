@@ -75,8 +75,9 @@ class FleetQueue:
 
     def submit(self, x0, xs, us, params=None, classes=None, n_classes=0):
         """One step: one batch of instances enters the queue (device tensors of `batch` instances; `params` [batch, N+1, np]
-        replaces that block's parameters; `classes` [batch] int32 labels them for queue_order 3, sddp.h).  Raises when the handle
-        is full: flush first."""
+        replaces that block's parameters; `classes` [batch] int32 labels them for queue_order 3, sddp.h).  On an engine with
+        enable_auto_classes() pass no `classes`: the flush's launch labels every instance it solves itself, from `params_all` as it
+        stands then (labels passed to such an engine raise).  Raises when the handle is full: flush first."""
         if self.pending == self.depth:
             raise RuntimeError("FleetQueue is full: flush() (and consume the results) before submitting another batch")
         lo = self.pending * self.batch

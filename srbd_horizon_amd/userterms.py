@@ -321,6 +321,7 @@ int alloc_cold_queue(sddp_handle* h) {{ return g_core->alloc_cold_queue(h); }}
 int launch_queue_order(sddp_handle* h, int first, int count) {{ return g_core->launch_queue_order(h, first, count); }}
 int launch_class_keys(sddp_handle* h, int count) {{ return g_core->launch_class_keys(h, count); }}
 int launch_class_update(sddp_handle* h, int first, int count) {{ return g_core->launch_class_update(h, first, count); }}
+int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {{ return g_core->launch_class_labels(h, P, first, count); }}
 }}  // namespace sddp
 
 #define SDDP_USER_EXPORT extern "C" __attribute__((visibility("default")))

@@ -214,3 +214,36 @@ def srbd13_schedule_classes(params, signed=True):
         return c + ((v < -1e-12) & signed) if signed else c
     label = ((stance0 * (N + 2) + first_change) * nv + cmd(P[:, N, 0])) * nv + cmd(P[:, N, 1])
     return label.astype(np.int32), 4 * (N + 2) * nv * nv
+
+
+# The parameter columns the class label reads, per model: the commanded velocity (rdot_ref x, y) and the switch of the FIRST contact
+# of the left and of the right foot (prb.py layouts: srbd13 cdot_switch 17:19; the contact-state SRBD builds (c_ref_i, cdot_switch_i)
+# pairs from column 7, contact i at 8 + 2 i with i = 0 and i = nc / 2; LIP pairs from column 3, 4 + 2 i with i = 0, 2).  The same
+# table as csrc/sddp_models.hpp P_CMD0 / P_CMD1 / P_SW_L / P_SW_R, which the handle's own labelling reads (sddp_enable_auto_classes).
+CLASS_COLUMNS = {"srbd13": dict(cmd=(0, 1), sw=(17, 18)), "srbd37": dict(cmd=(0, 1), sw=(8, 12)),
+                 "srbd61": dict(cmd=(0, 1), sw=(8, 16)), "lip30": dict(cmd=(0, 1), sw=(4, 8))}
+
+
+def schedule_classes(model: str, params):
+    """The class label the library computes itself (sddp.h sddp_enable_auto_classes), stated in numpy for every model: the
+    signed label of srbd13_schedule_classes read from `model`'s columns (CLASS_COLUMNS).  params [B, N+1, >= np]: the user rows'
+    reference columns of an `_x` or user build lie behind the model's own and are not read.
+        sw[k, j]     = P[b, k, sw_col[j]] > 0.5                    j = 0 (left foot), 1 (right foot); a NaN is "not in stance"
+        stance0      = 2 sw[0, 0] + sw[0, 1]
+        first_change = smallest k in 1..N with sw[k, :] != sw[0, :], N + 1 if none
+        cmd(v)       = 0 if |v| <= 1e-12, 1 if v > 1e-12, 2 if v < -1e-12
+        label        = ((stance0 (N + 2) + first_change) 3 + cmd(P[b, N, cmd_col[0]])) 3 + cmd(P[b, N, cmd_col[1]])
+    -> (labels [B] int32, n_classes = 36 (N + 2))"""
+    cols = CLASS_COLUMNS[model]
+    P = np.asarray(params)
+    N = P.shape[1] - 1
+    with np.errstate(invalid="ignore"):
+        sw = P[:, :, list(cols["sw"])] > 0.5
+        stance0 = sw[:, 0, 0].astype(np.int64) * 2 + sw[:, 0, 1].astype(np.int64)
+        changed = np.any(sw != sw[:, :1, :], axis=2)
+        first_change = np.where(changed.any(axis=1), changed.argmax(axis=1), N + 1)
+
+        def cmd(v):
+            return np.where(v > 1e-12, 1, np.where(v < -1e-12, 2, 0)).astype(np.int64)
+        label = ((stance0 * (N + 2) + first_change) * 3 + cmd(P[:, N, cols["cmd"][0]])) * 3 + cmd(P[:, N, cols["cmd"][1]])
+    return label.astype(np.int32), 36 * (N + 2)
