@@ -36,14 +36,20 @@ namespace sddp {
 SDDP_BUILDS
 #undef X
 
+// error of a call without a handle (sddp_create, sddp_eval_knots): one per thread
 std::string& create_error() {
     thread_local std::string e;
     return e;
 }
+int fail(std::nullptr_t, int code, const std::string& msg) { create_error() = msg; return code; }
 
+namespace {
+// queue order 1 (longest previous solve first): counting sort of [first, first + count) by h->hist into h->order, on the stream
 int launch_queue_order(sddp_handle* h, int first, int count) {
     return launch(h, queue_order_kernel, 1, 1024, 0, first, count, h->hist, h->order);
 }
+// queue order 3: h->qkey (initial costs of the launch's instances, order h->order_in) -> class-history keys; and the update of the
+// class statistics behind a solve launch
 int launch_class_keys(sddp_handle* h, int count) {
     return launch(h, class_key_kernel, (count + 255) / 256, 256, 0, count, h->order_in, h->cls, h->n_cls, h->cls_stat, h->qkey);
 }
@@ -53,13 +59,13 @@ int launch_class_update(sddp_handle* h, int first, int count) {
                       h->resumable, h->resumable + 2 * size_t(h->B), h->continuing ? 1 : 0);
     return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat);
 }
+// auto classes: the labels of [first, first + count) from the launch's parameter tensor into h->cls, in front of a fresh solve launch
 int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {      // one wavefront per instance, four per workgroup
     const ModelOps* o = h->ops;
     return launch(h, class_label_kernel, (count + 3) / 4, 256, 0, h->N, h->d.np, o->col_cmd[0], o->col_cmd[1], o->col_sw[0], o->col_sw[1], first,
                   count, P, h->cls);
 }
 
-namespace {
 // Buffer ownership: every device and pinned allocation of a handle is made by acquire(), which registers it in h->owned.
 // sddp_destroy frees what is registered; release() frees what a handle gives up earlier, and nulls the pointer.
 // sddp_create reserves kOwnedReserve entries (host out-of-memory is SDDP_ERR_NOMEM there), more than a handle has buffers, so the
@@ -91,8 +97,8 @@ void release(sddp_handle* h, T*& p) {
         if (e_ != hipSuccess)                                                                                                 \
             return fail(h, SDDP_ERR_HIP, std::string("hipMalloc((void**)&" #field ", " #bytes "): ") + hipGetErrorString(e_)); \
     } while (0)
-}  // namespace
 
+// the cold-queue buffers of a handle, all or nothing (a partial failure leaves every pointer null)
 int alloc_cold_queue(sddp_handle* h) {
     if (h->sort_tmp) return SDDP_OK;               // the last pointer of the group: set only when all of it exists
     size_t tb = 0;
@@ -108,6 +114,7 @@ int alloc_cold_queue(sddp_handle* h) {
     h->sort_tmp_bytes = tb;
     return SDDP_OK;
 }
+}  // namespace
 }  // namespace sddp
 
 namespace {
@@ -219,20 +226,71 @@ int invalidate_resume(sddp_handle* h, int first, int count) {
     return SDDP_OK;
 }
 
-// Where the solve and the continue entry points meet: one launch sequence of the handle's build over [first, first + count).  With a
-// time budget armed (sddp_set_time_budget) the deadline stamp leads it on the stream -- in front of the queue_order pre-pass and the
-// sort, which the budget therefore covers.
 unsigned long long* clock_words(sddp_handle* h) {
     return reinterpret_cast<unsigned long long*>(h->resumable + ResumeArgs::clock_offset(h->B));
 }
-int launch_solve_sequence(sddp_handle* h, const SolveArgs& a, int first, int count) {
+// Where the solve and the continue entry points meet: one launch over the instances [first, first + count), as a sequence on the
+// handle's stream.  The build says which solve kernel runs, launches it (ModelOps::solve of the variant the handle's state asks for)
+// and has the cost-key kernel; the rest is here.  More instances than the grid -> work queue, in the order opts.queue_order asks for.
+int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
+    // with a time budget armed (sddp_set_time_budget) the deadline stamp leads: in front of the queue_order pre-pass and the sort,
+    // which the budget therefore covers
     if (h->budget_us > 0.0 && h->resumable) {
         // 100 MHz clock: ticks = round(100 * budget_us); capped where deadline = start + ticks could wrap
         const double t = std::min(std::round(100.0 * h->budget_us), 4.0e18);
         const int rc = launch(h, deadline_stamp_kernel, 1, 1, 0, clock_words(h), (unsigned long long)t);
         if (rc != SDDP_OK) return rc;
     }
-    return h->ops->launch_solve(h, a, first, count);
+    const ModelOps::SolveOps& solve = h->ops->solve[h->ilog ? kSolveLog : h->carry ? kSolveResume : kSolvePlain];
+    if (!solve.launch) return fail(h, SDDP_ERR_ARG, "this build has no kernels of the solve variant that the handle asks for");
+    SolveChoice k;
+    int rc = solve.choose(h, &k);
+    if (rc != SDDP_OK) return rc;
+    a.first = first; a.count = count;
+    // the timed interval of a launch covers its queue-ordering pre-pass (key kernel + sort, or the counting sort) as well
+    if (h->timing) {
+        while (h->ev.size() < 2 * (h->pending + 1)) {
+            hipEvent_t e;
+            HIP_TRY(h, hipEventCreate(&e));
+            try { h->ev.push_back(e); } catch (...) { (void)hipEventDestroy(e); return fail(h, SDDP_ERR_NOMEM, "out of host memory"); }
+        }
+        HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending], h->stream));
+    }
+    if (h->auto_cls && !h->continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
+        rc = launch_class_labels(h, a.P, first, count);      // continue launch keeps the labels of the solve that was cut
+        if (rc != SDDP_OK) return rc;
+    }
+    int grid = 0;
+    rc = queue_grid(h, a, k.slots, count, &grid);
+    if (rc != SDDP_OK) return rc;
+    if (count > grid && h->opts.queue_order >= 1) {
+        if (h->opts.queue_order == 1) {            // longest previous solve first
+            rc = launch_queue_order(h, first, count);
+        } else {                                   // largest initial cost first: keys by a pre-pass over the launch's instances
+            rc = alloc_cold_queue(h);
+            if (rc == SDDP_OK) rc = h->ops->launch_cost_keys(h, a, first, count);
+            // ... queue_order 3: longest class history first, the initial cost breaking ties
+            if (rc == SDDP_OK && h->opts.queue_order == 3 && h->cls) rc = launch_class_keys(h, count);
+            if (rc == SDDP_OK)
+                HIP_TRY(h, sort_pairs_desc(h->sort_tmp, h->sort_tmp_bytes, h->qkey, h->qkey2, h->order_in, h->order, count, h->stream));
+        }
+        if (rc != SDDP_OK) return rc;
+        a.order = h->order;
+    }
+    h->last_grid = grid; h->last_queued = count > grid ? count : 0;
+    h->last_build = k.wps;
+    h->last_kernel = k.kern;
+    h->last_lds = int(k.lds);
+    h->last_per_cu = k.slots / std::max(1, h->cus);
+    h->gains_by_instance = (count <= grid && first == 0);
+    rc = solve.launch(h, k, grid, a);
+    if (rc == SDDP_OK && h->cls) rc = launch_class_update(h, first, count);      // labelled instances feed the class statistics
+    if (rc != SDDP_OK) return rc;
+    if (h->timing) {
+        HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending + 1], h->stream));
+        ++h->pending;
+    }
+    return SDDP_OK;
 }
 
 // Pinned host staging of a small payload, `images` copies of it: allocated on first use where the payload is at most `limit`
@@ -339,17 +397,13 @@ int sddp_register_user_build(const char* path, int* model_id) {
     auto base_fn = reinterpret_cast<IntFn>(dlsym(dl, "sddp_user_base_model"));
     auto rows_fn = reinterpret_cast<IntFn>(dlsym(dl, "sddp_user_rows"));
     auto stamp_fn = reinterpret_cast<StampFn>(dlsym(dl, "sddp_user_header_stamp"));
-    auto bind_fn = reinterpret_cast<void (*)(const CoreHooks*)>(dlsym(dl, "sddp_user_bind"));
     const char* err = nullptr;
-    if (!ops_fn || !base_fn || !rows_fn || !stamp_fn || !bind_fn) err = "user build: an accessor is missing (not a user build?)";
+    if (!ops_fn || !base_fn || !rows_fn || !stamp_fn) err = "user build: an accessor is missing (not a user build?)";
     else if (SDDP_HEADER_STAMP == 0ULL || stamp_fn() != SDDP_HEADER_STAMP)
         err = "user build: compiled against other headers than this library (rebuild it)";
     else if (base_fn() != SDDP_MODEL_SRBD13 && base_fn() != SDDP_MODEL_SRBD37) err = "user build: base model must be srbd13 or srbd37";
     else if (rows_fn() < 1 || rows_fn() > SDDP_MAX_EXTRA) err = "user build: 1..8 user rows";
     if (err) { dlclose(dl); return fail(nullptr, SDDP_ERR_ARG, err); }
-    static const CoreHooks hooks{&create_error, &alloc_cold_queue, &launch_queue_order, &launch_class_keys, &launch_class_update,
-                                  &launch_class_labels};
-    bind_fn(&hooks);
     try {
         v.push_back(UserBuild{std::string(path), ops_fn(), base_fn(), rows_fn()});
     } catch (...) {
@@ -658,7 +712,7 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     if (on && !plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build)");
-    if (on && !h->ops->launch_solve_variant[kSolveResume]) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no kernels of that solve variant");
+    if (on && !h->ops->solve[kSolveResume].launch) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no kernels of that solve variant");
     if (on && h->opts.second_order == 2)      // (lip30, whose one build takes the option: the resumable kernels are not tested with it)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no second_order = 2)");
     if ((on != 0) == (h->carry != nullptr)) return SDDP_OK;
@@ -760,7 +814,7 @@ int sddp_enable_iteration_log(sddp_handle* h, int rows) {
     if (rows > 0 && !plain_build(h))
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: the iteration log exists for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build), like sddp_enable_resume");
-    if (rows > 0 && !h->ops->launch_solve_variant[kSolveLog]) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no kernels of that solve variant");
+    if (rows > 0 && !h->ops->solve[kSolveLog].launch) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no kernels of that solve variant");
     if (rows > 0 && !h->carry)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: call sddp_enable_resume first (the log is kept by the resumable kernels; plain "
                                      "builds only)");

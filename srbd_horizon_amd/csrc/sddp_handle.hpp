@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -38,6 +39,14 @@ inline int model_of_name(const char* name) {
 // suffix in srbd_horizon_amd/_lib.py VARIANTS, in the same order.
 enum SolveVariant { kSolvePlain = 0, kSolveResume, kSolveLog, kSolveVariants };
 
+// the solve kernel of a launch (ModelOps::SolveOps::choose): its address, the build it belongs to (wavefronts per SIMD: 1, or 2 for
+// the half-register-file build), its resident workgroups on this device, and its launch shape
+struct SolveChoice {
+    const void* kern;
+    int wps, slots, threads;
+    size_t lds;
+};
+
 // what a model build is and provides (sddp_launch.hpp: make_ops<M>)
 struct ModelOps {
     // the build's key: a handle's build is the one whose model and traits are the ones asked for (sddp_api.hip model_ops)
@@ -52,12 +61,16 @@ struct ModelOps {
     bool w2_build;         // a half-register-file build exists (two instances per SIMD / two workgroups per CU)
     const char* name;      // kernel-facing model name (bench / profiles)
     int (*max_slots)(sddp_handle*, int*);
-    int (*launch_solve)(sddp_handle*, SolveArgs, int, int);      // picks the variant the handle's state asks for
-    // one launcher per variant of the solve kernels.  [kSolvePlain] is always set; the others are null where the build has none (every
-    // build with traits), and are compiled in a translation unit of their own each (sddp_inst.hip with -DSDDP_INST_VARIANT=<variant>).
-    // launch_cost_keys: the queue_order 2 / 3 key pre-pass, which those units call through this table instead of instantiating the key
-    // kernel a second time
-    int (*launch_solve_variant[kSolveVariants])(sddp_handle*, SolveArgs, int, int) = {};
+    // what a solve launch asks of the build, per variant of the solve kernels: choose = the kernel that the handle's state selects
+    // (waves_per_simd, the table), launch = that kernel on `grid` workgroups.  The launch sequence around them is the core's
+    // (sddp_api.hip launch_solve_sequence).  [kSolvePlain] is always set; the others are null where the build has none (every build
+    // with traits), and are compiled in a translation unit of their own each (sddp_inst.hip with -DSDDP_INST_VARIANT=<variant>).
+    struct SolveOps {
+        int (*choose)(sddp_handle*, SolveChoice*) = nullptr;
+        int (*launch)(sddp_handle*, const SolveChoice&, int grid, const SolveArgs&) = nullptr;
+    };
+    SolveOps solve[kSolveVariants];
+    // the queue_order 2 / 3 key pre-pass: the initial cost of every instance of the launch, into h->qkey / h->order_in (main unit)
     int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
@@ -170,13 +183,8 @@ struct sddp_handle {
 
 namespace sddp {
 
-// error of a call without a handle (sddp_create, sddp_eval_knots): one per thread, defined in sddp_api.hip
-std::string& create_error();
-
-inline int fail(sddp_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg; else create_error() = msg;
-    return code;
-}
+// (a call without a handle -- sddp_create, sddp_eval_knots -- reports through sddp_api.hip's own overload: no launcher sees one)
+inline int fail(sddp_handle* h, int code, const std::string& msg) { h->err = msg; return code; }
 
 #define HIP_TRY(h, expr)                                                                               \
     do {                                                                                               \
@@ -193,26 +201,16 @@ int launch(sddp_handle* h, Fn kern, int grid, int threads, size_t lds, const A&.
     return SDDP_OK;
 }
 
-// the cold-queue buffers of a handle, all or nothing (a partial failure leaves every pointer null)
-int alloc_cold_queue(sddp_handle* h);
-// queue order 1 (longest previous solve first): counting sort of [first, first + count) by h->hist into h->order, on the stream
-int launch_queue_order(sddp_handle* h, int first, int count);
-// queue order 3: h->qkey (initial costs of the launch's instances, order h->order_in) -> class-history keys; and the update of the
-// class statistics behind a solve launch
-int launch_class_keys(sddp_handle* h, int count);
-int launch_class_update(sddp_handle* h, int first, int count);
-// auto classes: the labels of [first, first + count) from the launch's parameter tensor into h->cls, in front of a fresh solve launch
-int launch_class_labels(sddp_handle* h, const double* P, int first, int count);
-
-// the services above as a user build reaches them (srbd_horizon_amd/userterms.py): it is loaded RTLD_LOCAL and cannot resolve this
-// library's symbols, so sddp_register_user_build hands it this table and the build's own definitions of them call through it
-struct CoreHooks {
-    std::string& (*create_error)();
-    int (*alloc_cold_queue)(sddp_handle*);
-    int (*launch_queue_order)(sddp_handle*, int, int);
-    int (*launch_class_keys)(sddp_handle*, int);
-    int (*launch_class_update)(sddp_handle*, int, int);
-    int (*launch_class_labels)(sddp_handle*, const double*, int, int);
-};
+// The grid of a launch over `count` instances by a kernel with `slots` resident workgroups: at most the slots the work buffers exist
+// for, and opts.max_slots.  More instances than that make a work queue: its head is zeroed on the stream and entered in `a`.
+inline int queue_grid(sddp_handle* h, SolveArgs& a, int slots, int count, int* grid) {
+    *grid = std::min(count, std::min(slots, h->wslots));
+    if (h->opts.max_slots > 0) *grid = std::min(*grid, h->opts.max_slots);
+    if (count > *grid) {
+        HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
+        a.qhead = h->qhead;
+    }
+    return SDDP_OK;
+}
 
 }  // namespace sddp

@@ -5,8 +5,8 @@
 // the accessors' names from the same list and finds a handle's build among them by (model, traits).
 // The plain builds (the entries without traits) are compiled once more per solve variant beyond kSolvePlain (sddp_handle.hpp
 // SolveVariant), with -DSDDP_INST_VARIANT=<its value>: such a side unit holds nothing but that variant's instantiations of the
-// solve kernels and their launcher, which the main unit (no such definition, or 0) enters in its table (sddp_launch.hpp
-// enter_side_launchers).  A side unit of a build with traits does not compile (launch_solve_variant).
+// solve kernels and their two table entries, which the main unit (no such definition, or 0) enters in its table (sddp_launch.hpp
+// enter_side_units).  A side unit of a build with traits does not compile (with_solve_kernels).
 #include "sddp_launch.hpp"
 
 #if !defined(SDDP_INST_MODEL) || !defined(SDDP_INST_FN) || !defined(SDDP_INST_NAME)
@@ -20,8 +20,8 @@ namespace sddp {
 #if SDDP_INST_VARIANT != 0
 static_assert(SDDP_INST_VARIANT > 0 && SDDP_INST_VARIANT < kSolveVariants, "-DSDDP_INST_VARIANT: a value of SolveVariant");
 template <>
-int side_launcher<SDDP_INST_MODEL, SolveVariant(SDDP_INST_VARIANT)>(sddp_handle* h, SolveArgs a, int first, int count) {
-    return launch_solve_variant<SDDP_INST_MODEL, SolveVariant(SDDP_INST_VARIANT)>(h, a, first, count);
+ModelOps::SolveOps side_solve_ops<SDDP_INST_MODEL, SolveVariant(SDDP_INST_VARIANT)>() {
+    return solve_ops<SDDP_INST_MODEL, SolveVariant(SDDP_INST_VARIANT)>();
 }
 #else
 const ModelOps* SDDP_INST_FN() {

@@ -9,7 +9,6 @@
 #include "sddp_kernels.hpp"
 #include "sddp_kernels_mw.hpp"
 #include "sddp_models.hpp"
-#include "sddp_sort.hpp"
 
 namespace sddp {
 
@@ -31,7 +30,7 @@ constexpr int threads_of() { return use_mw<M>() ? kThreadsMW : kWave; }
 
 // A build's traits are M::BAR (barrier build), M::SO2 (full second order) and M::NXR > 0 (user rows; the user builds too).  A
 // PLAIN build has none of them.  This is the one statement of the rule: what only the plain builds have refers to it, and
-// sddp_api.hip reads the outcome from the build's table (ModelOps::table_kernels, launch_solve_variant) instead of deriving it.
+// sddp_api.hip reads the outcome from the build's table (ModelOps::table_kernels, solve[]) instead of deriving it.
 template <class M>
 constexpr bool is_plain() { return !M::BAR && !M::SO2 && M::NXR == 0; }
 
@@ -58,7 +57,7 @@ inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return 
 // beyond kSolvePlain (without and with the table), told apart by what they take behind SolveArgs.  A handle with a carry buffer
 // (sddp_enable_resume) launches kSolveResume, one with a log buffer as well (sddp_enable_iteration_log) kSolveLog; sddp_api.hip
 // refuses either buffer on every other build.  Each variant is compiled in a translation unit of its own (sddp_inst.hip with
-// -DSDDP_INST_VARIANT; launch_solve_variant<M, V> is instantiated nowhere else): with them in the same device module the ordinary
+// -DSDDP_INST_VARIANT; solve_ops<M, V> is instantiated nowhere else): with them in the same device module the ordinary
 // one-wave kernels come out with another register allocation and 4 bytes less or more scratch, though not a statement of theirs
 // differs (profiles/resume/README.md, profiles/iteration_log/README.md).
 // What variant V passes behind SolveArgs, in the kernels' order (the table, if any, follows): the one place that says so.
@@ -124,103 +123,52 @@ int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
     });
 }
 
-// one launch over the instances [first, first + count): grid = resident slots, at most `count` and at most the slots the work
-// buffers exist for; more instances than slots -> work queue, in longest-previous-solve-first order when opts.queue_order is set
-template <class M, SolveVariant V, class... Tab>
-int launch_solve_on(sddp_handle* h, SolveArgs a, int first, int count, Tab... tab) {
-    int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
-    // the kernels' trailing arguments: they name the instantiation and are what the launch passes
-    const auto extra = std::tuple_cat(variant_args<V>(h), std::make_tuple(tab...));
-    auto pick = [&](int w) { return std::apply([w](const auto&... x) { return pick_solve<M, std::decay_t<decltype(x)>...>(w); }, extra); };
-    auto kern = pick(wps);
-    int slots = 0;
-    int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
-    if (rc != SDDP_OK) return rc;
-    if constexpr (use_mw<M>()) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
-        if (wps >= 2) {
-            auto k1 = pick(1);
-            int s1 = 0;
-            rc = kernel_slots<M>(h, k1, solve_cap<M>(1), &s1);
-            if (rc != SDDP_OK) return rc;
-            if (s1 >= slots) { kern = k1; slots = s1; wps = 1; }
-        }
-    }
-    int grid = std::min(count, std::min(slots, h->wslots));
-    if (h->opts.max_slots > 0) grid = std::min(grid, h->opts.max_slots);
-    a.first = first; a.count = count;
-    // the timed interval of a launch covers its queue-ordering pre-pass (key kernel + sort, or the counting sort) as well
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->timing) {
-        while (h->ev.size() < 2 * (h->pending + 1)) {
-            hipEvent_t e;
-            HIP_TRY(h, hipEventCreate(&e));
-            try { h->ev.push_back(e); } catch (...) { (void)hipEventDestroy(e); return fail(h, SDDP_ERR_NOMEM, "out of host memory"); }
-        }
-        e0 = h->ev[2 * h->pending];
-        e1 = h->ev[2 * h->pending + 1];
-        HIP_TRY(h, hipEventRecord(e0, h->stream));
-    }
-    if (h->auto_cls && !h->continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
-        rc = launch_class_labels(h, a.P, first, count);      // continue launch keeps the labels of the solve that was cut
-        if (rc != SDDP_OK) return rc;
-    }
-    if (count > grid) {
-        HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
-        a.qhead = h->qhead;
-        if (h->opts.queue_order == 1) {            // longest previous solve first
-            rc = launch_queue_order(h, first, count);
-            if (rc != SDDP_OK) return rc;
-            a.order = h->order;
-        } else if (h->opts.queue_order >= 2) {     // largest initial cost first: keys by a pre-pass over the launch's instances
-            rc = alloc_cold_queue(h);
-            if (rc != SDDP_OK) return rc;
-            if constexpr (V != kSolvePlain) rc = h->ops->launch_cost_keys(h, a, first, count);      // (the key kernel lives in the build's main unit)
-            else rc = launch_cost_keys<M>(h, a, first, count);
-            if (rc != SDDP_OK) return rc;
-            if (h->opts.queue_order == 3 && h->cls) {   // ... longest class history first, the initial cost breaking ties
-                rc = launch_class_keys(h, count);
-                if (rc != SDDP_OK) return rc;
-            }
-            HIP_TRY(h, sort_pairs_desc(h->sort_tmp, h->sort_tmp_bytes, h->qkey, h->qkey2, h->order_in, h->order, count, h->stream));
-            a.order = h->order;
-        }
-    }
-    h->last_grid = grid; h->last_queued = count > grid ? count : 0;
-    h->last_build = wps;
-    h->last_kernel = reinterpret_cast<const void*>(kern);
-    h->last_lds = int(lds_bytes<M>());
-    h->last_per_cu = slots / std::max(1, h->cus);
-    h->gains_by_instance = (count <= grid && first == 0);
-    rc = std::apply([&](const auto&... x) { return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, x...); }, extra);
-    if (rc != SDDP_OK) return rc;
-    if (h->cls) {                                       // labelled instances: their iteration counts feed the class statistics
-        rc = launch_class_update(h, first, count);
-        if (rc != SDDP_OK) return rc;
-    }
-    if (h->timing) {
-        HIP_TRY(h, hipEventRecord(e1, h->stream));
-        ++h->pending;
-    }
-    return SDDP_OK;
-}
-template <class M, SolveVariant V>
-int launch_solve_variant(sddp_handle* h, SolveArgs a, int first, int count) {
+// The solve kernels of variant V as the handle launches them: f(pick, extra...), with pick(w) the kernel of the build for w wavefronts
+// per SIMD and extra... the kernels' trailing arguments, the variant's and then the table when it is active.  That one pack names the
+// instantiation and is what the launch passes.
+template <class M, SolveVariant V, class F>
+int with_solve_kernels(sddp_handle* h, F f) {
     static_assert(V == kSolvePlain || is_plain<M>(), "the plain builds alone have solve variants");
-    return with_table<M>(h, [&](auto... tab) { return launch_solve_on<M, V>(h, a, first, count, tab...); });
+    return with_table<M>(h, [&](auto... tab) {
+        return std::apply([&](const auto&... x) { return f([](int w) { return pick_solve<M, std::decay_t<decltype(x)>...>(w); }, x...); },
+                          std::tuple_cat(variant_args<V>(h), std::make_tuple(tab...)));
+    });
 }
-// launch_solve_variant<M, V> for V > 0 as the build's main unit names it without instantiating it: declared here, defined (an
-// explicit specialisation) by the unit compiled with -DSDDP_INST_VARIANT=V alone.  A build whose side unit is missing does not load.
+// ModelOps::SolveOps of variant V.  choose: the build opts.waves_per_simd asks for, where the model has it
 template <class M, SolveVariant V>
-int side_launcher(sddp_handle* h, SolveArgs a, int first, int count);
-template <class M, int... V>
-void enter_side_launchers(ModelOps& o, std::integer_sequence<int, V...>) {
-    if constexpr (is_plain<M>()) ((o.launch_solve_variant[V + 1] = side_launcher<M, SolveVariant(V + 1)>), ...);
+int choose_solve(sddp_handle* h, SolveChoice* c) {
+    return with_solve_kernels<M, V>(h, [&](auto pick, const auto&...) {
+        int wps = h->opts.waves_per_simd >= 2 && has_w2<M>() ? 2 : 1;
+        auto kern = pick(wps);
+        int slots = 0;
+        int rc = kernel_slots<M>(h, kern, solve_cap<M>(wps), &slots);
+        if (rc != SDDP_OK) return rc;
+        if constexpr (use_mw<M>()) {   // a half-register-file build that the device still runs one per CU (barrier builds) has nothing to offer
+            if (wps >= 2) {
+                auto k1 = pick(1);
+                int s1 = 0;
+                rc = kernel_slots<M>(h, k1, solve_cap<M>(1), &s1);
+                if (rc != SDDP_OK) return rc;
+                if (s1 >= slots) { kern = k1; slots = s1; wps = 1; }
+            }
+        }
+        *c = {reinterpret_cast<const void*>(kern), wps, slots, threads_of<M>(), lds_bytes<M>()};
+        return SDDP_OK;
+    });
 }
-template <class M>
-int launch_solve(sddp_handle* h, SolveArgs a, int first, int count) {
-    const SolveVariant v = h->ilog ? kSolveLog : h->carry ? kSolveResume : kSolvePlain;
-    if (!h->ops->launch_solve_variant[v]) return fail(h, SDDP_ERR_ARG, "this build has no kernels of the solve variant that the handle asks for");
-    return h->ops->launch_solve_variant[v](h, a, first, count);
+template <class M, SolveVariant V>
+int launch_solve(sddp_handle* h, const SolveChoice& c, int grid, const SolveArgs& a) {
+    return with_solve_kernels<M, V>(h, [&](auto pick, const auto&... x) { return launch(h, pick(c.wps), grid, c.threads, c.lds, a, x...); });
+}
+template <class M, SolveVariant V>
+ModelOps::SolveOps solve_ops() { return {choose_solve<M, V>, launch_solve<M, V>}; }
+// solve_ops<M, V> for V > 0 as the build's main unit names it without instantiating it: declared here, defined (an explicit
+// specialisation) by the unit compiled with -DSDDP_INST_VARIANT=V alone.  A build whose side unit is missing does not load.
+template <class M, SolveVariant V>
+ModelOps::SolveOps side_solve_ops();
+template <class M, int... V>
+void enter_side_units(ModelOps& o, std::integer_sequence<int, V...>) {
+    if constexpr (is_plain<M>()) ((o.solve[V + 1] = side_solve_ops<M, SolveVariant(V + 1)>()), ...);
 }
 // resident capacity over the builds a handle may switch between (sddp_set_options): sizes the work buffers
 template <class M>
@@ -261,13 +209,10 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
         int slots = 0;
         int rc = kernel_slots<M>(h, kern, use_mw<M>() ? 0 : 8, &slots);
         if (rc != SDDP_OK) return rc;
-        int grid = std::min(count, std::min(slots, h->wslots));
-        if (h->opts.max_slots > 0) grid = std::min(grid, h->opts.max_slots);
         a.first = first; a.count = count; a.order = nullptr; a.qhead = nullptr;
-        if (count > grid) {
-            HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
-            a.qhead = h->qhead;
-        }
+        int grid = 0;
+        rc = queue_grid(h, a, slots, count, &grid);
+        if (rc != SDDP_OK) return rc;
         return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep, tab...);
     });
 }
@@ -297,9 +242,8 @@ ModelOps make_ops(const char* name) {
     o.w2_build = has_w2<M>();
     o.name = name;
     o.max_slots = max_slots<M>;
-    o.launch_solve = launch_solve<M>;
-    o.launch_solve_variant[kSolvePlain] = launch_solve_variant<M, kSolvePlain>;
-    enter_side_launchers<M>(o, std::make_integer_sequence<int, kSolveVariants - 1>());
+    o.solve[kSolvePlain] = solve_ops<M, kSolvePlain>();
+    enter_side_units<M>(o, std::make_integer_sequence<int, kSolveVariants - 1>());
     o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;

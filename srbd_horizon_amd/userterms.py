@@ -314,18 +314,9 @@ namespace sddp {{
 using SddpUserModel = SrbdModel<{targs}, false, false, kXrRows, ::SddpUserRows>;
 static_assert(SddpUserModel::NPB == {npb}, "parameter layout of the generated rows");
 {mw_check}
-// the core library's services (sddp_handle.hpp CoreHooks), reached through the table sddp_register_user_build hands over
-static const CoreHooks* g_core = nullptr;
-std::string& create_error() {{ return g_core->create_error(); }}
-int alloc_cold_queue(sddp_handle* h) {{ return g_core->alloc_cold_queue(h); }}
-int launch_queue_order(sddp_handle* h, int first, int count) {{ return g_core->launch_queue_order(h, first, count); }}
-int launch_class_keys(sddp_handle* h, int count) {{ return g_core->launch_class_keys(h, count); }}
-int launch_class_update(sddp_handle* h, int first, int count) {{ return g_core->launch_class_update(h, first, count); }}
-int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {{ return g_core->launch_class_labels(h, P, first, count); }}
 }}  // namespace sddp
 
 #define SDDP_USER_EXPORT extern "C" __attribute__((visibility("default")))
-SDDP_USER_EXPORT void sddp_user_bind(const sddp::CoreHooks* hooks) {{ sddp::g_core = hooks; }}
 SDDP_USER_EXPORT const sddp::ModelOps* sddp_user_ops() {{
     static const sddp::ModelOps ops = sddp::make_ops<sddp::SddpUserModel>("{spec.model}");
     return &ops;
@@ -339,18 +330,18 @@ SDDP_USER_EXPORT int sddp_user_rows() {{ return {len(spec.rows)}; }}
 # ---- compilation ------------------------------------------------------------------------------------------------------------
 def _command(src_path: str, out_path: str, root: str = _lib.ROOT):
     """A user build is compiled like a model build of the library (_lib.compile_command); the tail is its own: one shared object of
-    the generated unit and the queue sort, which exports the accessors alone."""
+    the generated unit, which exports the accessors alone."""
     return _lib.compile_command(root=root) + ["-fvisibility=hidden", f"-DSDDP_HEADER_STAMP={_lib.header_stamp(root)}ULL", "-shared", src_path,
-                                              os.path.join(root, "srbd_horizon_amd", "csrc", "sddp_sort.hip"), "-o", out_path]
+                                              "-o", out_path]
 
 
 def build_key(src: str, root: str = _lib.ROOT) -> str:
-    """Cache key of a user build: the generated source, csrc/*.hpp, csrc/sddp_sort.hip, include/sddp.h and the command line
+    """Cache key of a user build: the generated source, csrc/*.hpp, include/sddp.h and the command line
     (paths relative to the tree, so a tree built elsewhere finds its builds)."""
     h = hashlib.sha256(src.encode())
     csrc = os.path.join(root, "srbd_horizon_amd", "csrc")
     for f in sorted(os.listdir(csrc)):
-        if f.endswith(".hpp") or f == "sddp_sort.hip":
+        if f.endswith(".hpp"):
             h.update(f.encode())
             h.update(open(os.path.join(csrc, f), "rb").read())
     h.update(open(os.path.join(root, "include", "sddp.h"), "rb").read())

@@ -2,6 +2,7 @@
 sympy, what NonlinearTerm and the adapter refuse, the cache key, and a user build compiled for gfx950."""
 import ctypes.util
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -260,7 +261,7 @@ def test_user_build_compiles_for_gfx950_and_is_self_contained():
     path = userterms.ensure_build(spec)
     assert os.path.basename(path) == userterms.build_key(userterms.source(spec)) + ".so"
     exported = _dynamic_symbols(path)
-    for acc in ("sddp_user_ops", "sddp_user_base_model", "sddp_user_header_stamp", "sddp_user_rows", "sddp_user_bind"):
+    for acc in ("sddp_user_ops", "sddp_user_base_model", "sddp_user_header_stamp", "sddp_user_rows"):
         assert acc in exported
     assert not any(s.startswith("sddp_") and not s.startswith("sddp_user_") for s in exported)
     # gfx950 device code inside
@@ -280,6 +281,20 @@ def test_user_build_compiles_for_gfx950_and_is_self_contained():
     assert undef - provided == set(), undef - provided
     ldd = subprocess.run(["ldd", path], capture_output=True, text=True).stdout
     assert "libsddp_hip" not in ldd
+
+
+def test_user_build_is_one_unit_that_calls_nothing_of_the_core():
+    """The launch sequence is the core's (csrc/sddp_api.hip): a user build brings its kernels and their launchers, defines none of
+    the core's services and compiles no source but its own."""
+    spec = defs.spec_of(defs.srbd13_terrain(20)[1])
+    src = userterms.source(spec)
+    assert "CoreHooks" not in src and "sddp_user_bind" not in src
+    assert not re.search(r"\b(launch_class_\w*|launch_queue_order|alloc_cold_queue)\b", src)
+    cmd = userterms._command("/tmp/unit.hip", "/tmp/unit.so")
+    assert [a for a in cmd if a.endswith((".hip", ".cpp", ".cc", ".c", ".o"))] == ["/tmp/unit.hip"]
+    headers = os.path.join(ROOT, "srbd_horizon_amd", "csrc")
+    launch = open(os.path.join(headers, "sddp_launch.hpp")).read()
+    assert "sddp_sort" not in launch and "CoreHooks" not in open(os.path.join(headers, "sddp_handle.hpp")).read()
 
 
 def test_problem_without_declarations_keeps_no_user_rows():
