@@ -40,7 +40,7 @@ def main():
         eng.enable_auto_classes()                                         # no label is ever passed
         eng.enable_timing()
         eng.set_params(P_long[:, :N + 1])
-        eng.set_initial_state(long["x0"]); eng.set_x_warmstart(long["xs"][:, :N + 1]); eng.set_u_warmstart(long["us"][:, :N])
+        eng.load(long["x0"], long["xs"][:, :N + 1], long["us"][:, :N])
         return eng
 
     ok = True

@@ -24,7 +24,7 @@ def main():
     eng = DdpEngine("srbd13", N, B, opts=dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3), consts=b["consts"])
     eng.enable_resume()                      # the log is kept by the resumable kernels
     eng.enable_iteration_log(ROWS)
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
     eng.solve(b["params"])
     st = eng.stats.copy()
     rec, n = eng.iteration_log()

@@ -49,6 +49,10 @@ class DdpEngine:
     def _chk(self, rc):
         _lib.check(rc, self.h)
 
+    def _count(self, first, count):
+        """how many instances [first, first + count) are; count = None: all from `first` on"""
+        return int(self.B - first if count is None else count)
+
     @staticmethod
     def _c(a, shape):
         a = np.ascontiguousarray(a, dtype=np.float64)
@@ -75,6 +79,16 @@ class DdpEngine:
     def set_u_warmstart(self, u):
         a = self._c(u, (self.B, self.N, self.nu))
         self._chk(self.lib.sddp_set_u_warmstart(self.h, _lib.ptr(a)))
+
+    def load(self, x0=None, x=None, u=None):
+        """Initial state / warm start of every instance from host arrays (the host counterpart of load_range_device): the setters
+        of the arguments given, in this order."""
+        if x0 is not None:
+            self.set_initial_state(x0)
+        if x is not None:
+            self.set_x_warmstart(x)
+        if u is not None:
+            self.set_u_warmstart(u)
 
     def solve(self, params):
         p = self._c(params, (self.B, self.N + 1, self.np_))
@@ -143,11 +157,11 @@ class DdpEngine:
 
     def policy_range_device(self, first: int = 0, count: int | None = None):
         """One sweep per instance of [first, first + count) at the iterate the last solve returned; asynchronous, behind the solve."""
-        self._chk(self.lib.sddp_policy_range_device(self.h, int(first), int(self.B - first if count is None else count)))
+        self._chk(self.lib.sddp_policy_range_device(self.h, int(first), self._count(first, count)))
 
     def fetch_policy(self, first: int = 0, count: int | None = None):
         """The raw policy records [count, words] of the last policy launch (waits for the stream)."""
-        n = int(self.B - first if count is None else count)
+        n = self._count(first, count)
         out = np.empty((max(n, 0), self.policy_words()[0]))
         self._chk(self.lib.sddp_fetch_policy(self.h, int(first), n, _lib.ptr(out)))
         return out
@@ -166,7 +180,7 @@ class DdpEngine:
 
     def apply_policy_device(self, x_meas, u_out, first: int = 0, count: int | None = None):
         """u_out[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]), b = first + i: device tensors [count, nx] -> [count, nu]; asynchronous."""
-        n = int(self.B - first if count is None else count)
+        n = self._count(first, count)
         self._chk(self.lib.sddp_apply_policy_device(self.h, int(first), n, self._dev(x_meas, (n, self.nx)), self._dev(u_out, (n, self.nu))))
         return u_out
 
@@ -256,25 +270,29 @@ class DdpEngine:
         self._chk(self.lib.sddp_device_ptr(self.h, which, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def device_view(self, which: int, shape=None, typestr="<f8"):
+        """Zero-copy torch view of device_buffer(which); shape None: the whole buffer, flat.  No synchronisation: ordered behind the
+        handle's stream like any torch work on it."""
+        import torch
+        ptr, nbytes = self.device_buffer(which)
+        shape = (nbytes // int(typestr[2:]),) if shape is None else tuple(shape)
+
+        class _Dev:
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+        return torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device()))
+
+    def _host_copy(self, which, typestr):
+        """device_buffer(which), whole, as a host array; waits for the stream"""
+        self.synchronize()
+        return self.device_view(which, None, typestr).cpu().numpy().copy()
+
     def fetch_device_views(self):
         """Zero-copy torch views of the handle's HBM buffers: x [B,N+1,nx], u [B,N,nu], stats as f64 [B,8] and i32 [B,16]
         (sddp_stats: cost, alpha, gap, mu, expected, rho | iters, converged, status, rollouts = i32 words 12..15;
         _lib.STATS_I32_ITERS etc.)."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-        class _Dev:
-            def __init__(self, ptr, shape, typestr):
-                self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-
-        px, _ = self.device_buffer(0)
-        pu, _ = self.device_buffer(1)
-        ps, _ = self.device_buffer(2)
-        x = torch.as_tensor(_Dev(px, (self.B, self.N + 1, self.nx), "<f8"), device=dev)
-        u = torch.as_tensor(_Dev(pu, (self.B, self.N, self.nu), "<f8"), device=dev)
-        sf = torch.as_tensor(_Dev(ps, (self.B, _lib.STATS_F64_WORDS), "<f8"), device=dev)
-        si = torch.as_tensor(_Dev(ps, (self.B, _lib.STATS_I32_WORDS), "<i4"), device=dev)
-        return x, u, sf, si
+        return (self.device_view(0, (self.B, self.N + 1, self.nx)), self.device_view(1, (self.B, self.N, self.nu)),
+                self.device_view(2, (self.B, _lib.STATS_F64_WORDS)), self.device_view(2, (self.B, _lib.STATS_I32_WORDS), "<i4"))
 
     def fetch(self):
         """Copy the solution and stats of the last device solve to host numpy arrays (waits for the handle's stream)."""
@@ -310,7 +328,7 @@ class DdpEngine:
         """One asynchronous launch that takes up the unfinished instances (status 1) of [first, first + count) where they stopped and
         runs them while iters < max_iters -- the TOTAL cap: raise it with set_options(max_iters=...) first.  Every other instance
         is left untouched.  params: the device tensor [B, N+1, np] the cut solve ran on; None = the resident tensor."""
-        n = int(self.B - first if count is None else count)
+        n = self._count(first, count)
         if params is None and first == 0 and n == self.B:
             self._chk(self.lib.sddp_continue_resident(self.h))
             return
@@ -320,7 +338,7 @@ class DdpEngine:
     def unfinished(self, first: int = 0, count: int | None = None) -> int:
         """How many instances of [first, first + count) can be continued (waits for the stream)."""
         n = C.c_int()
-        self._chk(self.lib.sddp_unfinished_count(self.h, int(first), int(self.B - first if count is None else count), C.byref(n)))
+        self._chk(self.lib.sddp_unfinished_count(self.h, int(first), self._count(first, count), C.byref(n)))
         return n.value
 
     # ---- time-budgeted launches: a launch that ends at a device-clock deadline, resumable (include/sddp.h) --------------------
@@ -341,14 +359,7 @@ class DdpEngine:
     def deadline_clock(self):
         """(start, deadline) of the last launch sequence that ran under a budget, on the 100 MHz clock of slot_times() -- device
         buffer 11; waits for the stream."""
-        import torch
-        self.synchronize()
-        ptr, _ = self.device_buffer(11)
-
-        class _Dev:
-            __cuda_array_interface__ = {"shape": (2,), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
-
-        t = torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device())).cpu().numpy().copy().view(np.uint64)
+        t = self._host_copy(11, "<i8").view(np.uint64)
         return int(t[0]), int(t[1])
 
     def deadline_overrun_us(self) -> float:
@@ -374,7 +385,7 @@ class DdpEngine:
     def iteration_log(self, first: int = 0, count: int | None = None):
         """-> (records [count, rows, 16], n [count] int32) of the instances [first, first + count) as numpy (waits for the stream):
         the rows [0, n[i]) of instance first + i are the line searches of its last solve, continue launches included."""
-        n = int(self.B - first if count is None else count)
+        n = self._count(first, count)
         rec = np.empty((max(n, 0), self.iteration_log_rows(), _lib.LOG_WORDS))
         cnt = np.empty(max(n, 0), dtype=np.int32)
         self._chk(self.lib.sddp_fetch_iteration_log(self.h, int(first), n, _lib.ptr(rec), _lib.ptr(cnt)))
@@ -383,18 +394,8 @@ class DdpEngine:
     def iteration_log_device(self):
         """Zero-copy torch views of the log in HBM: (records [B, rows, 16] float64, n [B] int32) -- device_buffer(9) and (10);
         ordered behind the handle's stream like fetch_device_views."""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-        class _Dev:
-            def __init__(self, ptr, shape, typestr):
-                self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-
-        pl, nb = self.device_buffer(9)
-        pn, _ = self.device_buffer(10)
-        rows = nb // (self.B * _lib.LOG_WORDS * 8)
-        return (torch.as_tensor(_Dev(pl, (self.B, rows, _lib.LOG_WORDS), "<f8"), device=dev),
-                torch.as_tensor(_Dev(pn, (self.B,), "<i4"), device=dev))
+        rows = self.device_buffer(9)[1] // (self.B * _lib.LOG_WORDS * 8)
+        return self.device_view(9, (self.B, rows, _lib.LOG_WORDS)), self.device_view(10, (self.B,), "<i4")
 
     # ---- heterogeneous fleets: per-instance robot constants (include/sddp.h) ------------------------------------------------
     def set_instance_consts(self, overrides: dict, first: int = 0):
@@ -456,7 +457,7 @@ class DdpEngine:
 
     def instance_classes(self, first: int = 0, count: int | None = None):
         """-> the class labels [count] int32 of the instances [first, first + count) (-1: unlabelled); waits for the stream."""
-        n = int(self.B - first if count is None else count)
+        n = self._count(first, count)
         out = np.empty(max(n, 0), dtype=np.int32)
         self._chk(self.lib.sddp_fetch_instance_classes(self.h, int(first), n, _lib.ptr(out)))
         return out
@@ -493,27 +494,12 @@ class DdpEngine:
 
     def last_queue_order(self):
         """Instance indices in the order the last queued launch handed them out (queue_order 1 or 2); waits for the stream."""
-        import torch
-        self.synchronize()
-        ptr, nbytes = self.device_buffer(6)
-
-        class _Dev:
-            __cuda_array_interface__ = {"shape": (nbytes // 4,), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
-
-        return torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device())).cpu().numpy().copy()
+        return self._host_copy(6, "<i4")
 
     def slot_times(self):
         """[grid, 2] uint64: when each slot of the last solve launch started its first instance and when it found the queue empty
         (100 MHz constant-rate clock); waits for the stream."""
-        import torch
-        self.synchronize()
-        ptr, nbytes = self.device_buffer(7)
-
-        class _Dev:
-            __cuda_array_interface__ = {"shape": (nbytes // 8,), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
-
-        t = torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device())).cpu().numpy().copy()
-        return t.view(np.uint64).reshape(-1, 2)
+        return self._host_copy(7, "<i8").view(np.uint64).reshape(-1, 2)
 
     def queue_info(self):
         """(slots the work buffers exist for, grid of the last launch, queue length of the last launch or 0)."""

@@ -26,7 +26,7 @@ def main(seed, k, alpha, N=30):
     cst = omodels.RobotConsts(**b["consts"])
     m = omodels.make_model("srbd13", cst)
     eng = DdpEngine("srbd13", N, 1, opts=dict(OPTS, max_iters=k), consts=b["consts"])
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
     x, u = eng.solve(b["params"])
     st = eng.stats
     print(f"engine after {int(st['iters'][0])} steps: cost {st['cost'][0]:.12e} alpha {st['alpha'][0]} gap {st['gap'][0]:.3e} mu {st['mu'][0]} rho {st['rho'][0]:.3e}")

@@ -40,7 +40,7 @@ import numpy as np
 
 from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
-from tests import options_cases as oc
+from tests import options_cases as oc, parity
 
 BASE = oc.BASE
 SEEDS = tuple(range(8))
@@ -50,7 +50,7 @@ A05 = dict(alpha_0=0.5)
 SO2_HORIZONS = (1, 65)
 SO2_SEEDS = {1: SEEDS, 65: SEEDS}
 
-X_TOL, COST_RTOL = 1e-6, 1e-9                       # tests/test_gpu_horizons.py (the tolerances of tests/test_gpu_options.py)
+X_TOL, COST_RTOL = parity.X_TOL, parity.COST_RTOL   # what tests/test_gpu_horizons.py tolerates (parity.assert_matches_c_oracle)
 MARGIN_X, MARGIN_COST = 1e3 * X_TOL, 1e3 * COST_RTOL
 
 Case = namedtuple("Case", "name kind model N seeds over so")

@@ -23,7 +23,7 @@ import numpy as np
 
 from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
-from tests import resume_cases as rc
+from tests import options_cases as oc, parity, resume_cases as rc
 
 SETTINGS = ("base", "A", "E", "so0", "ir1", "T", "Z")
 EXTRA = {"T": dict(alpha_converge_threshold=0.9), "Z": dict(initial_rollout=1)}
@@ -38,8 +38,8 @@ IR1_SEEDS = (0, 1, 2, 5, 6, 7, 10, 11, 12, 15, 16, 17, 18, 19, 20, 21, 22, 25, 2
 # 1e-9), plus the relative bound of rho = 2 max(A1, A1 + B2) / gap, the one quantity made of them that test_gpu_options does bound
 # (RHO_RTOL = ten times the spread of the oracle's two builds).  tests/test_iteration_log_cpu.py asserts that the oracle's two builds
 # differ by at most a tenth of this bound.
-COST_RTOL = 1e-9
-MODEL_RTOL = 10.0 * 1.21e-9                  # options_cases.RHO_SPREAD: tests/test_gpu_options.py RHO_RTOL, which imports torch
+COST_RTOL = parity.COST_RTOL
+MODEL_RTOL = oc.RHO_RTOL
 ROWS = 128                                   # log rows per instance in the GPU tests: more than any solve here needs (max_iters = 100)
 F = {n: i for i, n in enumerate(("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", "theta", "mu", "tried", "slack",
                                  "iters", "rollouts", "mu_bumps", "reserved"))}

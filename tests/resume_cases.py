@@ -31,6 +31,11 @@ OVER = {"base": {}, "ir1": dict(initial_rollout=1), "so0": dict(second_order=0),
 CUT = {"srbd13": 4, "srbd37": 4, "lip30": 1, "srbd61": 4}      # cut + continue (lip30 is linear-quadratic: 2 iterations)
 CUTS3 = {"srbd13": (2, 5), "srbd37": (2, 5), "lip30": (0, 1), "srbd61": (2, 5)}      # cut, continue, continue
 TOTAL = 100
+# (model, setting, waves_per_simd) of the central identity tests: cut + continued (tests/test_gpu_resume.py), a budget that never runs out
+# (tests/test_gpu_deadline.py)
+IDENTITY = [("srbd13", "base", 1), ("srbd13", "base", 2), ("srbd13", "ir1", 2), ("srbd13", "so0", 1), ("srbd13", "A", 2), ("srbd13", "E", 1),
+            ("srbd37", "base", 1), ("srbd37", "base", 2), ("srbd37", "ir1", 2), ("srbd37", "so0", 1), ("srbd37", "E", 2),
+            ("lip30", "base", 2), ("lip30", "ir1", 2), ("srbd61", "base", 1), ("srbd61", "ir1", 1)]
 
 
 def options(case, **more):

@@ -10,6 +10,8 @@ closed gaps), let the oracle do ONE iteration from it, and compare with the engi
 cost, same trajectory.  One step amplifies rounding by at most the one-step factor, so the tolerance stays tight and a real
 defect of the kernel (a wrong gain, a wrong candidate, a wrong acceptance test) cannot hide behind "chaos".
 """
+import os
+
 import numpy as np
 
 from oracle import cport, ddp as oddp
@@ -264,7 +266,7 @@ def check_batch(model, N, batch, opts, engine_over, cst, threads=16):
     from srbd_horizon_amd.engine import DdpEngine
     B = batch["x0"].shape[0]
     eng = DdpEngine(model, N, B, opts=dict(opts, **engine_over), consts=batch["consts"])
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats.copy()
     qi = eng.queue_info()
@@ -302,3 +304,37 @@ def parity_record(res):
                                 ratio=r["shadow"]["max_ratio"], unstable=r["shadow"]["unstable_steps"],
                                 amis=r["shadow"]["alpha_mismatch"], end_linf=r["end_linf"],
                                 status=(r["gpu_status"], r["oracle_status"])) for r in ex])
+
+
+# ---- the whole-batch statement (tests/test_gpu_divergence.py and every test that solves a bench-sized batch; tests/soak_parity.py) ----
+OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
+THREADS = min(16, os.cpu_count() or 1)
+
+
+def assert_batch(res, key, record_property, tripwire=True, same_optimum=True):
+    """what every whole-batch test asserts of a check_batch result: end-to-end parity on the same path, one-step shadowing on the others"""
+    from tests.conftest import report_parity
+    x, u, st, xo, uo, so, same = (res[k] for k in ("x", "u", "st", "xo", "uo", "so", "same"))
+    report_parity(record_property, key, **parity_record(res))
+    # ---- same path: end-to-end parity at the north_star tolerance
+    np.testing.assert_array_equal(st["status"][same], so[same, 6].astype(int))
+    np.testing.assert_array_equal(st["converged"][same], so[same, 2].astype(int))
+    conv = same & (so[:, 2] == 1)
+    assert np.max(np.abs(x[conv] - xo[conv])) <= 1e-4 and np.max(np.abs(u[conv] - uo[conv])) <= 1e-4
+    np.testing.assert_allclose(st["cost"][conv], so[conv, 0], rtol=1e-8)
+    assert np.all(np.isfinite(x)) and np.all(np.isfinite(u)) and np.all(np.isfinite(st["cost"]))
+    # ---- another path: every accepted GPU step is the oracle's step from the same iterate
+    for rec in res["explained"]:
+        assert_shadowed(rec)
+        # no silent early split: the paths part only after their costs have drifted visibly, or the instance is one the two CPU
+        # builds of the oracle split on as well
+        sp = rec["split_gpu"]
+        assert sp is None or sp["drift_before"] >= 1e-9 or rec["oracle_fast_iters"] != rec["oracle_iters"] or sp["step"] >= 20, rec
+        # both converged: the same local optimum -- on every instance the tests and the bench touch.  (tests/soak_parity.py passes
+        # same_optimum=False and counts: over 204 800 further instances a handful of these crawls end in ANOTHER local optimum, for the
+        # GPU against the oracle as for one CPU build of the oracle against the other.)
+        if same_optimum and rec["gpu_status"] == 0 and rec["oracle_status"] == 0:
+            assert rec["end_linf"] <= 1e-4, rec
+    if tripwire:
+        # a tripwire, not the parity statement: the GPU may split from the oracle about as often as the oracle splits from itself
+        assert len(res["explained"]) <= 4 * res["n_cpu_pair"] + 8, (len(res["explained"]), res["n_cpu_pair"])

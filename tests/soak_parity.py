@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 from oracle import cport, ddp as oddp, models as omodels  # noqa: E402
 from srbd_horizon_amd import workload  # noqa: E402
 from tests import shadow  # noqa: E402
-from tests.test_gpu_divergence import OPTS, THREADS, assert_batch  # noqa: E402
+from tests.shadow import OPTS, THREADS, assert_batch  # noqa: E402
 
 
 def main(first, chunks, per, model="srbd13", N=30, over=None):

@@ -37,6 +37,7 @@ import numpy as np
 
 from oracle import ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
+from tests import variant_cases
 
 BASE = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
 CUT = 2
@@ -103,17 +104,14 @@ def _start(model, build, N, seeds, cut):
     batch = workload.make_batch(model, N, list(seeds))
     P, consts, table = batch["params"], dict(batch["consts"]), None
     if extra == "rows":                                   # the four user rows of tests/test_gpu_extra_rows.py
-        from tests import test_gpu_extra_rows
-        _, P, consts = test_gpu_extra_rows._problem(model, N, list(seeds))
+        _, P, consts = variant_cases.extra_rows_problem(model, N, list(seeds))
     elif extra == "bounds":
-        from tests import test_gpu_bounds
-        consts.update(test_gpu_bounds._bounds(model))
+        consts.update(variant_cases.bounds(model))
     elif extra != "table":
         consts.update(extra)
     csts = [omodels.RobotConsts(**consts)] * B
     if extra == "table":                                  # two different robots in one handle (sddp_set_instance_consts)
-        from tests import test_gpu_instance_consts as tic
-        table, csts = tic.draw(consts, B, tic.SRBD13_FIELDS)
+        table, csts = variant_cases.draw(consts, B, variant_cases.SRBD13_FIELDS)
         assert csts[0].m != csts[1].m
     models = [omodels.make_model(model, c) for c in csts]
     opt = oddp.DdpOptions(**dict(BASE, second_order=2 if so2 else 1, max_iters=cut))
@@ -232,5 +230,5 @@ def make_engine(case):
     eng = DdpEngine(case.model, case.N, len(case.seeds), opts=options(case), consts=consts)
     if s["table"] is not None:
         eng.set_instance_consts(s["table"])
-    eng.set_initial_state(s["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(us)
+    eng.load(s["x0"], xs, us)
     return eng

@@ -7,6 +7,7 @@ import re
 import pytest
 
 from srbd_horizon_amd import _lib
+from tests.c_host import build_c_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,16 +64,6 @@ def test_no_cpu_fallback_without_device(lib):
     from srbd_horizon_amd.engine import DdpEngine
     with pytest.raises(RuntimeError):
         DdpEngine("srbd13", 30, 1)
-
-
-def build_c_host(tmp_path):
-    """examples/c_abi_solve.c: a plain-C host on include/sddp.h (gcc, no Python, no torch in the process)"""
-    import subprocess
-    exe = str(tmp_path / "c_abi_solve")
-    libdir = os.path.join(ROOT, "srbd_horizon_amd")
-    subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "c_abi_solve.c"),
-                    "-o", exe, "-L" + libdir, "-lsddp_hip", "-Wl,-rpath," + libdir, "-lm"], check=True, capture_output=True)
-    return exe
 
 
 def test_c_host_program_links_against_the_abi_and_fails_loudly_without_a_device(lib, tmp_path):

@@ -11,7 +11,7 @@ from srbd_horizon_amd.ddp import DDPSolver
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.prb import LIPProblem, SRBD13Problem, SRBDProblem
 from tests import shadow
-from tests.test_gpu_divergence import assert_batch
+from tests.shadow import assert_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +47,7 @@ def test_non_finite_start_is_reported_not_propagated():
     x0[1, 3:7] = np.nan
     xs = batch["xs"].copy()
     xs[1, :, 3:7] = np.nan
-    eng.set_initial_state(x0); eng.set_x_warmstart(xs); eng.set_u_warmstart(batch["us"])
+    eng.load(x0, xs, batch["us"])
     eng.solve(batch["params"])
     assert eng.stats["status"][0] == 0 and eng.stats["converged"][0] == 1    # the healthy instance is unaffected
     assert eng.stats["status"][1] == 3 and eng.stats["converged"][1] == 0 and eng.stats["iters"][1] == 0
@@ -105,7 +105,7 @@ def test_throughput_build_returns_the_same_results_as_the_latency_build():
     res = []
     for w in (1, 2):
         eng = DdpEngine("srbd13", 30, len(seeds), opts=dict(opts, waves_per_simd=w))
-        eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+        eng.load(batch["x0"], batch["xs"], batch["us"])
         x, u = eng.solve(batch["params"])
         res.append((x, u, eng.stats.copy()))
     (x1, u1, s1), (x2, u2, s2) = res
@@ -118,7 +118,7 @@ def test_throughput_build_returns_the_same_results_as_the_latency_build():
         DdpEngine("srbd13", 30, 1, opts=dict(waves_per_simd=3))
     b37 = workload.make_batch("srbd37", 20, [0, 1])
     eng = DdpEngine("srbd37", 20, 2, opts=dict(opts, waves_per_simd=2))
-    eng.set_initial_state(b37["x0"]); eng.set_x_warmstart(b37["xs"]); eng.set_u_warmstart(b37["us"])
+    eng.load(b37["x0"], b37["xs"], b37["us"])
     eng.solve(b37["params"])
     assert np.all(eng.stats["converged"] == 1)
     # lip30: the tiles of TWO instances fit the LDS of a CU, so waves_per_simd = 2 selects the half-register-file build of the
@@ -127,7 +127,7 @@ def test_throughput_build_returns_the_same_results_as_the_latency_build():
     rl = []
     for w in (1, 2):
         eng = DdpEngine("lip30", 20, 700, opts=dict(opts, waves_per_simd=w))
-        eng.set_initial_state(bl["x0"]); eng.set_x_warmstart(bl["xs"]); eng.set_u_warmstart(bl["us"])
+        eng.load(bl["x0"], bl["xs"], bl["us"])
         x, u = eng.solve(bl["params"])
         rl.append((x, u, eng.stats.copy(), eng.queue_info()))
     np.testing.assert_array_equal(rl[0][2]["iters"], rl[1][2]["iters"])
@@ -139,7 +139,7 @@ def test_throughput_build_returns_the_same_results_as_the_latency_build():
     rs = []
     for w in (1, 2):
         eng = DdpEngine("srbd37", 20, 600, opts=dict(opts, waves_per_simd=w, queue_order=2))
-        eng.set_initial_state(bs["x0"]); eng.set_x_warmstart(bs["xs"]); eng.set_u_warmstart(bs["us"])
+        eng.load(bs["x0"], bs["xs"], bs["us"])
         x, u = eng.solve(bs["params"])
         rs.append((x, u, eng.stats.copy(), eng.queue_info()))
     np.testing.assert_array_equal(rs[0][2]["iters"], rs[1][2]["iters"])
@@ -152,7 +152,7 @@ def test_throughput_build_returns_the_same_results_as_the_latency_build():
     r2 = []
     for w in (1, 2):
         eng = DdpEngine("srbd37", 20, 24, opts=dict(opts, waves_per_simd=w, second_order=2))
-        eng.set_initial_state(b2["x0"]); eng.set_x_warmstart(b2["xs"]); eng.set_u_warmstart(b2["us"])
+        eng.load(b2["x0"], b2["xs"], b2["us"])
         x, u = eng.solve(b2["params"])
         r2.append((x, u, eng.stats.copy()))
     np.testing.assert_array_equal(r2[0][2]["iters"], r2[1][2]["iters"])
@@ -172,7 +172,7 @@ def test_batches_in_flight_on_separate_streams_equal_sequential_solves():
     ref = []
     for bt in batches:
         e = DdpEngine("srbd13", N, B, opts=opts)
-        e.set_initial_state(bt["x0"]); e.set_x_warmstart(bt["xs"]); e.set_u_warmstart(bt["us"])
+        e.load(bt["x0"], bt["xs"], bt["us"])
         x, u = e.solve(bt["params"])
         ref.append((x.copy(), u.copy(), e.stats.copy()))
     dev = torch.device("cuda", 0)
@@ -259,7 +259,7 @@ def test_fleet_tick_of_1024_robots_matches_the_c_oracle_tick_by_tick(record_prop
     N, B, ticks = 30, 1024, int(os.environ.get("SDDP_SOAK_TICKS", "6"))      # (a soak run by hand: 200 ticks)
     b = workload.make_batch("srbd13", N, np.arange(B) + 20000)
     eng = DdpEngine("srbd13", N, B, opts=dict(OPTS, waves_per_simd=1))
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
     eng.set_params(b["params"])
     x, u = eng.solve_resident()                                   # every robot's first (cold) tick
     P = b["params"].copy()
@@ -291,7 +291,7 @@ def test_first_knot_fetch_equals_the_full_fetch():
     engs = []
     for _ in range(2):
         e = DdpEngine("srbd13", N, B, opts=OPTS)
-        e.set_initial_state(b["x0"]); e.set_x_warmstart(b["xs"]); e.set_u_warmstart(b["us"]); e.set_params(b["params"])
+        e.load(b["x0"], b["xs"], b["us"]); e.set_params(b["params"])
         engs.append(e)
     full, first = engs
     p_last = b["params"][:, -1].copy()

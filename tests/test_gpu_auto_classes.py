@@ -21,7 +21,7 @@ QUEUE3 = dict(OPTS, max_slots=16, waves_per_simd=2, queue_order=3)         # the
 
 
 def _load(eng, b):
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
 
 
 def _solve(eng, b):

@@ -10,21 +10,11 @@ from srbd_horizon_amd import workload
 from srbd_horizon_amd.ddp import DDPSolver
 from srbd_horizon_amd.engine import DdpEngine, eval_knots
 from srbd_horizon_amd.prb import SRBD13Problem
+from tests.variant_cases import bounds as _bounds
 
 pytestmark = pytest.mark.gpu
 
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
-
-
-def _bounds(name):
-    """CoM height band and a cap / floor on every vertical contact force (scaled forces: static load = 0.196 resp. 0.098)"""
-    nx, nu = (13, 6) if name == "srbd13" else (37, 24)
-    lo, up = np.full(nx + nu, -np.inf), np.full(nx + nu, np.inf)
-    lo[2], up[2] = 0.80, 0.95
-    fz = [nx + 2, nx + 5] if name == "srbd13" else [nx + 6 * i + 5 for i in range(4)]
-    for j in fz:
-        lo[j], up[j] = 0.0, (0.25 if name == "srbd13" else 0.125)
-    return dict(bound_barrier_weight=1.0, bound_barrier_sharpness=6.0, lower=lo, upper=up)      # weight 1, exp_parameter 6: ddp.py:182, :205-208
 
 
 def _model(name, consts):
@@ -70,7 +60,7 @@ def test_bound_barrier_solve_matches_oracle_and_pulls_the_forces_inside(name, N,
     res = {}
     for tag, cc in (("off", dict(batch["consts"])), ("on", consts)):
         eng = DdpEngine(name, N, len(seeds), opts=dict(OPTS, second_order=so), consts=cc)
-        eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+        eng.load(batch["x0"], batch["xs"], batch["us"])
         x, u = eng.solve(batch["params"])
         res[tag] = (x, u, eng.stats.copy())
     x, u, st = res["on"]
@@ -108,11 +98,11 @@ def test_bound_barrier_through_the_problem_facade_and_error_paths():
     lo, up = np.full(19, -np.inf), np.full(19, np.inf)
     lo[[15, 18]], up[[15, 18]] = 0.0, 0.25
     e = DdpEngine("srbd13", N, 1, opts=OPTS, consts=dict(batch["consts"], bound_barrier_weight=1.0, lower=lo, upper=up))
-    e.set_initial_state(batch["x0"]); e.set_x_warmstart(batch["xs"]); e.set_u_warmstart(batch["us"])
+    e.load(batch["x0"], batch["xs"], batch["us"])
     x, u = e.solve(batch["params"])
     np.testing.assert_array_equal(sols["barrier"][0], u[0].T)
     e0 = DdpEngine("srbd13", N, 1, opts=OPTS, consts=dict(batch["consts"]))
-    e0.set_initial_state(batch["x0"]); e0.set_x_warmstart(batch["xs"]); e0.set_u_warmstart(batch["us"])
+    e0.load(batch["x0"], batch["xs"], batch["us"])
     x0, u0 = e0.solve(batch["params"])
     np.testing.assert_array_equal(sols["ignored"][0], u0[0].T)               # bounds without the option: the reference's behaviour
     assert sols["barrier"][0][[2, 5]].max() < sols["ignored"][0][[2, 5]].max()

@@ -20,7 +20,7 @@ def test_srbd37_n60_multiple_shooting_matches_oracle():
     xs[:, 0] = batch["x0"]
     opts = dict(max_iters=6, alpha_converge_threshold=1e-12, beta=1e-3, cost_reduction_ths=1e-12)
     eng = DdpEngine("srbd37", N, len(seeds), opts=opts)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], xs, batch["us"])
     x, u = eng.solve(batch["params"])
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], xs[b], batch["us"][b], oddp.DdpOptions(**opts))
@@ -44,7 +44,7 @@ def test_srbd37_n60_solved_to_convergence_matches_the_c_oracle():
     xs[:, 0] = batch["x0"]
     opts = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
     eng = DdpEngine("srbd37", N, len(seeds), opts=opts)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], xs, batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats.copy()
     xo, uo, so = cport.solve_batch(omodels.RobotConsts(**batch["consts"]), oddp.DdpOptions(**opts), batch["x0"], batch["params"], xs,

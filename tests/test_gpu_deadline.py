@@ -3,19 +3,20 @@
 Every claim reduces to a byte identity against kernels that exist without the budget: an instance cut by the clock after k accepted
 iterations holds the bytes of an ordinary handle's solve at max_iters = k, and continued to the end it is the uncut solve.  Shapes,
 inputs and slot counts are those of tests/resume_cases.py; every comparison is `==` on the raw bytes of xs, us and the sddp_stats
-records (tests/test_gpu_resume.py _same).
+records (tests/gpu_support.py same_bytes).
 
 TINY is one tick of the 100 MHz clock: the deadline has always passed by the time an instance reaches its first test, so what the
 launch does is decided by min_iters alone and is deterministic.  The cut in the middle (test 4) is the one test whose cut points the
 clock decides; it checks every instance against the reference for the iteration count it was cut at, whatever that is."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 from tests import resume_cases as rc
-from tests.test_gpu_resume import IDENTITY, _continue, _cut, _engine, _load, _same, _snap, uncut
+from tests.gpu_support import continue_to, cut_ref, log_engine, log_of, logged, resume_engine, same_bytes, snap, uncut, used_rows
+from tests.gpu_support import cut as cut_at
+from tests.resume_cases import IDENTITY
+from tests.variant_cases import SRBD13_FIELDS, draw
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +26,10 @@ BUILDS = [("srbd13", 1), ("srbd13", 2), ("srbd37", 1), ("srbd37", 2), ("lip30", 
 KS = {m: sorted({0, 1, rc.CUT[m]}) for m in rc.SHAPES}      # lip30: {0, 1}
 
 
-@functools.lru_cache(maxsize=None)
-def cut_ref(model, wps, k):
-    """an ordinary handle (no sddp_enable_resume) at max_iters = k: computed once, read-only"""
-    if k == rc.TOTAL:
-        return uncut(model, "base", wps)
-    eng = _engine(model, "base", wps, resume=False)
-    out = _cut(eng, rc.batch(model), k)
-    eng.close()
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
 def _budgeted(eng, b, budget_us, min_iters, total=rc.TOTAL):
     """a fresh solve of the whole batch at max_iters = total under the budget"""
     eng.set_time_budget(budget_us, min_iters)
-    return _cut(eng, b, total)
+    return cut_at(eng, b, total)
 
 
 # ---- 1. a deadline that never arrives ----------------------------------------------------------------------------------------------
@@ -50,10 +38,10 @@ def test_a_budget_that_never_runs_out_changes_nothing(model, case, wps):
     """Nothing is cut by time: unfinished() counts no instance but those the uncut solve itself leaves at the cap (status 1 with
     iters == max_iters; 4 of the 48 single-shooting srbd13 instances run into max_iters = 100, every other case has none)."""
     ref = uncut(model, case, wps)
-    eng = _engine(model, case, wps)
+    eng = resume_engine(model, case, wps)
     got = _budgeted(eng, rc.batch(model), NEVER, 0)
     assert eng.time_budget() == (NEVER, 0)
-    _same(got, ref)
+    same_bytes(got, ref)
     capped = (ref[2]["status"] == 1) & (ref[2]["iters"] == rc.TOTAL)
     assert eng.unfinished() == int(capped.sum()) == int((ref[2]["status"] == 1).sum())
     if (model, case) != ("srbd13", "ir1"):
@@ -65,17 +53,17 @@ def test_a_budget_that_never_runs_out_changes_nothing(model, case, wps):
 @pytest.mark.parametrize("model,wps", BUILDS)
 def test_expired_on_arrival_is_the_cut_at_min_iters(model, wps):
     b = rc.batch(model)
-    eng = _engine(model, "base", wps)
+    eng = resume_engine(model, "base", wps)
     for k in KS[model]:
         got = _budgeted(eng, b, TINY, k)
-        _same(got, cut_ref(model, wps, k), msg=f"(min_iters {k})")
+        same_bytes(got, cut_ref(model, wps, k), msg=f"(min_iters {k})")
         n_open = int((got[2]["status"] == 1).sum())
         assert eng.unfinished() == n_open and n_open >= 1
         assert (got[2]["iters"][got[2]["status"] == 1] == k).all()
         start, deadline = eng.deadline_clock()
         assert deadline - start == 1 and eng.deadline_overrun_us() > 0.0
     eng.set_time_budget(2.5, 0)
-    _cut(eng, b, 0)
+    cut_at(eng, b, 0)
     start, deadline = eng.deadline_clock()
     assert deadline - start == 250                              # round(100 * budget_us) ticks of the 100 MHz clock
     eng.close()
@@ -85,22 +73,22 @@ def test_expired_on_arrival_is_the_cut_at_min_iters(model, wps):
 @pytest.mark.parametrize("model,wps", BUILDS)
 def test_a_time_cut_continued_is_the_uncut_solve_and_min_iters_is_per_launch(model, wps):
     b, ref = rc.batch(model), uncut(model, "base", wps)
-    eng = _engine(model, "base", wps)
+    eng = resume_engine(model, "base", wps)
     for k in KS[model]:
         _budgeted(eng, b, TINY, k)
         eng.set_time_budget(0.0)
         assert eng.time_budget() == (0.0, 0)
-        _same(_continue(eng, rc.TOTAL), ref, msg=f"(cut by time at {k}, continued)")
+        same_bytes(continue_to(eng, rc.TOTAL), ref, msg=f"(cut by time at {k}, continued)")
         assert eng.unfinished() == 0
     # every continue launch under the expired budget owes its instances one iteration more: 1 + 3 launches = max_iters 4
     first = 1
     _budgeted(eng, b, TINY, first)
     eng.set_time_budget(TINY, 1)
     for _ in range(3):
-        got = _continue(eng, rc.TOTAL)
-    _same(got, cut_ref(model, wps, first + 3), msg="(three continue launches of one iteration each)")
+        got = continue_to(eng, rc.TOTAL)
+    same_bytes(got, cut_ref(model, wps, first + 3), msg="(three continue launches of one iteration each)")
     eng.set_time_budget(0.0)
-    _same(_continue(eng, rc.TOTAL), ref, msg="(cut by time four times, continued)")
+    same_bytes(continue_to(eng, rc.TOTAL), ref, msg="(cut by time four times, continued)")
     eng.close()
 
 
@@ -111,10 +99,10 @@ def test_a_cut_in_the_middle_leaves_every_instance_at_a_max_iters_cut(model):
     several instances deep per slot (srbd13: 12, srbd37: 4), so most of the work is undone when it runs out."""
     wps = 2
     b, ref = rc.batch(model), uncut(model, "base", wps)
-    eng = _engine(model, "base", wps, queue_order=0)
+    eng = resume_engine(model, "base", wps, queue_order=0)
     eng.enable_timing()
     for _ in range(2):                                           # the second launch: code and clocks are warm
-        _same(_cut(eng, b, rc.TOTAL), ref)
+        same_bytes(cut_at(eng, b, rc.TOTAL), ref)
         T_ms = eng.last_kernel_ms()
     budget_us = 1e3 * T_ms / 4.0
     got = _budgeted(eng, b, budget_us, 0)
@@ -125,62 +113,60 @@ def test_a_cut_in_the_middle_leaves_every_instance_at_a_max_iters_cut(model):
           f"{st['iters'][cut].tolist()} (uncut {ref[2]['iters'][cut].tolist()}), overrun {overrun:.1f} us")
     assert cut.any(), "nothing was cut: the test would pass empty"
     assert eng.unfinished() == int(cut.sum())
-    _same(got, ref, sel=~cut, msg="(finished inside the budget)")
+    same_bytes(got, ref, sel=~cut, msg="(finished inside the budget)")
     assert (st["iters"][cut] <= ref[2]["iters"][cut]).all()
     for k in sorted(set(st["iters"][cut].tolist())):
-        _same(got, cut_ref(model, wps, int(k)), sel=cut & (st["iters"] == k), msg=f"(cut by the clock at {k})")
+        same_bytes(got, cut_ref(model, wps, int(k)), sel=cut & (st["iters"] == k), msg=f"(cut by the clock at {k})")
     eng.set_time_budget(0.0)
-    _same(_continue(eng, rc.TOTAL), ref, msg="(cut in the middle, continued)")
+    same_bytes(continue_to(eng, rc.TOTAL), ref, msg="(cut in the middle, continued)")
     eng.close()
 
 
 # ---- 5. with the iteration log ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model,wps", [("srbd13", 2), ("srbd37", 2)])
 def test_the_log_of_a_time_cut_and_continued_solve_is_the_uncut_log(model, wps):
-    from tests.test_gpu_iteration_log import _engine as log_engine, _log, _solve, _used, full
-    b, ref = rc.batch(model), full(model, "base", wps)
+    b, ref = rc.batch(model), logged(model, "base", wps)
     eng = log_engine(model, "base", wps)
-    _solve(eng, b, rc.CUT[model])
-    log_k = _log(eng)
+    cut_at(eng, b, rc.CUT[model])
+    log_k = log_of(eng)
     eng.set_time_budget(TINY, rc.CUT[model])
-    at_cut = _solve(eng, b, rc.TOTAL)
-    log_cut = _log(eng)
+    at_cut = cut_at(eng, b, rc.TOTAL)
+    log_cut = log_of(eng)
     assert (at_cut[2]["status"] == 1).any()
-    assert (log_cut[1] == log_k[1]).all() and _used(*log_cut) == _used(*log_k)      # the records of the max_iters cut
+    assert (log_cut[1] == log_k[1]).all() and used_rows(*log_cut) == used_rows(*log_k)      # the records of the max_iters cut
     eng.set_time_budget(0.0)
     eng.set_options(max_iters=rc.TOTAL)
     eng.continue_solve()
-    done = _snap(eng)
-    lg = _log(eng)
+    done = snap(eng)
+    lg = log_of(eng)
     eng.close()
     assert done[2].tobytes() == ref[2].tobytes() and done[0].tobytes() == ref[0].tobytes() and done[1].tobytes() == ref[1].tobytes()
-    assert (lg[1] == ref[4]).all() and _used(*lg) == _used(ref[3], ref[4])
+    assert (lg[1] == ref[4]).all() and used_rows(*lg) == used_rows(ref[3], ref[4])
 
 
 # ---- 6. with an instance-constants table -------------------------------------------------------------------------------------------
 def test_a_heterogeneous_batch_is_cut_by_time_with_each_robots_own_constants():
-    from tests.test_gpu_instance_consts import SRBD13_FIELDS, draw
     model, wps = "srbd13", 2
     b, (N, B) = rc.batch(model), rc.SHAPES[model]
     over, _ = draw(b["consts"], B, SRBD13_FIELDS, seed=7)
-    plain = _engine(model, "base", wps, resume=False)
+    plain = resume_engine(model, "base", wps, resume=False)
     plain.set_instance_consts(over)
-    eng = _engine(model, "base", wps)
+    eng = resume_engine(model, "base", wps)
     eng.set_instance_consts(over)
-    total = _cut(plain, b, rc.TOTAL)
+    total = cut_at(plain, b, rc.TOTAL)
     assert (total[2]["iters"] != uncut(model, "base", wps)[2]["iters"]).any()      # a heterogeneous batch indeed
-    refs = {k: _cut(plain, b, k) for k in KS[model] + [4]}
+    refs = {k: cut_at(plain, b, k) for k in KS[model] + [4]}
     for k in KS[model]:
         got = _budgeted(eng, b, TINY, k)
-        _same(got, refs[k], msg=f"(table, min_iters {k})")
+        same_bytes(got, refs[k], msg=f"(table, min_iters {k})")
         assert eng.unfinished() == int((got[2]["status"] == 1).sum()) >= 1
         eng.set_time_budget(0.0)
-        _same(_continue(eng, rc.TOTAL), total, msg=f"(table, cut by time at {k}, continued)")
+        same_bytes(continue_to(eng, rc.TOTAL), total, msg=f"(table, cut by time at {k}, continued)")
     _budgeted(eng, b, TINY, 1)
     eng.set_time_budget(TINY, 1)
     for _ in range(3):
-        got = _continue(eng, rc.TOTAL)
-    _same(got, refs[4], msg="(table, three continue launches of one iteration each)")
+        got = continue_to(eng, rc.TOTAL)
+    same_bytes(got, refs[4], msg="(table, three continue launches of one iteration each)")
     plain.close(); eng.close()
 
 
@@ -189,7 +175,7 @@ def test_class_history_does_not_count_an_instance_cut_by_time():
     model = "srbd13"
     b, ref, B = rc.batch(model), uncut(model, "base", 2), rc.SHAPES[model][1]
     labels = (np.arange(B) % 3).astype(np.int32)
-    eng = _engine(model, "base", 2, queue_order=3)
+    eng = resume_engine(model, "base", 2, queue_order=3)
     eng.set_instance_classes(labels, 3)
     at_cut = _budgeted(eng, b, TINY, rc.CUT[model])
     open_ = at_cut[2]["status"] == 1
@@ -199,7 +185,7 @@ def test_class_history_does_not_count_an_instance_cut_by_time():
         sel = (labels == c) & ~open_
         assert n == sel.sum() and mean * n == pytest.approx(at_cut[2]["iters"][sel].sum())
     eng.set_time_budget(0.0)
-    _same(_continue(eng, rc.TOTAL), ref)
+    same_bytes(continue_to(eng, rc.TOTAL), ref)
     for c in range(3):
         mean, n = eng.class_history(c)
         sel = labels == c
@@ -211,13 +197,13 @@ def test_class_history_does_not_count_an_instance_cut_by_time():
 def test_the_budget_is_refused_where_it_cannot_work():
     model = "srbd13"
     b, ref = rc.batch(model), uncut(model, "base", 1)
-    eng = _engine(model, "base", resume=False)
+    eng = resume_engine(model, "base", resume=False)
     with pytest.raises(RuntimeError, match="sddp_enable_resume"):
         eng.set_time_budget(100.0)
     with pytest.raises(RuntimeError, match="sddp_enable_resume"):
         eng.device_buffer(11)
     assert eng.time_budget() == (0.0, 0)
-    _same(_cut(eng, b, rc.TOTAL), ref)
+    same_bytes(cut_at(eng, b, rc.TOTAL), ref)
     eng.enable_resume()
     for bad in (-1.0, float("nan"), float("inf")):
         with pytest.raises(RuntimeError, match="budget_us"):
@@ -226,21 +212,21 @@ def test_the_budget_is_refused_where_it_cannot_work():
         eng.set_time_budget(100.0, -1)
     assert eng.time_budget() == (0.0, 0)
     assert eng.device_buffer(11)[1] == 16
-    _same(_cut(eng, b, rc.TOTAL), ref)
+    same_bytes(cut_at(eng, b, rc.TOTAL), ref)
     eng.set_time_budget(TINY, 2)                                 # sddp_enable_resume(h, 0) disarms it
     eng.enable_resume(False)
     assert eng.time_budget() == (0.0, 0)
     eng.enable_resume()
     assert eng.time_budget() == (0.0, 0)
-    _same(_cut(eng, b, rc.TOTAL), ref)
+    same_bytes(cut_at(eng, b, rc.TOTAL), ref)
     eng.close()
     for kw in (dict(consts=dict(b["consts"], friction_barrier_weight=1e-3)), dict(second_order=2)):
-        eng = _engine(model, "base", resume=False, **kw)
+        eng = resume_engine(model, "base", resume=False, **kw)
         with pytest.raises(RuntimeError, match="plain builds only"):
             eng.enable_resume()
         with pytest.raises(RuntimeError, match="sddp_enable_resume"):
             eng.set_time_budget(100.0)
-        got = _cut(eng, b, rc.TOTAL)
+        got = cut_at(eng, b, rc.TOTAL)
         assert (got[2]["status"] != 1).all() and np.isfinite(got[2]["cost"]).all()
         eng.close()
 
@@ -253,12 +239,12 @@ def test_fleet_queue_solve_within_returns_the_records_of_solve_sliced():
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
     out = []
     for how in ("within", "sliced"):
-        eng = _engine(model, "base", 2, resume=False)
+        eng = resume_engine(model, "base", 2, resume=False)
         q = FleetQueue(eng, dev(b["params"]), B, 1)
         q.submit(dev(b["x0"]), dev(b["xs"]), dev(b["us"]))
         finished, records = q.solve_within(TINY, rc.TOTAL) if how == "within" else q.solve_sliced(rc.CUT[model], rc.TOTAL)
         torch.cuda.synchronize()
-        _same(_snap(eng), ref)
+        same_bytes(snap(eng), ref)
         assert q.launches == 2
         assert not eng.resume_enabled and eng.opts.max_iters == rc.TOTAL      # the engine is left as it was found
         with pytest.raises(RuntimeError, match="sddp_enable_resume"):

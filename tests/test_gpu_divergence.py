@@ -9,8 +9,6 @@ those the statement that can be made, and is asserted here, is one-step shadowin
 GPU path is the oracle's step from the GPU's own previous iterate (same step length; cost within 1e-3 on the worst step, 1e-7
 on the median step).  The counts of the former "allowances" are reported beside the count on which the two CPU builds of the
 oracle disagree with each other; they are no longer what the tests assert."""
-import os
-
 import numpy as np
 import pytest
 
@@ -18,38 +16,9 @@ import bench
 from oracle import models as omodels
 from srbd_horizon_amd import workload
 from tests import shadow
-from tests.conftest import report_parity
+from tests.shadow import OPTS, THREADS, assert_batch
 
 pytestmark = pytest.mark.gpu
-OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
-THREADS = min(16, os.cpu_count() or 1)
-
-
-def assert_batch(res, key, record_property, tripwire=True, same_optimum=True):
-    x, u, st, xo, uo, so, same = (res[k] for k in ("x", "u", "st", "xo", "uo", "so", "same"))
-    report_parity(record_property, key, **shadow.parity_record(res))
-    # ---- same path: end-to-end parity at the north_star tolerance
-    np.testing.assert_array_equal(st["status"][same], so[same, 6].astype(int))
-    np.testing.assert_array_equal(st["converged"][same], so[same, 2].astype(int))
-    conv = same & (so[:, 2] == 1)
-    assert np.max(np.abs(x[conv] - xo[conv])) <= 1e-4 and np.max(np.abs(u[conv] - uo[conv])) <= 1e-4
-    np.testing.assert_allclose(st["cost"][conv], so[conv, 0], rtol=1e-8)
-    assert np.all(np.isfinite(x)) and np.all(np.isfinite(u)) and np.all(np.isfinite(st["cost"]))
-    # ---- another path: every accepted GPU step is the oracle's step from the same iterate
-    for rec in res["explained"]:
-        shadow.assert_shadowed(rec)
-        # no silent early split: the paths part only after their costs have drifted visibly, or the instance is one the two CPU
-        # builds of the oracle split on as well
-        sp = rec["split_gpu"]
-        assert sp is None or sp["drift_before"] >= 1e-9 or rec["oracle_fast_iters"] != rec["oracle_iters"] or sp["step"] >= 20, rec
-        # both converged: the same local optimum -- on every instance the tests and the bench touch.  (tests/soak_parity.py passes
-        # same_optimum=False and counts: over 204 800 further instances a handful of these crawls end in ANOTHER local optimum, for the
-        # GPU against the oracle as for one CPU build of the oracle against the other.)
-        if same_optimum and rec["gpu_status"] == 0 and rec["oracle_status"] == 0:
-            assert rec["end_linf"] <= 1e-4, rec
-    if tripwire:
-        # a tripwire, not the parity statement: the GPU may split from the oracle about as often as the oracle splits from itself
-        assert len(res["explained"]) <= 4 * res["n_cpu_pair"] + 8, (len(res["explained"]), res["n_cpu_pair"])
 
 
 def test_every_instance_the_bench_times(record_property):

@@ -5,38 +5,14 @@ import numpy as np
 import pytest
 
 from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
 from srbd_horizon_amd.ddp import DDPSolver
 from srbd_horizon_amd.engine import DdpEngine, eval_knots
 from srbd_horizon_amd.prb import SRBDProblem
 from srbd_horizon_amd.problem import LinearTerm
+from tests.variant_cases import extra_rows_problem as _problem
 
 pytestmark = pytest.mark.gpu
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
-
-
-def _rows(model):
-    nx, nu, _ = cport.DIMS[model]
-    nz = nx + nu
-    rng = np.random.default_rng(5)
-    a0 = np.zeros(nz); a0[0] = 1.0                                  # r_x tracking (state row)
-    a1 = np.zeros(nz); a1[1] = 1.0; a1[0] = -0.5                    # r_y - r_x / 2 (state row)
-    a2 = np.zeros(nz); a2[nx + 2] = 1.0; a2[nx + (5 if model != "lip30" else 1)] = -1.0       # a difference of inputs (stage row)
-    a3 = np.zeros(nz); a3[:nx] = 0.05 * rng.standard_normal(nx); a3[nx:] = 0.05 * rng.standard_normal(nu)   # dense (stage row)
-    return (dict(a=a0, w=2e3, kind="state", const=0.0), dict(a=a1, w=5e2, kind="state", const=0.01),
-            dict(a=a2, w=3.0, kind="stage", const=0.0), dict(a=a3, w=40.0, kind="stage", const=-0.2))
-
-
-def _problem(model, N, seeds):
-    batch = workload.make_batch(model, N, seeds)
-    rows = _rows(model)
-    npb = cport.DIMS[model][2]
-    B = len(seeds)
-    P = np.concatenate([batch["params"], np.zeros((B, N + 1, 8))], axis=2)
-    P[:, :, npb + 0] = 0.02 * np.sin(np.arange(N + 1) / 5.0)[None]              # per-knot reference of row 0
-    P[:, :, npb + 3] = 0.1 * np.cos(np.arange(N + 1) / 3.0)[None]               # ... and of row 3
-    consts = dict(batch["consts"], extra_rows=rows)
-    return batch, P, consts
 
 
 @pytest.mark.parametrize("model", ["srbd13", "srbd37", "lip30", "srbd61"])
@@ -68,7 +44,7 @@ def test_solves_with_extra_rows_match_the_c_oracle(model, N, B, wps):
     batch, P, consts = _problem(model, N, np.arange(B) + 1)
     eng = DdpEngine(model, N, B, opts=dict(OPTS, waves_per_simd=wps), consts=consts)
     assert eng.np_ == cport.DIMS[model][2] + 8
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(P)
     xo, uo, so = cport.solve_batch(omodels.RobotConsts(**consts), oddp.DdpOptions(**OPTS), batch["x0"], P, batch["xs"], batch["us"],
                                    threads=4, model=model)
@@ -78,7 +54,7 @@ def test_solves_with_extra_rows_match_the_c_oracle(model, N, B, wps):
     np.testing.assert_allclose(eng.stats["cost"], so[:, 0], rtol=1e-9)
     # the rows act: the solution differs from the plain model's
     e0 = DdpEngine(model, N, B, opts=OPTS, consts=batch["consts"])
-    e0.set_initial_state(batch["x0"]); e0.set_x_warmstart(batch["xs"]); e0.set_u_warmstart(batch["us"])
+    e0.load(batch["x0"], batch["xs"], batch["us"])
     x0, u0 = e0.solve(batch["params"])
     assert np.max(np.abs(x - x0)) > 1e-4
 
@@ -89,7 +65,7 @@ def test_one_sweep_and_one_pass_with_extra_rows():
     batch, P, consts = _problem(model, N, [4])
     m = omodels.make_model(model, omodels.RobotConsts(**consts))
     eng = DdpEngine(model, N, 1, opts=OPTS, consts=consts)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     kff, K, scal = eng.backward(P, mu=0.0)
     xs = batch["xs"][0].copy(); xs[0] = batch["x0"][0]
     d = oddp.defects(m, xs, batch["us"][0], P[0])

@@ -15,6 +15,7 @@ from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
+from tests.variant_cases import SRBD13_FIELDS, TRACKING, draw
 
 pytestmark = pytest.mark.gpu
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
@@ -22,7 +23,7 @@ SMALL = {"srbd13": (30, 40), "srbd37": (20, 6), "lip30": (20, 6), "srbd61": (20,
 
 
 def _load(eng, batch):
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
 
 
 def _solve(eng, batch):
@@ -35,27 +36,6 @@ def _same(got, ref):
     np.testing.assert_array_equal(got[0], ref[0])
     np.testing.assert_array_equal(got[1], ref[1])
     assert got[2].tobytes() == ref[2].tobytes()                  # the raw sddp_stats records
-
-
-def draw(consts: dict, B: int, fields, seed=2026):
-    """Per instance, in this order: m x U(0.75, 1.25), I x U(0.8, 1.25), then every gain of `fields` x U(0.5, 2), from ONE
-    default_rng(seed).  -> (overrides for set_instance_consts, [RobotConsts] for the oracle)"""
-    base = omodels.RobotConsts(**consts)
-    rng = np.random.default_rng(seed)
-    over = {k: [] for k in ("m", "I", *fields)}
-    csts = []
-    for _ in range(B):
-        v = dict(m=base.m * rng.uniform(0.75, 1.25), I=np.asarray(base.I, dtype=float) * rng.uniform(0.8, 1.25))
-        for k in fields:
-            v[k] = getattr(base, k) * rng.uniform(0.5, 2.0)
-        for k in over:
-            over[k].append(v[k])
-        csts.append(dataclasses.replace(base, **v))
-    return {k: np.asarray(v) for k, v in over.items()}, csts
-
-
-SRBD13_FIELDS = ("r_tracking_gain", "rdot_tracking_gain", "w_tracking_gain", "min_f_gain")
-TRACKING = ("r_tracking_gain", "rdot_tracking_gain", "w_tracking_gain")
 
 
 def _oracle(model, csts, batch, opts=None):
@@ -240,7 +220,7 @@ def test_backward_sweep_uses_each_robots_own_constants(model, N):
     xs[:, 0] = batch["x0"]
     eng = DdpEngine(model, N, B, opts=OPTS, consts=batch["consts"])
     eng.set_instance_consts(over)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(us)
+    eng.load(batch["x0"], xs, us)
     kff, K, scal = eng.backward(batch["params"], mu=0.0)
     xg, ug, Jg = eng.forward(batch["params"], 0.25)
     for b in range(B):

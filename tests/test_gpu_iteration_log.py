@@ -3,77 +3,23 @@
 Inputs, cut points and slot counts are those of tests/resume_cases.py; the settings and the instances left out of the oracle
 comparison are those of tests/iteration_log_cases.py, decided on the C oracle by tests/test_iteration_log_cpu.py.  Comparisons between
 GPU results are `==` on raw bytes.  Against the oracle's trace: record count, accepted alpha, theta, candidates tried and the
-iteration count exact; J, accepted J and gap rel 1e-9, mu rel 1e-12, rho RHO_RTOL (tests/test_gpu_options.py, the same quantities);
+iteration count exact; J, accepted J and gap rel 1e-9, mu rel 1e-12, rho RHO_RTOL (tests/parity.py, the same quantities);
 expected, A1, B2 within MODEL_RTOL |value| + COST_RTOL |J| (iteration_log_cases: reasoning and the oracle's own scatter).
 
 Test 1 as the issue words it asks that the record after the one of iteration k carries stats.rho of the solve cut at k.  A record
 holds rho as the oracle's trace does, AFTER the sweep's update rho = max(rho, 2 max(A1, A1 + B2, 0) / gap), and a solve cut at k has
 not run that sweep; so the test asserts the one value the rule allows: stats.rho where the gaps are closed, and the maximum above --
 formed from the record's own A1, B2, gap, which is exact in IEEE doubles -- where they are open.  That asks no less."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-from srbd_horizon_amd.engine import DdpEngine
-from tests import iteration_log_cases as lc, resume_cases as rc
+from tests import iteration_log_cases as lc, options_cases as oc, resume_cases as rc
+from tests.gpu_support import continue_to as _continue, cut as _solve, log_engine as _engine, log_of as _log, logged as full, used_rows as _used
 
 pytestmark = pytest.mark.gpu
 F = lc.F
 BUILDS = [("srbd13", 1), ("srbd13", 2), ("srbd37", 1), ("srbd37", 2), ("lip30", 1), ("lip30", 2), ("srbd61", 1)]
-
-
-def _engine(model, case, wps=1, rows=lc.ROWS, resume=True, consts=None, **over):
-    N, B = rc.SHAPES[model]
-    opts = dict(lc.options(case), waves_per_simd=wps, max_slots=rc.MAX_SLOTS[model])
-    opts.update(over)
-    eng = DdpEngine(model, N, B, opts=opts, consts=lc.batch(model, case)["consts"] if consts is None else consts)
-    if resume:
-        eng.enable_resume()
-    if rows:
-        eng.enable_iteration_log(rows)
-    return eng
-
-
-def _solve(eng, b, k=rc.TOTAL):
-    eng.set_options(max_iters=k)
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
-    eng.solve(b["params"])
-    x, u, st = eng.fetch()
-    return x.copy(), u.copy(), st.copy()
-
-
-def _continue(eng, k, first=0, count=None):
-    eng.set_options(max_iters=k)
-    eng.continue_solve(None, first, count)
-    x, u, st = eng.fetch()
-    return x.copy(), u.copy(), st.copy()
-
-
-def _log(eng):
-    rec, n = eng.iteration_log()
-    return rec.copy(), n.copy()
-
-
-def _used(rec, n):
-    """the bytes of the rows in use, instance by instance"""
-    return [rec[b, :n[b]].tobytes() for b in range(len(n))]
-
-
-@functools.lru_cache(maxsize=None)
-def full(model, case, wps):
-    """(x, u, stats, records, counts) of the uncut logged solve on seeds 0..B-1 (resume_cases' batch; "Z": restarted), read-only"""
-    eng = _engine(model, case, wps)
-    out = _solve(eng, _gpu_batch(model, case)) + _log(eng)
-    eng.close()
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-def _gpu_batch(model, case):
-    return lc.batch(model, case) if case == "Z" else rc.batch(model)
 
 
 # ---- 1. a prefix is a prefix ------------------------------------------------------------------------------------------------------
@@ -132,8 +78,6 @@ ORACLE = [(m, c, w) for m, w in BUILDS for c in lc.SETTINGS if not (m != "srbd13
 
 @pytest.mark.parametrize("model,case,wps", ORACLE)
 def test_the_records_are_the_oracles_trace(model, case, wps):
-    from tests.test_gpu_options import RHO_RTOL
-    assert lc.MODEL_RTOL == RHO_RTOL
     b = lc.batch(model, case)
     if model == "srbd13" and case == "ir1":                               # its own seeds (iteration_log_cases.IR1_SEEDS)
         eng = _engine(model, case, wps)
@@ -154,7 +98,7 @@ def test_the_records_are_the_oracles_trace(model, case, wps):
             np.testing.assert_array_equal(g[:, F[f]], o[:, F[f]], err_msg=f"instance {i} {f}")
         acc = np.cumsum(o[:, F["alpha"]] > 0.0)
         np.testing.assert_array_equal(g[:, F["iters"]], acc, err_msg=f"instance {i} iters")
-        for f, tol in (("J", lc.COST_RTOL), ("J_accepted", lc.COST_RTOL), ("gap", 1e-9), ("mu", 1e-12), ("rho", RHO_RTOL)):
+        for f, tol in (("J", lc.COST_RTOL), ("J_accepted", lc.COST_RTOL), ("gap", 1e-9), ("mu", 1e-12), ("rho", oc.RHO_RTOL)):
             d = np.abs(g[:, F[f]] - o[:, F[f]])
             lim = tol * np.abs(o[:, F[f]])
             worst[f] = max(worst.get(f, 0.0), float((d / np.maximum(lim, 1e-300)).max()) if len(d) and d.max() > 0 else 0.0)
@@ -196,7 +140,7 @@ def test_a_range_launch_leaves_the_other_instances_records_alone():
     before = _log(eng)
     assert (before[1] > 8).all()
     eng.set_options(alpha_0=1.0)                                         # the range is solved again under the base options: fewer records
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
     P = torch.from_numpy(b["params"].copy()).to("cuda:0")
     eng.solve_range_device(P, 16, 16)
     after = _log(eng)
@@ -349,7 +293,7 @@ def test_a_logged_solve_does_not_depend_on_what_the_lds_held(model, wps):
     b, ref = rc.batch(model), full(model, "A", wps)
     eng = _engine(model, "A", wps)
     eng.set_options(max_iters=rc.TOTAL)
-    eng.set_initial_state(b["x0"]); eng.set_x_warmstart(b["xs"]); eng.set_u_warmstart(b["us"])
+    eng.load(b["x0"], b["xs"], b["us"])
     eng.poison_lds()
     eng.solve(b["params"])
     x, u, st = eng.fetch()

@@ -22,7 +22,7 @@ STEPS = ("solve_w1", "solve_w2", "policy", "backward", "forward")
 
 
 def _load(eng, batch):
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
 
 
 def _info(eng):

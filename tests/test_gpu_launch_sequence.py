@@ -11,7 +11,7 @@ import torch
 
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
-from tests.test_gpu_user_terms import _user_case, _widen
+from tests.user_terms_defs import user_case as _user_case, widen as _widen
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,7 @@ N_CLASSES = 3
 
 
 def _solve(eng, batch, P):
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(P)
     return x.copy(), u.copy(), eng.stats.tobytes()
 

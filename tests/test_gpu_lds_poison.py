@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 def _run(eng, batch, xs, us, poison):
     out = []
     for phase in ("backward", "forward", "solve"):
-        eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(us)
+        eng.load(batch["x0"], xs, us)
         if phase == "forward":                       # the forward pass applies the gains the sweep left in the slots' buffers
             eng.backward(batch["params"], mu=0.0)
         if poison:

@@ -20,7 +20,7 @@ OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsr
 @pytest.mark.parametrize("model,N,B,wps", [("srbd37", 20, 2048, 2), ("srbd37", 60, 1024, 2), ("lip30", 20, 4096, 2), ("srbd61", 20, 1024, 1)])
 def test_whole_batch_matches_the_c_oracle(model, N, B, wps, record_property):
     from tests import shadow
-    from tests.test_gpu_divergence import assert_batch
+    from tests.shadow import assert_batch
     batch = workload.make_batch(model, N, np.arange(B))
     cst = omodels.make_model(model).cst if model == "srbd61" else omodels.RobotConsts(**batch["consts"])
     res = shadow.check_batch(model, N, batch, OPTS, dict(waves_per_simd=wps, queue_order=2), cst, threads=8)

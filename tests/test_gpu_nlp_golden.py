@@ -18,7 +18,7 @@ def test_hip_solve_lands_on_the_nlp_optimum(fx, second_order):
     # from the KKT point in u on one fixture; the test of where it converges TO gives that mode a tighter stopping test and more iterations
     over = dict(second_order=second_order) if second_order else dict(second_order=0, cost_reduction_ths=1e-8, max_iters=400)
     eng = DdpEngine(fx["model"], fx["N"], 1, opts=dict(nf.OPTS, **over), consts=fx["consts"])
-    eng.set_initial_state(fx["x0"][None]); eng.set_x_warmstart(fx["xs0"][None]); eng.set_u_warmstart(fx["us0"][None])
+    eng.load(fx["x0"][None], fx["xs0"][None], fx["us0"][None])
     x, u = eng.solve(fx["params"][None])
     st = eng.stats
     assert st["converged"][0] == 1 and st["status"][0] == 0

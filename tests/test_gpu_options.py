@@ -14,10 +14,10 @@ What no test at the default options reaches, and which case reaches it:
   * has_gap = st.gap > gap_tol in the policy kernels with 0 < gap <= gap_tol: B.
   * mu_min in the bump and a positive mu0 as the floor of mu = max(mu0, 0.1 mu): E, D.
 
-Tolerances: iters, status, converged and alpha exact; mu rel 1e-12 (tests/test_gpu_parity.py, regularisation bump); l-inf of x and u 1e-6
-and cost rel 1e-9 (test_converged_solve_matches_oracle); gap rel 1e-9 (the start's defect norm times exact factors 1 - alpha).
-rho: the two CPU builds of the oracle (-ffp-contract=off / fast) differ by at most 1.21e-9 relative over the whole table (C-srbd13;
-options_cases.RHO_SPREAD, asserted on the CPU); the GPU may differ from the oracle by ten times that, 1.21e-8.
+Tolerances (tests/parity.py assert_matches_c_oracle): iters, status, converged and alpha exact; mu rel 1e-12 (tests/test_gpu_parity.py,
+regularisation bump); l-inf of x and u 1e-6 and cost rel 1e-9 (test_converged_solve_matches_oracle); gap rel 1e-9 (the start's defect norm
+times exact factors 1 - alpha).  rho: the two CPU builds of the oracle (-ffp-contract=off / fast) differ by at most 1.21e-9 relative over
+the whole table (C-srbd13; options_cases.RHO_SPREAD, asserted on the CPU); the GPU may differ from the oracle by ten times that, 1.21e-8.
 
 Measured on an MI355X over the 56 parity cases: l-inf x 1.0e-9, u 5.3e-10, cost 8.8e-16, gap 1.6e-12, rho 3.1e-9 (relative), every
 iteration count, status and step length the oracle's; F and G take 10 rollouts for 5 searches plus one re-roll each (15).
@@ -34,35 +34,12 @@ import pytest
 
 from oracle import ddp as oddp, models as omodels
 from srbd_horizon_amd.engine import DdpEngine
-from tests import options_cases as oc, policy_cases as pc
+from tests import options_cases as oc, parity, policy_cases as pc
+from tests.gpu_support import BUILDS, explain, solve as _solve
 
 pytestmark = pytest.mark.gpu
 
-RHO_RTOL = 10.0 * oc.RHO_SPREAD
-BUILDS = {"srbd13": (1, 2), "srbd37": (1, 2), "lip30": (2,), "srbd61": (1,)}          # waves_per_simd per model
 PARITY = [(c.name, w, 1) for c in oc.cases() for w in BUILDS[c.model]] + [(n, 1, so) for n, so in oc.SO_EXTRA]
-
-
-def _solve(eng, s):
-    eng.set_initial_state(s["x0"]); eng.set_x_warmstart(s["xs"]); eng.set_u_warmstart(s["us"])
-    x, u = eng.solve(s["params"])
-    return x.copy(), u.copy(), eng.stats.copy()
-
-
-def _explain(c, s, opts, engine_over, idx):
-    """the instances on another iteration count than the oracle: one-step shadowing of the GPU path (tests/shadow.py)"""
-    from tests import shadow
-    recs = shadow.explain_divergent(c.model, c.N, opts, engine_over, s["consts"], omodels.RobotConsts(**s["consts"]), s, idx)
-    out = []
-    for r in recs:
-        try:
-            shadow.assert_shadowed(r)
-            verdict = "every GPU step is the oracle's step from the same iterate (a step the oracle cannot decide either)"
-        except AssertionError:
-            verdict = "NOT explained by one-step shadowing: a kernel bug"
-        out.append(f"instance {r['instance']}: GPU {r['gpu_iters']} oracle {r['oracle_iters']} / {r['oracle_fast_iters']} iterations; "
-                   f"first split {r['split_gpu']}; {verdict}")
-    return out
 
 
 @pytest.mark.parametrize("name,wps,so", PARITY)
@@ -78,25 +55,11 @@ def test_case_matches_the_c_oracle(name, wps, so):
     xo, uo, so_ = oc.oracle(name, "off", so)
     it_o = oc.stat(so_, "iters").astype(int)
     print(f"{name} {info['kernel']}: iterations GPU {st['iters'].tolist()} oracle {it_o.tolist()}; rollouts {st['rollouts'].tolist()}; "
-          f"linf x {np.max(np.abs(x - xo)):.2e} u {np.max(np.abs(u - uo)):.2e}; "
-          f"rel cost {np.max(np.abs(st['cost'] - so_[:, 0]) / np.abs(so_[:, 0])):.2e}; "
-          f"rel rho {np.max(np.abs(st['rho'] - so_[:, 7]) / np.maximum(np.abs(so_[:, 7]), 1e-300)):.2e}; "
-          f"rel gap {np.max(np.abs(st['gap'] - so_[:, 4]) / np.maximum(np.abs(so_[:, 4]), 1e-300)):.2e}")
-    differ = np.flatnonzero(st["iters"] != it_o)
-    if differ.size:
-        pytest.fail("\n".join(_explain(c, s, opts, over, differ)))
-    np.testing.assert_array_equal(st["status"], oc.stat(so_, "status").astype(int))
-    np.testing.assert_array_equal(st["converged"], oc.stat(so_, "converged").astype(int))
-    np.testing.assert_array_equal(st["alpha"], oc.stat(so_, "alpha"))                       # the same double
-    for b in range(B):
-        assert st["mu"][b] == pytest.approx(so_[b, 5], rel=1e-12), (b, st["mu"][b], so_[b, 5])
-        assert np.max(np.abs(x[b] - xo[b])) <= 1e-6 and np.max(np.abs(u[b] - uo[b])) <= 1e-6, b
-        assert abs(st["cost"][b] - so_[b, 0]) <= 1e-9 * abs(so_[b, 0]), b
-        # gap: the start's defect norm times exact factors 1 - alpha.  A restart (G) begins at a trajectory that closes its gaps in
-        # the OTHER side's arithmetic: there the start's own defects are rounding of f, at most 8 eps |x| per entry
-        slack = c.N * x.shape[2] * 8 * np.finfo(float).eps * np.max(np.abs(xo[b])) if c.start == "restart" else 0.0
-        assert abs(st["gap"][b] - so_[b, 4]) <= 1e-9 * abs(so_[b, 4]) + slack, (b, st["gap"][b], so_[b, 4])
-        assert abs(st["rho"][b] - so_[b, 7]) <= RHO_RTOL * abs(so_[b, 7]), (b, st["rho"][b], so_[b, 7])
+          f"{parity.summary(parity.deviations(x, u, st, xo, uo, so_))}")
+    # gap: the start's defect norm times exact factors 1 - alpha.  A restart (G) begins at a trajectory that closes its gaps in
+    # the OTHER side's arithmetic: there the start's own defects are rounding of f, at most 8 eps |x| per entry
+    slack = c.N * x.shape[2] * 8 * np.finfo(float).eps * np.max(np.abs(xo), axis=(1, 2)) if c.start == "restart" else 0.0
+    parity.assert_matches_c_oracle(x, u, st, xo, uo, so_, gap_slack=slack, explain=lambda differ: explain(c, s, opts, over, differ))
     if c.kind in "FG":                                                                      # the later trips really ran
         for b, tried in enumerate(oc.oracle_tried(name)):
             lo = sum(math.ceil(t / 64) for t in tried)

@@ -13,10 +13,12 @@ from oracle import ddp as oddp
 from oracle import models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine, eval_knots
+from tests import options_cases as oc, parity
 
 pytestmark = pytest.mark.gpu
 
-MODELS = ["srbd13", "srbd37", "lip30"]
+MODELS = ["srbd13", "srbd37", "lip30", "srbd61"]
+SOLVED = [("srbd13", 30), ("srbd37", 20), ("lip30", 20), ("srbd61", 20)]      # model, N of the whole-solve and one-sweep tests
 
 
 def _oracle_model(name, consts=None):
@@ -28,9 +30,13 @@ def _oracle_model(name, consts=None):
 
 
 def _opts(**over):
-    o = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
-    o.update(over)
-    return o
+    return dict(oc.BASE, **over)      # dsrbd_example.py:55-58
+
+
+def _engine_consts(name, batch):
+    """srbd61's handles are built with the workload's explicit constants (tests/test_gpu_srbd61.py checks that the defaults are the same
+    robot); the other models' with the defaults"""
+    return batch["consts"] if name == "srbd61" else None
 
 
 def _oracle_opts(**over):
@@ -50,7 +56,10 @@ def test_eval_knots_matches_oracle(name, imode, lever):
     X = np.tile(m.initial_state(), (nk, 1)) + 0.05 * rng.standard_normal((nk, m.nx))
     U = np.tile(m.static_input(), (nk, 1)) + 0.05 * rng.standard_normal((nk, m.nu))
     P = np.tile(m.default_params(N)[3], (nk, 1)) + 0.05 * rng.standard_normal((nk, m.np_))
-    f, F, H, g, L = eval_knots(name, N, ks, X, U, P, consts=dict(inertia_mode=imode, lever_sign=lever))
+    consts = dict(inertia_mode=imode, lever_sign=lever)
+    if name == "srbd61":
+        consts["feet"] = m.cst.feet8[:4]
+    f, F, H, g, L = eval_knots(name, N, ks, X, U, P, consts=consts)
     for t, k in enumerate(ks):
         if k < N:
             np.testing.assert_allclose(f[t], m.f(X[t], U[t], P[t]), rtol=1e-12, atol=1e-13)
@@ -68,7 +77,7 @@ def test_eval_knots_matches_oracle(name, imode, lever):
         np.testing.assert_allclose(H[t], Ho, rtol=1e-11, atol=1e-11 * max(1.0, np.max(np.abs(Ho))))
 
 
-@pytest.mark.parametrize("name,N", [("srbd13", 30), ("srbd37", 20), ("lip30", 20)])
+@pytest.mark.parametrize("name,N", SOLVED)
 def test_backward_and_forward_pass_match_oracle(name, N):
     seeds = [0, 5, 13]
     batch = workload.make_batch(name, N, seeds)
@@ -77,8 +86,8 @@ def test_backward_and_forward_pass_match_oracle(name, N):
     xs = batch["xs"] + 1e-3 * rng.standard_normal(batch["xs"].shape)       # open gaps: multiple shooting
     us = batch["us"] + 1e-3 * rng.standard_normal(batch["us"].shape)
     xs[:, 0] = batch["x0"]
-    eng = DdpEngine(name, N, len(seeds), opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(xs); eng.set_u_warmstart(us)
+    eng = DdpEngine(name, N, len(seeds), opts=_opts(), consts=_engine_consts(name, batch))
+    eng.load(batch["x0"], xs, us)
     kff, K, scal = eng.backward(batch["params"], mu=0.0)
     xg, ug, Jg = eng.forward(batch["params"], 0.25)
     for b in range(len(seeds)):
@@ -98,26 +107,22 @@ def test_backward_and_forward_pass_match_oracle(name, N):
         assert abs(Jg[b] - Jo) <= 1e-9 * abs(Jo)
 
 
-@pytest.mark.parametrize("name,N", [("srbd13", 30), ("srbd37", 20), ("lip30", 20)])
+@pytest.mark.parametrize("name,N", SOLVED)
 def test_converged_solve_matches_oracle(name, N):
     """Multiple-shooting solves to convergence (options of dsrbd_example.py:55-58).  Seeds 0,1,6,16 converge in 8-18
     Gauss-Newton iterations on srbd13 (commanded-velocity seeds need up to 100)."""
     seeds = [0, 1, 6, 16]
     batch = workload.make_batch(name, N, seeds)
     m = _oracle_model(name)
-    eng = DdpEngine(name, N, len(seeds), opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng = DdpEngine(name, N, len(seeds), opts=_opts(), consts=_engine_consts(name, batch))
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats
     conv = eng.is_converged()
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], _oracle_opts())
-        assert r.converged and conv[b] and st["status"][b] == 0
-        assert st["iters"][b] == r.iters, (st["iters"][b], r.iters)
-        assert np.max(np.abs(x[b] - r.xs)) <= 1e-6
-        assert np.max(np.abs(u[b] - r.us)) <= 1e-6
-        assert abs(st["cost"][b] - r.cost) <= 1e-9 * abs(r.cost)
-        assert st["gap"][b] <= 1e-9
+        assert r.converged and conv[b] and st["converged"][b] and st["status"][b] == 0
+        parity.assert_matches_numpy_oracle(x[b], u[b], st[b], r, b)
 
 
 def test_single_shooting_start_matches_oracle():
@@ -127,7 +132,7 @@ def test_single_shooting_start_matches_oracle():
     batch = workload.make_batch("srbd13", N, seeds)
     m = _oracle_model("srbd13")
     eng = DdpEngine("srbd13", N, len(seeds), opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     _, u0 = eng.solve(batch["params"])
     u0 = u0 + 1e-3 * np.random.default_rng(0).standard_normal(u0.shape)
     eng.set_options(initial_rollout=1)
@@ -150,7 +155,7 @@ def test_iteration_by_iteration_trace_matches_oracle():
     m = _oracle_model("srbd13")
     for it in (1, 2, 3):
         eng = DdpEngine("srbd13", N, 1, opts=_opts(max_iters=it, cost_reduction_ths=1e-12))
-        eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+        eng.load(batch["x0"], batch["xs"], batch["us"])
         x, u = eng.solve(batch["params"])
         r = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0],
                        _oracle_opts(max_iters=it, cost_reduction_ths=1e-12))
@@ -161,16 +166,17 @@ def test_iteration_by_iteration_trace_matches_oracle():
         eng.close()
 
 
-@pytest.mark.parametrize("model,N", [("srbd13", 30), ("srbd37", 20), ("lip30", 20)])
+@pytest.mark.parametrize("model,N", SOLVED)
 def test_regularisation_bump_on_indefinite_quu(model, N):
     """mu0 < 0 large makes Quu indefinite: the engine must bump mu (ddp.py:34-35) exactly like the oracle.  On the 4-wavefront
-    kernel (srbd37, lip30) a failed sweep leaves tiles that alias each other half-written: the retry must not see them."""
+    kernel (srbd37, lip30; srbd61 in its W-free layout: the gains over GC | WC) a failed sweep leaves tiles that alias each other
+    half-written: the retry must not see them."""
     seeds = [3]
     batch = workload.make_batch(model, N, seeds)
     m = _oracle_model(model)
     over = dict(mu0=-1e9, max_iters=3)
-    eng = DdpEngine(model, N, 1, opts=_opts(**over))
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng = DdpEngine(model, N, 1, opts=_opts(**over), consts=_engine_consts(model, batch))
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     r = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0], _oracle_opts(**over))
     assert eng.stats["mu"][0] == pytest.approx(r.mu, rel=1e-12)
@@ -189,7 +195,7 @@ def test_backtracking_line_search_picks_the_same_alpha():
         for it in (1, 2, 3, 8):
             over = dict(max_iters=it, cost_reduction_ths=1e-12)
             eng = DdpEngine("srbd13", N, 1, opts=_opts(**over))
-            eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+            eng.load(batch["x0"], batch["xs"], batch["us"])
             x, u = eng.solve(batch["params"])
             r = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0], _oracle_opts(**over))
             assert eng.stats["iters"][0] == r.iters == it
@@ -209,7 +215,7 @@ def test_exhausted_line_search_stops_with_status_4():
     m = _oracle_model("srbd13")
     over = dict(alpha_converge_threshold=0.5, max_iters=5)        # seed 7 needs alpha = 0.125 in iteration 1
     eng = DdpEngine("srbd13", N, 1, opts=_opts(**over))
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     r = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0], _oracle_opts(**over))
     assert r.iters == 0 and not r.converged and r.status == 4 and r.alpha == 0.0
@@ -228,13 +234,13 @@ def test_exhausted_line_search_at_an_optimum_is_status_0():
     batch = workload.make_batch("srbd13", N, [7])
     m = _oracle_model("srbd13")
     eng = DdpEngine("srbd13", N, 1, opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     xo, uo = eng.solve(batch["params"])
     assert eng.stats["status"][0] == 0 and eng.stats["converged"][0] == 1
     for ths, status, conv in ((1e-12, 0, 1), (1e-30, 4, 0)):
         over = dict(max_iters=5, alpha_converge_threshold=0.5, beta=1e6, cost_reduction_ths=ths)
         e2 = DdpEngine("srbd13", N, 1, opts=_opts(**over))
-        e2.set_initial_state(batch["x0"]); e2.set_x_warmstart(xo); e2.set_u_warmstart(uo)
+        e2.load(batch["x0"], xo, uo)
         x2, u2 = e2.solve(batch["params"])
         st = e2.stats
         r = oddp.solve(m, batch["x0"][0], batch["params"][0], xo[0], uo[0], _oracle_opts(**over))
@@ -249,7 +255,7 @@ def test_full_size_batch_properties():
     N, B = 30, 1024
     batch = workload.make_batch("srbd13", N, np.arange(B))
     eng = DdpEngine("srbd13", N, B, opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats.copy()
     assert np.all((st["status"] == 0) | (st["status"] == 1) | (st["status"] == 4))     # converged, max_iters or stalled, never a failure
@@ -277,7 +283,7 @@ def test_full_size_batch_properties():
     # batch independence: instance b solved alone gives bit-identical output
     for b in (0, 511, 1023):
         e1 = DdpEngine("srbd13", N, 1, opts=_opts())
-        e1.set_initial_state(batch["x0"][b:b + 1]); e1.set_x_warmstart(batch["xs"][b:b + 1]); e1.set_u_warmstart(batch["us"][b:b + 1])
+        e1.load(batch["x0"][b:b + 1], batch["xs"][b:b + 1], batch["us"][b:b + 1])
         x1, u1 = e1.solve(batch["params"][b:b + 1])
         np.testing.assert_array_equal(x1[0], x[b]); np.testing.assert_array_equal(u1[0], u[b])
         e1.close()
@@ -373,7 +379,7 @@ def test_whole_bench_batch_matches_the_c_oracle(record_property):
     line-search path whose winner is not one of the kept candidates).  An instance on another path is explained step by step
     (tests/shadow.py); the full set of instances bench.py times is tests/test_gpu_divergence.py."""
     from tests import shadow
-    from tests.test_gpu_divergence import assert_batch
+    from tests.shadow import assert_batch
     N, B = 30, 1024
     batch = workload.make_batch("srbd13", N, np.arange(B))
     res = shadow.check_batch("srbd13", N, batch, dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3), {},
@@ -389,7 +395,7 @@ def test_extreme_horizons_and_ragged_batches(name, N, B):
     """Shortest horizons, a horizon longer than a wavefront (the lane-per-knot phases wrap), odd batch sizes."""
     batch = workload.make_batch(name, N, np.arange(B) + 3)
     eng = DdpEngine(name, N, B, opts=_opts())
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats.copy()
     assert np.all(np.isfinite(x)) and np.all(np.isfinite(u))
@@ -437,7 +443,7 @@ def test_friction_cone_barrier_solve_matches_oracle_and_tightens_the_cone(name, 
     res = {}
     for tag, consts in (("off", dict(batch["consts"])), ("on", dict(batch["consts"], **BARRIER))):
         eng = DdpEngine(name, N, len(seeds), opts=_opts(), consts=consts)
-        eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+        eng.load(batch["x0"], batch["xs"], batch["us"])
         x, u = eng.solve(batch["params"])
         res[tag] = (x, u, eng.stats.copy())
     x, u, st = res["on"]
@@ -465,7 +471,7 @@ def test_full_second_order_mode_matches_oracle(name, N, seeds):
     batch = workload.make_batch(name, N, seeds)
     m = _oracle_model(name)
     eng = DdpEngine(name, N, len(seeds), opts=_opts(second_order=2))
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     st = eng.stats.copy()
     differs = 0
@@ -495,7 +501,7 @@ def test_full_second_order_mode_other_constants_and_short_horizons(name, N, cons
     batch = workload.make_batch(name, N, seeds)
     m = _oracle_model(name, consts)
     eng = DdpEngine(name, N, len(seeds), opts=_opts(second_order=2), consts=dict(batch["consts"], **consts))
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], _oracle_opts(second_order=2))
@@ -513,7 +519,7 @@ def test_converged_solves_with_the_optional_model_conventions(name, N, consts, s
     batch = workload.make_batch(name, N, seeds)
     m = _oracle_model(name, consts)
     eng = DdpEngine(name, N, len(seeds), opts=_opts(second_order=so), consts=dict(batch["consts"], **consts))
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], _oracle_opts(second_order=so))
@@ -528,7 +534,7 @@ def test_full_second_order_whole_batch_iteration_histogram(record_property):
     step shadowed on the others (tests/shadow.py, as tests/test_gpu_divergence.py does for the default mode); prints the iteration
     histogram DESIGN.md quotes."""
     from tests import shadow
-    from tests.test_gpu_divergence import assert_batch
+    from tests.shadow import assert_batch
     N, B = 30, 1024
     batch = workload.make_batch("srbd13", N, np.arange(B))
     res = shadow.check_batch("srbd13", N, batch, _opts(second_order=2), {}, omodels.RobotConsts(**batch["consts"]), threads=8)

@@ -46,7 +46,7 @@ def test_solves_without_relative_velocity_rows_match_the_c_oracle(model, N, B):
     batch = workload.make_batch(model, N, np.arange(B) + 3)
     consts = dict(batch["consts"], relative_velocity_constraints=0)
     eng = DdpEngine(model, N, B, opts=OPTS, consts=consts)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     xo, uo, so = cport.solve_batch(omodels.RobotConsts(**consts), oddp.DdpOptions(**OPTS), batch["x0"], batch["params"], batch["xs"],
                                    batch["us"], threads=4, model=model)

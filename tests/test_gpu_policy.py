@@ -12,6 +12,7 @@ from srbd_horizon_amd import dist as sdist, workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.mpc import MpcLoop
 from tests import policy_cases as pc
+from tests.variant_cases import extra_rows_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -20,21 +21,14 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _solve(eng, batch, params=None):
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"] if params is None else params)
     return x.copy(), u.copy(), eng.stats.copy()
 
 
-def _dev_view(ptr, shape):
-    class _Dev:
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Dev(), device=torch.device("cuda", torch.cuda.current_device()))
-
-
 def _x_problem(model, N, seeds):
     """the "_x" build's problem of tests/test_gpu_extra_rows.py: four linear user rows, two with per-knot references"""
-    from tests.test_gpu_extra_rows import _problem
-    return _problem(model, N, seeds)
+    return extra_rows_problem(model, N, seeds)
 
 
 @pytest.mark.parametrize("model,N,B,slots,xr,max_iters", [
@@ -88,8 +82,7 @@ def test_policy_differs_from_the_slot_gains_after_max_iters(model, N, B):
     x, u, st = _solve(eng, batch)
     eng.policy_range_device()
     kff, K, info = eng.policy()
-    ptr, nbytes = eng.device_buffer(3)
-    g = _dev_view(ptr, (B, N, eng.nu * (eng.nx + 1))).cpu().numpy().copy()
+    g = eng.device_view(3, (B, N, eng.nu * (eng.nx + 1))).cpu().numpy().copy()
     K3 = g[:, :M, eng.nu:].reshape(B, M, eng.nu, eng.nx)
     m = omodels.make_model(model, omodels.RobotConsts(**batch["consts"]))
     cut = np.flatnonzero((st["status"] == 1) & (st["iters"] == 3))
@@ -203,7 +196,7 @@ def test_first_order_property_of_the_exported_gains(model):
     x0 = b["x0"].copy()
     x0[1] += pc.FO_EPS[0] * v
     x0[2] += pc.FO_EPS[1] * v
-    eng.set_initial_state(x0); eng.set_x_warmstart(x); eng.set_u_warmstart(u)
+    eng.load(x0, x, u)
     x2, u2 = eng.solve(b["params"])
     assert eng.stats["converged"].all()
     pc.assert_first_order(model, pc.fo_errors(u[0, 0], K[0, 0], v, lambda eps: u2[1 + pc.FO_EPS.index(eps), 0]))

@@ -27,7 +27,7 @@ def _engine(model, N, B, max_slots=None, **over):
 
 
 def _solve(eng, batch):
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(batch["params"])
     return x.copy(), u.copy(), eng.stats.copy()
 
@@ -119,7 +119,7 @@ def test_configs3_all_eight_rank_shards_match_the_c_oracle(record_property):
     through ONE handle on one GPU: a queue of 8192 instances on the device's resident slots, against the plain-C oracle.  The
     instances that take another iteration count are explained step by step (tests/shadow.py, tests/test_gpu_divergence.py)."""
     from tests import shadow
-    from tests.test_gpu_divergence import assert_batch
+    from tests.shadow import assert_batch
     N, B, R = 30, 1024, 8
     batch = workload.make_batch("srbd13", N, np.arange(R * B))
     res = shadow.check_batch("srbd13", N, batch, OPTS, dict(waves_per_simd=2), omodels.RobotConsts(**batch["consts"]),

@@ -34,7 +34,7 @@ def test_pyddp_call_shapes_give_the_engines_result(model, N):
     assert solver.is_converged() is True                                     # :106
     # ---- the same problem through the batched engine
     eng = DdpEngine(model, N, 1, opts=EX, consts=batch["consts"])
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     xe, ue = eng.solve(batch["params"])
     np.testing.assert_array_equal(x, xe[0].T)
     np.testing.assert_array_equal(u, ue[0].T)
@@ -86,7 +86,7 @@ def test_c_host_program_gets_the_same_solve(tmp_path):
     import subprocess
     from oracle import ddp as oddp, models as omodels
     from srbd_horizon_amd import _lib
-    from tests.test_abi import build_c_host
+    from tests.c_host import build_c_host
     out = json.loads(subprocess.run([build_c_host(tmp_path), "12"], check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
     N = 30
     c = _lib.default_consts()
@@ -101,7 +101,7 @@ def test_c_host_program_gets_the_same_solve(tmp_path):
     assert out["cold_iters"] == r.iters and out["cold_converged"] == int(r.converged)
     assert abs(out["cold_cost"] - r.cost) <= 1e-9 * abs(r.cost)
     eng = DdpEngine("srbd13", N, 1, opts=opts)
-    eng.set_initial_state(x0[None]); eng.set_x_warmstart(xs[None]); eng.set_u_warmstart(us[None])
+    eng.load(x0[None], xs[None], us[None])
     x, u = eng.solve(P[None])
     assert eng.stats["cost"][0] == out["cold_cost"]                       # the same library, the same bits
     eng.set_params(P[None])

@@ -6,31 +6,15 @@ import numpy as np
 import pytest
 
 from oracle import ddp as oddp, models as omodels
-from srbd_horizon_amd import userterms, workload
+from srbd_horizon_amd import workload
 from srbd_horizon_amd.ddp import DDPSolver
 from srbd_horizon_amd.engine import DdpEngine, eval_knots
 from tests import user_terms_defs as defs
+from tests.user_terms_defs import NPB, user_case as _user_case, widen as _widen
 from tests.user_terms_oracle import WithUserRows
 
 pytestmark = pytest.mark.gpu
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
-NPB = 19
-
-
-def _user_case(case, N):
-    pb, prb = {"srbd13_terrain": lambda: defs.srbd13_terrain(N), "srbd37_reach": lambda: defs.srbd37_reach(N),
-               "srbd13_pair": lambda: defs.srbd13_pair(N, True)}[case]()
-    spec = defs.spec_of(prb)
-    return spec, userterms.register(spec)
-
-
-def _widen(params, spec, vary=0.0):
-    """the batch's parameters plus the 8 user columns, filled from the parameters the spec's rows read (vary: a per-node ripple)"""
-    B, K, _ = params.shape
-    P = np.concatenate([params, np.zeros((B, K, 8))], axis=2)
-    for j, (par, r) in enumerate(spec.cols):
-        P[:, :, NPB + j] = par.values[r, :K][None] * (1.0 + vary * np.sin(np.arange(K) / 3.0))[None]
-    return P
 
 
 def _oracle(model, consts, spec):
@@ -68,7 +52,7 @@ def test_knots_of_a_user_build(case, model):
 
 def _solve(model, N, batch, P, consts, mid=None, wps=1):
     eng = DdpEngine(model, N, P.shape[0], opts=dict(OPTS, waves_per_simd=wps), consts=consts, model_id=mid)
-    eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+    eng.load(batch["x0"], batch["xs"], batch["us"])
     x, u = eng.solve(P)
     return eng, x, u
 
@@ -135,7 +119,7 @@ def test_receding_horizon_on_resident_data():
     dev = DdpEngine("srbd13", N, B, opts=OPTS, consts=consts, model_id=mid)
     host = DdpEngine("srbd13", N, B, opts=OPTS, consts=consts, model_id=mid)
     for e in (dev, host):
-        e.set_initial_state(batch["x0"]); e.set_x_warmstart(batch["xs"]); e.set_u_warmstart(batch["us"])
+        e.load(batch["x0"], batch["xs"], batch["us"])
     dev.set_params(P)
     xd, ud = dev.solve_resident()
     xh, uh = host.solve(P)

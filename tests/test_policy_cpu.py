@@ -14,7 +14,7 @@ from oracle import ddp as oddp, models as omodels
 from srbd_horizon_amd import _lib, dist as sdist, workload
 from srbd_horizon_amd.fleet import FleetQueue
 from tests import policy_cases as pc
-from tests.test_fleet_gloo import N, NP, NU, NX, OPTS, OracleEngine, _free_port, _seeds
+from tests.fleet_support import N, NP, NU, NX, OPTS, OracleEngine, free_port as _free_port, seeds_of as _seeds
 
 
 def test_policy_record_layout_arithmetic():

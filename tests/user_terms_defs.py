@@ -78,6 +78,25 @@ def spec_of(prb):
     return userterms.spec_from_problem(prb, nx, nu)
 
 
+NPB = 19      # parameter columns of the SRBD models in front of the 8 user columns
+
+
+def user_case(case, N):
+    pb, prb = {"srbd13_terrain": lambda: srbd13_terrain(N), "srbd37_reach": lambda: srbd37_reach(N),
+               "srbd13_pair": lambda: srbd13_pair(N, True)}[case]()
+    spec = spec_of(prb)
+    return spec, userterms.register(spec)
+
+
+def widen(params, spec, vary=0.0):
+    """the batch's parameters plus the 8 user columns, filled from the parameters the spec's rows read (vary: a per-node ripple)"""
+    B, K, _ = params.shape
+    P = np.concatenate([params, np.zeros((B, K, 8))], axis=2)
+    for j, (par, r) in enumerate(spec.cols):
+        P[:, :, NPB + j] = par.values[r, :K][None] * (1.0 + vary * np.sin(np.arange(K) / 3.0))[None]
+    return P
+
+
 # horizon lengths the tests use (the generated code does not depend on N, but the node ranges are part of the declaration)
 def all_specs():
     out = []

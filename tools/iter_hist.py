@@ -9,7 +9,7 @@ MODEL = sys.argv[2] if len(sys.argv) > 2 else "srbd13"
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 30
 batch = workload.make_batch(MODEL, N, np.arange(B))
 eng = DdpEngine(MODEL, N, B, opts=dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3))
-eng.set_initial_state(batch["x0"]); eng.set_x_warmstart(batch["xs"]); eng.set_u_warmstart(batch["us"])
+eng.load(batch["x0"], batch["xs"], batch["us"])
 eng.enable_timing(True)
 eng.solve(batch["params"])
 it, ro = eng.stats["iters"], eng.stats["rollouts"]

@@ -16,7 +16,7 @@ for seed in range(8):
     b1 = workload.make_batch(model, N, [seed])
     t = []
     for _ in range(12):
-        e1.set_initial_state(b1["x0"]); e1.set_x_warmstart(b1["xs"]); e1.set_u_warmstart(b1["us"])
+        e1.load(b1["x0"], b1["xs"], b1["us"])
         t1 = time.perf_counter()
         e1.solve(b1["params"])
         t.append(1e3 * (time.perf_counter() - t1))
