@@ -147,7 +147,8 @@ typedef struct sddp_stats {
     int    iters;      /* accepted iterations                               */
     int    converged;  /* 1/0                                               */
     int    status;     /* 0 ok (converged = 1), 1 max_iters -- or, on a handle with a time budget (sddp_set_time_budget), cut by the
-                          deadline: iters < options.max_iters tells the time cut from the cap --, 2 regularisation overflow, 3 non-finite cost, 4 line search
+                          deadline: iters < options.max_iters tells the time cut from the cap --, 2 regularisation overflow (a sweep fails on a Quu pivot that is non-positive, non-finite or >= 1e300;
+                          mu grew past mu_max), 3 non-finite cost, 4 line search
                           exhausted with the optimality conditions not met (converged = 0).  An exhausted line search (no step
                           length >= alpha_converge_threshold decreases the merit function) counts as converged -- status 0 -- only
                           with closed gaps (gap <= gap_tol) and expected <= cost_reduction_ths * max(1, |cost|): a RELATIVE test,
@@ -218,7 +219,8 @@ int  sddp_pack_records_device(sddp_handle* h, int first, int count, int mode, do
  * theta -> 0, then mu <- 10 max(mu, 0) + mu_min, giving up above mu_max -- and keeps the gains of the first `knots` knots:
  *     policy [B][words],  words = knots * nu * (nx + 1) + 4:
  *         knot 0 .. knots - 1: kff [nu] then K [nu][nx] row-major (the layout of sddp_device_ptr(3))
- *         then mu_used | theta_used | expected = -(dV1 + dV2) | ok   (ok = 0: the regularisation overflowed; the gains are zeros)
+ *         then mu_used | theta_used | expected = -(dV1 + dV2) | ok   (ok = 0: the regularisation overflowed, or the solve ended with status 3 -- no
+ *         sweep is made at a non-finite iterate; the gains are zeros)
  * It is a work queue over the resident workgroups like the solve launch (any batch size, any range), the policy of an instance does
  * not depend on the range or slot it ran in, and no solve result changes.  Plain builds only: a handle with a barrier or with
  * second_order = 2 has no policy kernel (SDDP_ERR_ARG).
@@ -227,7 +229,7 @@ int  sddp_pack_records_device(sddp_handle* h, int first, int count, int mode, do
  *   last sddp_solve* launch (the resident one for sddp_solve / sddp_solve_resident*).  SDDP_ERR_ARG if no solve ran.  It uses the
  *   slots' dft / rec work buffers (not their gains): a sddp_forward after it needs a new sddp_backward.
  * sddp_fetch_policy: records [first, first + count) to a host pointer [count][words]; waits for the stream.
- * sddp_apply_policy_device: u[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]), b = first + i, from the policy buffer and the handle's
+ * sddp_apply_policy_device: u[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]) -- u_0[b] itself where the record says ok = 0 --, b = first + i, from the policy buffer and the handle's
  *   xs / us: what a fleet applies between two ticks.  d_x_meas [count][nx], d_u_out [count][nu] device pointers; asynchronous. */
 int  sddp_enable_policy(sddp_handle* h, int knots);
 int  sddp_policy_words(sddp_handle* h, int* words, int* knots);

@@ -125,7 +125,7 @@ static void world_inertia_d(const consts_t* c, const double* R, const double* dR
 static int chol(double* A, int n) {
     for (int j = 0; j < n; ++j) {
         double d = A[j * n + j]; for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k];
-        if (!(d > 0.0)) return 0;
+        if (!(d > 0.0) || !(d < 1e300)) return 0;      /* the pivot L_jj^2 in (0, 1e300): include/sddp.h, status 2 */
         d = sqrt(d); A[j * n + j] = d;
         for (int i = j + 1; i < n; ++i) { double s = A[i * n + j]; for (int k = 0; k < j; ++k) s -= A[i * n + k] * A[j * n + k]; A[i * n + j] = s / d; }
     }

@@ -80,6 +80,9 @@ def rollout_open_loop(model, x0, us, P):
     return xs
 
 
+PIVOT_MAX = 1e300        # a Quu pivot must lie in (0, PIVOT_MAX): the rule of the device sweeps (include/sddp.h, status 2)
+
+
 def backward_pass(model, xs, us, P, d, mu, theta=0.0, mode=1):
     """-> ok, K [N,nu,nx], kff [N,nu], dV1, dV2, G1, G2, Vx0, Vxx0, qu_inf"""
     N = us.shape[0]
@@ -110,6 +113,8 @@ def backward_pass(model, xs, us, P, d, mu, theta=0.0, mode=1):
         try:
             L = np.linalg.cholesky(Quu)
         except np.linalg.LinAlgError:
+            return False, K, kff, 0, 0, 0, 0, None, None, 0
+        if not np.all(np.diag(L) ** 2 < PIVOT_MAX):       # a pivot L_ii^2 that is not < 1e300 (inf, NaN or huge) fails the sweep too
             return False, K, kff, 0, 0, 0, 0, None, None, 0
         sol = -np.linalg.solve(L.T, np.linalg.solve(L, np.column_stack([Qu, Qux])))
         kff[k] = sol[:, 0]

@@ -1201,7 +1201,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void
 // carries in is what the solve would carry into its NEXT sweep: mu = stats.mu, theta = 1 iff second_order and the last step was a
 // full one, the defects of the returned trajectory -- exact zeros once the gaps are closed (stats.gap <= gap_tol: the engines carry
 // exact zeros from the first full step on) -- and on a non-positive pivot the solve's rule (theta -> 0, then mu <- 10 max(mu, 0) +
-// mu_min, give up above mu_max: ok = 0 and the record's gains are zeros).  dft / rec are the work buffers of the queue SLOT; the
+// mu_min, give up above mu_max: ok = 0 and the record's gains are zeros); behind a solve that ended with status 3 (non-finite cost)
+// no sweep is made: ok = 0, zeros, mu_used = stats.mu.  dft / rec are the work buffers of the queue SLOT; the
 // slot's gains buffer (sddp_device_ptr(3)) is not touched.
 // -----------------------------------------------------------------------------------------------------------------
 constexpr int kPolicyTail = 4;
@@ -1229,16 +1230,18 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     wave_sync();
     double mu = st.mu, theta = (o.second_order && st.alpha == o.alpha_0) ? 1.0 : 0.0;
     double dV1, G1, G2, qu_inf;
-    bool ok;
+    bool ok = false;
     SDDP_T_DECL
-    while (true) {
+    // an iterate the solve refused for its non-finite cost (status 3) has no policy: the solve makes no sweep there, and a sweep
+    // whose Quu happens to stay finite would pass and put the NaN into the gains.  Wave-uniform: one record read by every lane.
+    if (st.status != 3) while (true) {
         ok = backward_sweep<M, true>(A.c, N, P, dft, rec, out, mu, theta, s, lane, dV1, G1, G2, qu_inf, has_gap SDDP_T_PASS, keep);
         if (ok) break;
         if (theta != 0.0) { theta = 0.0; continue; }
         mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
         if (!(mu <= o.mu_max)) break;
     }
-    if (!ok) {   // regularisation overflow: zeros, never the rows a failed sweep left behind
+    if (!ok) {   // regularisation overflow or a status-3 iterate: zeros, never the rows a failed sweep left behind
         drain_vmem();
         for (int e = lane; e < keep * NGW; e += kWave) out[e] = 0.0;
     }

@@ -1426,15 +1426,15 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
     __syncthreads();
     double mu = st.mu, theta = (o.second_order && st.alpha == o.alpha_0) ? 1.0 : 0.0;
     double dV1, G1, G2, qu_inf;
-    bool ok;
-    while (true) {
+    bool ok = false;
+    if (st.status != 3) while (true) {   // a status-3 iterate has no policy (policy_instance); workgroup-uniform
         ok = backward_sweep_mw<M, SINK, true>(A.c, N, P, dft, rec, out, mu, theta, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS, keep);
         if (ok) break;
         if (theta != 0.0) { theta = 0.0; continue; }
         mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
         if (!(mu <= o.mu_max)) break;
     }
-    if (!ok) {   // regularisation overflow: zeros, never the rows a failed sweep left behind
+    if (!ok) {   // regularisation overflow or a status-3 iterate: zeros, never the rows a failed sweep left behind
         __syncthreads();
         for (int e = tid; e < keep * NGW; e += kThreadsMW) out[e] = 0.0;
     }

@@ -7,7 +7,10 @@ the same double); mu rel 1e-12 (regularisation bump: exact factors of ten); l-in
 solve, fp64 on both sides); gap rel 1e-9 (the start's defect norm times exact factors 1 - alpha); rho within RHO_RTOL, ten times the
 spread of the oracle's own two builds.
 Against the numpy oracle's result object (oddp.solve), per instance: the same iteration count, l-inf 1e-6, cost rel 1e-9, gaps closed
-to 1e-9."""
+to 1e-9.
+A failed instance (status 2, 3, 4; assert_failed_matches_c_oracle): the same exact fields and the same bounds, no new one; cost and gap
+non-finite exactly where the oracle's are; the trajectory either the start's bytes or the oracle's iterate at 1e-6 on its finite entries.
+deviations() divides by the cost: failed instances go through failed_deviations(), which looks at the oracle's finite entries only."""
 import numpy as np
 import pytest
 
@@ -62,3 +65,56 @@ def assert_matches_numpy_oracle(x, u, st, r, b=None):
     assert ex <= X_TOL and eu <= X_TOL, (b, ex, eu)
     assert abs(st["cost"] - r.cost) <= COST_RTOL * abs(r.cost), (b, st["cost"], r.cost)
     assert st["gap"] <= GAP_CLOSED, (b, st["gap"])
+
+
+def _close_or_same_non_finite(got, ref, rtol, what):
+    """non-finite exactly where the oracle is (inf for inf of the same sign, NaN for NaN); within rtol where it is finite"""
+    if np.isfinite(ref):
+        assert np.isfinite(got) and abs(got - ref) <= rtol * abs(ref), (what, got, ref)
+    elif np.isnan(ref):
+        assert np.isnan(got), (what, got, ref)
+    else:
+        assert got == ref, (what, got, ref)
+
+
+def failed_deviations(x, u, st, xo, uo, so, sel):
+    """deviations() over the instances `sel`, on the finite entries of the oracle only (a failed instance may hold NaNs)"""
+    sel = np.asarray(sel, dtype=int)
+    def linf(a, b):
+        m = np.isfinite(b)
+        return float(np.max(np.abs(a[m] - b[m]))) if m.any() else 0.0
+    def rel(f):
+        g, o = st[f][sel], stat(so, f)[sel]
+        m = np.isfinite(o) & (o != 0.0)
+        return float(np.max(np.abs(g[m] - o[m]) / np.abs(o[m]))) if m.any() else 0.0
+    return dict(x=linf(x[sel], xo[sel]), u=linf(u[sel], uo[sel]), cost=rel("cost"), gap=rel("gap"), rho=rel("rho"))
+
+
+def assert_failed_matches_c_oracle(x, u, st, xo, uo, so, b, *, start=None, rollouts=None):
+    """instance b of a GPU solve that gave up (status 2, 3 or 4) against cport.solve_batch's: status, iters, converged and alpha exact
+    (alpha: the same double); mu rel MU_RTOL; cost and gap at COST_RTOL / GAP_RTOL where the oracle's are finite, non-finite exactly
+    where they are not; rollouts exact where given.  The returned trajectory: start = (x0, xs, us) -> the start's bytes with row 0 =
+    x0 (a solve that gave up before any accepted step on multiple shooting); None -> the oracle's iterate, the same non-finite mask
+    and X_TOL on the finite entries."""
+    assert st["status"][b] == int(stat(so, "status")[b]) and st["status"][b] in (2, 3, 4), (b, st["status"][b], stat(so, "status")[b])
+    assert st["iters"][b] == int(stat(so, "iters")[b]), (b, st["iters"][b], stat(so, "iters")[b])
+    assert st["converged"][b] == int(stat(so, "converged")[b]) == 0, (b, st["converged"][b])
+    assert st["alpha"][b].tobytes() == np.float64(stat(so, "alpha")[b]).tobytes(), (b, st["alpha"][b], stat(so, "alpha")[b])
+    if rollouts is not None:
+        assert st["rollouts"][b] == rollouts, (b, st["rollouts"][b], rollouts)
+    mu = stat(so, "mu")[b]
+    assert st["mu"][b] == pytest.approx(mu, rel=MU_RTOL), (b, st["mu"][b], mu)
+    _close_or_same_non_finite(st["cost"][b], stat(so, "cost")[b], COST_RTOL, ("cost", b))
+    _close_or_same_non_finite(st["gap"][b], stat(so, "gap")[b], GAP_RTOL, ("gap", b))
+    if start is not None:
+        x0, xs, us = start
+        want = np.array(xs, copy=True)
+        want[0] = x0
+        assert x[b].tobytes() == want.tobytes(), f"instance {b}: xs is not the start with row 0 = x0"
+        assert u[b].tobytes() == np.ascontiguousarray(us).tobytes(), f"instance {b}: us is not the start"
+        return
+    for got, ref, what in ((x[b], xo[b], "x"), (u[b], uo[b], "u")):
+        fin = np.isfinite(ref)
+        np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=f"instance {b}: non-finite entries of {what}")
+        e = float(np.max(np.abs(got[fin] - ref[fin]))) if fin.any() else 0.0
+        assert e <= X_TOL, (b, what, e)

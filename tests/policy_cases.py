@@ -8,6 +8,8 @@ iteration would carry into its next sweep:
   * regularisation: the solve's final mu; if a Quu is not positive definite, first the second-order term is dropped, then
     mu <- 10 max(mu, 0) + mu_min until the sweep passes, giving up above mu_max (ok = 0, all gains zero);
   * second-order term: on (theta = 1) iff the options ask for it and the solve's last step length was the full one, alpha_0.
+An iterate the solve refused for its non-finite cost (status 3) has no policy: no sweep, ok = 0, all gains zero, mu_used = the
+solve's mu.  (A Quu that does not depend on the non-finite entry would otherwise pass the sweep and carry the NaN into the gains.)
 The record per instance: kff_k, K_k for the first M knots, then mu_used, theta_used, expected = -(dV1 + dV2), ok.
 """
 import numpy as np
@@ -16,9 +18,11 @@ from oracle import ddp as oddp
 
 
 def oracle_policy(m, xs, us, P, stats, opt: oddp.DdpOptions, knots: int):
-    """-> kff [M, nu], K [M, nu, nx], info [4] by the rule above; stats: the solve's record (alpha, gap, mu)"""
+    """-> kff [M, nu], K [M, nu, nx], info [4] by the rule above; stats: the solve's record (alpha, gap, mu, status)"""
     N = us.shape[0]
     M = min(knots, N)
+    if int(stats["status"]) == 3:
+        return np.zeros((M, m.nu)), np.zeros((M, m.nu, m.nx)), np.array([float(stats["mu"]), 0.0, 0.0, 0.0])
     d = oddp.defects(m, xs, us, P) if float(stats["gap"]) > opt.gap_tol else np.zeros((N, m.nx))
     mu = float(stats["mu"])
     theta = 1.0 if (opt.second_order and float(stats["alpha"]) == opt.alpha_0) else 0.0

@@ -40,19 +40,6 @@ def test_engine_rejects_bad_calls():
         DdpEngine("srbd13", 0, 1)                                    # N < 1
 
 
-def test_non_finite_start_is_reported_not_propagated():
-    eng = DdpEngine("srbd13", 30, 2)
-    batch = workload.make_batch("srbd13", 30, [0, 1])
-    x0 = batch["x0"].copy()
-    x0[1, 3:7] = np.nan
-    xs = batch["xs"].copy()
-    xs[1, :, 3:7] = np.nan
-    eng.load(x0, xs, batch["us"])
-    eng.solve(batch["params"])
-    assert eng.stats["status"][0] == 0 and eng.stats["converged"][0] == 1    # the healthy instance is unaffected
-    assert eng.stats["status"][1] == 3 and eng.stats["converged"][1] == 0 and eng.stats["iters"][1] == 0
-
-
 @pytest.mark.parametrize("builder,name,ns", [(SRBDProblem, "createSRBDProblem", 20), (LIPProblem, "createLIPProblem", 20),
                                               (SRBD13Problem, "createSRBD13Problem", 30)])
 def test_ddpsolver_surface_matches_reference_adapter(builder, name, ns):

@@ -25,7 +25,7 @@ Deliberate breaks, tried on a scratch build: `a_base = lane 63's step * 0.5` (bo
 the six kernel builds, and nothing else; `alpha == 1.0` for `alpha == alpha_0` (both solve kernels, both policy kernels) fails every
 A, B and C case of srbd13, srbd37 and srbd61 (lip30 has no second-order term), the live-handle test on srbd13 and all four policy cases.
 
-Not covered: status 2 (regularisation overflow) -- no input reaches it robustly (tests).
+Status 2 (regularisation overflow) and the other failure exits: tests/test_gpu_failure_exits.py (mu0 = 2e300 reaches it robustly).
 """
 import math
 
@@ -135,7 +135,7 @@ def test_policy_export_under_alpha0_and_gap_tol(model, B, which):
         pc.assert_policy_matches(kff[b], K[b], info[b], ref, label=f"{name} instance {b}")
         assert info[b, 1] == 1.0 and info[b, 3] == 1.0                                      # theta_used, ok
         if which == "B":
-            true = pc.oracle_policy(m, x[b], u[b], sub["params"][b], dict(gap=np.inf, mu=st["mu"][b], alpha=st["alpha"][b]), opt, M)
+            true = pc.oracle_policy(m, x[b], u[b], sub["params"][b], dict(gap=np.inf, mu=st["mu"][b], alpha=st["alpha"][b], status=st["status"][b]), opt, M)
             print(f"{name} instance {b}: gap {st['gap'][b]:.3e}; max |kff(true defects) - kff(zero defects)| = "
                   f"{np.max(np.abs(true[0] - ref[0])):.3e}, max |kff| = {np.max(np.abs(ref[0])):.3e}")
             try:

@@ -132,3 +132,84 @@ def test_the_numpy_oracle_comparison_of_one_instance():
     x[0, 1, 1] += 1.5 * parity.X_TOL
     with pytest.raises(AssertionError):
         parity.assert_matches_numpy_oracle(x[0], u[0], st[0], r)
+
+
+# ---- the failed-instance comparison (status 2, 3, 4): the same bounds, NaNs allowed ------------------------------------------------------
+def _failed(status=4, cost=12.0, gap=3.0):
+    xo, uo, so = _oracle()
+    for f, v in dict(status=status, converged=0, iters=2, alpha=0.0, cost=cost, gap=gap, mu=30.0).items():
+        so[1, oc.STAT_FIELDS.index(f)] = v
+    return xo, uo, so
+
+
+def _check_failed(change=None, start=False, **so_kw):
+    xo, uo, so = _failed(**so_kw)
+    x, u, st = _gpu(xo, uo, so)
+    st["rollouts"][1] = 5
+    begin = None
+    if start:
+        begin = (xo[1, 0].copy(), xo[1].copy(), uo[1].copy())
+        begin[1][0] = -1.0                                       # row 0 of the warm start is not what comes back: x0 is
+    if change:
+        change(x, u, st, so)
+    parity.assert_failed_matches_c_oracle(x, u, st, xo, uo, so, 1, start=begin, rollouts=5)
+
+
+def test_failed_instance_equal_results_pass_with_and_without_nans():
+    _check_failed()
+    _check_failed(start=True)
+    _check_failed(status=3, cost=np.nan, gap=np.nan, start=True)
+    _check_failed(status=3, cost=np.inf, gap=1e160)
+
+    def nan_entries(x, u, st, so):
+        x[1, 1, 2] = np.nan
+    xo, uo, so = _failed(status=3, cost=np.nan)
+    xo[1, 1, 2] = np.nan
+    x, u, st = _gpu(xo, uo, so)
+    parity.assert_failed_matches_c_oracle(x, u, st, xo, uo, so, 1)
+    d = parity.failed_deviations(x, u, st, xo, uo, so, [1])
+    assert all(np.isfinite(v) and v == 0.0 for v in d.values()), d
+
+
+FAILED_SCALED = {"x": _shift_x, "u": lambda f: (lambda x, u, st, so: u.__setitem__((1, 0, 1), u[1, 0, 1] - f * parity.X_TOL)),
+                 "cost": _scale("cost", parity.COST_RTOL, 1), "gap": _scale("gap", parity.GAP_RTOL, 1), "mu": _scale("mu", parity.MU_RTOL, 1)}
+
+
+@pytest.mark.parametrize("what", list(FAILED_SCALED))
+def test_failed_instance_half_the_bound_passes_and_twice_the_bound_fails(what):
+    change = FAILED_SCALED[what]
+    _check_failed(change(0.5))
+    _check_failed(change(-0.5))
+    for f in (2.0, -2.0):
+        with pytest.raises(AssertionError):
+            _check_failed(change(f))
+
+
+def _set(field, b, v):
+    return lambda x, u, st, so: st[field].__setitem__(b, v)
+
+
+@pytest.mark.parametrize("change", [_set("status", 1, 3), _set("status", 1, 0), _set("iters", 1, 3), _set("converged", 1, 1), _set("rollouts", 1, 4),
+                                    _set("alpha", 1, 5e-324), _set("cost", 1, np.nan), _set("gap", 1, np.inf)])
+def test_failed_instance_exact_fields_fail_on_one_unit(change):
+    with pytest.raises(AssertionError):
+        _check_failed(change)
+
+
+def test_failed_instance_non_finite_must_sit_where_the_oracles_does():
+    with pytest.raises(AssertionError):
+        _check_failed(_set("cost", 1, 12.0), status=3, cost=np.nan)
+    with pytest.raises(AssertionError):
+        _check_failed(_set("cost", 1, np.nan), status=3, cost=np.inf)
+    with pytest.raises(AssertionError):
+        _check_failed(_set("cost", 1, -np.inf), status=3, cost=np.inf)
+
+    def one_nan(x, u, st, so):
+        x[1, 2, 0] = np.nan
+    with pytest.raises(AssertionError):
+        _check_failed(one_nan)
+
+    def one_bit(x, u, st, so):
+        u[1, 1, 1] = np.nextafter(u[1, 1, 1], 9.0)
+    with pytest.raises(AssertionError):
+        _check_failed(one_bit, start=True)                       # the start comes back byte for byte

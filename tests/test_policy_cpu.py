@@ -62,7 +62,7 @@ class PolicyOracleEngine(OracleEngine):
         opt = oddp.DdpOptions(**OPTS)
         for b in range(first, first + count):
             # (the C oracle's record keeps cost and iterations only: a converged solve ends with closed gaps, mu0 and a full step)
-            st = dict(gap=0.0, mu=opt.mu0, alpha=opt.alpha_0)
+            st = dict(gap=0.0, mu=opt.mu0, alpha=opt.alpha_0, status=0)
             kff, K, info = pc.oracle_policy(m, self.x[b].numpy(), self.u[b].numpy(), self._P[b].numpy(), st, opt, 1)
             self.policy_records[b] = torch.from_numpy(np.concatenate([kff[0], K[0].reshape(-1), info]))
 
@@ -136,7 +136,7 @@ def test_first_order_property_in_the_oracle(model):
     x0, P = b["x0"][0], b["params"][0]
     r = oddp.solve(m, x0, P, b["xs"][0], b["us"][0], opt)
     assert r.converged
-    _, K, info = pc.oracle_policy(m, r.xs, r.us, P, dict(gap=r.gap, mu=r.mu, alpha=r.alpha), opt, 1)
+    _, K, info = pc.oracle_policy(m, r.xs, r.us, P, dict(gap=r.gap, mu=r.mu, alpha=r.alpha, status=r.status), opt, 1)
     assert info[3] == 1.0 and info[1] == (1.0 if model != "lip30" or r.alpha == 1.0 else 0.0)
     v = pc.fo_direction(model, m.nx)
 
