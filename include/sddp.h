@@ -423,7 +423,7 @@ int  sddp_debug_poison_lds(sddp_handle* h);
 int  sddp_fetch(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats /*[B] or NULL*/);
 /* which: 0 xs [B][N+1][nx], 1 us [B][N][nu], 2 stats [B] (sddp_stats), 3 gains [slots][N][nu*(nx+1)], 4 x0 [B][nx],
  * 5 params [B][N+1][np] (the resident tensor of sddp_set_params), 6 order [last_queued] (int: the instance indices in the
- * order the last queued launch handed them out; queue_order 1 or 2 only), 7 slot times [last_grid][2] (uint64: the 100 MHz
+ * order the last queued launch handed them out; queue_order 1, 2 or 3), 7 slot times [last_grid][2] (uint64: the 100 MHz
  * constant-rate clock at which each slot of the last solve launch started and found the queue empty), 8 policy [B][words] (the
  * policy export above; SDDP_ERR_ARG without sddp_enable_policy), 9 iteration log [B][rows][16] and 10 its record counts [B] (int)
  * (SDDP_ERR_ARG without sddp_enable_iteration_log), 11 time-budget clock words [2] (uint64, the clock of 7: start and deadline of

@@ -493,7 +493,7 @@ class DdpEngine:
         return out
 
     def last_queue_order(self):
-        """Instance indices in the order the last queued launch handed them out (queue_order 1 or 2); waits for the stream."""
+        """Instance indices in the order the last queued launch handed them out (queue_order 1, 2 or 3); waits for the stream."""
         return self._host_copy(6, "<i4")
 
     def slot_times(self):
