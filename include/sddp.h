@@ -236,6 +236,27 @@ int  sddp_policy_words(sddp_handle* h, int* words, int* knots);
 int  sddp_policy_range_device(sddp_handle* h, int first, int count);
 int  sddp_fetch_policy(sddp_handle* h, int first, int count, double* out /*[count][words]*/);
 int  sddp_apply_policy_device(sddp_handle* h, int first, int count, const double* d_x_meas, double* d_u_out);
+/* The later knots of the policy, on the device: what a robot whose new plan is not ready at the tick (a budgeted or sliced launch)
+ * stays on, and where it goes under it.
+ * sddp_apply_policy_knot_device: u[i] = u_k[b] + K_k[b] (x_meas[i] - x_k[b]), b = first + i, k = knot in 0 .. knots - 1 (the knots of
+ *   sddp_enable_policy); u_k[b] itself where the record says ok = 0.  knot = 0 is sddp_apply_policy_device, bit for bit.
+ * sddp_policy_rollout_device: the closed-loop rollout of the policy through the handle's device model from a measured state at
+ *   node `start`:
+ *       x_0' = x_meas[i];   u_j' = u_{start+j}[b] + K_{start+j}[b] (x_j' - x_{start+j}[b]);   x_{j+1}' = f(x_j', u_j'; P[b][start+j], node start+j)
+ *   for j = 0 .. steps - 1, with 0 <= start, steps >= 1, start + steps <= knots.  f and the stage cost L are the model code of the
+ *   solve's own rollout and of sddp_model_step: the solver's prediction model, no quaternion renormalisation, no sub-stepping.  P is
+ *   the parameter tensor of the last sddp_solve* launch, as for sddp_policy_range_device (SDDP_ERR_ARG if no solve ran); with
+ *   per-instance constants (sddp_set_instance_consts) instance b rolls out through its own robot.  ok = 0: K is not multiplied, the
+ *   open-loop rollout of u_k from x_meas.
+ *       d_x_meas [count][nx];  d_x_out [count][steps + 1][nx] (row 0 = x_meas);  d_u_out [count][steps][nu];
+ *       d_cost_out [count] or NULL: the sum over j of L_{start+j}(x_j', u_j'), added in knot order.
+ * Both are asynchronous on the handle's stream, behind the solve and the policy launch, write nothing but the caller's outputs and
+ * use none of the slots' work buffers: no solve result, policy record, resume flag or log record changes, and a sddp_forward after
+ * them needs no new sddp_backward.  The result of an instance does not depend on the range it was part of.  They exist where the
+ * policy export does. */
+int  sddp_apply_policy_knot_device(sddp_handle* h, int first, int count, int knot, const double* d_x_meas, double* d_u_out);
+int  sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
+                                double* d_u_out, double* d_cost_out);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

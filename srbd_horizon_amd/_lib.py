@@ -101,6 +101,8 @@ SYMBOLS = {
     "sddp_policy_range_device": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sddp_fetch_policy": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sddp_apply_policy_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "sddp_apply_policy_knot_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "sddp_policy_rollout_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),

@@ -1273,14 +1273,34 @@ int sddp_fetch_policy(sddp_handle* h, int first, int count, double* out) {
     return sddp_synchronize(h);
 }
 
-int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double* d_x_meas, double* d_u_out) {
+int sddp_apply_policy_knot_device(sddp_handle* h, int first, int count, int knot, const double* d_x_meas, double* d_u_out) {
     if (!h) return SDDP_ERR_ARG;
     if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!d_x_meas || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (knot < 0 || knot >= h->policy_knots)
+        return fail(h, SDDP_ERR_ARG, "sddp_apply_policy_knot_device: knot must be a kept knot, 0 <= knot < " + std::to_string(h->policy_knots) +
+                                         " (the knots of sddp_enable_policy)");
     const int grid = int(std::min<size_t>((size_t(count) * h->d.nu + 255) / 256, 2048));
-    return launch(h, apply_policy_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, h->xs, h->us, h->policy, h->policy_words(),
+    return launch(h, apply_policy_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, knot, h->xs, h->us, h->policy, h->policy_words(),
                   d_x_meas, d_u_out);
+}
+
+int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double* d_x_meas, double* d_u_out) {
+    return sddp_apply_policy_knot_device(h, first, count, 0, d_x_meas, d_u_out);
+}
+
+int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
+                               double* d_u_out, double* d_cost_out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (start < 0 || steps < 1 || start > h->policy_knots - steps)
+        return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->policy_knots) +
+                                         " (the knots of sddp_enable_policy)");
+    if (!d_x_meas || !d_x_out || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    return h->ops->launch_policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
 }
 
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {

@@ -75,6 +75,8 @@ struct ModelOps {
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
+    // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
+    int (*launch_policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);

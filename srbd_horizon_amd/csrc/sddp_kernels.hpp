@@ -1361,6 +1361,71 @@ __global__ __launch_bounds__(kWave) void model_step_kernel(ConstsArg<Tab...> con
 }
 
 // -----------------------------------------------------------------------------------------------------------------
+// Closed-loop rollout of the exported policy from a measured state (sddp_policy_rollout_device): for the instances b = first + i,
+//   x_0' = x_meas[i];  u_j' = u_k[b] + K_k[b] (x_j' - x_k[b]);  x_{j+1}' = f(x_j', u_j'; P[b][k], k),  k = start + j,  j < steps,
+// through M::step, the model code of the solve's own rollout: its prediction, no renormalisation.  cost (may be null): the sum of
+// the stage costs L_k(x_j', u_j') in knot order.  ok = 0 in the policy record `pol` [B][pol_words]: K is not multiplied (0 x NaN is
+// not 0), the open-loop rollout of u_k from x_meas.
+// One wavefront per instance.  Per knot, lane r < NU owns row r of K_k with apply_policy_kernel's FMA chain (u' at start = 0 is
+// bit-equal to it), reading x_j' from LDS (every lane the same word: a broadcast, no conflict); lane 0 then runs the scalar model
+// code as eval_knots_kernel does and leaves x_{j+1}' in LDS, from where the wave stores it.  Static LDS only, nothing of the
+// slots' work buffers, plain vector stores to the caller's outputs alone.
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void policy_rollout_kernel(ConstsArg<Tab...> consts, int N, int first, int count, int start, int steps,
+                                                               const double* __restrict__ xs, const double* __restrict__ us,
+                                                               const double* __restrict__ P, const double* __restrict__ pol, int pol_words,
+                                                               const double* __restrict__ x_meas, double* __restrict__ x_out,
+                                                               double* __restrict__ u_out, double* __restrict__ cost_out) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    static_assert(NU <= kWave, "one lane per row of K_k");
+    __shared__ double sz[NX + NU];                         // x_j' | u_j'
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = xs + size_t(b) * (N + 1) * NX;
+    const double* ub = us + size_t(b) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    const double* rec = pol + size_t(b) * pol_words;
+    const bool feedback = rec[pol_words - 1] != 0.0;
+    double* xo = x_out + size_t(i) * (steps + 1) * NX;
+    double* uo = u_out + size_t(i) * steps * NU;
+    for (int e = lane; e < NX; e += kWave) {
+        const double v = x_meas[size_t(i) * NX + e];
+        sz[e] = v;
+        xo[e] = v;
+    }
+    wave_sync();
+    double J = 0.0;
+    for (int j = 0; j < steps; ++j) {
+        const int k = start + j;
+        if (lane < NU) {
+            const double* K = rec + size_t(k) * NU * (NX + 1) + NU + size_t(lane) * NX;
+            const double* xk = xb + k * NX;
+            double acc = ub[k * NU + lane];
+            if (feedback)
+                for (int t = 0; t < NX; ++t) acc = fma(K[t], sz[t] - xk[t], acc);
+            sz[NX + lane] = acc;
+            uo[j * NU + lane] = acc;
+        }
+        wave_sync();
+        if (lane == 0) {
+            double xl[NX], ul[NU], xn[NX];
+#pragma unroll
+            for (int t = 0; t < NX; ++t) xl[t] = sz[t];
+#pragma unroll
+            for (int t = 0; t < NU; ++t) ul[t] = sz[NX + t];
+            J += M::step(c, xl, ul, Pb + k * NP, k, xn);
+#pragma unroll
+            for (int t = 0; t < NX; ++t) sz[t] = xn[t];
+        }
+        wave_sync();
+        for (int e = lane; e < NX; e += kWave) xo[(j + 1) * NX + e] = sz[e];
+    }
+    if (lane == 0 && cost_out) cost_out[i] = J;
+}
+
+// -----------------------------------------------------------------------------------------------------------------
 // one wavefront per knot: lane 0 runs the scalar model code, all lanes expand the dense tiles
 template <class M>
 __global__ __launch_bounds__(kWave) void eval_knots_kernel(DevConsts c, int N, int nk, const int* __restrict__ kk,

@@ -186,20 +186,21 @@ __global__ __launch_bounds__(256) void pack_records_kernel(int N, int nx, int nu
     }
 }
 
-// The feedback policy between two ticks of a fleet (sddp_apply_policy_device): u[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]) for the
-// instances b = first + i of a range, from the policy buffer (knot 0: kff [nu] then K [nu][nx] row-major) and the handle's xs / us.
-// An instance without a policy (ok = 0: zero gains) gets u_0[b] exactly.
-// A B x nu x nx mat-vec: nu lanes per instance, one row of K_0 each (nx <= 61 terms, fp64 FMA chain); no LDS.
-__global__ __launch_bounds__(256) void apply_policy_kernel(int N, int nx, int nu, int first, int count, const double* __restrict__ xs,
+// The feedback policy between two ticks of a fleet (sddp_apply_policy_device, sddp_apply_policy_knot_device):
+// u[i] = u_k[b] + K_k[b] (x_meas[i] - x_k[b]) for the instances b = first + i of a range, k = `knot` < the knots kept, from the policy
+// buffer (per knot: kff [nu] then K [nu][nx] row-major) and the handle's xs / us.
+// An instance without a policy (ok = 0: zero gains) gets u_k[b] exactly.
+// A B x nu x nx mat-vec: nu lanes per instance, one row of K_k each (nx <= 61 terms, fp64 FMA chain); no LDS.
+__global__ __launch_bounds__(256) void apply_policy_kernel(int N, int nx, int nu, int first, int count, int knot, const double* __restrict__ xs,
                                                            const double* __restrict__ us, const double* __restrict__ pol, int pol_words,
                                                            const double* __restrict__ x_meas, double* __restrict__ u_out) {
     for (size_t e = size_t(blockIdx.x) * 256 + threadIdx.x; e < size_t(count) * nu; e += size_t(gridDim.x) * 256) {
         const int i = int(e / nu), r = int(e % nu), b = first + i;
-        const double* K = pol + size_t(b) * pol_words + nu + size_t(r) * nx;
-        const double* x0 = xs + size_t(b) * (N + 1) * nx;
+        const double* K = pol + size_t(b) * pol_words + size_t(knot) * nu * (nx + 1) + nu + size_t(r) * nx;
+        const double* x0 = xs + (size_t(b) * (N + 1) + knot) * nx;
         const double* xm = x_meas + size_t(i) * nx;
-        double acc = us[size_t(b) * N * nu + r];
-        // ok = 0 (the record's last word): there is no feedback -- u_0 itself, whatever x_0 holds (0 x NaN is not 0)
+        double acc = us[(size_t(b) * N + knot) * nu + r];
+        // ok = 0 (the record's last word): there is no feedback -- u_k itself, whatever x_k holds (0 x NaN is not 0)
         if (pol[size_t(b) * pol_words + pol_words - 1] != 0.0)
             for (int j = 0; j < nx; ++j) acc = fma(K[j], xm[j] - x0[j], acc);
         u_out[e] = acc;

@@ -217,6 +217,16 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
     });
 }
 
+// the exported policy rolled out through the model from a measured state (policy_rollout_kernel): one wavefront per instance of
+// the range, static LDS only -- no kernel_slots entry, no work buffer.  has_policy<M>() builds only, like launch_policy.
+template <class M>
+int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int steps, const double* dxm, double* dx, double* du, double* dcost) {
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, policy_rollout_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, start, steps, h->xs,
+                      h->us, h->last_params, (const double*)h->policy, h->policy_words(), dxm, dx, du, dcost);
+    });
+}
+
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
     return with_table<M>(h, [&](auto... tab) {
@@ -247,7 +257,7 @@ ModelOps make_ops(const char* name) {
     o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
-    if constexpr (has_policy<M>()) o.launch_policy = launch_policy<M>;
+    if constexpr (has_policy<M>()) { o.launch_policy = launch_policy<M>; o.launch_policy_rollout = launch_policy_rollout<M>; }
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

@@ -178,11 +178,45 @@ class DdpEngine:
         solver's next step and u_k + K_k (x - x_k) the feedback law around the plan."""
         return self.split_policy(self.fetch_policy(first, count))
 
-    def apply_policy_device(self, x_meas, u_out, first: int = 0, count: int | None = None):
-        """u_out[i] = u_0[b] + K_0[b] (x_meas[i] - x_0[b]), b = first + i: device tensors [count, nx] -> [count, nu]; asynchronous."""
+    def apply_policy_device(self, x_meas, u_out, first: int = 0, count: int | None = None, knot: int = 0):
+        """u_out[i] = u_k[b] + K_k[b] (x_meas[i] - x_k[b]), b = first + i, k = knot < the knots kept: device tensors [count, nx] ->
+        [count, nu]; asynchronous."""
         n = self._count(first, count)
-        self._chk(self.lib.sddp_apply_policy_device(self.h, int(first), n, self._dev(x_meas, (n, self.nx)), self._dev(u_out, (n, self.nu))))
+        xm, uo = self._dev(x_meas, (n, self.nx)), self._dev(u_out, (n, self.nu))
+        if knot == 0:
+            self._chk(self.lib.sddp_apply_policy_device(self.h, int(first), n, xm, uo))
+        else:
+            self._chk(self.lib.sddp_apply_policy_knot_device(self.h, int(first), n, int(knot), xm, uo))
         return u_out
+
+    def policy_rollout_device(self, x_meas, x_out, u_out, cost_out=None, first: int = 0, count: int | None = None, start: int = 0,
+                              steps: int | None = None):
+        """The exported policy rolled out through the solver's device model from the measured states x_meas [count, nx] at node
+        `start`: x_out [count, steps + 1, nx] (row 0 = x_meas), u_out [count, steps, nu] with u_j = u_k + K_k (x_j - x_k), k = start + j,
+        cost_out [count] or None: the stage costs along it, summed.  Device tensors; steps None: to the last kept knot.  Asynchronous,
+        behind the solve and the policy launch."""
+        n = self._count(first, count)
+        s = int(self.policy_words()[1] - start if steps is None else steps)
+        rows = max(s, 0)                      # (a refused steps < 1 reaches the library, which says what is allowed)
+        self._chk(self.lib.sddp_policy_rollout_device(self.h, int(first), n, int(start), s, self._dev(x_meas, (n, self.nx)),
+                                                      self._dev(x_out, (n, rows + 1, self.nx)), self._dev(u_out, (n, rows, self.nu)),
+                                                      self._dev_or_null(cost_out, (n,))))
+        return x_out, u_out, cost_out
+
+    def policy_rollout(self, x_meas, first: int = 0, count: int | None = None, start: int = 0, steps: int | None = None):
+        """policy_rollout_device from and to numpy: x_meas [n, nx] -> (x [n, steps + 1, nx], u [n, steps, nu], cost [n]); waits for
+        the stream."""
+        import torch
+        n = self._count(first, count)
+        s = int(self.policy_words()[1] - start if steps is None else steps)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        xm = torch.from_numpy(self._c(x_meas, (n, self.nx))).to(dev)
+        x = torch.empty((n, max(s, 0) + 1, self.nx), dtype=torch.float64, device=dev)
+        u = torch.empty((n, max(s, 0), self.nu), dtype=torch.float64, device=dev)
+        cost = torch.empty((n,), dtype=torch.float64, device=dev)
+        self.policy_rollout_device(xm, x, u, cost, first, n, start, s)
+        self.synchronize()
+        return x.cpu().numpy(), u.cpu().numpy(), cost.cpu().numpy()
 
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
