@@ -257,6 +257,37 @@ int  sddp_apply_policy_device(sddp_handle* h, int first, int count, const double
 int  sddp_apply_policy_knot_device(sddp_handle* h, int first, int count, int knot, const double* d_x_meas, double* d_u_out);
 int  sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
                                 double* d_u_out, double* d_cost_out);
+/* ---- plan audit (v9): constraint violations of a plan, computed on the device ---------------------------------------------------
+ * The solver treats every inequality and every contact constraint softly (a barrier that is off by default, penalty rows, Euler
+ * steps without renormalisation), so converged = 1 and a low cost do not say whether a plan is admissible.  The audit measures it:
+ * SDDP_AUDIT_WORDS doubles per instance, maxima over the nodes of a trajectory.  Forces are in the input's units (force_scaling N);
+ * ml = coefficient / sqrt(2), the inner pyramid of the barrier.  Stage nodes are start + j, j < steps; state nodes start + j,
+ * j <= steps; contact i is in stance at a node iff its switch parameter there is > 0.5.
+ *    0  cone: max over stage nodes and stance contacts of max(|f_x|, |f_y|) - ml f_z; -inf without a stance contact
+ *    1, 2  node and contact of word 0 (-1: none; the first in node-major order on ties)
+ *    3  pull: max over stage nodes and stance contacts of -f_z; -inf without one          4  its node
+ *    5  swing load: max over stage nodes and contacts not in stance of max_a |f_a|; 0 without one
+ *    6  quaternion drift: max over state nodes of | ||o|| - 1 |
+ *    7  foot height: max over stage nodes and contacts of |c_z - c_ref|
+ *    8  slip: max over stage nodes and stance contacts of max(|cdot_x|, |cdot_y|)
+ *    9  rigid foot: max over stage nodes and the relative-velocity pairs (first contact of a foot, another of it) of
+ *       |cdot_lead,xy - cdot_i,xy|; 0 with relative_velocity_constraints = 0
+ *   10  defect: max over stage nodes of || x_{k+1} - f(x_k, u_k; p_k) ||_inf, f the handle's device model      11  its node
+ *   12  stage nodes audited (steps)      13  stance (node, contact) pairs counted      14, 15  reserved, 0
+ * srbd13 (contacts are parameters): words 7 - 9 are 0.  lip30 (no forces, no quaternion): words 0 and 3 are -inf, 1, 2 and 4 are -1,
+ * 5, 6 and 13 are 0.  A maximum whose operands include a NaN is NaN, and its index words are -1.
+ * sddp_audit_range_device: d_x == NULL and d_u == NULL audit the handle's own xs / us (start = 0 and steps = N are required); both
+ *   given audit a caller's trajectory in the layout of sddp_policy_rollout_device's outputs, d_x [count][steps + 1][nx] and
+ *   d_u [count][steps][nu], row j at node start + j, with 0 <= start, steps >= 1, start + steps <= N.  The parameters are those of the
+ *   last sddp_solve* launch (SDDP_ERR_ARG if no solve ran); with per-instance constants instance b is stepped through its own robot.
+ *   friction_coefficient > 0: the ground's coefficient for this call; otherwise (<= 0 or NaN) the friction_cone_coefficient given at
+ *   sddp_create.  Asynchronous on the handle's stream; it writes nothing but d_out [count][SDDP_AUDIT_WORDS], uses none of the slots'
+ *   work buffers, and the result of an instance does not depend on the range it was part of.  Every build has it.
+ * sddp_audit: the handle's own plan into a host array; waits for the stream. */
+#define SDDP_AUDIT_WORDS 16
+int  sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
+                             double friction_coefficient, double* d_out /*[count][SDDP_AUDIT_WORDS]*/);
+int  sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out /*[count][SDDP_AUDIT_WORDS], host*/);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

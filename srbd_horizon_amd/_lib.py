@@ -57,6 +57,10 @@ LOG_WORDS, LOG_MAX_ROWS = 16, 4096      # one record of the iteration log (inclu
 # the words of a record, by name
 LOG_FIELDS = ("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", "theta", "mu", "tried", "slack", "iters", "rollouts",
               "mu_bumps", "reserved")
+# one record of the plan audit (include/sddp.h sddp_audit_range_device), and its words by name
+AUDIT_WORDS = 16
+(AUDIT_CONE, AUDIT_CONE_NODE, AUDIT_CONE_CONTACT, AUDIT_PULL, AUDIT_PULL_NODE, AUDIT_SWING_LOAD, AUDIT_QUAT_DRIFT, AUDIT_FOOT_HEIGHT,
+ AUDIT_SLIP, AUDIT_RIGID_FOOT, AUDIT_DEFECT, AUDIT_DEFECT_NODE, AUDIT_NODES, AUDIT_STANCE_PAIRS) = range(14)
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = 8, 16
 STATS_F64_COST, STATS_I32_ITERS, STATS_I32_STATUS, STATS_I32_ROLLOUTS = 0, 12, 14, 15
@@ -103,6 +107,8 @@ SYMBOLS = {
     "sddp_apply_policy_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sddp_apply_policy_knot_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "sddp_policy_rollout_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sddp_audit_range_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp]),
+    "sddp_audit": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),

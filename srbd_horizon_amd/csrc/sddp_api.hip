@@ -1303,6 +1303,39 @@ int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, 
     return h->ops->launch_policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
 }
 
+int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
+                            double friction_coefficient, double* d_out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if ((d_x == nullptr) != (d_u == nullptr)) return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
+    const bool own = d_x == nullptr;
+    if (own && (start != 0 || steps != h->N))
+        return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: the handle's own plan is audited whole, start = 0 and steps = " + std::to_string(h->N));
+    if (start < 0 || steps < 1 || start > h->N - steps)
+        return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->N));
+    // the call's coefficient, or the handle's: linearised as DevConsts::mu_lin is
+    const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
+    return h->ops->launch_audit(h, first, count, start, steps, own ? h->xs : d_x, own ? h->us : d_u, own, mu / sqrt(2.0), d_out);
+}
+
+int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t bytes = size_t(count) * SDDP_AUDIT_WORDS * sizeof(double);
+    double* d_out = nullptr;
+    HIP_TRY(h, hipMalloc(&d_out, bytes));
+    int rc = sddp_audit_range_device(h, first, count, 0, h->N, nullptr, nullptr, friction_coefficient, d_out);
+    if (rc == SDDP_OK) {
+        const hipError_t e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
+        rc = e == hipSuccess ? sddp_synchronize(h) : fail(h, SDDP_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {
     if (!h || !x || !u || !p || !x_next) return SDDP_ERR_ARG;
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");

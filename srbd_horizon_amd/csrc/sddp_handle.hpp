@@ -77,6 +77,8 @@ struct ModelOps {
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
     // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
     int (*launch_policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
+    // the plan audit: first, count, start, steps, x, u, own (the handle's xs / us) or the caller's, linearised friction coefficient, out
+    int (*launch_audit)(sddp_handle*, int, int, int, int, const double*, const double*, bool, double, double*) = nullptr;
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);

@@ -1426,6 +1426,127 @@ __global__ __launch_bounds__(kWave) void policy_rollout_kernel(ConstsArg<Tab...>
 }
 
 // -----------------------------------------------------------------------------------------------------------------
+// Plan audit (sddp_audit_range_device): how far a trajectory is from what the solver only penalises -- friction cone, unilateral
+// force, load on a swing foot, quaternion norm, foot height, slip, rigid foot, dynamics defect -- as SDDP_AUDIT_WORDS maxima per
+// instance (include/sddp.h has the table).  x [..][steps + 1][NX], u [..][steps][NU]: row j sits at node start + j; instance
+// b = first + i reads block xoff + i of them (the handle's own xs / us: xoff = first, steps = N; a caller's: xoff = 0) and row b of P.
+// ml: the linearised friction coefficient of the call.
+// One wavefront per instance; lane l audits the nodes j = l, l + 64, ... on its own (one M::step per stage node, the model code of
+// the solve's rollout) into private maxima, one butterfly of shuffles merges them, lane 0 stores the record.  Read-only but for
+// `out`: no LDS, no atomics, no work buffer.
+// Every maximum propagates NaN (fmax would drop it), and a NaN maximum has no index.
+__device__ __forceinline__ double nan_max(const double a, const double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
+// a maximum with the place it was found at: key = node * NC + contact, smaller key on ties (first in node-major order)
+struct AuditMax {
+    double v;
+    int key;
+};
+constexpr int kAuditNoKey = 0x7fffffff;
+__device__ __forceinline__ void audit_take(AuditMax& m, const double v, const int key) {
+    if (m.v != m.v) return;
+    if (v != v) { m.v = v; m.key = kAuditNoKey; }
+    else if (v > m.v || (v == m.v && key < m.key)) { m.v = v; m.key = key; }
+}
+__device__ __forceinline__ void audit_merge(AuditMax& m) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v = __shfl_xor(m.v, o, kWave);
+        const int key = __shfl_xor(m.key, o, kWave);
+        audit_take(m, v, key);
+    }
+}
+__device__ __forceinline__ double audit_merge(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+__device__ __forceinline__ double audit_index(const AuditMax& m, const int div, const bool rem) {
+    if (m.v != m.v || m.key == kAuditNoKey) return -1.0;
+    return double(rem ? m.key % div : m.key / div);
+}
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void plan_audit_kernel(ConstsArg<Tab...> consts, int N, int first, int count, int start, int steps,
+                                                            const double* __restrict__ x, const double* __restrict__ u, int xoff,
+                                                            const double* __restrict__ P, double ml, double* __restrict__ out) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NC = M::NC;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = x + size_t(xoff + i) * (steps + 1) * NX;
+    const double* ub = u + size_t(xoff + i) * steps * NU;
+    const double* Pb = P + (size_t(b) * (N + 1) + start) * NP;
+    const double inf = __builtin_huge_val();
+    AuditMax cone{-inf, kAuditNoKey}, pull{-inf, kAuditNoKey}, defect{0.0, kAuditNoKey};
+    double swing = 0.0, drift = 0.0, height = 0.0, slip = 0.0, rigid = 0.0;
+    int stance_pairs = 0;
+    for (int j = lane; j <= steps; j += kWave) {
+        const double* xj = xb + size_t(j) * NX;
+        if constexpr (M::AUDIT_QUAT) {
+            const double* o = xj + M::XO;
+            drift = nan_max(drift, fabs(sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3]) - 1.0));
+        }
+        if (j == steps) break;
+        const int k = start + j;
+        const double* uj = ub + size_t(j) * NU;
+        const double* pj = Pb + size_t(j) * NP;
+#pragma unroll
+        for (int n = 0; n < NC; ++n) {
+            const bool stance = M::p_sw(pj, n) > 0.5;
+            if constexpr (M::AUDIT_FORCES) {
+                const double* f = uj + M::uf(n);
+                const double side = nan_max(fabs(f[0]), fabs(f[1]));
+                if (stance) {
+                    audit_take(cone, side - ml * f[2], k * NC + n);
+                    audit_take(pull, -f[2], k * NC + n);
+                    ++stance_pairs;
+                } else {
+                    swing = nan_max(swing, nan_max(side, fabs(f[2])));
+                }
+            }
+            if constexpr (M::AUDIT_CONTACT_STATES) {
+                height = nan_max(height, fabs(xj[M::XC + 3 * n + 2] - M::p_cref(pj, n)));
+                if (stance) slip = nan_max(slip, nan_max(fabs(xj[M::XCD + 3 * n]), fabs(xj[M::XCD + 3 * n + 1])));
+            }
+        }
+        if constexpr (M::AUDIT_CONTACT_STATES) {
+            if (c.w_rv != 0.0) {
+#pragma unroll
+                for (int q = 0; q < M::NRV; ++q)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e)
+                        rigid = nan_max(rigid, fabs(xj[M::XCD + 3 * M::rv_a(q) + e] - xj[M::XCD + 3 * M::rv_b(q) + e]));
+            }
+        }
+        double xn[NX];
+        (void)M::step(c, xj, uj, pj, k, xn);
+        double d = 0.0;
+#pragma unroll
+        for (int e = 0; e < NX; ++e) d = nan_max(d, fabs(xj[NX + e] - xn[e]));
+        audit_take(defect, d, k);
+    }
+    audit_merge(cone);
+    audit_merge(pull);
+    audit_merge(defect);
+    swing = audit_merge(swing);
+    drift = audit_merge(drift);
+    height = audit_merge(height);
+    slip = audit_merge(slip);
+    rigid = audit_merge(rigid);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) stance_pairs += __shfl_xor(stance_pairs, o, kWave);
+    if (lane == 0) {
+        double* r = out + size_t(i) * SDDP_AUDIT_WORDS;
+        r[0] = cone.v;  r[1] = audit_index(cone, NC, false);  r[2] = audit_index(cone, NC, true);
+        r[3] = pull.v;  r[4] = audit_index(pull, NC, false);
+        r[5] = swing;   r[6] = drift;  r[7] = height;  r[8] = slip;  r[9] = rigid;
+        r[10] = defect.v;  r[11] = audit_index(defect, 1, false);
+        r[12] = double(steps);  r[13] = double(stance_pairs);
+        r[14] = 0.0;  r[15] = 0.0;
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------------------
 // one wavefront per knot: lane 0 runs the scalar model code, all lanes expand the dense tiles
 template <class M>
 __global__ __launch_bounds__(kWave) void eval_knots_kernel(DevConsts c, int N, int nk, const int* __restrict__ kk,

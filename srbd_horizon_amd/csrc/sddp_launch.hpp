@@ -227,6 +227,16 @@ int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int s
     });
 }
 
+// the plan audit (plan_audit_kernel): one wavefront per instance of the range, nothing but registers -- no kernel_slots entry, no work
+// buffer.  Every build has it.  own: the handle's xs / us (block first + i), else the caller's trajectory (block i).
+template <class M>
+int launch_audit(sddp_handle* h, int first, int count, int start, int steps, const double* dx, const double* du, bool own, double ml, double* dout) {
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, plan_audit_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, start, steps, dx, du,
+                      own ? first : 0, h->last_params, ml, dout);
+    });
+}
+
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
     return with_table<M>(h, [&](auto... tab) {
@@ -258,6 +268,7 @@ ModelOps make_ops(const char* name) {
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
     if constexpr (has_policy<M>()) { o.launch_policy = launch_policy<M>; o.launch_policy_rollout = launch_policy_rollout<M>; }
+    o.launch_audit = launch_audit<M>;
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

@@ -378,6 +378,9 @@ struct SrbdModel {
                          NSO2L = SO2 ? 2 * NTRI : 0;       // ints: pair codes of the contraction (so2_pair_code), built once per instance
 
     __device__ __forceinline__ static int uf(int i) { return CS ? 6 * i + 3 : 3 * i; }  // prb.py:66-68 interleaved
+    // what the plan audit (plan_audit_kernel) finds in this model: contact forces in u (at uf), a quaternion (at XO), and the contact
+    // points and their velocities as states (at XC / XCD, with the pairs rv_a / rv_b and the references p_cref)
+    static constexpr bool AUDIT_FORCES = true, AUDIT_QUAT = true, AUDIT_CONTACT_STATES = CS;
     // parameter layouts: srbd37 = creation order; srbd13 = App. A.7
     __device__ __forceinline__ static double p_rdref(const double* p, int a) { return p[a]; }
     __device__ __forceinline__ static double p_wref(const double* p, int a) { return p[3 + a]; }
@@ -1433,6 +1436,11 @@ struct LipModel {
     __device__ __forceinline__ static void so2_knot(const DevConsts&, const double*, const double*, const double*, double*) {}
     __device__ __forceinline__ static double p_cref(const double* p, int i) { return p[3 + 2 * i]; }
     __device__ __forceinline__ static double p_sw(const double* p, int i) { return p[4 + 2 * i]; }
+    // the plan audit (see SrbdModel): no forces and no quaternion; contact states, the relative-velocity pairs (0, 1) and (2, 3) of step()
+    static constexpr bool AUDIT_FORCES = false, AUDIT_QUAT = false, AUDIT_CONTACT_STATES = true;
+    static constexpr int NRV = 2;
+    __device__ __forceinline__ static constexpr int rv_a(int q) { return 2 * q; }
+    __device__ __forceinline__ static constexpr int rv_b(int q) { return 2 * q + 1; }
 
     template <class XV>
     __device__ __forceinline__ static double state_cost(const DevConsts& c, XV x, const double* p) {

@@ -218,6 +218,28 @@ class DdpEngine:
         self.synchronize()
         return x.cpu().numpy(), u.cpu().numpy(), cost.cpu().numpy()
 
+    # ---- plan audit: constraint violations of a plan, computed on the device (include/sddp.h) -----------------------------------
+    def audit_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, start: int = 0, steps: int | None = None,
+                     friction: float = 0.0):
+        """The audit records (_lib.AUDIT_* words) of the instances [first, first + count) into the device tensor out
+        [count, AUDIT_WORDS].  x, u None: the handle's own plan; else device tensors x [count, steps + 1, nx], u [count, steps, nu]
+        whose row j sits at node start + j (the outputs of policy_rollout_device); steps None: to node N.  friction > 0: the ground's
+        coefficient for this call, else the handle's friction_cone_coefficient.  Every build has it; asynchronous, behind the solve."""
+        n = self._count(first, count)
+        s = int(self.N - start if steps is None else steps)
+        rows = max(s, 0)                      # (a refused steps < 1 reaches the library, which says what is allowed)
+        self._chk(self.lib.sddp_audit_range_device(self.h, int(first), n, int(start), s, self._dev_or_null(x, (n, rows + 1, self.nx)),
+                                                   self._dev_or_null(u, (n, rows, self.nu)), float(friction),
+                                                   self._dev(out, (n, _lib.AUDIT_WORDS))))
+        return out
+
+    def audit(self, first: int = 0, count: int | None = None, friction: float = 0.0):
+        """The audit records [count, AUDIT_WORDS] of the handle's own plan as a numpy array; waits for the stream."""
+        n = self._count(first, count)
+        out = np.empty((max(n, 0), _lib.AUDIT_WORDS))
+        self._chk(self.lib.sddp_audit(self.h, int(first), n, float(friction), _lib.ptr(out)))
+        return out
+
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
         self._chk(self.lib.sddp_is_converged(self.h, _lib.ptr(f)))

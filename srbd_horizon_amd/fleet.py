@@ -97,15 +97,19 @@ class FleetQueue:
     def clear_instance_consts(self):
         self.eng.clear_instance_consts()
 
-    def flush(self):
+    def flush(self, audit_out=None):
         """Solve the pending batches in one launch (asynchronous); with a process group, start the all-gather of their solution
-        records (asynchronous too: `wait()` before reading `gathered`)."""
+        records (asynchronous too: `wait()` before reading `gathered`).
+        audit_out: a device tensor [>= n, AUDIT_WORDS]; the plan audit of the solved instances (DdpEngine.audit_device) is launched
+        behind the solve and the policy launch into its first n rows."""
         n = self.pending * self.batch
         if n == 0:
             return 0
         self.eng.solve_range_device(self.P, 0, n)
         if self.policy:
             self.eng.policy_range_device(0, n)                               # one sweep per instance at the returned iterate
+        if audit_out is not None:
+            self.eng.audit_device(audit_out[:n], 0, n)
         self.launches += 1
         if self.collective:
             import torch.distributed as dist
