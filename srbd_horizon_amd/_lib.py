@@ -19,7 +19,11 @@ LIB_PATH = os.environ.get("SDDP_LIB", os.path.join(_HERE, "libsddp_hip.so"))   #
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 
+ABI_VERSION = 9      # SDDP_ABI_VERSION of include/sddp.h: what load() asks of the library
 MODEL_IDS = {"srbd13": 0, "srbd37": 1, "lip30": 2, "srbd61": 3}
+# the buffer ids of sddp_device_ptr (include/sddp.h SDDP_BUF_*; engine.device_buffer)
+(BUF_XS, BUF_US, BUF_STATS, BUF_GAINS, BUF_X0, BUF_PARAMS, BUF_ORDER, BUF_SLOT_TIMES, BUF_POLICY, BUF_LOG, BUF_LOG_COUNTS, BUF_CLOCK,
+ BUF_CLASSES) = range(13)
 
 
 class SddpOptions(C.Structure):
@@ -62,8 +66,9 @@ AUDIT_WORDS = 16
 (AUDIT_CONE, AUDIT_CONE_NODE, AUDIT_CONE_CONTACT, AUDIT_PULL, AUDIT_PULL_NODE, AUDIT_SWING_LOAD, AUDIT_QUAT_DRIFT, AUDIT_FOOT_HEIGHT,
  AUDIT_SLIP, AUDIT_RIGID_FOOT, AUDIT_DEFECT, AUDIT_DEFECT_NODE, AUDIT_NODES, AUDIT_STANCE_PAIRS) = range(14)
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
-STATS_F64_WORDS, STATS_I32_WORDS = 8, 16
-STATS_F64_COST, STATS_I32_ITERS, STATS_I32_STATUS, STATS_I32_ROLLOUTS = 0, 12, 14, 15
+STATS_F64_WORDS, STATS_I32_WORDS = C.sizeof(SddpStats) // 8, C.sizeof(SddpStats) // 4
+STATS_F64_COST = SddpStats.cost.offset // 8
+STATS_I32_ITERS, STATS_I32_STATUS, STATS_I32_ROLLOUTS = (getattr(SddpStats, f).offset // 4 for f in ("iters", "status", "rollouts"))
 
 _P = C.POINTER
 _dp = _P(C.c_double)
@@ -322,7 +327,7 @@ def load():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.sddp_abi_version() != 9:
+    if lib.sddp_abi_version() != ABI_VERSION:
         raise RuntimeError("libsddp_hip.so ABI version mismatch")
     _lib = lib
     return lib

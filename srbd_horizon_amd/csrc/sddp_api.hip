@@ -1380,35 +1380,35 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
     if (!h || !ptr) return SDDP_ERR_ARG;
     long long n = 0;
     switch (which) {
-        case 0: *ptr = h->xs; n = (long long)(h->n_x() * sizeof(double)); break;
-        case 1: *ptr = h->us; n = (long long)(h->n_u() * sizeof(double)); break;
-        case 2: *ptr = h->stats; n = (long long)(size_t(h->B) * sizeof(sddp_stats)); break;
-        case 3:   // per slot: row b is instance b's only after a launch without a queue that started at instance 0
+        case SDDP_BUF_XS: *ptr = h->xs; n = (long long)(h->n_x() * sizeof(double)); break;
+        case SDDP_BUF_US: *ptr = h->us; n = (long long)(h->n_u() * sizeof(double)); break;
+        case SDDP_BUF_STATS: *ptr = h->stats; n = (long long)(size_t(h->B) * sizeof(sddp_stats)); break;
+        case SDDP_BUF_GAINS:   // per slot: row b is instance b's only after a launch without a queue that started at instance 0
             if (!h->gains_by_instance)
                 return fail(h, SDDP_ERR_ARG, "the gains are per queue slot: the last solve launch was queued or did not start at instance 0, "
                                              "so row b is not instance b's (solve with B <= slots, sddp_queue_info)");
             *ptr = h->gains; n = (long long)(size_t(h->wslots) * h->N * h->d.nu * (h->d.nx + 1) * sizeof(double)); break;
-        case 4: *ptr = h->x0; n = (long long)(size_t(h->B) * h->d.nx * sizeof(double)); break;
-        case 5: *ptr = h->P; n = (long long)(h->n_p() * sizeof(double)); break;
-        case 6:   // the order the last queued launch handed its instances out in (absolute instance indices)
+        case SDDP_BUF_X0: *ptr = h->x0; n = (long long)(size_t(h->B) * h->d.nx * sizeof(double)); break;
+        case SDDP_BUF_PARAMS: *ptr = h->P; n = (long long)(h->n_p() * sizeof(double)); break;
+        case SDDP_BUF_ORDER:   // the order the last queued launch handed its instances out in (absolute instance indices)
             if (!h->last_queued || h->opts.queue_order == 0) return fail(h, SDDP_ERR_ARG, "the last solve launch had no ordered queue");
             *ptr = h->order; n = (long long)(size_t(h->last_queued) * sizeof(int)); break;
-        case 7:   // per slot of the last solve launch: (start, queue found empty) on the 100 MHz constant-rate clock
+        case SDDP_BUF_SLOT_TIMES:   // per slot of the last solve launch: (start, queue found empty) on the 100 MHz constant-rate clock
             if (h->last_grid < 1) return fail(h, SDDP_ERR_ARG, "no solve launch yet");
             *ptr = h->hist + ((h->B + 1) & ~1); n = (long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;
-        case 8:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
+        case SDDP_BUF_POLICY:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
             if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
             *ptr = h->policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
-        case 9:   // the iteration log [B][rows][16] and (10) its record counts [B] of sddp_enable_iteration_log
-        case 10:
+        case SDDP_BUF_LOG:   // the iteration log [B][rows][16] and its record counts [B] of sddp_enable_iteration_log
+        case SDDP_BUF_LOG_COUNTS:
             if (!h->ilog) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
-            if (which == 9) { *ptr = h->ilog; n = (long long)(size_t(h->B) * h->ilog_rows * kLogWords * sizeof(double)); }
+            if (which == SDDP_BUF_LOG) { *ptr = h->ilog; n = (long long)(size_t(h->B) * h->ilog_rows * kLogWords * sizeof(double)); }
             else { *ptr = h->ilog_n; n = (long long)(size_t(h->B) * sizeof(int)); }
             break;
-        case 11:  // the time budget's clock words: start | deadline of the last budgeted launch sequence (zeros before the first)
+        case SDDP_BUF_CLOCK:  // the time budget's clock words: start | deadline of the last budgeted launch sequence (zeros before the first)
             if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume has not been called");
             *ptr = clock_words(h); n = (long long)(2 * sizeof(unsigned long long)); break;
-        case 12:  // the class labels [B] (int; -1: unlabelled): the caller's, or the handle's own under sddp_enable_auto_classes
+        case SDDP_BUF_CLASSES:  // the class labels [B] (int; -1: unlabelled): the caller's, or the handle's own under sddp_enable_auto_classes
             if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
             *ptr = h->cls; n = (long long)(size_t(h->B) * sizeof(int)); break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");

@@ -322,6 +322,7 @@ class DdpEngine:
         return sm.value, n.value
 
     def device_buffer(self, which: int):
+        """(device pointer, bytes) of the buffer with the id `which`: one of _lib.BUF_* (include/sddp.h SDDP_BUF_*)"""
         p, n = C.c_void_p(), C.c_longlong()
         self._chk(self.lib.sddp_device_ptr(self.h, which, C.byref(p), C.byref(n)))
         return p.value, n.value
@@ -345,10 +346,11 @@ class DdpEngine:
 
     def fetch_device_views(self):
         """Zero-copy torch views of the handle's HBM buffers: x [B,N+1,nx], u [B,N,nu], stats as f64 [B,8] and i32 [B,16]
-        (sddp_stats: cost, alpha, gap, mu, expected, rho | iters, converged, status, rollouts = i32 words 12..15;
+        (sddp_stats: cost, alpha, gap, mu, expected, rho | iters, converged, status, rollouts = the last four i32 words;
         _lib.STATS_I32_ITERS etc.)."""
-        return (self.device_view(0, (self.B, self.N + 1, self.nx)), self.device_view(1, (self.B, self.N, self.nu)),
-                self.device_view(2, (self.B, _lib.STATS_F64_WORDS)), self.device_view(2, (self.B, _lib.STATS_I32_WORDS), "<i4"))
+        return (self.device_view(_lib.BUF_XS, (self.B, self.N + 1, self.nx)), self.device_view(_lib.BUF_US, (self.B, self.N, self.nu)),
+                self.device_view(_lib.BUF_STATS, (self.B, _lib.STATS_F64_WORDS)),
+                self.device_view(_lib.BUF_STATS, (self.B, _lib.STATS_I32_WORDS), "<i4"))
 
     def fetch(self):
         """Copy the solution and stats of the last device solve to host numpy arrays (waits for the handle's stream)."""
@@ -388,7 +390,7 @@ class DdpEngine:
         if params is None and first == 0 and n == self.B:
             self._chk(self.lib.sddp_continue_resident(self.h))
             return
-        p = C.c_void_p(self.device_buffer(5)[0]) if params is None else self._dev(params, (self.B, self.N + 1, self.np_))
+        p = C.c_void_p(self.device_buffer(_lib.BUF_PARAMS)[0]) if params is None else self._dev(params, (self.B, self.N + 1, self.np_))
         self._chk(self.lib.sddp_continue_range_device(self.h, p, int(first), n))
 
     def unfinished(self, first: int = 0, count: int | None = None) -> int:
@@ -414,13 +416,13 @@ class DdpEngine:
 
     def deadline_clock(self):
         """(start, deadline) of the last launch sequence that ran under a budget, on the 100 MHz clock of slot_times() -- device
-        buffer 11; waits for the stream."""
-        t = self._host_copy(11, "<i8").view(np.uint64)
+        buffer _lib.BUF_CLOCK; waits for the stream."""
+        t = self._host_copy(_lib.BUF_CLOCK, "<i8").view(np.uint64)
         return int(t[0]), int(t[1])
 
     def deadline_overrun_us(self) -> float:
-        """How far the last launch ran past its deadline, in microseconds: the latest slot end time (device buffer 7) minus the
-        deadline (device buffer 11).  Negative: the launch was over that long before the deadline.  Meaningful only when the last
+        """How far the last launch ran past its deadline, in microseconds: the latest slot end time (_lib.BUF_SLOT_TIMES) minus the
+        deadline (_lib.BUF_CLOCK).  Negative: the launch was over that long before the deadline.  Meaningful only when the last
         solve / continue launch ran with a budget armed; waits for the stream."""
         _, deadline = self.deadline_clock()
         end = int(self.slot_times()[:, 1].max())
@@ -448,10 +450,10 @@ class DdpEngine:
         return rec, cnt
 
     def iteration_log_device(self):
-        """Zero-copy torch views of the log in HBM: (records [B, rows, 16] float64, n [B] int32) -- device_buffer(9) and (10);
+        """Zero-copy torch views of the log in HBM: (records [B, rows, 16] float64, n [B] int32) -- the buffers _lib.BUF_LOG and BUF_LOG_COUNTS;
         ordered behind the handle's stream like fetch_device_views."""
-        rows = self.device_buffer(9)[1] // (self.B * _lib.LOG_WORDS * 8)
-        return self.device_view(9, (self.B, rows, _lib.LOG_WORDS)), self.device_view(10, (self.B,), "<i4")
+        rows = self.device_buffer(_lib.BUF_LOG)[1] // (self.B * _lib.LOG_WORDS * 8)
+        return self.device_view(_lib.BUF_LOG, (self.B, rows, _lib.LOG_WORDS)), self.device_view(_lib.BUF_LOG_COUNTS, (self.B,), "<i4")
 
     # ---- heterogeneous fleets: per-instance robot constants (include/sddp.h) ------------------------------------------------
     def set_instance_consts(self, overrides: dict, first: int = 0):
@@ -550,12 +552,12 @@ class DdpEngine:
 
     def last_queue_order(self):
         """Instance indices in the order the last queued launch handed them out (queue_order 1, 2 or 3); waits for the stream."""
-        return self._host_copy(6, "<i4")
+        return self._host_copy(_lib.BUF_ORDER, "<i4")
 
     def slot_times(self):
         """[grid, 2] uint64: when each slot of the last solve launch started its first instance and when it found the queue empty
         (100 MHz constant-rate clock); waits for the stream."""
-        return self._host_copy(7, "<i8").view(np.uint64).reshape(-1, 2)
+        return self._host_copy(_lib.BUF_SLOT_TIMES, "<i8").view(np.uint64).reshape(-1, 2)
 
     def queue_info(self):
         """(slots the work buffers exist for, grid of the last launch, queue length of the last launch or 0)."""

@@ -1,18 +1,16 @@
 """The class label that a handle computes itself (include/sddp.h sddp_enable_auto_classes), without a device: the numpy statement
 workload.schedule_classes against the labels written down with the hand-built cases (tests/auto_class_cases.py) and against
-srbd13_schedule_classes, which bench.py passes today; the columns of the other three models; the new symbols."""
+srbd13_schedule_classes, which bench.py passes today; the columns of the other three models."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from srbd_horizon_amd import _lib, workload
+from srbd_horizon_amd import workload
 from tests import auto_class_cases as acc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("sddp_enable_auto_classes", "sddp_auto_classes_info", "sddp_fetch_instance_classes", "sddp_get_class_stats",
-               "sddp_add_class_stats")
 
 
 @pytest.mark.parametrize("N,B", [(30, 37), (70, 37), (8, 8)])
@@ -86,11 +84,3 @@ def test_the_columns_are_the_device_models():
     src = open(os.path.join(ROOT, "srbd_horizon_amd", "csrc", "sddp_models.hpp")).read()
     assert len(re.findall(r"\bP_SW_L\b", src)) >= 2 and len(re.findall(r"\bP_SW_R\b", src)) >= 2       # SRBD family and LIP
 
-
-def test_the_new_symbols_are_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "sddp.h")).read()
-    declared = set(re.findall(r"\b(sddp_[a-z_0-9]+)\s*\(", hdr))
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert name in _lib.SYMBOLS, name
-    assert re.search(r"#define\s+SDDP_ABI_VERSION\s+9\b", hdr)

@@ -1,19 +1,11 @@
-"""Per-instance robot constants (sddp_set_instance_consts), the parts that need no device: the three symbols are declared in
-include/sddp.h and bound in _lib with matching signatures, and the `overrides` -> SddpModelConsts[count] packing."""
+"""Per-instance robot constants (sddp_set_instance_consts), the part that needs no device: the `overrides` -> SddpModelConsts[count]
+packing."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 from srbd_horizon_amd import _lib
-
-HEADER = os.path.join(_lib.ROOT, "include", "sddp.h")
-NEW = {"sddp_set_instance_consts": ["sddp_handle*", "int", "int", "const sddp_model_consts*"],
-       "sddp_clear_instance_consts": ["sddp_handle*"],
-       "sddp_instance_consts_active": ["sddp_handle*", "int*"]}
-CTYPE = {"sddp_handle*": C.c_void_p, "int": C.c_int, "int*": C.POINTER(C.c_int), "const sddp_model_consts*": C.POINTER(_lib.SddpModelConsts)}
 
 
 def _base():
@@ -23,18 +15,6 @@ def _base():
                     r_tracking_gain=1e3, rdot_tracking_gain=1e4, w_tracking_gain=1e4, min_f_gain=1e-2, lip_height=0.88, lever_sign=1.0,
                     relative_velocity_constraints=1)
     return c
-
-
-def test_the_three_symbols_are_declared_and_bound_with_matching_signatures():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    for name, args in NEW.items():
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, f"{name} is not declared in include/sddp.h"
-        declared = [re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*") for a in m.group(1).split(",")]
-        assert declared == args, (name, declared)
-        res, argtypes = _lib.SYMBOLS[name]
-        assert res is C.c_int and argtypes == [CTYPE[a] for a in args], name
-    assert "#define SDDP_ABI_VERSION 9" in open(HEADER).read()             # additive: the ABI version stays
 
 
 def test_packing_keeps_the_defaults_and_replaces_the_named_fields():

@@ -1,31 +1,17 @@
-"""Iteration log without a GPU: the ABI surface and the build list, the refusals that need no device, and -- on the C oracle alone --
+"""Iteration log without a GPU: the names of the record's words and the build list, the refusals that need no device, and -- on the C oracle alone --
 that the settings of tests/iteration_log_cases.py show every kind of record the GPU test compares, and on which instances the
 oracle is a stable reference."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
 from srbd_horizon_amd import _lib
 from tests import iteration_log_cases as lc, options_cases as oc, resume_cases as rc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"sddp_enable_iteration_log": 2, "sddp_iteration_log_info": 3, "sddp_fetch_iteration_log": 5}
 F = lc.F
 
 
-def test_header_declares_the_log_functions_and_ctypes_binds_them_with_matching_argument_counts():
-    hdr = open(os.path.join(ROOT, "include", "sddp.h")).read()
-    for name, nargs in NEW.items():
-        m = re.search(r"^int\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr, re.M)
-        assert m, f"{name} is not declared in include/sddp.h"
-        assert len(re.sub(r"/\*.*?\*/", "", m.group(1)).split(",")) == nargs, (name, m.group(1))
-        res, args = _lib.SYMBOLS[name]
-        assert len(args) == nargs and res is not None, (name, args)
-    assert re.search(r"#define SDDP_ABI_VERSION 9\b", hdr)              # functions only: no layout changed
-    assert re.search(r"#define SDDP_LOG_WORDS 16\b", hdr) and _lib.LOG_WORDS == 16 == len(_lib.LOG_FIELDS)
-    assert re.search(r"#define SDDP_LOG_MAX_ROWS 4096\b", hdr) and _lib.LOG_MAX_ROWS == 4096
+def test_the_first_twelve_words_of_a_record_are_the_oracles_trace_record():
     assert list(_lib.LOG_FIELDS[:12]) == ["J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", "theta", "mu", "tried", "slack"]
 
 

@@ -1,9 +1,6 @@
 """Plan audit (include/sddp.h sddp_audit_range_device, sddp_audit), what needs no GPU: the record of tests/plan_audit_cases.py on
-hand-made trajectories with known answers, the two declarations against their ctypes signatures, and the Python signatures."""
-import ctypes as C
+hand-made trajectories with known answers, the parameter names of the two declarations, and the Python signatures."""
 import inspect
-import os
-import re
 
 import numpy as np
 
@@ -11,9 +8,8 @@ from oracle import models as omodels
 from srbd_horizon_amd import _lib
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
-from tests import plan_audit_cases as pac
+from tests import abi_header, plan_audit_cases as pac
 
-HEADER = os.path.join(_lib.INCLUDE, "sddp.h")
 A = _lib
 N = 5
 MU = 0.8
@@ -37,7 +33,6 @@ def test_words_and_constants():
     assert (A.AUDIT_CONE, A.AUDIT_CONE_NODE, A.AUDIT_CONE_CONTACT, A.AUDIT_PULL, A.AUDIT_PULL_NODE, A.AUDIT_SWING_LOAD, A.AUDIT_QUAT_DRIFT,
             A.AUDIT_FOOT_HEIGHT, A.AUDIT_SLIP, A.AUDIT_RIGID_FOOT, A.AUDIT_DEFECT, A.AUDIT_DEFECT_NODE, A.AUDIT_NODES,
             A.AUDIT_STANCE_PAIRS) == tuple(range(14))
-    assert re.search(r"^#define SDDP_AUDIT_WORDS 16$", open(HEADER).read(), flags=re.M)
 
 
 def test_a_standing_plan_is_admissible_and_an_exact_rollout_has_a_rounding_level_defect():
@@ -161,29 +156,12 @@ def test_assert_record_accepts_the_reference_and_refuses_a_wrong_place():
             pac.assert_record(bad, rec, ops, values, 0, 1e-12)
 
 
-def _declaration(name):
-    """the argument list of `int name(...);` in the header, comments stripped"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    mt = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert mt, f"{name} is not declared in include/sddp.h"
-    return [a.strip() for a in mt.group(1).split(",")]
-
-
 def test_header_and_ctypes_agree_on_the_two_symbols():
-    vp, i, d = C.c_void_p, C.c_int, C.c_double
-    res, args = _lib.SYMBOLS["sddp_audit_range_device"]
-    assert res is i and args == [vp, i, i, i, i, vp, vp, d, vp]
-    res, args = _lib.SYMBOLS["sddp_audit"]
-    assert res is i and args == [vp, i, i, d, vp]
-    for name in ("sddp_audit_range_device", "sddp_audit"):
-        decl = _declaration(name)
-        assert len(_lib.SYMBOLS[name][1]) == len(decl) and "sddp_handle" in decl[0]
-    decl = _declaration("sddp_audit_range_device")
-    assert [a.split()[-1] for a in decl[1:5]] == ["first", "count", "start", "steps"]
-    assert decl[5].startswith("const double*") and decl[6].startswith("const double*") and decl[7] == "double friction_coefficient"
-    assert decl[8].startswith("double*")
-    assert _declaration("sddp_audit")[3] == "double friction_coefficient"
-    assert re.search(r"^#define SDDP_ABI_VERSION 9$", open(HEADER).read(), flags=re.M)      # additive: no struct changed
+    """the order of the integers, which no type tells apart, and what is read-only (the types: tests/test_abi.py, for every symbol)"""
+    declared = abi_header.functions()
+    assert declared["sddp_audit_range_device"][1] == ["sddp_handle* h", "int first", "int count", "int start", "int steps", "const double* d_x",
+                                                      "const double* d_u", "double friction_coefficient", "double* d_out"]
+    assert declared["sddp_audit"][1][3] == "double friction_coefficient"
 
 
 def test_python_signatures():

@@ -1,45 +1,24 @@
-"""Policy rollout (include/sddp.h sddp_apply_policy_knot_device, sddp_policy_rollout_device), what needs no GPU: the two
-declarations and their ctypes signatures, the engine's methods, and the rule of tests/policy_rollout_cases.py on the oracle alone."""
-import ctypes as C
+"""Policy rollout (include/sddp.h sddp_apply_policy_knot_device, sddp_policy_rollout_device), what needs no GPU: the parameter names
+of the two declarations, the engine's methods, and the rule of tests/policy_rollout_cases.py on the oracle alone."""
 import functools
 import inspect
-import os
-import re
 
 import numpy as np
 
 from oracle import ddp as oddp, models as omodels
-from srbd_horizon_amd import _lib, workload
+from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
-from tests import policy_cases as pc, policy_rollout_cases as prc
+from tests import abi_header, policy_cases as pc, policy_rollout_cases as prc
 
-HEADER = os.path.join(_lib.INCLUDE, "sddp.h")
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 M = 4
 
 
-def _declaration(name):
-    """the argument list of `int name(...);` in the header, comments stripped"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"{name} is not declared in include/sddp.h"
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 def test_header_and_ctypes_agree_on_the_two_symbols():
-    vp, i = C.c_void_p, C.c_int
-    res, args = _lib.SYMBOLS["sddp_apply_policy_knot_device"]
-    assert res is i and args == [vp, i, i, i, vp, vp]
-    res, args = _lib.SYMBOLS["sddp_policy_rollout_device"]
-    assert res is i and args == [vp, i, i, i, i, vp, vp, vp, vp]
-    for name in ("sddp_apply_policy_knot_device", "sddp_policy_rollout_device"):
-        decl = _declaration(name)
-        assert len(_lib.SYMBOLS[name][1]) == len(decl) and "sddp_handle" in decl[0]
-    decl = _declaration("sddp_apply_policy_knot_device")
-    assert [a.split()[-1] for a in decl[1:4]] == ["first", "count", "knot"] and decl[4].startswith("const double*")
-    decl = _declaration("sddp_policy_rollout_device")
-    assert [a.split()[-1] for a in decl[1:5]] == ["first", "count", "start", "steps"] and decl[5].startswith("const double*")
-    assert re.search(r"^#define SDDP_ABI_VERSION 9$", open(HEADER).read(), flags=re.M)      # additive: no struct changed
+    """the order of the integers, which no type tells apart, and what is read-only (the types: tests/test_abi.py, for every symbol)"""
+    declared = abi_header.functions()
+    assert declared["sddp_apply_policy_knot_device"][1][:5] == ["sddp_handle* h", "int first", "int count", "int knot", "const double* d_x_meas"]
+    assert declared["sddp_policy_rollout_device"][1][:6] == ["sddp_handle* h", "int first", "int count", "int start", "int steps", "const double* d_x_meas"]
 
 
 def test_engine_methods_and_defaults():

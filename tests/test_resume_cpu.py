@@ -1,28 +1,8 @@
-"""Resumable solves without a GPU: the ABI surface, and the fixture selection of tests/test_gpu_resume.py on the C oracle."""
-import os
-import re
-
+"""Resumable solves without a GPU: the fixture selection of tests/test_gpu_resume.py on the C oracle."""
 import numpy as np
 
 from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import _lib
 from tests import options_cases as oc, resume_cases as rc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"sddp_enable_resume": 2, "sddp_continue_range_device": 4, "sddp_continue_device": 2, "sddp_continue_resident": 1,
-       "sddp_unfinished_count": 4}
-
-
-def test_header_declares_the_resume_functions_and_ctypes_binds_them_with_matching_argument_counts():
-    hdr = open(os.path.join(ROOT, "include", "sddp.h")).read()
-    for name, nargs in NEW.items():
-        m = re.search(r"^int\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr, re.M)
-        assert m, f"{name} is not declared in include/sddp.h"
-        assert len(m.group(1).split(",")) == nargs, (name, m.group(1))
-        assert name in _lib.SYMBOLS, f"{name} has no ctypes signature"
-        res, args = _lib.SYMBOLS[name]
-        assert len(args) == nargs and res is not None, (name, args)
-    assert re.search(r"#define SDDP_ABI_VERSION 9\b", hdr)              # functions only: no layout changed
 
 
 def _trace(model, case, b):
