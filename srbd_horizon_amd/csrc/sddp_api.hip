@@ -48,22 +48,24 @@ namespace {
 int launch_queue_order(sddp_handle* h, int first, int count) {
     return launch(h, queue_order_kernel, 1, 1024, 0, first, count, h->hist, h->order);
 }
-// queue order 3: h->qkey (initial costs of the launch's instances, order h->order_in) -> class-history keys; and the update of the
+// queue order 3: cold.qkey (initial costs of the launch's instances, order cold.order_in) -> class-history keys; and the update of the
 // class statistics behind a solve launch
 int launch_class_keys(sddp_handle* h, int count) {
-    return launch(h, class_key_kernel, (count + 255) / 256, 256, 0, count, h->order_in, h->cls, h->n_cls, h->cls_stat, h->qkey);
+    const auto& c = h->classes;
+    return launch(h, class_key_kernel, (count + 255) / 256, 256, 0, count, h->cold.order_in, c.cls, c.n_cls, c.cls_stat, h->cold.qkey);
 }
 int launch_class_update(sddp_handle* h, int first, int count) {
-    if (h->resumable)   // resumable solves: an instance is counted by the launch in which it leaves status 1
-        return launch(h, class_update_resume_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat,
-                      h->resumable, h->resumable + 2 * size_t(h->B), h->continuing ? 1 : 0);
-    return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, h->cls, h->n_cls, h->stats, h->cls_stat);
+    const auto& c = h->classes;
+    if (h->resume.on())   // resumable solves: an instance is counted by the launch in which it leaves status 1
+        return launch(h, class_update_resume_kernel, (count + 255) / 256, 256, 0, first, count, c.cls, c.n_cls, h->stats, c.cls_stat,
+                      h->resume.resumable, h->resume.resumable + 2 * size_t(h->B), h->resume.continuing ? 1 : 0);
+    return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, c.cls, c.n_cls, h->stats, c.cls_stat);
 }
-// auto classes: the labels of [first, first + count) from the launch's parameter tensor into h->cls, in front of a fresh solve launch
+// auto classes: the labels of [first, first + count) from the launch's parameter tensor into classes.cls, in front of a fresh solve launch
 int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {      // one wavefront per instance, four per workgroup
     const ModelOps* o = h->ops;
     return launch(h, class_label_kernel, (count + 3) / 4, 256, 0, h->N, h->d.np, o->col_cmd[0], o->col_cmd[1], o->col_sw[0], o->col_sw[1], first,
-                  count, P, h->cls);
+                  count, P, h->classes.cls);
 }
 
 // Buffer ownership: every device and pinned allocation of a handle is made by acquire(), which registers it in h->owned.
@@ -90,7 +92,7 @@ void release(sddp_handle* h, T*& p) {
         if (h->owned[i].p == p) { free_owned(h->owned[i]); h->owned.erase(h->owned.begin() + i); break; }
     p = nullptr;
 }
-// a device buffer made on first use; the message names the allocation as the call sites always did
+// a device buffer made on first use and kept for the handle's life; the message names the allocation
 #define ACQUIRE_TRY(h, field, bytes)                                                                                          \
     do {                                                                                                                      \
         hipError_t e_ = acquire(h, field, bytes);                                                                             \
@@ -98,20 +100,53 @@ void release(sddp_handle* h, T*& p) {
             return fail(h, SDDP_ERR_HIP, std::string("hipMalloc((void**)&" #field ", " #bytes "): ") + hipGetErrorString(e_)); \
     } while (0)
 
-// the cold-queue buffers of a handle, all or nothing (a partial failure leaves every pointer null)
+// The device buffers of an optional group, all or nothing: every buffer is allocated, then those with a fill (its byte: 0x00, 0xFF)
+// are cleared on the handle's stream.  On any failure what was acquired is released, HIP's sticky error is cleared, every p stays null
+// and the error is returned: the caller reports it in its own words, and assigns the group's fields only after success.
+constexpr int kNoFill = -1;
+struct GroupBuf {
+    size_t bytes; int fill = kNoFill; void* p = nullptr;
+    template <class T> operator T*() const { return static_cast<T*>(p); }
+};
+template <size_t n>
+hipError_t acquire_group(sddp_handle* h, GroupBuf (&g)[n]) {
+    hipError_t e = hipSuccess;
+    for (GroupBuf& b : g) if (e == hipSuccess) e = acquire(h, b.p, b.bytes);
+    for (GroupBuf& b : g) if (e == hipSuccess && b.fill != kNoFill) e = hipMemsetAsync(b.p, b.fill, b.bytes, h->stream);
+    if (e == hipSuccess) return e;
+    (void)hipGetLastError();
+    for (GroupBuf& b : g) release(h, b.p);
+    return e;
+}
+
+// Wait for the handle's stream: nothing in flight touches a buffer of the handle any more, and the pinned upload ring and both tick
+// images have been read.  Whoever gives a buffer up calls this first.  (The timing events are sddp_synchronize's to read, not ours.)
+int quiesce(sddp_handle* h) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->stage.tick_unsynced = 0; h->stage.up_off = 0;
+    return SDDP_OK;
+}
+
+// Giving a group up: its buffers released, its scalars as sddp_create left them.  The caller has quiesced the handle.
+void drop_log(sddp_handle* h) { release(h, h->log.ilog); release(h, h->log.ilog_n); h->log.ilog_rows = 0; }
+void drop_policy(sddp_handle* h) { release(h, h->pol.policy); h->pol.policy_knots = 0; }
+void drop_table(sddp_handle* h) { release(h, h->table.ctab); }
+// THE statement of what rides on the resumable kernels: the time budget is disarmed and the iteration log goes with them
+void drop_resume(sddp_handle* h) {
+    release(h, h->resume.carry); release(h, h->resume.resumable);
+    h->resume.budget_us = 0.0; h->resume.budget_min_iters = 0;
+    drop_log(h);
+}
+
+// the cold-queue buffers of a handle
 int alloc_cold_queue(sddp_handle* h) {
-    if (h->sort_tmp) return SDDP_OK;               // the last pointer of the group: set only when all of it exists
+    if (h->cold.on()) return SDDP_OK;
     size_t tb = 0;
-    hipError_t e = acquire(h, h->qkey, size_t(h->B) * sizeof(double));
-    if (e == hipSuccess) e = acquire(h, h->qkey2, size_t(h->B) * sizeof(double));
-    if (e == hipSuccess) e = acquire(h, h->order_in, size_t(h->B) * sizeof(int));
-    if (e == hipSuccess) e = sort_pairs_desc_temp_bytes(h->B, &tb);
-    if (e == hipSuccess) e = acquire(h, h->sort_tmp, std::max<size_t>(tb, 16));
-    if (e != hipSuccess) {
-        release(h, h->qkey); release(h, h->qkey2); release(h, h->order_in);
-        return fail(h, SDDP_ERR_HIP, std::string("cold-queue buffers: ") + hipGetErrorString(e));
-    }
-    h->sort_tmp_bytes = tb;
+    hipError_t e = sort_pairs_desc_temp_bytes(h->B, &tb);
+    GroupBuf g[] = {{size_t(h->B) * sizeof(double)}, {size_t(h->B) * sizeof(double)}, {size_t(h->B) * sizeof(int)}, {std::max<size_t>(tb, 16)}};
+    if (e == hipSuccess) e = acquire_group(h, g);
+    if (e != hipSuccess) return fail(h, SDDP_ERR_HIP, std::string("cold-queue buffers: ") + hipGetErrorString(e));
+    h->cold = {g[0], g[1], g[2], g[3], tb};
     return SDDP_OK;
 }
 }  // namespace
@@ -222,12 +257,12 @@ int check_range(sddp_handle* h, int first, int count) {
 // Resumable solves: a call that rewrites x0, xs, us, the resident params row or the constants row of the instances
 // [first, first + count) makes what their cut solve carried meaningless; their flags are cleared, on the stream, behind the rewrite.
 int invalidate_resume(sddp_handle* h, int first, int count) {
-    if (h->resumable) HIP_TRY(h, hipMemsetAsync(h->resumable + first, 0, size_t(count) * sizeof(int), h->stream));
+    if (h->resume.on()) HIP_TRY(h, hipMemsetAsync(h->resume.resumable + first, 0, size_t(count) * sizeof(int), h->stream));
     return SDDP_OK;
 }
 
 unsigned long long* clock_words(sddp_handle* h) {
-    return reinterpret_cast<unsigned long long*>(h->resumable + ResumeArgs::clock_offset(h->B));
+    return reinterpret_cast<unsigned long long*>(h->resume.resumable + ResumeArgs::clock_offset(h->B));
 }
 // Where the solve and the continue entry points meet: one launch over the instances [first, first + count), as a sequence on the
 // handle's stream.  The build says which solve kernel runs, launches it (ModelOps::solve of the variant the handle's state asks for)
@@ -235,13 +270,13 @@ unsigned long long* clock_words(sddp_handle* h) {
 int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
     // with a time budget armed (sddp_set_time_budget) the deadline stamp leads: in front of the queue_order pre-pass and the sort,
     // which the budget therefore covers
-    if (h->budget_us > 0.0 && h->resumable) {
+    if (h->resume.budget_us > 0.0 && h->resume.on()) {
         // 100 MHz clock: ticks = round(100 * budget_us); capped where deadline = start + ticks could wrap
-        const double t = std::min(std::round(100.0 * h->budget_us), 4.0e18);
+        const double t = std::min(std::round(100.0 * h->resume.budget_us), 4.0e18);
         const int rc = launch(h, deadline_stamp_kernel, 1, 1, 0, clock_words(h), (unsigned long long)t);
         if (rc != SDDP_OK) return rc;
     }
-    const ModelOps::SolveOps& solve = h->ops->solve[h->ilog ? kSolveLog : h->carry ? kSolveResume : kSolvePlain];
+    const ModelOps::SolveOps& solve = h->ops->solve[h->log.on() ? kSolveLog : h->resume.on() ? kSolveResume : kSolvePlain];
     if (!solve.launch) return fail(h, SDDP_ERR_ARG, "this build has no kernels of the solve variant that the handle asks for");
     SolveChoice k;
     int rc = solve.choose(h, &k);
@@ -256,7 +291,7 @@ int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
         }
         HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending], h->stream));
     }
-    if (h->auto_cls && !h->continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
+    if (h->classes.auto_cls && !h->resume.continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
         rc = launch_class_labels(h, a.P, first, count);      // continue launch keeps the labels of the solve that was cut
         if (rc != SDDP_OK) return rc;
     }
@@ -270,9 +305,9 @@ int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
             rc = alloc_cold_queue(h);
             if (rc == SDDP_OK) rc = h->ops->launch_cost_keys(h, a, first, count);
             // ... queue_order 3: longest class history first, the initial cost breaking ties
-            if (rc == SDDP_OK && h->opts.queue_order == 3 && h->cls) rc = launch_class_keys(h, count);
+            if (rc == SDDP_OK && h->opts.queue_order == 3 && h->classes.on()) rc = launch_class_keys(h, count);
             if (rc == SDDP_OK)
-                HIP_TRY(h, sort_pairs_desc(h->sort_tmp, h->sort_tmp_bytes, h->qkey, h->qkey2, h->order_in, h->order, count, h->stream));
+                HIP_TRY(h, sort_pairs_desc(h->cold.sort_tmp, h->cold.sort_tmp_bytes, h->cold.qkey, h->cold.qkey2, h->cold.order_in, h->order, count, h->stream));
         }
         if (rc != SDDP_OK) return rc;
         a.order = h->order;
@@ -284,7 +319,7 @@ int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
     h->last_per_cu = k.slots / std::max(1, h->cus);
     h->gains_by_instance = (count <= grid && first == 0);
     rc = solve.launch(h, k, grid, a);
-    if (rc == SDDP_OK && h->cls) rc = launch_class_update(h, first, count);      // labelled instances feed the class statistics
+    if (rc == SDDP_OK && h->classes.on()) rc = launch_class_update(h, first, count);      // labelled instances feed the class statistics
     if (rc != SDDP_OK) return rc;
     if (h->timing) {
         HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending + 1], h->stream));
@@ -602,7 +637,7 @@ int sddp_set_options(sddp_handle* h, const sddp_options* opts) {
     if (rc != SDDP_OK) return rc;
     if ((opts->second_order == 2) != (h->opts.second_order == 2) && h->model_id != SDDP_MODEL_LIP30)
         return fail(h, SDDP_ERR_ARG, "second_order = 2 selects another kernel build and record size: choose it at sddp_create");
-    if (opts->second_order == 2 && h->carry)
+    if (opts->second_order == 2 && h->resume.on())
         return fail(h, SDDP_ERR_ARG, "second_order = 2 on a handle with resumable solves: call sddp_enable_resume(h, 0) first");
     h->opts = *opts;
     return SDDP_OK;
@@ -610,8 +645,7 @@ int sddp_set_options(sddp_handle* h, const sddp_options* opts) {
 
 int sddp_set_stream(sddp_handle* h, void* s) {
     if (!h) return SDDP_ERR_ARG;
-    if (h->stream) (void)hipStreamSynchronize(h->stream);      // uploads enqueued from the pinned ring belong to the old stream
-    h->up_off = 0;
+    if (h->stream) (void)quiesce(h);      // uploads enqueued from the pinned ring belong to the old stream
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     h->stream = reinterpret_cast<hipStream_t>(s);
     h->own_stream = false;
@@ -622,21 +656,26 @@ int sddp_set_stream(sddp_handle* h, void* s) {
 // stream (a copy from pageable memory would have to be waited for before the caller may reuse its buffer).  The ring is reused
 // from the start after a stream synchronisation; large uploads go directly and are waited for.
 static int upload(sddp_handle* h, void* dst, const void* src, size_t bytes) {
-    if (bytes <= kPinLimit / 4 && staging(h, h->up_pin, kPinLimit)) {
+    if (bytes <= kPinLimit / 4 && staging(h, h->stage.up_pin, kPinLimit)) {
         const size_t need = (bytes + 63) & ~size_t(63);
-        if (h->up_off + need > kPinLimit) {
+        if (h->stage.up_off + need > kPinLimit) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            h->up_off = 0;
+            h->stage.up_off = 0;
         }
-        std::memcpy(h->up_pin + h->up_off, src, bytes);
-        HIP_TRY(h, hipMemcpyAsync(dst, h->up_pin + h->up_off, bytes, hipMemcpyHostToDevice, h->stream));
-        h->up_off += need;
+        std::memcpy(h->stage.up_pin + h->stage.up_off, src, bytes);
+        HIP_TRY(h, hipMemcpyAsync(dst, h->stage.up_pin + h->stage.up_off, bytes, hipMemcpyHostToDevice, h->stream));
+        h->stage.up_off += need;
         return SDDP_OK;
     }
     HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->up_off = 0;
+    h->stage.up_off = 0;
     return SDDP_OK;
+}
+// the counterpart: device->host, waited for (sddp_synchronize: the timing events of the launches in front are read as well)
+static int download(sddp_handle* h, void* dst, const void* src, size_t bytes) {
+    HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
 }
 
 // ---- host-pointer setters -------------------------------------------------------------------------------------------
@@ -715,50 +754,32 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     if (on && !h->ops->solve[kSolveResume].launch) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: this build has no kernels of that solve variant");
     if (on && h->opts.second_order == 2)      // (lip30, whose one build takes the option: the resumable kernels are not tested with it)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_resume: resumable solves exist for the plain builds only (no second_order = 2)");
-    if ((on != 0) == (h->carry != nullptr)) return SDDP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still use the buffers
-    h->up_off = 0;
-    release(h, h->carry);
-    release(h, h->resumable);
-    h->budget_us = 0.0;      // the time budget rides on the resumable kernels too: disarmed
-    h->budget_min_iters = 0;
-    if (!on) {   // the iteration log rides on the resumable kernels: it goes with them
-        release(h, h->ilog);
-        release(h, h->ilog_n);
-        h->ilog_rows = 0;
-        return SDDP_OK;
-    }
-    // flags [3][B] | the unfinished count | (padding) | the time budget's clock words [2] uint64
-    const size_t flag_bytes = ResumeArgs::clock_offset(h->B) * sizeof(int) + 2 * sizeof(unsigned long long);
-    int* flags = nullptr;
-    double* carry = nullptr;
-    hipError_t e = acquire(h, carry, size_t(h->B) * h->N * h->d.nx * sizeof(double));
-    if (e == hipSuccess) e = acquire(h, flags, flag_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, flag_bytes, h->stream);
-    if (e != hipSuccess) {      // all or nothing
-        (void)hipGetLastError();
-        release(h, carry); release(h, flags);
-        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_resume: out of device memory");
-    }
-    h->carry = carry;
-    h->resumable = flags;
+    if ((on != 0) == h->resume.on()) return SDDP_OK;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still use the buffers
+    drop_resume(h);
+    if (!on) return SDDP_OK;
+    // carry; flags [3][B] | the unfinished count | (padding) | the time budget's clock words [2] uint64
+    GroupBuf g[] = {{size_t(h->B) * h->N * h->d.nx * sizeof(double)},
+                    {ResumeArgs::clock_offset(h->B) * sizeof(int) + 2 * sizeof(unsigned long long), 0x00}};
+    if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_resume: out of device memory");
+    h->resume.carry = g[0]; h->resume.resumable = g[1];
     return SDDP_OK;
 }
 
 int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first, int count) {
     int rc = check_ready(h);
     if (rc != SDDP_OK) return rc;
-    if (!h->carry) return fail(h, SDDP_ERR_ARG, "sddp_continue: sddp_enable_resume has not been called (plain builds only: no barrier, no "
+    if (!h->resume.on()) return fail(h, SDDP_ERR_ARG, "sddp_continue: sddp_enable_resume has not been called (plain builds only: no barrier, no "
                                                 "second_order = 2, no user rows)");
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_continue: no solve has run on this handle");
     if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
-    if (h->cls)   // which instances this launch resumes: the class statistics count those that it also finishes
-        HIP_TRY(h, hipMemsetAsync(h->resumable + 2 * size_t(h->B) + first, 0, size_t(count) * sizeof(int), h->stream));
-    h->continuing = true;
+    if (h->classes.on())   // which instances this launch resumes: the class statistics count those that it also finishes
+        HIP_TRY(h, hipMemsetAsync(h->resume.resumable + 2 * size_t(h->B) + first, 0, size_t(count) * sizeof(int), h->stream));
+    h->resume.continuing = true;
     rc = launch_solve_sequence(h, a, first, count);
-    h->continuing = false;
+    h->resume.continuing = false;
     if (rc == SDDP_OK) h->last_params = d_params;
     return rc;
 }
@@ -771,20 +792,18 @@ int sddp_continue_device(sddp_handle* h, const double* d_params) {
 int sddp_continue_resident(sddp_handle* h) {
     if (!h) return SDDP_ERR_ARG;
     if (!h->have_params && h->last_params != h->P)      // resident: sddp_set_params, or the tensor sddp_solve uploaded
-        return fail(h, SDDP_ERR_ARG, h->carry ? "sddp_continue_resident: no resident parameters (sddp_set_params or sddp_solve)"
+        return fail(h, SDDP_ERR_ARG, h->resume.on() ? "sddp_continue_resident: no resident parameters (sddp_set_params or sddp_solve)"
                                               : "sddp_continue: sddp_enable_resume has not been called");
     return sddp_continue_range_device(h, h->P, 0, h->B);
 }
 
 int sddp_unfinished_count(sddp_handle* h, int first, int count, int* n) {
     if (!h || !n) return SDDP_ERR_ARG;
-    if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_unfinished_count: sddp_enable_resume has not been called");
+    if (!h->resume.on()) return fail(h, SDDP_ERR_ARG, "sddp_unfinished_count: sddp_enable_resume has not been called");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    int* d_n = h->resumable + 3 * size_t(h->B);
-    const int rc = launch(h, unfinished_count_kernel, 1, 256, 0, first, count, (const int*)h->resumable, d_n);
-    if (rc != SDDP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(n, d_n, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
+    int* d_n = h->resume.resumable + 3 * size_t(h->B);
+    const int rc = launch(h, unfinished_count_kernel, 1, 256, 0, first, count, (const int*)h->resume.resumable, d_n);
+    return rc == SDDP_OK ? download(h, n, d_n, sizeof(int)) : rc;
 }
 
 // ---- time budget ----------------------------------------------------------------------------------------------------------
@@ -792,18 +811,18 @@ int sddp_set_time_budget(sddp_handle* h, double budget_us, int min_iters) {
     if (!h) return SDDP_ERR_ARG;
     if (!std::isfinite(budget_us) || budget_us < 0.0) return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: budget_us must be finite and >= 0 (0: off)");
     if (min_iters < 0) return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: min_iters must be >= 0");
-    if (budget_us > 0.0 && !h->carry)
+    if (budget_us > 0.0 && !h->resume.on())
         return fail(h, SDDP_ERR_ARG, "sddp_set_time_budget: call sddp_enable_resume first (the budget is kept by the resumable kernels; plain "
                                      "builds only)");
-    h->budget_us = budget_us;      // host state only: it takes effect with the next launch sequence
-    h->budget_min_iters = budget_us > 0.0 ? min_iters : 0;
+    h->resume.budget_us = budget_us;      // host state only: it takes effect with the next launch sequence
+    h->resume.budget_min_iters = budget_us > 0.0 ? min_iters : 0;
     return SDDP_OK;
 }
 
 int sddp_time_budget_info(sddp_handle* h, double* budget_us, int* min_iters) {
     if (!h) return SDDP_ERR_ARG;
-    if (budget_us) *budget_us = h->budget_us;
-    if (min_iters) *min_iters = h->budget_min_iters;
+    if (budget_us) *budget_us = h->resume.budget_us;
+    if (min_iters) *min_iters = h->resume.budget_min_iters;
     return SDDP_OK;
 }
 
@@ -815,50 +834,36 @@ int sddp_enable_iteration_log(sddp_handle* h, int rows) {
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: the iteration log exists for the plain builds only (no user rows, no barrier, "
                                      "no second_order = 2, no user build), like sddp_enable_resume");
     if (rows > 0 && !h->ops->solve[kSolveLog].launch) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: this build has no kernels of that solve variant");
-    if (rows > 0 && !h->carry)
+    if (rows > 0 && !h->resume.on())
         return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log: call sddp_enable_resume first (the log is kept by the resumable kernels; plain "
                                      "builds only)");
-    if (rows == h->ilog_rows) return SDDP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still write the buffers
-    h->up_off = 0;
-    release(h, h->ilog);
-    release(h, h->ilog_n);
-    h->ilog_rows = 0;
+    if (rows == h->log.ilog_rows) return SDDP_OK;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still write the buffers
+    drop_log(h);
     if (rows == 0) return SDDP_OK;
-    double* log = nullptr;
-    int* n = nullptr;
-    const size_t log_bytes = size_t(h->B) * rows * kLogWords * sizeof(double);
-    hipError_t e = acquire(h, log, log_bytes);
-    if (e == hipSuccess) e = acquire(h, n, size_t(h->B) * sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(log, 0, log_bytes, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(n, 0, size_t(h->B) * sizeof(int), h->stream);
-    if (e != hipSuccess) {      // all or nothing
-        (void)hipGetLastError();
-        release(h, log); release(h, n);
-        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_iteration_log: out of device memory");
-    }
-    h->ilog = log;
-    h->ilog_n = n;
-    h->ilog_rows = rows;
+    GroupBuf g[] = {{size_t(h->B) * rows * kLogWords * sizeof(double), 0x00}, {size_t(h->B) * sizeof(int), 0x00}};
+    if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_iteration_log: out of device memory");
+    h->log = {g[0], g[1], rows};
     return SDDP_OK;
 }
 
 int sddp_iteration_log_info(sddp_handle* h, int* rows, int* words) {
     if (!h) return SDDP_ERR_ARG;
-    if (rows) *rows = h->ilog_rows;
+    if (rows) *rows = h->log.ilog_rows;
     if (words) *words = kLogWords;
     return SDDP_OK;
 }
 
 int sddp_fetch_iteration_log(sddp_handle* h, int first, int count, double* out, int* n_out) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->ilog) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
+    if (!h->log.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
     if (!out && !n_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    const size_t w = size_t(h->ilog_rows) * kLogWords;
-    if (out) HIP_TRY(h, hipMemcpyAsync(out, h->ilog + size_t(first) * w, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (n_out) HIP_TRY(h, hipMemcpyAsync(n_out, h->ilog_n + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
+    const size_t w = size_t(h->log.ilog_rows) * kLogWords;
+    const double* rec = h->log.ilog + size_t(first) * w;
+    if (!n_out) return download(h, out, rec, size_t(count) * w * sizeof(double));
+    if (out) HIP_TRY(h, hipMemcpyAsync(out, rec, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));      // one wait for both
+    return download(h, n_out, h->log.ilog_n + first, size_t(count) * sizeof(int));
 }
 
 int sddp_queue_info(sddp_handle* h, int* slots, int* last_grid, int* last_queued) {
@@ -905,9 +910,7 @@ int sddp_debug_poison_lds(sddp_handle* h) {
 
 int sddp_synchronize(sddp_handle* h) {
     if (!h) return SDDP_ERR_ARG;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->tick_unsynced = 0;
-    h->up_off = 0;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;
     for (size_t i = 0; i < h->pending; ++i) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]) == hipSuccess) {
@@ -925,7 +928,7 @@ int sddp_synchronize(sddp_handle* h) {
 static int fetch_results(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats) {
     if (!x_out || !u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     const size_t bx = h->n_x() * sizeof(double), bu = h->n_u() * sizeof(double), bs = size_t(h->B) * sizeof(sddp_stats);
-    if (char* st = staging(h, h->pinned, bx + bu + bs)) {
+    if (char* st = staging(h, h->stage.pinned, bx + bu + bs)) {
         HIP_TRY(h, hipMemcpyAsync(st, h->xs, bx + bu + (stats ? bs : 0), hipMemcpyDeviceToHost, h->stream));   // xs | us | stats are contiguous
         const int rc = sddp_synchronize(h);
         if (rc != SDDP_OK) return rc;
@@ -972,17 +975,17 @@ int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
     if (!h->have_params) return fail(h, SDDP_ERR_ARG, "sddp_set_params has not been called");
     if (!h->have_xws || !h->have_uws) return fail(h, SDDP_ERR_ARG, "sddp_advance needs a previous solution or warm start");
     if ((h->N + 1) * std::max(h->d.np, h->d.nx) > kAdvanceWords) return fail(h, SDDP_ERR_ARG, "horizon too long for sddp_advance");
-    if (!h->tick_in) ACQUIRE_TRY(h, h->tick_in, size_t(h->B) * (h->d.np + h->d.nx) * sizeof(double));
-    double* d_pl = h->tick_in;
-    double* d_x0 = h->tick_in + size_t(h->B) * h->d.np;
+    if (!h->stage.tick_in) ACQUIRE_TRY(h, h->stage.tick_in, size_t(h->B) * (h->d.np + h->d.nx) * sizeof(double));
+    double* d_pl = h->stage.tick_in;
+    double* d_x0 = h->stage.tick_in + size_t(h->B) * h->d.np;
     const size_t bp = size_t(h->B) * h->d.np * sizeof(double), bx0 = size_t(h->B) * h->d.nx * sizeof(double);
-    if (staging(h, h->tick_pin, bp + bx0, 2)) {   // one enqueued upload from pinned memory; two alternating images, so that the call need not wait for it
-        if (h->tick_unsynced >= 2) {   // both images may still be read by earlier uploads: wait (a solve in between does it anyway)
+    if (staging(h, h->stage.tick_pin, bp + bx0, 2)) {   // one enqueued upload from pinned memory; two alternating images, so that the call need not wait for it
+        if (h->stage.tick_unsynced >= 2) {   // both images may still be read by earlier uploads: wait (a solve in between does it anyway)
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            h->tick_unsynced = 0;
+            h->stage.tick_unsynced = 0;
         }
-        ++h->tick_unsynced;
-        char* hp = h->tick_pin + (h->tick_flip ^= 1) * (bp + bx0);
+        ++h->stage.tick_unsynced;
+        char* hp = h->stage.tick_pin + (h->stage.tick_flip ^= 1) * (bp + bx0);
         std::memcpy(hp, p_last, bp);
         std::memcpy(hp + bp, x0, bx0);
         HIP_TRY(h, hipMemcpyAsync(d_pl, hp, bp + bx0, hipMemcpyHostToDevice, h->stream));
@@ -1016,19 +1019,18 @@ int sddp_solve_resident_first(sddp_handle* h, double* u0_out, double* x1_out, do
     if (rc != SDDP_OK) return rc;
     const int w = h->d.nu + h->d.nx + 3;
     const size_t bytes = size_t(h->B) * w * sizeof(double);
-    if (!h->first_dev) {      // with its pinned host image, of any size (one copy per tick) and asked for this once
-        ACQUIRE_TRY(h, h->first_dev, bytes);
-        staging(h, h->first_pin, bytes, 1, SIZE_MAX);
+    if (!h->stage.first_dev) {      // with its pinned host image, of any size (one copy per tick) and asked for this once
+        ACQUIRE_TRY(h, h->stage.first_dev, bytes);
+        staging(h, h->stage.first_pin, bytes, 1, SIZE_MAX);
     }
-    double* host = h->first_pin;
+    double* host = h->stage.first_pin;
     const int grid = int(std::min<size_t>((size_t(h->B) * w + 255) / 256, 1024));
-    rc = launch(h, first_knot_kernel, grid, 256, 0, h->N, h->B, h->d.nx, h->d.nu, h->xs, h->us, h->stats, h->first_dev);
+    rc = launch(h, first_knot_kernel, grid, 256, 0, h->N, h->B, h->d.nx, h->d.nu, h->xs, h->us, h->stats, h->stage.first_dev);
     if (rc != SDDP_OK) return rc;
     host_buf tmp(host ? 0 : bytes);
     if (!tmp.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
     if (!host) host = tmp.as<double>();
-    HIP_TRY(h, hipMemcpyAsync(host, h->first_dev, bytes, hipMemcpyDeviceToHost, h->stream));
-    rc = sddp_synchronize(h);
+    rc = download(h, host, h->stage.first_dev, bytes);
     if (rc != SDDP_OK) return rc;
     for (int b = 0; b < h->B; ++b) {
         const double* r = host + size_t(b) * w;
@@ -1045,25 +1047,19 @@ int sddp_solve_resident_first(sddp_handle* h, double* u0_out, double* x1_out, do
 // class labels of the instances (queue_order = 3).  The class table is allocated on the first call; n_classes is fixed then.
 static int class_buffers(sddp_handle* h, int n_classes) {
     if (n_classes < 1 || n_classes > (1 << 20)) return fail(h, SDDP_ERR_ARG, "n_classes must be 1 .. 2^20");
-    if (h->cls) {
-        if (n_classes != h->n_cls) return fail(h, SDDP_ERR_ARG, "n_classes differs from the first call's");
+    if (h->classes.on()) {
+        if (n_classes != h->classes.n_cls) return fail(h, SDDP_ERR_ARG, "n_classes differs from the first call's");
         return SDDP_OK;
     }
-    hipError_t e = acquire(h, h->cls, size_t(h->B) * sizeof(int));
-    if (e == hipSuccess) e = acquire(h, h->cls_stat, size_t(n_classes) * 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(h->cls, 0xFF, size_t(h->B) * sizeof(int), h->stream);       // -1: unlabelled
-    if (e == hipSuccess) e = hipMemsetAsync(h->cls_stat, 0, size_t(n_classes) * 2 * sizeof(unsigned long long), h->stream);
-    if (e != hipSuccess) {      // all or nothing
-        release(h, h->cls); release(h, h->cls_stat);
-        return fail(h, SDDP_ERR_HIP, std::string("class buffers: ") + hipGetErrorString(e));
-    }
-    h->n_cls = n_classes;
+    GroupBuf g[] = {{size_t(h->B) * sizeof(int), 0xFF}, {size_t(n_classes) * 2 * sizeof(unsigned long long), 0x00}};      // -1: unlabelled
+    if (const hipError_t e = acquire_group(h, g); e != hipSuccess) return fail(h, SDDP_ERR_HIP, std::string("class buffers: ") + hipGetErrorString(e));
+    h->classes.cls = g[0]; h->classes.cls_stat = g[1]; h->classes.n_cls = n_classes;
     return SDDP_OK;
 }
 
 // the labels are the handle's own while auto classes are on (sddp_enable_auto_classes)
 static int check_caller_labels(sddp_handle* h) {
-    if (h->auto_cls) return fail(h, SDDP_ERR_ARG, "the handle labels its instances itself (sddp_enable_auto_classes): call sddp_enable_auto_classes(h, 0) first");
+    if (h->classes.auto_cls) return fail(h, SDDP_ERR_ARG, "the handle labels its instances itself (sddp_enable_auto_classes): call sddp_enable_auto_classes(h, 0) first");
     return SDDP_OK;
 }
 
@@ -1072,7 +1068,7 @@ int sddp_set_instance_classes(sddp_handle* h, const int* classes, int n_classes)
     if (check_caller_labels(h) != SDDP_OK) return SDDP_ERR_ARG;
     int rc = class_buffers(h, n_classes);
     if (rc != SDDP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->cls, classes, size_t(h->B) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->classes.cls, classes, size_t(h->B) * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SDDP_OK;
 }
@@ -1083,15 +1079,15 @@ int sddp_set_instance_classes_range_device(sddp_handle* h, int first, int count,
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     int rc = class_buffers(h, n_classes);
     if (rc != SDDP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->cls + first, d_classes, size_t(count) * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->classes.cls + first, d_classes, size_t(count) * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
     return SDDP_OK;
 }
 
 int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* solves) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->cls || cls < 0 || cls >= h->n_cls) return fail(h, SDDP_ERR_ARG, "no such class");
+    if (!h->classes.on() || cls < 0 || cls >= h->classes.n_cls) return fail(h, SDDP_ERR_ARG, "no such class");
     unsigned long long st[2];
-    HIP_TRY(h, hipMemcpyAsync(st, h->cls_stat + 2 * cls, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(st, h->classes.cls_stat + 2 * cls, sizeof(st), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (solves) *solves = (long long)st[1];
     if (mean_iters) *mean_iters = st[1] ? double(st[0]) / double(st[1]) : 0.0;
@@ -1101,37 +1097,36 @@ int sddp_class_history(sddp_handle* h, int cls, double* mean_iters, long long* s
 // ---- auto classes: the handle labels its instances itself; the history leaves and enters a handle ---------------------------
 int sddp_enable_auto_classes(sddp_handle* h, int on) {
     if (!h) return SDDP_ERR_ARG;
-    if (!on) { h->auto_cls = false; return SDDP_OK; }      // labels and history stay
+    if (!on) { h->classes.auto_cls = false; return SDDP_OK; }      // labels and history stay
     const long long n = 36LL * (h->N + 2);                 // 4 stance patterns x (N + 2) values of first_change x 3 x 3 commands
-    if (h->cls && h->n_cls != n)
+    if (h->classes.on() && h->classes.n_cls != n)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_auto_classes: the handle has a class table with another n_classes (caller labels were set "
                                      "first); the library's labels need 36 (N + 2)");
     if (n > (1 << 20)) return fail(h, SDDP_ERR_ARG, "sddp_enable_auto_classes: horizon too long (36 (N + 2) classes must be <= 2^20)");
     const int rc = class_buffers(h, int(n));
     if (rc != SDDP_OK) return rc;
-    h->auto_cls = true;
+    h->classes.auto_cls = true;
     return SDDP_OK;
 }
 
 int sddp_auto_classes_info(sddp_handle* h, int* on, int* n_classes) {
     if (!h) return SDDP_ERR_ARG;
-    if (on) *on = h->auto_cls ? 1 : 0;
-    if (n_classes) *n_classes = h->cls ? h->n_cls : 0;
+    if (on) *on = h->classes.auto_cls ? 1 : 0;
+    if (n_classes) *n_classes = h->classes.on() ? h->classes.n_cls : 0;
     return SDDP_OK;
 }
 
 int sddp_fetch_instance_classes(sddp_handle* h, int first, int count, int* out) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+    if (!h->classes.on()) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
     if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    HIP_TRY(h, hipMemcpyAsync(out, h->cls + first, size_t(count) * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
+    return download(h, out, h->classes.cls + first, size_t(count) * sizeof(int));
 }
 
 static int check_class_range(sddp_handle* h, int first_class, int count) {
-    if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
-    if (first_class < 0 || count < 1 || first_class > h->n_cls - count) return fail(h, SDDP_ERR_ARG, "class range outside the class table");
+    if (!h->classes.on()) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+    if (first_class < 0 || count < 1 || first_class > h->classes.n_cls - count) return fail(h, SDDP_ERR_ARG, "class range outside the class table");
     return SDDP_OK;
 }
 
@@ -1139,22 +1134,20 @@ int sddp_get_class_stats(sddp_handle* h, int first_class, int count, unsigned lo
     if (!h) return SDDP_ERR_ARG;
     if (check_class_range(h, first_class, count) != SDDP_OK) return SDDP_ERR_ARG;
     if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    HIP_TRY(h, hipMemcpyAsync(out, h->cls_stat + 2 * size_t(first_class), size_t(count) * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              h->stream));
-    return sddp_synchronize(h);
+    return download(h, out, h->classes.cls_stat + 2 * size_t(first_class), size_t(count) * 2 * sizeof(unsigned long long));
 }
 
 int sddp_add_class_stats(sddp_handle* h, int first_class, int count, const unsigned long long* in) {
     if (!h) return SDDP_ERR_ARG;
     if (check_class_range(h, first_class, count) != SDDP_OK) return SDDP_ERR_ARG;
     if (!in) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (!h->cls_in) ACQUIRE_TRY(h, h->cls_in, size_t(h->n_cls) * 2 * sizeof(unsigned long long));
+    if (!h->classes.cls_in) ACQUIRE_TRY(h, h->classes.cls_in, size_t(h->classes.n_cls) * 2 * sizeof(unsigned long long));
     // staged on the stream (the pinned ring for a small table), then added there: ordered with the launches that read and update the table
-    unsigned long long* d_in = h->cls_in + 2 * size_t(first_class);
+    unsigned long long* d_in = h->classes.cls_in + 2 * size_t(first_class);
     const int rc = upload(h, d_in, in, size_t(count) * 2 * sizeof(unsigned long long));
     if (rc != SDDP_OK) return rc;
     return launch(h, class_stats_add_kernel, (2 * count + 255) / 256, 256, 0, 2 * count, (const unsigned long long*)d_in,
-                  h->cls_stat + 2 * size_t(first_class));
+                  h->classes.cls_stat + 2 * size_t(first_class));
 }
 
 // ---- heterogeneous fleets: per-instance constants ---------------------------------------------------------------------------
@@ -1172,44 +1165,40 @@ int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_mo
             return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: friction_barrier_weight and bound_barrier_weight must be 0 in every entry");
     }
     const size_t B = size_t(h->B), n = size_t(count);
-    host_buf rows(std::max(h->ctab ? n : B, n) * sizeof(DevConsts));
+    host_buf rows(std::max(h->table.on() ? n : B, n) * sizeof(DevConsts));
     if (!rows.p) return fail(h, SDDP_ERR_NOMEM, "out of host memory");
     DevConsts* r = rows.as<DevConsts>();
-    if (!h->ctab) {   // first call: every row starts as the handle's own constants
-        DevConsts* t = nullptr;
-        if (acquire(h, t, B * sizeof(DevConsts)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(h, SDDP_ERR_NOMEM, "sddp_set_instance_consts: out of device memory");
-        }
+    if (!h->table.on()) {   // first call: every row starts as the handle's own constants
+        GroupBuf g[] = {{B * sizeof(DevConsts)}};
+        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_set_instance_consts: out of device memory");
         for (size_t b = 0; b < B; ++b) r[b] = h->dc;
-        const int rc = upload(h, t, r, B * sizeof(DevConsts));
-        if (rc != SDDP_OK) { release(h, t); return rc; }
-        h->ctab = t;
+        const int rc = upload(h, g[0].p, r, B * sizeof(DevConsts));
+        if (rc != SDDP_OK) { release(h, g[0].p); return rc; }
+        h->table.ctab = g[0];
     }
     for (size_t i = 0; i < n; ++i) r[i] = make_dev_consts(consts[i]);
-    const int rc = upload(h, h->ctab + first, r, n * sizeof(DevConsts));
+    const int rc = upload(h, h->table.ctab + first, r, n * sizeof(DevConsts));
     return rc == SDDP_OK ? invalidate_resume(h, first, count) : rc;
 }
 
 int sddp_clear_instance_consts(sddp_handle* h) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->ctab) return SDDP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still read the table
-    h->up_off = 0;
-    release(h, h->ctab);
+    if (!h->table.on()) return SDDP_OK;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still read the table
+    drop_table(h);
     return invalidate_resume(h, 0, h->B);
 }
 
 int sddp_instance_consts_active(sddp_handle* h, int* on) {
     if (!h || !on) return SDDP_ERR_ARG;
-    *on = h->ctab ? 1 : 0;
+    *on = h->table.on() ? 1 : 0;
     return SDDP_OK;
 }
 
 int sddp_record_words(sddp_handle* h, int mode, int* words) {
     if (!h || !words) return SDDP_ERR_ARG;
     if (mode < 0 || mode > 2) return fail(h, SDDP_ERR_ARG, "record mode must be 0 (whole plan), 1 (first knot) or 2 (first knot and its gains)");
-    if (mode == 2 && !h->policy) return fail(h, SDDP_ERR_ARG, "record mode 2 carries the first knot's gains: call sddp_enable_policy first");
+    if (mode == 2 && !h->pol.on()) return fail(h, SDDP_ERR_ARG, "record mode 2 carries the first knot's gains: call sddp_enable_policy first");
     *words = mode == 0 ? (h->N + 1) * h->d.nx + h->N * h->d.nu + 2 : h->d.nu + h->d.nx + 2 + (mode == 2 ? h->d.nu * (h->d.nx + 1) : 0);
     return SDDP_OK;
 }
@@ -1221,8 +1210,8 @@ int sddp_pack_records_device(sddp_handle* h, int first, int count, int mode, dou
     if (rc != SDDP_OK) return rc;
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const int grid = int(std::min<size_t>((size_t(count) * w + 255) / 256, 2048));
-    return launch(h, pack_records_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, mode, h->xs, h->us, h->stats, d_out, h->policy,
-                  h->policy ? h->policy_words() : 0);
+    return launch(h, pack_records_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, mode, h->xs, h->us, h->stats, d_out, h->pol.policy,
+                  h->pol.on() ? h->policy_words() : 0);
 }
 
 // ---- policy export ------------------------------------------------------------------------------------------------------
@@ -1231,58 +1220,52 @@ int sddp_enable_policy(sddp_handle* h, int knots) {
     if (knots < 0 || knots > h->N) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy: knots must be in 1..N (0 frees the buffer)");
     if (knots > 0 && !h->ops->launch_policy)
         return fail(h, SDDP_ERR_ARG, "sddp_enable_policy: no policy kernel for this build (barrier and second_order = 2 builds have none)");
-    if (knots == h->policy_knots) return SDDP_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // a launch in flight may still write the old buffer
-    release(h, h->policy);
-    h->policy_knots = 0;
+    if (knots == h->pol.policy_knots) return SDDP_OK;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still write the old buffer
+    drop_policy(h);
     if (knots == 0) return SDDP_OK;
-    const size_t bytes = size_t(h->B) * (size_t(knots) * h->d.nu * (h->d.nx + 1) + 4) * sizeof(double);
-    if (acquire(h, h->policy, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, SDDP_ERR_NOMEM, "sddp_enable_policy: out of device memory");
-    }
-    h->policy_knots = knots;
-    HIP_TRY(h, hipMemsetAsync(h->policy, 0, bytes, h->stream));      // ok = 0 until a policy launch covered the instance
+    GroupBuf g[] = {{size_t(h->B) * (size_t(knots) * h->d.nu * (h->d.nx + 1) + 4) * sizeof(double), 0x00}};      // ok = 0 until a policy launch covered the instance
+    if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_policy: out of device memory");
+    h->pol = {g[0], knots};
     return SDDP_OK;
 }
 
 int sddp_policy_words(sddp_handle* h, int* words, int* knots) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (words) *words = h->policy_words();
-    if (knots) *knots = h->policy_knots;
+    if (knots) *knots = h->pol.policy_knots;
     return SDDP_OK;
 }
 
 int sddp_policy_range_device(sddp_handle* h, int first, int count) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_range_device: no solve has run on this handle");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, h->last_params);
-    return h->ops->launch_policy(h, a, first, count, h->policy, h->policy_knots);
+    return h->ops->launch_policy(h, a, first, count, h->pol.policy, h->pol.policy_knots);
 }
 
 int sddp_fetch_policy(sddp_handle* h, int first, int count, double* out) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     const size_t w = size_t(h->policy_words());
-    HIP_TRY(h, hipMemcpyAsync(out, h->policy + size_t(first) * w, size_t(count) * w * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
+    return download(h, out, h->pol.policy + size_t(first) * w, size_t(count) * w * sizeof(double));
 }
 
 int sddp_apply_policy_knot_device(sddp_handle* h, int first, int count, int knot, const double* d_x_meas, double* d_u_out) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!d_x_meas || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (knot < 0 || knot >= h->policy_knots)
-        return fail(h, SDDP_ERR_ARG, "sddp_apply_policy_knot_device: knot must be a kept knot, 0 <= knot < " + std::to_string(h->policy_knots) +
+    if (knot < 0 || knot >= h->pol.policy_knots)
+        return fail(h, SDDP_ERR_ARG, "sddp_apply_policy_knot_device: knot must be a kept knot, 0 <= knot < " + std::to_string(h->pol.policy_knots) +
                                          " (the knots of sddp_enable_policy)");
     const int grid = int(std::min<size_t>((size_t(count) * h->d.nu + 255) / 256, 2048));
-    return launch(h, apply_policy_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, knot, h->xs, h->us, h->policy, h->policy_words(),
+    return launch(h, apply_policy_kernel, grid, 256, 0, h->N, h->d.nx, h->d.nu, first, count, knot, h->xs, h->us, h->pol.policy, h->policy_words(),
                   d_x_meas, d_u_out);
 }
 
@@ -1293,11 +1276,11 @@ int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double*
 int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
                                double* d_u_out, double* d_cost_out) {
     if (!h) return SDDP_ERR_ARG;
-    if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: no solve has run on this handle");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (start < 0 || steps < 1 || start > h->policy_knots - steps)
-        return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->policy_knots) +
+    if (start < 0 || steps < 1 || start > h->pol.policy_knots - steps)
+        return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->pol.policy_knots) +
                                          " (the knots of sddp_enable_policy)");
     if (!d_x_meas || !d_x_out || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     return h->ops->launch_policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
@@ -1328,10 +1311,7 @@ int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient
     double* d_out = nullptr;
     HIP_TRY(h, hipMalloc(&d_out, bytes));
     int rc = sddp_audit_range_device(h, first, count, 0, h->N, nullptr, nullptr, friction_coefficient, d_out);
-    if (rc == SDDP_OK) {
-        const hipError_t e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
-        rc = e == hipSuccess ? sddp_synchronize(h) : fail(h, SDDP_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-    }
+    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
     (void)hipFree(d_out);
     return rc;
 }
@@ -1341,18 +1321,17 @@ int sddp_model_step(sddp_handle* h, const double* x, const double* u, const doub
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");
     const size_t B = size_t(h->B), nx = h->d.nx, nu = h->d.nu, np = h->d.np, D = sizeof(double);
     const size_t words = B * (2 * nx + nu + np);
-    if (!h->step_buf) ACQUIRE_TRY(h, h->step_buf, words * D);
-    double *dx = h->step_buf, *du = dx + B * nx, *dp = du + B * nu, *dxn = dp + B * np;
+    if (!h->stage.step_buf) ACQUIRE_TRY(h, h->stage.step_buf, words * D);
+    double *dx = h->stage.step_buf, *du = dx + B * nx, *dp = du + B * nu, *dxn = dp + B * np;
     int rc = SDDP_OK;
-    if (double* hp = staging(h, h->step_pin, words * D)) {   // x | u | p packed in pinned memory: one enqueued upload and download, one wait
+    if (double* hp = staging(h, h->stage.step_pin, words * D)) {   // x | u | p packed in pinned memory: one enqueued upload and download, one wait
         std::memcpy(hp, x, B * nx * D);
         std::memcpy(hp + B * nx, u, B * nu * D);
         std::memcpy(hp + B * (nx + nu), p, B * np * D);
         HIP_TRY(h, hipMemcpyAsync(dx, hp, B * (nx + nu + np) * D, hipMemcpyHostToDevice, h->stream));
         rc = h->ops->launch_model_step(h, k, dx, du, dp, dxn);
         if (rc != SDDP_OK) return rc;
-        HIP_TRY(h, hipMemcpyAsync(hp + B * (nx + nu + np), dxn, B * nx * D, hipMemcpyDeviceToHost, h->stream));
-        rc = sddp_synchronize(h);
+        rc = download(h, hp + B * (nx + nu + np), dxn, B * nx * D);
         if (rc == SDDP_OK) std::memcpy(x_next, hp + B * (nx + nu + np), B * nx * D);
         return rc;
     }
@@ -1361,8 +1340,7 @@ int sddp_model_step(sddp_handle* h, const double* x, const double* u, const doub
     HIP_TRY(h, hipMemcpyAsync(dp, p, B * np * D, hipMemcpyHostToDevice, h->stream));
     rc = h->ops->launch_model_step(h, k, dx, du, dp, dxn);
     if (rc != SDDP_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(x_next, dxn, B * nx * D, hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
+    return download(h, x_next, dxn, B * nx * D);
 }
 
 int sddp_is_converged(sddp_handle* h, int* flags) {
@@ -1397,20 +1375,20 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
             if (h->last_grid < 1) return fail(h, SDDP_ERR_ARG, "no solve launch yet");
             *ptr = h->hist + ((h->B + 1) & ~1); n = (long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;
         case SDDP_BUF_POLICY:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
-            if (!h->policy) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
-            *ptr = h->policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
+            if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+            *ptr = h->pol.policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
         case SDDP_BUF_LOG:   // the iteration log [B][rows][16] and its record counts [B] of sddp_enable_iteration_log
         case SDDP_BUF_LOG_COUNTS:
-            if (!h->ilog) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
-            if (which == SDDP_BUF_LOG) { *ptr = h->ilog; n = (long long)(size_t(h->B) * h->ilog_rows * kLogWords * sizeof(double)); }
-            else { *ptr = h->ilog_n; n = (long long)(size_t(h->B) * sizeof(int)); }
+            if (!h->log.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");
+            if (which == SDDP_BUF_LOG) { *ptr = h->log.ilog; n = (long long)(size_t(h->B) * h->log.ilog_rows * kLogWords * sizeof(double)); }
+            else { *ptr = h->log.ilog_n; n = (long long)(size_t(h->B) * sizeof(int)); }
             break;
         case SDDP_BUF_CLOCK:  // the time budget's clock words: start | deadline of the last budgeted launch sequence (zeros before the first)
-            if (!h->resumable) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume has not been called");
+            if (!h->resume.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_resume has not been called");
             *ptr = clock_words(h); n = (long long)(2 * sizeof(unsigned long long)); break;
         case SDDP_BUF_CLASSES:  // the class labels [B] (int; -1: unlabelled): the caller's, or the handle's own under sddp_enable_auto_classes
-            if (!h->cls) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
-            *ptr = h->cls; n = (long long)(size_t(h->B) * sizeof(int)); break;
+            if (!h->classes.on()) return fail(h, SDDP_ERR_ARG, "no class table (sddp_enable_auto_classes or sddp_set_instance_classes)");
+            *ptr = h->classes.cls; n = (long long)(size_t(h->B) * sizeof(int)); break;
         default: return fail(h, SDDP_ERR_ARG, "unknown buffer id");
     }
     if (bytes) *bytes = n;

@@ -70,7 +70,7 @@ struct ModelOps {
         int (*launch)(sddp_handle*, const SolveChoice&, int grid, const SolveArgs&) = nullptr;
     };
     SolveOps solve[kSolveVariants];
-    // the queue_order 2 / 3 key pre-pass: the initial cost of every instance of the launch, into h->qkey / h->order_in (main unit)
+    // the queue_order 2 / 3 key pre-pass: the initial cost of every instance of the launch, into h->cold.qkey / h->cold.order_in (main unit)
     int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
@@ -107,12 +107,6 @@ struct sddp_handle {
     long long n_ms = 0;
     std::string err;
     bool have_x0 = false, have_xws = false, have_uws = false, have_params = false;
-    double* tick_in = nullptr;      // [B][np + nx] staging of sddp_advance
-    double* step_buf = nullptr;     // [B][2 nx + nu + np] operands and result of sddp_model_step
-    char* tick_pin = nullptr;       // two pinned images of tick_in (small batches)
-    int tick_flip = 0, tick_unsynced = 0;
-    double* step_pin = nullptr;     // pinned host image of step_buf (small batches)
-    char* pinned = nullptr;         // small batches: pinned host staging of x | u | stats, so the three result copies are truly asynchronous
     // work queue: the solve launch runs on `slots` resident workgroups that pull instances from a queue
     int wslots = 0;                 // slots the work buffers (xn un xc uc dft gains rec) are allocated for = min(B, resident capacity)
     int cus = 0;
@@ -120,60 +114,86 @@ struct sddp_handle {
     int* order = nullptr;           // [B] queue order of the next launch
     int* hist = nullptr;            // [B] iterations of each instance's previous solve (-1: none), then the slot clocks [wslots][2]
                                     // (uint64, SolveArgs::slot_clock)
-    // cold-queue order (queue_order = 2): initial-cost keys of the launch, their sorted copy, the unsorted index list, sort scratch;
-    // allocated together at sddp_create when the option asks for it, or on the first launch that needs them (all or nothing)
-    double *qkey = nullptr, *qkey2 = nullptr;
-    int* order_in = nullptr;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    // class history (queue_order = 3): the class label per instance -- the caller's, or the handle's own (auto_cls) --, and per class
-    // the iterations / solves so far
-    int* cls = nullptr;             // [B], -1: unlabelled
-    int n_cls = 0;
-    unsigned long long* cls_stat = nullptr;   // [n_cls][2]
-    bool auto_cls = false;          // sddp_enable_auto_classes: every fresh solve launch labels its range first (implies cls != nullptr)
-    unsigned long long* cls_in = nullptr;     // [n_cls][2] device staging of sddp_add_class_stats, made by its first call
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
     // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward, without and with
     // the constants table), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.
     // An entry is made by the first launch of the kernel and kept for the handle's life (sddp_launch.hpp kernel_slots)
     struct KInfo { const void* fn; int slots; };
     std::vector<KInfo> kernels;
-    // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; non-null = active, and every kernel of the
-    // handle is launched in its table instantiation, which reads instance b's row instead of the kernel-argument copy of `dc`
-    sddp::DevConsts* ctab = nullptr;   // [B]
     int last_grid = 0, last_queued = 0;
     int last_build = 0;             // waves_per_simd of the kernel build the last solve launch ran (sddp_kernel_info)
     const void* last_kernel = nullptr;   // ... and that kernel, its dynamic LDS bytes and its workgroups per CU (sddp_kernel_resources)
     int last_lds = 0, last_per_cu = 0;
     double* box_dev = nullptr;      // lower[64] | upper[64] of the bound barrier (barrier builds)
     double* xr_dev = nullptr;       // user rows: coefficients | weights | constants (DevConsts::xr, "_x" builds)
-    double* first_dev = nullptr;    // [B][nu + nx + 3] packed first knots of sddp_solve_resident_first, and its pinned host image
-    double* first_pin = nullptr;
-    // policy export (sddp_enable_policy): [B][policy_knots * nu * (nx + 1) + 4], and the parameter tensor of the last solve launch
-    double* policy = nullptr;
-    int policy_knots = 0;
-    const double* last_params = nullptr;
-    // resumable solves (sddp_enable_resume): non-null = on, and every solve launch runs the kernels' kSolveResume variant
-    double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
-    int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
-                                    // then one word: the result of sddp_unfinished_count; then, at ResumeArgs::clock_offset(B), the
-                                    // time budget's clock words [2] uint64 (start | deadline of the last budgeted launch)
-    // time budget (sddp_set_time_budget; needs `carry`): budget_us > 0 = armed, and every solve / continue launch sequence is led
-    // by deadline_stamp_kernel and passes budget_min_iters to the resumable kernels (ResumeArgs::budget_iters; -1 while not armed)
-    double budget_us = 0.0;
-    int budget_min_iters = 0;
-    bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
-    // iteration log (sddp_enable_iteration_log; needs `carry`): non-null = on, and every solve launch runs the kSolveLog variant
-    double* ilog = nullptr;         // [B][ilog_rows][kLogWords] one record per line search of an instance's last solve (LogArgs::log)
-    int* ilog_n = nullptr;          // [B] records written (LogArgs::count)
-    int ilog_rows = 0;
+    const double* last_params = nullptr;   // the parameter tensor of the last solve launch (continue launches, policy export, audit)
     // phase-level mode (sddp_debug_set_phase_mode, diagnostics): what sddp_backward / sddp_forward launch with.  Default (0, 0): the
     // Gauss-Newton sweep on open gaps, as those entry points always ran
     double phase_theta = 0.0;       // weight of the second-order term of the sweep (the solve's theta: 0 or 1)
     int phase_closed = 0;           // 1: the one-wave kernels take their closed-gap path (has_gap = false: all defects count as zero)
-    char* up_pin = nullptr;         // pinned ring for small host->device uploads of the setters (no wait per call)
-    size_t up_off = 0;
+    // The optional state, one group per feature.  The buffers of a group exist together or not at all (sddp_api.hip acquire_group), and
+    // on() is the one statement of whether they do.
+    // cold-queue order (queue_order = 2): initial-cost keys of the launch, their sorted copy, the unsorted index list, sort scratch;
+    // allocated together at sddp_create when the option asks for it, or on the first launch that needs them
+    struct ColdQueue {
+        double *qkey = nullptr, *qkey2 = nullptr;
+        int* order_in = nullptr;
+        void* sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
+        bool on() const { return sort_tmp != nullptr; }
+    } cold;
+    // class history (queue_order = 3): the class label per instance -- the caller's, or the handle's own (auto_cls) --, and per class
+    // the iterations / solves so far.  Made by the first call that labels, for the handle's life
+    struct Classes {
+        int* cls = nullptr;             // [B], -1: unlabelled
+        int n_cls = 0;
+        unsigned long long* cls_stat = nullptr;   // [n_cls][2]
+        unsigned long long* cls_in = nullptr;     // [n_cls][2] device staging of sddp_add_class_stats, made by its first call
+        bool auto_cls = false;          // sddp_enable_auto_classes: every fresh solve launch labels its range first (implies on())
+        bool on() const { return cls != nullptr; }
+    } classes;
+    // resumable solves (sddp_enable_resume): on = every solve launch runs the kernels' kSolveResume variant.  The time budget and the
+    // iteration log ride on those kernels: neither exists while this group is off (sddp_api.hip drop_resume)
+    struct Resume {
+        double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
+        int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
+                                        // then one word: the result of sddp_unfinished_count; then, at ResumeArgs::clock_offset(B), the
+                                        // time budget's clock words [2] uint64 (start | deadline of the last budgeted launch)
+        // time budget (sddp_set_time_budget): budget_us > 0 = armed, and every solve / continue launch sequence is led by
+        // deadline_stamp_kernel and passes budget_min_iters to the resumable kernels (ResumeArgs::budget_iters; -1 while not armed)
+        double budget_us = 0.0; int budget_min_iters = 0;
+        bool continuing = false;        // the solve launch being enqueued is a continue launch (sddp_continue_*)
+        bool on() const { return carry != nullptr; }
+    } resume;
+    // iteration log (sddp_enable_iteration_log; needs `resume`): on = every solve launch runs the kSolveLog variant
+    struct IterationLog {
+        double* ilog = nullptr;         // [B][ilog_rows][kLogWords] one record per line search of an instance's last solve (LogArgs::log)
+        int* ilog_n = nullptr;          // [B] records written (LogArgs::count)
+        int ilog_rows = 0;
+        bool on() const { return ilog != nullptr; }
+    } log;
+    // policy export (sddp_enable_policy)
+    struct Policy {
+        double* policy = nullptr;       // [B][policy_knots * nu * (nx + 1) + 4]
+        int policy_knots = 0;
+        bool on() const { return policy != nullptr; }
+    } pol;
+    // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; on = every kernel of the handle is launched in
+    // its table instantiation, which reads instance b's row instead of the kernel-argument copy of `dc`
+    struct InstanceTable {
+        sddp::DevConsts* ctab = nullptr;   // [B]
+        bool on() const { return ctab != nullptr; }
+    } table;
+    // host staging: each buffer is made by the first call that uses it and kept for the handle's life, so there is nothing to switch
+    // and no on(); a pinned buffer that could not be had stays null and its caller takes the pageable path (sddp_api.hip staging)
+    struct Staging {
+        double* tick_in = nullptr;      // [B][np + nx] staging of sddp_advance
+        char* tick_pin = nullptr; int tick_flip = 0, tick_unsynced = 0;   // two pinned images of tick_in (small batches): the one last used, uploads not waited for
+        double* step_buf = nullptr;     // [B][2 nx + nu + np] operands and result of sddp_model_step
+        double* step_pin = nullptr;     // pinned host image of step_buf (small batches)
+        char* pinned = nullptr;         // small batches: pinned host staging of x | u | stats, so the three result copies are truly asynchronous
+        double *first_dev = nullptr, *first_pin = nullptr;   // [B][nu + nx + 3] packed first knots of sddp_solve_resident_first, and its pinned host image
+        char* up_pin = nullptr; size_t up_off = 0;   // pinned ring for small host->device uploads of the setters (no wait per call), and its fill
+    } stage;
     // every device and pinned allocation above, registered where it is made (sddp_api.hip acquire / release): what sddp_destroy frees
     struct Owned { void* p; bool pinned; };
     std::vector<Owned> owned;
@@ -181,7 +201,7 @@ struct sddp_handle {
     size_t n_x() const { return size_t(B) * (N + 1) * d.nx; }
     size_t n_u() const { return size_t(B) * N * d.nu; }
     size_t n_p() const { return size_t(B) * (N + 1) * d.np; }
-    int policy_words() const { return policy_knots * d.nu * (d.nx + 1) + 4; }
+    int policy_words() const { return pol.policy_knots * d.nu * (d.nx + 1) + 4; }
     size_t n_g() const { return size_t(B) * N * d.nu * (d.nx + 1); }
 };
 

@@ -37,7 +37,7 @@ constexpr bool is_plain() { return !M::BAR && !M::SO2 && M::NXR == 0; }
 // Heterogeneous fleets (sddp_set_instance_consts): on the plain builds every kernel has a table form that takes the handle's
 // constants table behind its arguments and reads instance b's row of it (sddp_kernels.hpp args_of): a second instantiation of
 // the same template, except for the policy export, whose table form is a kernel of its own (policy_kernel[_mw]_h).  sddp_api.hip
-// refuses the table on every other build, so h->ctab != nullptr implies has_hetero<M>().
+// refuses the table on every other build, so h->table.on() implies has_hetero<M>().
 template <class M>
 constexpr bool has_hetero() { return is_plain<M>(); }
 // f(tab...): a launcher with the kernels' trailing argument pack, the handle's table when it is active and nothing otherwise.  A
@@ -45,7 +45,7 @@ constexpr bool has_hetero() { return is_plain<M>(); }
 template <class M, class F>
 int with_table(sddp_handle* h, F f) {
     if constexpr (has_hetero<M>()) {
-        if (h->ctab) return f((const DevConsts*)h->ctab);
+        if (h->table.on()) return f((const DevConsts*)h->table.ctab);
     }
     return f();
 }
@@ -63,9 +63,10 @@ inline const DevConsts* consts_arg(sddp_handle*, const DevConsts* tab) { return 
 // What variant V passes behind SolveArgs, in the kernels' order (the table, if any, follows): the one place that says so.
 template <SolveVariant V>
 auto variant_args(const sddp_handle* h) {
-    [[maybe_unused]] const ResumeArgs res{h->carry, h->resumable, h->continuing ? 1 : 0, h->budget_us > 0.0 ? h->budget_min_iters : -1};
+    [[maybe_unused]] const ResumeArgs res{h->resume.carry, h->resume.resumable, h->resume.continuing ? 1 : 0,
+                                          h->resume.budget_us > 0.0 ? h->resume.budget_min_iters : -1};
     if constexpr (V == kSolveResume) return std::make_tuple(res);
-    else if constexpr (V == kSolveLog) return std::make_tuple(res, LogArgs{h->ilog, h->ilog_n, h->ilog_rows});
+    else if constexpr (V == kSolveLog) return std::make_tuple(res, LogArgs{h->log.ilog, h->log.ilog_n, h->log.ilog_rows});
     else return std::tuple<>();
 }
 // Policy export: the plain builds and their user-row forms, which are plain builds but for the rows (sddp_models.hpp: NXR > 0
@@ -114,12 +115,12 @@ int kernel_slots(sddp_handle* h, Fn kern, int cap, int* slots) {
 template <class M>
 constexpr int solve_cap(int wps) { return use_mw<M>() ? 0 : 4 * (wps >= 2 ? 2 : 1); }
 
-// the queue_order 2 / 3 pre-pass: the initial cost of every instance of the launch, into h->qkey / h->order_in
+// the queue_order 2 / 3 pre-pass: the initial cost of every instance of the launch, into h->cold.qkey / h->cold.order_in
 template <class M>
 int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
     return with_table<M>(h, [&](auto... tab) {
         return launch(h, queue_cost_key_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), a.N, first, count, a.x0, a.P, a.xs, a.us,
-                      h->qkey, h->order_in);
+                      h->cold.qkey, h->cold.order_in);
     });
 }
 
@@ -223,7 +224,7 @@ template <class M>
 int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int steps, const double* dxm, double* dx, double* du, double* dcost) {
     return with_table<M>(h, [&](auto... tab) {
         return launch(h, policy_rollout_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, start, steps, h->xs,
-                      h->us, h->last_params, (const double*)h->policy, h->policy_words(), dxm, dx, du, dcost);
+                      h->us, h->last_params, (const double*)h->pol.policy, h->policy_words(), dxm, dx, du, dcost);
     });
 }
 
