@@ -58,7 +58,7 @@ int launch_class_update(sddp_handle* h, int first, int count) {
     const auto& c = h->classes;
     if (h->resume.on())   // resumable solves: an instance is counted by the launch in which it leaves status 1
         return launch(h, class_update_resume_kernel, (count + 255) / 256, 256, 0, first, count, c.cls, c.n_cls, h->stats, c.cls_stat,
-                      h->resume.resumable, h->resume.resumable + 2 * size_t(h->B), h->resume.continuing ? 1 : 0);
+                      h->resume.resumable, h->resume.resumable + ResumeLayout::ran(size_t(h->B)), h->resume.continuing ? 1 : 0);
     return launch(h, class_update_kernel, (count + 255) / 256, 256, 0, first, count, c.cls, c.n_cls, h->stats, c.cls_stat);
 }
 // auto classes: the labels of [first, first + count) from the launch's parameter tensor into classes.cls, in front of a fresh solve launch
@@ -257,12 +257,13 @@ int check_range(sddp_handle* h, int first, int count) {
 // Resumable solves: a call that rewrites x0, xs, us, the resident params row or the constants row of the instances
 // [first, first + count) makes what their cut solve carried meaningless; their flags are cleared, on the stream, behind the rewrite.
 int invalidate_resume(sddp_handle* h, int first, int count) {
-    if (h->resume.on()) HIP_TRY(h, hipMemsetAsync(h->resume.resumable + first, 0, size_t(count) * sizeof(int), h->stream));
+    if (h->resume.on())
+        HIP_TRY(h, hipMemsetAsync(h->resume.resumable + ResumeLayout::flags(size_t(h->B)) + first, 0, size_t(count) * sizeof(int), h->stream));
     return SDDP_OK;
 }
 
 unsigned long long* clock_words(sddp_handle* h) {
-    return reinterpret_cast<unsigned long long*>(h->resume.resumable + ResumeArgs::clock_offset(h->B));
+    return reinterpret_cast<unsigned long long*>(h->resume.resumable + ResumeLayout::clock_words(h->B));
 }
 // Where the solve and the continue entry points meet: one launch over the instances [first, first + count), as a sequence on the
 // handle's stream.  The build says which solve kernel runs, launches it (ModelOps::solve of the variant the handle's state asks for)
@@ -598,8 +599,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     if (e == hipSuccess) e = alloc(h->scal, size_t(batch) * kScal * D);
     if (e == hipSuccess) e = alloc(h->qhead, sizeof(int));
     if (e == hipSuccess) e = alloc(h->order, size_t(batch) * sizeof(int));
-    // hist [B] (padded to a multiple of two ints), then the slot clocks [W][2] uint64 (SolveArgs::slot_clock)
-    if (e == hipSuccess) e = alloc(h->hist, size_t((batch + 1) & ~1) * sizeof(int) + std::max<size_t>(W, 1) * 2 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = alloc(h->hist, HistLayout::bytes(batch, h->wslots));      // the iteration counts, then the slot clocks
     // on the handle's own stream, and complete before sddp_create returns: a null-stream hipMemset is asynchronous to the host
     // and is NOT ordered with a non-blocking stream, so it could land in the middle of the first solve (seen once as a
     // different iteration count on a 1-knot problem)
@@ -758,9 +758,8 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still use the buffers
     drop_resume(h);
     if (!on) return SDDP_OK;
-    // carry; flags [3][B] | the unfinished count | (padding) | the time budget's clock words [2] uint64
-    GroupBuf g[] = {{size_t(h->B) * h->N * h->d.nx * sizeof(double)},
-                    {ResumeArgs::clock_offset(h->B) * sizeof(int) + 2 * sizeof(unsigned long long), 0x00}};
+    GroupBuf g[] = {{size_t(h->B) * h->N * h->d.nx * sizeof(double)},      // carry; the flags and what shares their buffer
+                    {ResumeLayout::ints(h->B) * sizeof(int), 0x00}};
     if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_resume: out of device memory");
     h->resume.carry = g[0]; h->resume.resumable = g[1];
     return SDDP_OK;
@@ -776,7 +775,7 @@ int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
     if (h->classes.on())   // which instances this launch resumes: the class statistics count those that it also finishes
-        HIP_TRY(h, hipMemsetAsync(h->resume.resumable + 2 * size_t(h->B) + first, 0, size_t(count) * sizeof(int), h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->resume.resumable + ResumeLayout::ran(size_t(h->B)) + first, 0, size_t(count) * sizeof(int), h->stream));
     h->resume.continuing = true;
     rc = launch_solve_sequence(h, a, first, count);
     h->resume.continuing = false;
@@ -801,7 +800,7 @@ int sddp_unfinished_count(sddp_handle* h, int first, int count, int* n) {
     if (!h || !n) return SDDP_ERR_ARG;
     if (!h->resume.on()) return fail(h, SDDP_ERR_ARG, "sddp_unfinished_count: sddp_enable_resume has not been called");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    int* d_n = h->resume.resumable + 3 * size_t(h->B);
+    int* d_n = h->resume.resumable + ResumeLayout::count_word(size_t(h->B));
     const int rc = launch(h, unfinished_count_kernel, 1, 256, 0, first, count, (const int*)h->resume.resumable, d_n);
     return rc == SDDP_OK ? download(h, n, d_n, sizeof(int)) : rc;
 }
@@ -1373,7 +1372,7 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
             *ptr = h->order; n = (long long)(size_t(h->last_queued) * sizeof(int)); break;
         case SDDP_BUF_SLOT_TIMES:   // per slot of the last solve launch: (start, queue found empty) on the 100 MHz constant-rate clock
             if (h->last_grid < 1) return fail(h, SDDP_ERR_ARG, "no solve launch yet");
-            *ptr = h->hist + ((h->B + 1) & ~1); n = (long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;
+            *ptr = h->hist + HistLayout::counts(h->B); n =(long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;
         case SDDP_BUF_POLICY:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
             if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
             *ptr = h->pol.policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;

@@ -112,8 +112,7 @@ struct sddp_handle {
     int cus = 0;
     int* qhead = nullptr;           // device queue head
     int* order = nullptr;           // [B] queue order of the next launch
-    int* hist = nullptr;            // [B] iterations of each instance's previous solve (-1: none), then the slot clocks [wslots][2]
-                                    // (uint64, SolveArgs::slot_clock)
+    int* hist = nullptr;            // iterations of each instance's previous solve (-1: none), then the slot clocks (HistLayout)
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
     // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward, without and with
     // the constants table), by address: its dynamic-LDS attribute is set and `slots` workgroups of it are resident on this device.
@@ -155,9 +154,7 @@ struct sddp_handle {
     // iteration log ride on those kernels: neither exists while this group is off (sddp_api.hip drop_resume)
     struct Resume {
         double* carry = nullptr;        // [B][N][nx] defects of the instances cut at max_iters (SolveArgs::carry)
-        int* resumable = nullptr;       // [3][B] flag | stored line-search lane | resumed by the launch in flight (SolveArgs::resumable),
-                                        // then one word: the result of sddp_unfinished_count; then, at ResumeArgs::clock_offset(B), the
-                                        // time budget's clock words [2] uint64 (start | deadline of the last budgeted launch)
+        int* resumable = nullptr;       // ResumeArgs::resumable: the flags and what shares their buffer (sddp_kernels.hpp ResumeLayout)
         // time budget (sddp_set_time_budget): budget_us > 0 = armed, and every solve / continue launch sequence is led by
         // deadline_stamp_kernel and passes budget_min_iters to the resumable kernels (ResumeArgs::budget_iters; -1 while not armed)
         double budget_us = 0.0; int budget_min_iters = 0;

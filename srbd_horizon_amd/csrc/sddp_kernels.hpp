@@ -49,6 +49,17 @@ constexpr int kScal = 24;  // doubles per instance in the scratch `scal` record 
 #define SDDP_TICK(i)
 #endif
 
+// THE layout of the packed buffer `hist` (SolveArgs::hist, sddp_handle::hist): the iteration counts [B], padded to an even count of
+// ints so that the slot clocks [wslots][2] of uint64 behind them are 8-byte aligned.
+struct HistLayout {
+    __host__ __device__ static constexpr int counts(int B) { return (B + 1) & ~1; }      // ints in front of the slot clocks
+    __host__ __device__ static constexpr size_t bytes(int B, int wslots) {               // (a handle has at least one slot)
+        return size_t(counts(B)) * sizeof(int) + size_t(wslots > 1 ? wslots : 1) * 2 * sizeof(unsigned long long);
+    }
+};
+static_assert(HistLayout::counts(1) == 2 && HistLayout::counts(2) == 2 && HistLayout::counts(3) == 4, "the counts are padded to an even count");
+static_assert(HistLayout::bytes(1, 1) == 24 && HistLayout::bytes(2, 0) == 24 && HistLayout::bytes(3, 4) == 80, "counts, then 16 bytes a slot");
+
 struct SolveArgs {
     DevConsts c;
     sddp_options o;
@@ -80,11 +91,11 @@ struct SolveArgs {
     int* qhead;
     const int* order;   // [count] absolute instance indices, or nullptr
     int* hist;          // [B] iterations of the last solve of each instance (-1: never solved): the queue-order key; behind it (no
-                        // kernel argument of its own: the solve kernels live on their scalar registers) the slot clocks [slots][2]:
-                        // constant-rate clock (wall_clock64, 100 MHz) when a slot started its first instance and when it found the
-                        // queue empty -- how long a launch drains (bench.py drain_frac)
+                        // kernel argument of its own: the solve kernels live on their scalar registers; HistLayout) the slot clocks
+                        // [slots][2]: constant-rate clock (wall_clock64, 100 MHz) when a slot started its first instance and when it
+                        // found the queue empty -- how long a launch drains (bench.py drain_frac)
     __device__ __forceinline__ unsigned long long* slot_clock(int slot) const {
-        return reinterpret_cast<unsigned long long*>(hist + ((B + 1) & ~1)) + 2 * slot;
+        return reinterpret_cast<unsigned long long*>(hist + HistLayout::counts(B)) + 2 * slot;
     }
 };
 // the size of the kernel-argument segment is part of the solve kernels' code (see ResumeArgs): a new field goes elsewhere
@@ -94,21 +105,46 @@ static_assert(sizeof(SolveArgs) == 584, "SolveArgs must not grow or shrink: it c
 // argument of their own behind it.  (Not fields of SolveArgs: the size of the kernel-argument segment decides how the compiler
 // widens the scalar loads of the arguments, and 24 bytes more moved the register allocation of the ordinary one-wave kernels.)
 // Both buffers are per INSTANCE: slots are reused within a launch and differ from one launch to the next.
+// THE layout of the packed buffer `resumable` (ResumeArgs::resumable, sddp_handle::Resume::resumable), in ints: three rows of B, one
+// word, and (padded to 8 bytes) the two uint64 clock words of the time budget.  The rows take the type of B they are asked with: the
+// kernels index in int, as they always did, the host in size_t.
+struct ResumeLayout {
+    template <class I> __host__ __device__ static constexpr I flags(I) { return 0; }            // 1: instance b can be continued
+    template <class I> __host__ __device__ static constexpr I lanes(I B) { return B; }          // the 4-wave kernel's stored `guess`
+    template <class I> __host__ __device__ static constexpr I ran(I B) { return 2 * B; }        // 1: resumed by the launch in flight
+    template <class I> __host__ __device__ static constexpr I count_word(I B) { return 3 * B; } // result of sddp_unfinished_count
+    __host__ __device__ static constexpr size_t clock_words(size_t B) { return (count_word(B) + 2) & ~size_t(1); }
+    __host__ __device__ static constexpr size_t ints(size_t B) { return clock_words(B) + 2 * sizeof(unsigned long long) / sizeof(int); }
+};
+// pinned at an odd, an even and an odd B again: rows disjoint, the count word behind them, the clock words aligned and clear of it;
+// and the offsets are what every place of use once wrote out (B | 2 B | 3 B | (3 B + 2) & ~1)
+constexpr bool resume_layout_is(int B, int lanes, int ran, int count_word, size_t clock_words, size_t ints) {
+    using L = ResumeLayout;
+    return L::flags(B) == 0 && L::lanes(B) == lanes && L::ran(B) == ran && L::count_word(B) == count_word
+        && L::clock_words(size_t(B)) == clock_words && L::ints(size_t(B)) == ints
+        && L::flags(B) + B <= L::lanes(B) && L::lanes(B) + B <= L::ran(B) && L::ran(B) + B <= L::count_word(B)
+        && size_t(L::count_word(B)) + 1 <= L::clock_words(size_t(B)) && L::clock_words(size_t(B)) % 2 == 0
+        && L::lanes(size_t(B)) == size_t(lanes) && L::ran(size_t(B)) == size_t(ran) && L::count_word(size_t(B)) == size_t(count_word);
+}
+static_assert(resume_layout_is(1, 1, 2, 3, 4, 8) && resume_layout_is(2, 2, 4, 6, 8, 12) && resume_layout_is(3, 3, 6, 9, 10, 14),
+              "the layout of ResumeArgs::resumable moved");
+
 struct ResumeArgs {
     double* carry;      // [B][N][NX]  the defects (the slot's dft) of an instance whose solve was cut at max_iters (status 1)
-    int* resumable;     // [3][B]  1: instance b can be continued (its last solve ended with status 1 and nothing of it was rewritten
-                        //         since) | the lane whose trajectory the 4-wave kernel's next pass stores (its `guess`) | 1: the
-                        //         continue launch in flight resumed instance b (class history, sddp_api.hip launch_class_update)
+    int* resumable;     // ResumeLayout.  flag: the instance's last solve ended with status 1 and nothing of it was rewritten since;
+                        // ran: class history (sddp_api.hip launch_class_update)
     int cont;           // 1: a continue launch (sddp_continue_*): resumable instances are taken up where they stopped, every other
                         // instance is left as it is
     int budget_iters;   // time budget (sddp_set_time_budget).  < 0: not armed -- the clock and the clock words are never read.
                         // >= 0: armed, and the iterations every instance that THIS launch runs is owed before the deadline is
                         // consulted (min_iters).  It sits in the struct's tail padding: the argument segment keeps its size
-    // the clock words [2] uint64 behind the flags (padded to 8 bytes): the constant-rate clock at the start of the launch sequence
-    // and the deadline, written by deadline_stamp_kernel (sddp_kernels_host.hpp) in front of the launch on the same stream
-    __host__ __device__ static size_t clock_offset(int B) { return (3 * size_t(B) + 2) & ~size_t(1); }      // in ints
+    __device__ __forceinline__ int& flag(int b) const { return resumable[b]; }
+    __device__ __forceinline__ int& lane(int B, int b) const { return resumable[ResumeLayout::lanes(B) + b]; }
+    __device__ __forceinline__ int& ran(int B, int b) const { return resumable[ResumeLayout::ran(B) + b]; }
+    // the clock words: the constant-rate clock at the start of the launch sequence and the deadline, written by
+    // deadline_stamp_kernel (sddp_kernels_host.hpp) in front of the launch on the same stream
     __device__ __forceinline__ const unsigned long long* clock_words(int B) const {
-        return reinterpret_cast<const unsigned long long*>(resumable + clock_offset(B));
+        return reinterpret_cast<const unsigned long long*>(resumable + ResumeLayout::clock_words(B));
     }
 };
 static_assert(sizeof(ResumeArgs) == 24, "ResumeArgs must not grow: budget_iters lives in what was padding");
@@ -880,7 +916,7 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
     std::conditional_t<RESUME, bool, const std::false_type> resumed{};
     if constexpr (RESUME) {
         if (R.cont) {   // wave-uniform: a kernel argument and instance b's flag
-            if (R.resumable[b] != 1) return;
+            if (R.flag(b) != 1) return;
             resumed = true;
         }
     }
@@ -928,7 +964,7 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
             J = st.cost; gap = st.gap; mu = st.mu; rho = st.rho; alpha = st.alpha; expected = st.expected;
             theta = (o.second_order && alpha == o.alpha_0) ? 1.0 : 0.0;
             iters = st.iters; rollouts = st.rollouts;
-            if (lane == 0) R.resumable[2 * A.B + b] = 1;
+            if (lane == 0) R.ran(A.B, b) = 1;
         }
     }
     LogState<LOG> lg;
@@ -1064,7 +1100,7 @@ __device__ __forceinline__ void solve_instance(const SolveArgs& A, double* s, co
             double* cr = R.carry + size_t(b) * N * NX;
             for (int e = lane; e < N * NX; e += kWave) cr[e] = dft[e];
         }
-        if (lane == 0) R.resumable[b] = status == 1 ? 1 : 0;
+        if (lane == 0) R.flag(b) = status == 1 ? 1 : 0;
     }
     if constexpr (LOG) {
         if (lane == 0) G.count[b] = lg.n;      // (a fresh solve that wrote nothing: 0)

@@ -1116,7 +1116,7 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
     std::conditional_t<RESUME, bool, const std::false_type> resumed{};      // (see solve_instance)
     if constexpr (RESUME) {
         if (R.cont) {   // the same for every thread of the workgroup: a kernel argument and instance b's flag
-            if (R.resumable[b] != 1) return;
+            if (R.flag(b) != 1) return;
             resumed = true;
         }
     }
@@ -1178,8 +1178,8 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
             J = st.cost; gap = st.gap; mu = st.mu; rho = st.rho; alpha = st.alpha; expected = st.expected;
             theta = (o.second_order && alpha == o.alpha_0) ? 1.0 : 0.0;
             iters = st.iters; rollouts = st.rollouts;
-            guess = R.resumable[A.B + b];
-            if (tid == 0) R.resumable[2 * A.B + b] = 1;
+            guess = R.lane(A.B, b);
+            if (tid == 0) R.ran(A.B, b) = 1;
         }
     }
     LogState<LOG> lg;
@@ -1344,7 +1344,7 @@ __device__ __forceinline__ void solve_instance_mw(const SolveArgs& A, double* s,
             double* cr = R.carry + size_t(b) * N * NX;
             for (int e = tid; e < N * NX; e += kThreadsMW) cr[e] = dft[e];
         }
-        if (tid == 0) { R.resumable[b] = status == 1 ? 1 : 0; R.resumable[A.B + b] = guess; }
+        if (tid == 0) { R.flag(b) = status == 1 ? 1 : 0; R.lane(A.B, b) = guess; }
     }
     if constexpr (LOG) {
         if (tid == 0) G.count[b] = lg.n;

@@ -19,7 +19,7 @@ from typing import Dict
 
 import numpy as np
 
-from .engine import DdpEngine
+from .engine import DdpEngine, default_warm_start, reference_layout
 from .problem import LinearTerm, NonlinearTerm, Problem
 
 # option keys the reference forwards to pyddp.DdpSolverOptions (ddp.py:16-35) + engine extras
@@ -145,14 +145,11 @@ class DDPSolver:
         """solve() -> (x, u) on the engine, in slices when set_slices asked for them"""
         if self.slices is None:
             return solve()
-        eng, (k, total) = self.ddp_solver, self.slices
-        eng.set_options(max_iters=k)
-        x, u = solve()
-        eng.set_options(max_iters=total)
-        if eng.unfinished() > 0:
-            eng.continue_solve()
-            x, u, _ = eng.fetch()
-        return x, u
+        first = []
+        if self.ddp_solver.cut_and_continue(lambda: first.append(solve()), first_slice=self.slices[0], total=self.slices[1],
+                                            keep_resume=True) > 0:
+            return self.ddp_solver.fetch()[:2]
+        return first[0]
 
     # ---- reference surface -----------------------------------------------------------------------------------------
     def setInitialState(self, x0):
@@ -174,22 +171,21 @@ class DDPSolver:
     def solve(self) -> bool:
         if not self._have_x0:
             raise RuntimeError("setInitialState() must be called before solve()")
-        # Warm start is never passed by the reference examples and pyddp's default is unpinned:
-        # the documented default here is x = x0 at every node, u = 0; afterwards the previous solution is kept.
-        if not self._have_u:
-            self.ddp_solver.set_u_warmstart(np.zeros((1, self.prb.nodes - 1, self.input_size)))
-            self._have_u = True
-        if not self._have_x:
-            self.ddp_solver.set_x_warmstart(np.repeat(self._x0[:, None, :], self.prb.nodes, axis=1))
-            self._have_x = True
+        self._default_warm_start()
         params = self._parameter_matrix()[None]                             # ddp.py:98-99, vectorised
-        x, u = self._launch(lambda: self.ddp_solver.solve(params))          # ddp.py:101
-        x, u = np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)   # reference layout [dim, nodes]
+        return self._solved(*self._launch(lambda: self.ddp_solver.solve(params)))      # ddp.py:101
+
+    def _default_warm_start(self):
+        default_warm_start(self.ddp_solver, self._x0, self._have_x, self._have_u)
+        self._have_x = self._have_u = True
+
+    def _solved(self, x, u) -> bool:
+        """the engine's result as the solution dictionary (ddp.py:103-104) and `stats`; -> converged (ddp.py:106)"""
+        x, u, self.stats = reference_layout(x, u, self.ddp_solver.stats)
         self.var_solution = self._createVarSolDict(x, u)
-        self.var_solution["x_opt"] = x                                      # ddp.py:103
-        self.var_solution["u_opt"] = u                                      # ddp.py:104
-        self.stats = self.ddp_solver.stats[0]
-        return bool(self.stats["converged"])                                # ddp.py:106
+        self.var_solution["x_opt"] = x
+        self.var_solution["u_opt"] = u
+        return bool(self.stats["converged"])
 
     def solve_receding(self, x0) -> bool:
         """One tick of the receding-horizon loop with device-resident data.
@@ -204,12 +200,7 @@ class DDPSolver:
         pm = self._parameter_matrix()
         if not getattr(self, "_resident", False):
             self.setInitialState(x0)
-            if not self._have_u:
-                self.ddp_solver.set_u_warmstart(np.zeros((1, self.prb.nodes - 1, self.input_size)))
-                self._have_u = True
-            if not self._have_x:
-                self.ddp_solver.set_x_warmstart(np.repeat(self._x0[:, None, :], self.prb.nodes, axis=1))
-                self._have_x = True
+            self._default_warm_start()
             self.ddp_solver.set_params(pm[None])
             self._resident = True
             self._shadow = pm.copy()
@@ -227,13 +218,7 @@ class DDPSolver:
                 self._shadow = pm.copy()
                 self.ddp_solver.advance(pm[-1][None], x0)             # warm start and state advance as usual ...
                 self.ddp_solver.set_params(pm[None])                  # ... then the parameters as the host has them
-        x, u = self._launch(self.ddp_solver.solve_resident)
-        x, u = np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)
-        self.var_solution = self._createVarSolDict(x, u)
-        self.var_solution["x_opt"] = x
-        self.var_solution["u_opt"] = u
-        self.stats = self.ddp_solver.stats[0]
-        return bool(self.stats["converged"])
+        return self._solved(*self._launch(self.ddp_solver.solve_resident))
 
     def getSolutionDict(self):
         return self.var_solution

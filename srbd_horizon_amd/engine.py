@@ -90,11 +90,12 @@ class DdpEngine:
         if u is not None:
             self.set_u_warmstart(u)
 
+    def _results(self):                           # host arrays for what a solve returns: x [B, N+1, nx], u [B, N, nu], stats [B]
+        return np.empty((self.B, self.N + 1, self.nx)), np.empty((self.B, self.N, self.nu)), np.zeros(self.B, dtype=_lib.STATS_DTYPE)
+
     def solve(self, params):
         p = self._c(params, (self.B, self.N + 1, self.np_))
-        x = np.empty((self.B, self.N + 1, self.nx))
-        u = np.empty((self.B, self.N, self.nu))
-        st = np.zeros(self.B, dtype=_lib.STATS_DTYPE)
+        x, u, st = self._results()
         self._chk(self.lib.sddp_solve(self.h, _lib.ptr(p), _lib.ptr(x), _lib.ptr(u), _lib.ptr(st)))
         self.stats = st
         return x, u
@@ -119,9 +120,7 @@ class DdpEngine:
         return out
 
     def solve_resident(self):
-        x = np.empty((self.B, self.N + 1, self.nx))
-        u = np.empty((self.B, self.N, self.nu))
-        st = np.zeros(self.B, dtype=_lib.STATS_DTYPE)
+        x, u, st = self._results()
         self._chk(self.lib.sddp_solve_resident(self.h, _lib.ptr(x), _lib.ptr(u), _lib.ptr(st)))
         self.stats = st
         return x, u
@@ -354,9 +353,7 @@ class DdpEngine:
 
     def fetch(self):
         """Copy the solution and stats of the last device solve to host numpy arrays (waits for the handle's stream)."""
-        x = np.empty((self.B, self.N + 1, self.nx))
-        u = np.empty((self.B, self.N, self.nu))
-        st = np.zeros(self.B, dtype=_lib.STATS_DTYPE)
+        x, u, st = self._results()
         self._chk(self.lib.sddp_fetch(self.h, _lib.ptr(x), _lib.ptr(u), _lib.ptr(st)))
         self.stats = st
         return x, u, st
@@ -398,6 +395,46 @@ class DdpEngine:
         n = C.c_int()
         self._chk(self.lib.sddp_unfinished_count(self.h, int(first), self._count(first, count), C.byref(n)))
         return n.value
+
+    def cut_and_continue(self, launch, *, total, first_slice=None, budget_us=None, min_iters=0, first=0, count=None, params=None,
+                         between=None, drained=None, behind=None, keep_resume=False) -> int:
+        """THE two-launch sequence of a solve that is cut and continued; it leaves the engine as it found it.  `launch()` enqueues a
+        solve that covers the instances [first, first + count); it is cut at `first_slice` iterations or, at max_iters = total, after
+        `budget_us` microseconds of device time with `min_iters` owed (exactly one of the two).  `between()` runs behind it; then
+        the cut is lifted and, if any instance of the range is unfinished, a continue launch on `params` finishes those alone.
+        `drained()` runs once the count is known (the stream has drained, the first launch's clocks still stand), `behind()` behind
+        a continue launch.  -> the unfinished count: > 0 says that a second launch ran.
+        Restored: max_iters; where resumable solves were on, the budget that was armed before; where they were off they go off
+        again (which waits for the stream, frees the carry buffer and disarms any budget) unless keep_resume, the caller's
+        persistent mode: they stay on, and are not touched if they were."""
+        if (first_slice is None) == (budget_us is None):
+            raise ValueError("exactly one of first_slice and budget_us cuts the first launch")
+        nothing = lambda: None
+        was_on, was_iters = self.resume_enabled, int(self.opts.max_iters)
+        was_budget = self.time_budget() if was_on and budget_us is not None else None
+        if not (was_on and keep_resume):
+            self.enable_resume(True)                    # (nothing happens in the library when they are on)
+        self.set_options(max_iters=int(total if first_slice is None else first_slice))
+        if budget_us is not None:
+            self.set_time_budget(budget_us, min_iters)
+        launch()
+        (between or nothing)()
+        if budget_us is not None:
+            self.set_time_budget(0.0)
+        else:
+            self.set_options(max_iters=int(total))
+        n = self.unfinished(first, count)               # (waits for the stream)
+        (drained or nothing)()
+        if n > 0:
+            self.continue_solve(params, first, count)
+            (behind or nothing)()
+        if not (was_on or keep_resume):
+            self.enable_resume(False)
+        elif was_budget is not None:
+            self.set_time_budget(*was_budget)
+        if int(self.opts.max_iters) != was_iters:
+            self.set_options(max_iters=was_iters)
+        return n
 
     # ---- time-budgeted launches: a launch that ends at a device-clock deadline, resumable (include/sddp.h) --------------------
     def set_time_budget(self, budget_us: float, min_iters: int = 0):
@@ -584,6 +621,20 @@ class DdpEngine:
             out["resources"] = dict(vgprs=v.value, scratch_bytes_per_lane=sc.value, lds_bytes_per_workgroup=lds.value,
                                     workgroups_per_cu=per.value)
         return out
+
+
+# ---- what the two single-robot adapters (ddp.DDPSolver, pyddp_hip.DdpSolver) share: an engine of batch 1 in the reference's layout ----
+def default_warm_start(eng: DdpEngine, x0, have_x: bool, have_u: bool):
+    """What the caller never set: x = x0 [1, nx] at every node, u = 0 (the examples pass no warm start; pyddp's default is unpinned)"""
+    if not have_u:
+        eng.set_u_warmstart(np.zeros((1, eng.N, eng.nu)))
+    if not have_x:
+        eng.set_x_warmstart(np.repeat(x0[:, None, :], eng.N + 1, axis=1))
+
+
+def reference_layout(x, u, stats):
+    """engine results x [1, N+1, nx], u [1, N, nu], stats [1] -> the reference's x [nx, N+1], u [nu, N], and the stats row"""
+    return np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T), stats[0]
 
 
 def eval_knots(model: str, N: int, k, x, u, p, consts: dict | None = None, model_id: int | None = None):

@@ -138,37 +138,9 @@ class FleetQueue:
         -> (finished [n] bool device tensor: which instances the first slice finished; records [n, words] of all of them after the
         last slice).  `first_records` keeps the records packed behind the first slice.
         The records are always the "first_knot" ones and there is no collective and no policy launch, whatever `gather` / `policy`
-        the queue was made with: the caller owns the two record tensors.  The engine is left as it was found: resumable solves are
-        switched on for this call only when they were off (so later flush() calls run the ordinary kernels and the carry buffer is
-        freed; a caller that slices every tick calls `engine.enable_resume()` once itself and saves the allocation per call), and
-        `max_iters` is restored."""
-        import torch
-        n = self.pending * self.batch
-        if n == 0:
-            return None, None
-        eng = self.eng
-        was_on, was_iters = eng.resume_enabled, int(eng.opts.max_iters)
-        eng.enable_resume(True)
-        words = eng.record_words("first_knot")
-        if getattr(self, "_sliced", None) is None or self._sliced[0].shape != (self.batch * self.depth, words):
-            mk = lambda: torch.empty((self.batch * self.depth, words), dtype=torch.float64, device=self.x.device)
-            self._sliced = [mk(), mk()]
-        eng.set_options(max_iters=int(first_slice))
-        eng.solve_range_device(self.P, 0, n)
-        self.first_records = eng.pack_records_device(self._sliced[0][:n], 0, n, "first_knot")
-        finished = self.si[:n, _lib.STATS_I32_STATUS] != 1
-        self.launches += 1
-        eng.set_options(max_iters=int(max_iters))
-        records = self.first_records
-        if eng.unfinished(0, n) > 0:
-            eng.continue_solve(self.P, 0, n)
-            records = eng.pack_records_device(self._sliced[1][:n], 0, n, "first_knot")
-            self.launches += 1
-        if not was_on:
-            eng.enable_resume(False)                                         # (waits for the stream: the records are complete)
-        eng.set_options(max_iters=was_iters)
-        self.pending = 0
-        return finished, records
+        the queue was made with: the caller owns the two record tensors.  The engine is left as it was found (DdpEngine.
+        cut_and_continue); a caller that slices every tick calls `engine.enable_resume()` once and saves the carry's allocation."""
+        return self._cut_and_continue(total=max_iters, first_slice=first_slice)
 
     def solve_within(self, budget_us: float, total: int, min_iters: int = 0):
         """The pending batches under a TIME budget (time-budgeted launches, include/sddp.h): solve_sliced with the first slice
@@ -178,39 +150,36 @@ class FleetQueue:
         the budget OFF finishes the stragglers alone.  Every instance ends with exactly the bytes of one uncut solve at `total`.
         -> (finished [n] bool device tensor: which instances the budgeted launch finished; records [n, words] of all of them
         after the last launch).  `first_records` keeps the records packed behind the first launch, `overrun_us` how far that launch
-        ran past its deadline.  Records, collective and policy as in solve_sliced; the engine is left as it was found: resumable
-        solves, the time budget and max_iters are restored."""
+        ran past its deadline.  Records, collective, policy and the state of the engine as in solve_sliced."""
+        return self._cut_and_continue(total=total, budget_us=budget_us, min_iters=min_iters)
+
+    def _cut_and_continue(self, **cut):
+        """the pending batches by DdpEngine.cut_and_continue, the records packed behind each launch -> (finished, records)"""
         import torch
         n = self.pending * self.batch
         if n == 0:
             return None, None
         eng = self.eng
-        was_on, was_iters = eng.resume_enabled, int(eng.opts.max_iters)
-        was_budget = eng.time_budget() if was_on else (0.0, 0)
-        eng.enable_resume(True)
-        words = eng.record_words("first_knot")
-        if getattr(self, "_sliced", None) is None or self._sliced[0].shape != (self.batch * self.depth, words):
-            mk = lambda: torch.empty((self.batch * self.depth, words), dtype=torch.float64, device=self.x.device)
-            self._sliced = [mk(), mk()]
-        eng.set_options(max_iters=int(total))
-        eng.set_time_budget(budget_us, min_iters)
-        eng.solve_range_device(self.P, 0, n)
-        self.first_records = eng.pack_records_device(self._sliced[0][:n], 0, n, "first_knot")
-        finished = self.si[:n, _lib.STATS_I32_STATUS] != 1
-        self.launches += 1
-        eng.set_time_budget(0.0)
-        records = self.first_records
-        unfinished = eng.unfinished(0, n)                                    # (waits for the stream)
-        self.overrun_us = eng.deadline_overrun_us()                          # before the second launch rewrites the slot times
-        if unfinished > 0:
-            eng.continue_solve(self.P, 0, n)
+        shape = (self.batch * self.depth, eng.record_words("first_knot"))
+        if getattr(self, "_sliced", None) is None or self._sliced[0].shape != shape:
+            self._sliced = [torch.empty(shape, dtype=torch.float64, device=self.x.device) for _ in range(2)]
+        finished = records = None
+
+        def between():
+            nonlocal finished, records
+            self.first_records = records = eng.pack_records_device(self._sliced[0][:n], 0, n, "first_knot")
+            finished = self.si[:n, _lib.STATS_I32_STATUS] != 1
+
+        def overrun():                               # before the second launch rewrites the slot times
+            self.overrun_us = eng.deadline_overrun_us()
+
+        def behind():
+            nonlocal records
             records = eng.pack_records_device(self._sliced[1][:n], 0, n, "first_knot")
-            self.launches += 1
-        if not was_on:
-            eng.enable_resume(False)                                         # (waits for the stream: the records are complete)
-        else:
-            eng.set_time_budget(*was_budget)
-        eng.set_options(max_iters=was_iters)
+
+        more = eng.cut_and_continue(lambda: eng.solve_range_device(self.P, 0, n), count=n, params=self.P, between=between,
+                                    drained=overrun if "budget_us" in cut else None, behind=behind, **cut)
+        self.launches += 2 if more > 0 else 1
         self.pending = 0
         return finished, records
 

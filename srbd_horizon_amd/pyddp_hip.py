@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .engine import DdpEngine
+from .engine import DdpEngine, default_warm_start, reference_layout
 
 
 class DdpSolverOptions:
@@ -105,15 +105,10 @@ class DdpSolver:
             raise ValueError(f"every node needs {self.np_} parameter values")
         if not self._have_x0:
             raise RuntimeError("set_initial_state() must be called before solve()")
-        if not self._have_u:       # default warm start (the examples never pass one): x = x0 everywhere, u = 0
-            self._eng.set_u_warmstart(np.zeros((1, self.N, self.nu)))
-            self._have_u = True
-        if not self._have_x:
-            self._eng.set_x_warmstart(np.repeat(self._x0[:, None, :], self.N + 1, axis=1))
-            self._have_x = True
-        x, u = self._eng.solve(P[None])
-        self.stats = self._eng.stats[0]
-        return np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)
+        default_warm_start(self._eng, self._x0, self._have_x, self._have_u)
+        self._have_x = self._have_u = True
+        x, u, self.stats = reference_layout(*self._eng.solve(P[None]), self._eng.stats)
+        return x, u
 
     def is_converged(self) -> bool:
         return bool(self._eng.is_converged()[0])
@@ -127,9 +122,8 @@ class DdpSolver:
         one solve() gives with that max_iters from the start, bit for bit.  -> (x [nx, N+1], u [nu, N]) like solve()."""
         self._eng.set_options(max_iters=int(max_iters))
         self._eng.continue_solve()
-        x, u, st = self._eng.fetch()
-        self.stats = st[0]
-        return np.ascontiguousarray(x[0].T), np.ascontiguousarray(u[0].T)
+        x, u, self.stats = reference_layout(*self._eng.fetch())
+        return x, u
 
     def get_feedback_gains(self):
         """The local feedback policy of the last solve, u = u_k + K_k (x - x_k): a list of N matrices K_k [nu, nx] (rows: inputs,
