@@ -288,6 +288,38 @@ int  sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start,
 int  sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
                              double friction_coefficient, double* d_out /*[count][SDDP_AUDIT_WORDS]*/);
 int  sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out /*[count][SDDP_AUDIT_WORDS], host*/);
+/* ---- stationarity certificate (v9): reduced gradient and costates of a plan, computed on the device ------------------------------
+ * converged, status and expected do not say how far a returned plan is from a stationary point of the problem it was solved for:
+ * status 0 rests on the expected reduction of the regularised model, a cut (status 1) and an exhausted line search (status 4) say
+ * nothing.  The audit above is the feasibility half of the first-order conditions; this is the other half.  For a whole-horizon
+ * trajectory x_0 .. x_N, u_0 .. u_{N-1} and the Lagrangian  sum L_k + L_N + sum lambda_{k+1}^T (f(x_k, u_k) - x_{k+1}),  stationarity in
+ * x_k defines the costates and leaves a residual in the inputs alone:
+ *       lambda_N = l_x,N;    q_k = [l_x,k ; l_u,k] + F_k^T lambda_{k+1},  F_k = [f_x f_u] at (x_k, u_k, p_k),  k = N - 1 .. 0;
+ *       lambda_k = q_k[0 : nx];    s_k = q_k[nx : nx + nu]   (the reduced gradient: dJ/du_k of the rollout where the gaps are closed).
+ * Every derivative is taken at the STORED (x_k, u_k), whatever the gaps: the multiple-shooting linearisation.  l and F are the
+ * handle's device model code, what sddp_eval_knots returns (barrier terms and user rows included where the build has them);
+ * second_order plays no part.  Entry z of q_k starts at g[z] and adds fma(F[j][z], lambda_{k+1}[j], .) for j = 0 .. nx - 1, in this order.
+ * One record is sddp_stationarity_words() = 8 doubles per instance:
+ *    0  stationarity: max over stage nodes of || s_k ||_inf
+ *    1, 2  its node and input index (the first in node-major order on ties; -1 where word 0 is NaN)
+ *    3  scale: max over k, i of |l_u,k[i]| + sum_j |F_k[j][nx + i]| |lambda_{k+1}[j]|, the size of what cancels in s; word 0 / word 3 is
+ *       the relative measure
+ *    4  || lambda_0 ||_inf: the sensitivity of the cost to the initial state          5  max over k = 1 .. N of || lambda_k ||_inf
+ *    6  defect: max over stage nodes of || x_{k+1} - f(x_k, u_k; p_k) ||_inf (the bits of audit word 10)          7  N
+ * A maximum whose operands include a NaN is NaN.  No threshold comes with the record: how small word 0 / word 3 of a converged solve
+ * is belongs to the algorithm, not to this call.
+ * sddp_stationarity_range_device: d_x == NULL and d_u == NULL take the handle's own xs / us; both given take a caller's trajectory,
+ *   d_x [count][N + 1][nx] and d_u [count][N][nu], block i for instance first + i.  d_lambda [count][N + 1][nx] and d_grad [count][N][nu]
+ *   receive every lambda_k and s_k; either may be NULL.  The parameters are those of the last sddp_solve* launch (SDDP_ERR_ARG if no
+ *   solve ran, if only one of d_x / d_u is given, or for a range outside the handle); with per-instance constants instance b is
+ *   differentiated through its own robot.  Asynchronous on the handle's stream, behind the solve; it writes nothing but d_out, d_lambda
+ *   and d_grad and uses none of the slots' work buffers: no solve result, policy record, resume flag or log record changes, and the
+ *   result of an instance does not depend on the range it was part of.  Every build has it.
+ * sddp_stationarity: the records of the handle's own plan into a host array; waits for the stream. */
+int  sddp_stationarity_words(sddp_handle* h, int* words);
+int  sddp_stationarity_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
+                                    double* d_out /*[count][8]*/, double* d_lambda, double* d_grad);
+int  sddp_stationarity(sddp_handle* h, int first, int count, double* out /*[count][8], host*/);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

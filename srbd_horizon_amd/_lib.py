@@ -65,6 +65,8 @@ LOG_FIELDS = ("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", 
 AUDIT_WORDS = 16
 (AUDIT_CONE, AUDIT_CONE_NODE, AUDIT_CONE_CONTACT, AUDIT_PULL, AUDIT_PULL_NODE, AUDIT_SWING_LOAD, AUDIT_QUAT_DRIFT, AUDIT_FOOT_HEIGHT,
  AUDIT_SLIP, AUDIT_RIGID_FOOT, AUDIT_DEFECT, AUDIT_DEFECT_NODE, AUDIT_NODES, AUDIT_STANCE_PAIRS) = range(14)
+# the words of one record of the stationarity certificate (include/sddp.h sddp_stationarity_range_device), by name
+STATIONARITY_FIELDS = ("stationarity", "node", "input", "scale", "lambda_0", "lambda_max", "defect", "nodes")
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = C.sizeof(SddpStats) // 8, C.sizeof(SddpStats) // 4
 STATS_F64_COST = SddpStats.cost.offset // 8
@@ -114,6 +116,9 @@ SYMBOLS = {
     "sddp_policy_rollout_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sddp_audit_range_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp]),
     "sddp_audit": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp]),
+    "sddp_stationarity_words": (C.c_int, [_vp, _P(C.c_int)]),
+    "sddp_stationarity_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "sddp_stationarity": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),

@@ -1315,6 +1315,38 @@ int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient
     return rc;
 }
 
+int sddp_stationarity_words(sddp_handle* h, int* words) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!words) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    *words = kStationarityWords;
+    return SDDP_OK;
+}
+
+int sddp_stationarity_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out,
+                                   double* d_lambda, double* d_grad) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_stationarity_range_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if ((d_x == nullptr) != (d_u == nullptr))
+        return fail(h, SDDP_ERR_ARG, "sddp_stationarity_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
+    const bool own = d_x == nullptr;
+    return h->ops->launch_stationarity(h, first, count, own ? h->xs : d_x, own ? h->us : d_u, own, d_out, d_lambda, d_grad);
+}
+
+int sddp_stationarity(sddp_handle* h, int first, int count, double* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t bytes = size_t(count) * kStationarityWords * sizeof(double);
+    double* d_out = nullptr;
+    HIP_TRY(h, hipMalloc(&d_out, bytes));
+    int rc = sddp_stationarity_range_device(h, first, count, nullptr, nullptr, d_out, nullptr, nullptr);
+    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {
     if (!h || !x || !u || !p || !x_next) return SDDP_ERR_ARG;
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");

@@ -79,6 +79,8 @@ struct ModelOps {
     int (*launch_policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
     // the plan audit: first, count, start, steps, x, u, own (the handle's xs / us) or the caller's, linearised friction coefficient, out
     int (*launch_audit)(sddp_handle*, int, int, int, int, const double*, const double*, bool, double, double*) = nullptr;
+    // the stationarity certificate: first, count, x, u, own (the handle's xs / us) or the caller's, out, lambda or null, reduced gradient or null
+    int (*launch_stationarity)(sddp_handle*, int, int, const double*, const double*, bool, double*, double*, double*) = nullptr;
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);

@@ -28,6 +28,7 @@ namespace sddp {
 constexpr int kWave = 64;
 constexpr int kSlots = 6;   // line-search candidates whose trajectories are kept per pass (one-wave kernel)
 constexpr int kScal = 24;  // doubles per instance in the scratch `scal` record (test kernels / diagnostic stamps)
+constexpr int kStationarityWords = 8;      // doubles per record of the stationarity certificate (sddp.h sddp_stationarity_words)
 
 // Diagnostic build only (-DSDDP_STAMPS): per-phase shader-cycle sums, written to `scal`; never in the shipped library.
 #ifdef SDDP_STAMPS
@@ -1579,6 +1580,109 @@ __global__ __launch_bounds__(kWave) void plan_audit_kernel(ConstsArg<Tab...> con
         r[10] = defect.v;  r[11] = audit_index(defect, 1, false);
         r[12] = double(steps);  r[13] = double(stance_pairs);
         r[14] = 0.0;  r[15] = 0.0;
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------------------
+// Stationarity certificate (sddp_stationarity_range_device): the costates and the reduced gradient of a whole-horizon trajectory,
+//   lambda_N = l_x,N;   q_k = [l_x,k ; l_u,k] + F_k^T lambda_{k+1},  F_k = [f_x f_u] at (x_k, u_k, p_k);   lambda_k = q_k[0:NX],  s_k = q_k[NX:NZ],
+// k = N - 1 .. 0, every derivative at the STORED (x_k, u_k) whatever the gaps (the multiple-shooting linearisation), and 8 doubles per
+// instance (include/sddp.h has the table).  x [..][N + 1][NX], u [..][N][NU]; instance b = first + i reads block xoff + i of them
+// (the handle's own xs / us: xoff = first; a caller's: xoff = 0) and row b of P.
+// One wavefront per instance, the knots backward.  Per knot, lane 0 runs the scalar model code as eval_knots_kernel does -- M::derivs
+// into a knot record in LDS, with a zero input vector at the terminal knot -- and M::step on the operands plan_audit_kernel gives it
+// (word 6 is its word 10); the wave then expands F_k into an LDS tile through M::F_entry exactly as eval_knots_kernel does, and lane
+// z < NZ, two passes where NZ > 64, forms q[z] = g[z] + sum_j F[j][z] lambda_{k+1}[j] as one FMA chain over j = 0 .. NX - 1, lambda_{k+1}
+// read from LDS (every lane the same word: a broadcast; F[j][.]: consecutive words).  The tile is not a convenience: calling M::F_entry
+// with any other index expressions than eval_knots_kernel's changes what the compiler knows about its arguments over the whole
+// translation unit, and with it the instruction streams of the srbd13 solve, backward and policy kernels (profiles/stationarity).
+// lambda ping-pongs between two LDS vectors, so a pass never reads what it writes.  The maxima are the audit's: NaN propagates, a NaN
+// maximum has no index, the smaller key = node * NU + input wins a tie.  Static LDS only (NREC + 2 NX + NX NZ doubles: 56.7 KB for
+// srbd61), nothing of the slots' work buffers, plain vector stores to the caller's outputs alone (lam / grad may be null).
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void stationarity_kernel(ConstsArg<Tab...> consts, int N, int first, int count,
+                                                              const double* __restrict__ x, const double* __restrict__ u, int xoff,
+                                                              const double* __restrict__ P, double* __restrict__ out,
+                                                              double* __restrict__ lam_out, double* __restrict__ grad_out) {
+    constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NP = M::NP, NREC = M::NREC;
+    __shared__ double srec[NREC];                          // the record of knot k
+    __shared__ double slam[2][NX];                         // lambda_{k+1} | lambda_k, swapping
+    __shared__ double sF[NX * NZ];                         // F_k, row-major
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
+    const double* ub = u + size_t(xoff + i) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    double* lo = lam_out ? lam_out + size_t(i) * (N + 1) * NX : nullptr;
+    double* go = grad_out ? grad_out + size_t(i) * N * NU : nullptr;
+    AuditMax stat{0.0, kAuditNoKey}, defect{0.0, kAuditNoKey};
+    double scale = 0.0, lam0 = 0.0, lam_rest = 0.0;
+    int cur = 0;
+    for (int k = N; k >= 0; --k) {
+        const double* xk = xb + size_t(k) * NX;
+        const double* pk = Pb + size_t(k) * NP;
+        if (lane == 0) {
+            double xl[NX], ul[NU];
+#pragma unroll
+            for (int t = 0; t < NX; ++t) xl[t] = xk[t];
+#pragma unroll
+            for (int t = 0; t < NU; ++t) ul[t] = k < N ? ub[size_t(k) * NU + t] : 0.0;
+            M::derivs(c, xl, ul, pk, k, N, srec);
+            if (k < N) {
+                double xn[NX];
+                (void)M::step(c, xk, ub + size_t(k) * NU, pk, k, xn);
+                double d = 0.0;
+#pragma unroll
+                for (int e = 0; e < NX; ++e) d = nan_max(d, fabs(xk[NX + e] - xn[e]));
+                audit_take(defect, d, k);
+            }
+        }
+        wave_sync();
+        if (k == N) {
+            for (int z = lane; z < NX; z += kWave) {
+                const double v = srec[M::REC_G + z];
+                slam[cur][z] = v;
+                if (lo) lo[size_t(k) * NX + z] = v;
+                lam_rest = nan_max(lam_rest, fabs(v));
+            }
+        } else {
+            const double* ln = slam[cur];
+            for (int e = lane; e < NX * NZ; e += kWave) sF[e] = M::F_entry(c, srec, e / NZ, e % NZ);
+            wave_sync();
+            for (int z = lane; z < NZ; z += kWave) {
+                const double g = srec[M::REC_G + z];
+                double acc = g, mag = fabs(g);
+                for (int j = 0; j < NX; ++j) {
+                    const double f = sF[j * NZ + z], l = ln[j];
+                    acc = fma(f, l, acc);
+                    mag = fma(fabs(f), fabs(l), mag);
+                }
+                if (z < NX) {
+                    slam[cur ^ 1][z] = acc;
+                    if (lo) lo[size_t(k) * NX + z] = acc;
+                    if (k == 0) lam0 = nan_max(lam0, fabs(acc));
+                    else lam_rest = nan_max(lam_rest, fabs(acc));
+                } else {
+                    if (go) go[size_t(k) * NU + (z - NX)] = acc;
+                    audit_take(stat, fabs(acc), k * NU + (z - NX));
+                    scale = nan_max(scale, mag);
+                }
+            }
+            cur ^= 1;
+        }
+        wave_sync();                                       // lambda_k is in LDS, and the record is free for knot k - 1
+    }
+    audit_merge(stat);
+    scale = audit_merge(scale);
+    lam0 = audit_merge(lam0);
+    lam_rest = audit_merge(lam_rest);
+    if (lane == 0) {
+        double* r = out + size_t(i) * kStationarityWords;
+        r[0] = stat.v;  r[1] = audit_index(stat, NU, false);  r[2] = audit_index(stat, NU, true);
+        r[3] = scale;  r[4] = lam0;  r[5] = lam_rest;
+        r[6] = defect.v;  r[7] = double(N);
     }
 }
 

@@ -238,6 +238,16 @@ int launch_audit(sddp_handle* h, int first, int count, int start, int steps, con
     });
 }
 
+// the stationarity certificate (stationarity_kernel): one wavefront per instance of the range, static LDS only -- no kernel_slots entry,
+// no work buffer.  Every build has it.  own: the handle's xs / us (block first + i), else the caller's whole-horizon trajectory (block i).
+template <class M>
+int launch_stationarity(sddp_handle* h, int first, int count, const double* dx, const double* du, bool own, double* dout, double* dlam, double* dgrad) {
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, stationarity_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, dx, du, own ? first : 0,
+                      h->last_params, dout, dlam, dgrad);
+    });
+}
+
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
     return with_table<M>(h, [&](auto... tab) {
@@ -270,6 +280,7 @@ ModelOps make_ops(const char* name) {
     o.launch_forward = launch_forward<M>;
     if constexpr (has_policy<M>()) { o.launch_policy = launch_policy<M>; o.launch_policy_rollout = launch_policy_rollout<M>; }
     o.launch_audit = launch_audit<M>;
+    o.launch_stationarity = launch_stationarity<M>;
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

@@ -239,6 +239,36 @@ class DdpEngine:
         self._chk(self.lib.sddp_audit(self.h, int(first), n, float(friction), _lib.ptr(out)))
         return out
 
+    # ---- stationarity certificate: reduced gradient and costates of a plan, computed on the device (include/sddp.h) ------------------
+    def stationarity_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, lam=None, grad=None):
+        """The stationarity records (_lib.STATIONARITY_FIELDS) of the instances [first, first + count) into the device tensor out
+        [count, 8].  x, u None: the handle's own plan; else device tensors x [count, N + 1, nx], u [count, N, nu], a caller's
+        whole-horizon trajectory.  lam [count, N + 1, nx] / grad [count, N, nu]: device tensors for every costate / reduced gradient,
+        or None.  Every build has it; asynchronous, behind the solve."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_stationarity_range_device(self.h, int(first), n, self._dev_or_null(x, (n, self.N + 1, self.nx)),
+                                                          self._dev_or_null(u, (n, self.N, self.nu)),
+                                                          self._dev(out, (n, len(_lib.STATIONARITY_FIELDS))),
+                                                          self._dev_or_null(lam, (n, self.N + 1, self.nx)),
+                                                          self._dev_or_null(grad, (n, self.N, self.nu))))
+        return out
+
+    def stationarity(self, first: int = 0, count: int | None = None, full: bool = False):
+        """The stationarity records [count, 8] of the handle's own plan as a numpy array; full: -> (records, lambda [count, N + 1, nx],
+        s [count, N, nu]).  Waits for the stream."""
+        n = self._count(first, count)
+        if not full:
+            out = np.empty((max(n, 0), len(_lib.STATIONARITY_FIELDS)))
+            self._chk(self.lib.sddp_stationarity(self.h, int(first), n, _lib.ptr(out)))
+            return out
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        mk = lambda *shape: torch.empty((max(n, 0), *shape), dtype=torch.float64, device=dev)
+        out, lam, grad = mk(len(_lib.STATIONARITY_FIELDS)), mk(self.N + 1, self.nx), mk(self.N, self.nu)
+        self.stationarity_device(out, first, n, lam=lam, grad=grad)
+        self.synchronize()
+        return out.cpu().numpy(), lam.cpu().numpy(), grad.cpu().numpy()
+
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
         self._chk(self.lib.sddp_is_converged(self.h, _lib.ptr(f)))

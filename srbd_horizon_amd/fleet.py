@@ -47,6 +47,7 @@ class FleetQueue:
         if tuple(params_all.shape[:1]) != (self.batch * self.depth,):
             raise ValueError("params_all must hold depth * batch instances")
         self.pending = 0            # batches loaded and not yet solved
+        self.solved = 0             # instances [0, solved) of the handle: what the most recent solving call covered
         self.launches = 0
         self.gather_bytes = 0       # bytes this rank contributed to the collectives so far
         self.x, self.u, self.sf, self.si = engine.fetch_device_views()
@@ -127,6 +128,18 @@ class FleetQueue:
             self._last = k
             self._k ^= 1
         self.pending = 0
+        self.solved = n
+        return n
+
+    def stationarity(self, out, lam=None, grad=None):
+        """The stationarity records (DdpEngine.stationarity_device) of the instances the last flush / solve_sliced / solve_within
+        solved, into the first n rows of the device tensor out [>= n, 8] (lam, grad: likewise, or None); launched behind whatever
+        that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet server whether a cut robot is
+        worth a second slice: word 0 / word 3 of its record."""
+        n = self.solved
+        if n == 0:
+            return 0
+        self.eng.stationarity_device(out[:n], 0, n, lam=None if lam is None else lam[:n], grad=None if grad is None else grad[:n])
         return n
 
     def solve_sliced(self, first_slice: int, max_iters: int):
@@ -181,6 +194,7 @@ class FleetQueue:
                                     drained=overrun if "budget_us" in cut else None, behind=behind, **cut)
         self.launches += 2 if more > 0 else 1
         self.pending = 0
+        self.solved = n
         return finished, records
 
     def _wait(self, k):
