@@ -320,6 +320,45 @@ int  sddp_stationarity_words(sddp_handle* h, int* words);
 int  sddp_stationarity_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
                                     double* d_out /*[count][8]*/, double* d_lambda, double* d_grad);
 int  sddp_stationarity(sddp_handle* h, int first, int count, double* out /*[count][8], host*/);
+/* ---- cost breakdown (v9): the cost of a plan term family by term family, computed on the device ------------------------------------
+ * sddp_stats.cost is one number: the sum of up to thirteen differently weighted families of terms.  This call says which of them a
+ * plan pays for.  It has no cost code of its own: a family's value at a node is the model's stage cost (terminal cost at node N)
+ * evaluated on a copy of the instance's constants that KEEPS the weights of that family and has 0.0 in every other one, so the
+ * terms of a family are formed and added in the same order as inside the full cost.  The families, and what each keeps:
+ *    0  r_tracking        r_tracking_gain                       7  zmp_tracking      zmp_tracking_gain
+ *    1  rdot_tracking     rdot_tracking_gain                    8  constraints       the fixed 1e6 of the contact penalties and of the
+ *    2  w_tracking        w_tracking_gain                                            relative-velocity rows
+ *    3  rel_pos           rel_pos_gain                          9  friction_barrier  friction_barrier_weight
+ *    4  min_f             min_f_gain                           10  bound_barrier     bound_barrier_weight
+ *    5  force_switch      force_switch_weight                  11  user_rows         the weights of the user rows (extra_weight)
+ *    6  min_qddot         min_qddot_gain                       12  unweighted        nothing
+ * Family 12 is what a model adds when every weight above is zero: on the srbd models the orientation tracking term, whose gain is no
+ * constant but the parameter orientation_tracking_gain (column 6 of a parameter row); nothing, 0.0, on lip30.  That parameter is
+ * treated as the weights are: families 0 .. 11 are evaluated with it 0.0, so they hold their own terms alone.  (A user build's rows
+ * may read any parameter: there family 11 is evaluated with the parameters as they are, and the node's family 12 is subtracted.)
+ * sddp_cost_terms_words: one record is 16 doubles, of 13 families.  sddp_cost_terms_name: the name of family 0 .. 12 (a static string;
+ * SDDP_ERR_ARG outside, the message under sddp_last_error(NULL)).  The record of an instance:
+ *    0  total: the cost with the constants as they are          1 .. 13  families 0 .. 12
+ *    14  the largest of the families 0 .. 11 (the first on ties; -1 if one of them is NaN)          15  N
+ * Each of the words 0 .. 13 is  sum_{k = 0}^{N - 1} L_k + L_N  added one node after the other in node order, L the model's cost code as
+ * above; d_nodes [count][N + 1][14], when given, receives the addends (column 0: the total of node k, column 1 + f: family f), so a
+ * record is the in-order sum of its rows, bit for bit.  Nothing ties the total to the bits of sddp_stats.cost: the solve has its own sum.
+ * A gain that is 0 gives a family that is exactly 0.0; twice the gain gives exactly twice the family.  NaN propagates: a NaN in the
+ * trajectory makes the total and every family NaN (0 x NaN).
+ * sddp_cost_terms_range_device: d_x == NULL and d_u == NULL take the handle's own xs / us; both given take a caller's trajectory,
+ *   d_x [count][N + 1][nx] and d_u [count][N][nu], block i for instance first + i.  The parameters are those of the last sddp_solve*
+ *   launch (SDDP_ERR_ARG if no solve ran, if only one of d_x / d_u is given, for a range outside the handle, or for a horizon whose
+ *   addends do not fit one workgroup's 64 KB of LDS: (N + 1) (14 + 2 np) + 14 doubles, so N <= 96 fits on every build -- there is no chunked path); with per-instance
+ *   constants instance b is costed with its own robot's gains.  Asynchronous on the handle's stream, behind the solve; it writes nothing
+ *   but d_out and d_nodes and uses none of the slots' work buffers: no solve result, policy record, resume flag, log record or class
+ *   table changes, and the result of an instance does not depend on the range it was part of.  Every build has it.  (A handle with
+ *   user rows makes, on its first call, a second device copy of their table with zero weights.)
+ * sddp_cost_terms: the records of the handle's own plan into a host array; waits for the stream. */
+int  sddp_cost_terms_words(sddp_handle* h, int* words, int* families);
+int  sddp_cost_terms_name(int family, const char** name);
+int  sddp_cost_terms_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
+                                  double* d_out /*[count][16]*/, double* d_nodes /*[count][N + 1][14] or NULL*/);
+int  sddp_cost_terms(sddp_handle* h, int first, int count, double* out /*[count][16], host*/);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

@@ -67,6 +67,10 @@ AUDIT_WORDS = 16
  AUDIT_SLIP, AUDIT_RIGID_FOOT, AUDIT_DEFECT, AUDIT_DEFECT_NODE, AUDIT_NODES, AUDIT_STANCE_PAIRS) = range(14)
 # the words of one record of the stationarity certificate (include/sddp.h sddp_stationarity_range_device), by name
 STATIONARITY_FIELDS = ("stationarity", "node", "input", "scale", "lambda_0", "lambda_max", "defect", "nodes")
+# one record of the cost breakdown (include/sddp.h sddp_cost_terms_range_device): total | the families | largest | N.  The families'
+# names are the library's (sddp_cost_terms_name): load() reads them into COST_TERM_NAMES, empty until then
+COST_TERMS_WORDS, COST_TERMS_COLS = 16, 14
+COST_TERM_NAMES = ()
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = C.sizeof(SddpStats) // 8, C.sizeof(SddpStats) // 4
 STATS_F64_COST = SddpStats.cost.offset // 8
@@ -119,6 +123,10 @@ SYMBOLS = {
     "sddp_stationarity_words": (C.c_int, [_vp, _P(C.c_int)]),
     "sddp_stationarity_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "sddp_stationarity": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_cost_terms_words": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_cost_terms_name": (C.c_int, [C.c_int, _P(C.c_char_p)]),
+    "sddp_cost_terms_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sddp_cost_terms": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),
@@ -334,6 +342,11 @@ def load():
         fn.argtypes = args
     if lib.sddp_abi_version() != ABI_VERSION:
         raise RuntimeError("libsddp_hip.so ABI version mismatch")
+    global COST_TERM_NAMES
+    names, name = [], C.c_char_p()
+    while lib.sddp_cost_terms_name(len(names), C.byref(name)) == 0:
+        names.append(name.value.decode())
+    COST_TERM_NAMES = tuple(names)
     _lib = lib
     return lib
 

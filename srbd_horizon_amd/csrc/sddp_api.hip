@@ -1347,6 +1347,62 @@ int sddp_stationarity(sddp_handle* h, int first, int count, double* out) {
     return rc;
 }
 
+int sddp_cost_terms_words(sddp_handle* h, int* words, int* families) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!words || !families) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    *words = kCostTermsWords;
+    *families = kCostTermsFamilies;
+    return SDDP_OK;
+}
+
+int sddp_cost_terms_name(int family, const char** name) {
+    static const char* const names[kCostTermsFamilies] = {"r_tracking", "rdot_tracking", "w_tracking", "rel_pos", "min_f", "force_switch", "min_qddot",
+                                                          "zmp_tracking", "constraints", "friction_barrier", "bound_barrier", "user_rows",
+                                                          "unweighted"};
+    if (!name) return fail(nullptr, SDDP_ERR_ARG, "NULL argument");
+    if (family < 0 || family >= kCostTermsFamilies)
+        return fail(nullptr, SDDP_ERR_ARG, "sddp_cost_terms_name: family must be 0 .. " + std::to_string(kCostTermsFamilies - 1));
+    *name = names[family];
+    return SDDP_OK;
+}
+
+int sddp_cost_terms_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out, double* d_nodes) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if ((d_x == nullptr) != (d_u == nullptr))
+        return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
+    if (h->xr_dev && !h->xr_zero) {      // the user rows' table once more, its weight words (state rows | stage rows) zero: a group of one buffer
+        GroupBuf g[] = {{kXrWords * sizeof(double)}};
+        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_cost_terms_range_device: out of device memory");
+        double t[kXrWords];
+        fill_extra_table(h->consts, t);
+        for (int j = kXrWS; j < kXrC; ++j) t[j] = 0.0;
+        double* z = g[0];
+        if (const hipError_t e = hipMemcpy(z, t, sizeof(t), hipMemcpyHostToDevice); e != hipSuccess) {
+            release(h, z);
+            return fail(h, SDDP_ERR_HIP, std::string("hipMemcpy(xr_zero, t, sizeof(t), hipMemcpyHostToDevice): ") + hipGetErrorString(e));
+        }
+        h->xr_zero = z;
+    }
+    const bool own = d_x == nullptr;
+    return h->ops->launch_cost_terms(h, first, count, own ? h->xs : d_x, own ? h->us : d_u, own, h->xr_zero, d_out, d_nodes);
+}
+
+int sddp_cost_terms(sddp_handle* h, int first, int count, double* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t bytes = size_t(count) * kCostTermsWords * sizeof(double);
+    double* d_out = nullptr;
+    HIP_TRY(h, hipMalloc(&d_out, bytes));
+    int rc = sddp_cost_terms_range_device(h, first, count, nullptr, nullptr, d_out, nullptr);
+    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {
     if (!h || !x || !u || !p || !x_next) return SDDP_ERR_ARG;
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");

@@ -81,6 +81,9 @@ struct ModelOps {
     int (*launch_audit)(sddp_handle*, int, int, int, int, const double*, const double*, bool, double, double*) = nullptr;
     // the stationarity certificate: first, count, x, u, own (the handle's xs / us) or the caller's, out, lambda or null, reduced gradient or null
     int (*launch_stationarity)(sddp_handle*, int, int, const double*, const double*, bool, double*, double*, double*) = nullptr;
+    // the cost breakdown: first, count, x, u, own (the handle's xs / us) or the caller's, the user rows' table with zero weights or null, out,
+    // the per-node addends or null
+    int (*launch_cost_terms)(sddp_handle*, int, int, const double*, const double*, bool, const double*, double*, double*) = nullptr;
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);
@@ -127,6 +130,7 @@ struct sddp_handle {
     int last_lds = 0, last_per_cu = 0;
     double* box_dev = nullptr;      // lower[64] | upper[64] of the bound barrier (barrier builds)
     double* xr_dev = nullptr;       // user rows: coefficients | weights | constants (DevConsts::xr, "_x" builds)
+    double* xr_zero = nullptr;      // ... the same table with its weight words zeroed: made by the first cost breakdown (sddp_cost_terms_range_device)
     const double* last_params = nullptr;   // the parameter tensor of the last solve launch (continue launches, policy export, audit)
     // phase-level mode (sddp_debug_set_phase_mode, diagnostics): what sddp_backward / sddp_forward launch with.  Default (0, 0): the
     // Gauss-Newton sweep on open gaps, as those entry points always ran

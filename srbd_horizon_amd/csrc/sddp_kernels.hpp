@@ -1687,6 +1687,122 @@ __global__ __launch_bounds__(kWave) void stationarity_kernel(ConstsArg<Tab...> c
 }
 
 // -----------------------------------------------------------------------------------------------------------------
+// Cost breakdown (sddp_cost_terms_range_device): the cost of a whole-horizon trajectory family by family, kCostTermsWords doubles per
+// instance (include/sddp.h has the table).  No model code of its own: column 0 of a node is M::step / M::term_cost on the instance's
+// constants as they are, column 1 + f the same code on a copy that keeps family f's weights and has 0.0 in every other one, so the
+// terms of a family are formed and added exactly as inside the full cost.  The copy is made BY DATA (w' = keep ? w : 0.0, a pointer
+// select for the user rows' table, whose second copy `xr_zero` has zero weights), so the wave runs one instruction stream whatever
+// families its lanes hold; what diverges is k == N (term_cost) and what the model branches on itself.  One weight is no constant but
+// a parameter (M::P_WEIGHT, orientation_tracking_gain): the instance's parameter rows are staged in LDS twice, as they are and with
+// that column 0.0, and a column reads the second copy unless it is the total or `unweighted` -- the family of what is left when every
+// weight of DevConsts is 0.0.  A user build's rows may read any parameter, so there family 11 is evaluated on the rows as they are
+// and the node's `unweighted` is taken off it afterwards (the one place a family is a difference).
+// x [..][N + 1][NX], u [..][N][NU]; instance b = first + i reads block xoff + i of them (the handle's own xs / us: xoff = first; a
+// caller's: xoff = 0) and row b of P.  One wavefront per instance; the work items are the (node, column) pairs e = k * 14 + col,
+// strided over the lanes; M::step's next state is discarded.  The addends go to a tile [N + 1][14] in dynamic LDS (the launcher
+// refuses horizons whose tile and parameter copies exceed it) and from there to `nodes` when given; then lane col < 14 adds its
+// column in node order, which is the record: no lane mapping enters a sum.  Plain vector stores to out / nodes alone.
+constexpr int kCostTermsWords = 16, kCostTermsFamilies = 13, kCostTermsCols = kCostTermsFamilies + 1;
+template <class M>
+constexpr size_t cost_terms_lds(int N) {
+    return sizeof(double) * (size_t(N + 1) * (kCostTermsCols + (M::P_WEIGHT >= 0 ? 2 * M::NP : 0)) + kCostTermsCols);
+}
+// the constants of column col: the total (0) keeps everything, family f = col - 1 what include/sddp.h's table says
+__device__ __forceinline__ DevConsts cost_terms_consts(const DevConsts& c, const int col, const double* xr_zero) {
+    const int f = col - 1;
+    const bool all = col == 0;
+    DevConsts m = c;
+    m.w_rz = (all || f == 0) ? c.w_rz : 0.0;
+    m.w_rxy = (all || f == 0) ? c.w_rxy : 0.0;
+    m.w_rd = (all || f == 1) ? c.w_rd : 0.0;
+    m.w_w = (all || f == 2) ? c.w_w : 0.0;
+    m.w_rel = (all || f == 3) ? c.w_rel : 0.0;
+    m.w_f = (all || f == 4) ? c.w_f : 0.0;
+    m.w_sw = (all || f == 5) ? c.w_sw : 0.0;
+    m.gq = (all || f == 6) ? c.gq : 0.0;
+    m.w_zmp = (all || f == 7) ? c.w_zmp : 0.0;
+    m.w_pen = (all || f == 8) ? c.w_pen : 0.0;
+    m.w_rv = (all || f == 8) ? c.w_rv : 0.0;
+    m.bar_w = (all || f == 9) ? c.bar_w : 0.0;
+    m.box_w = (all || f == 10) ? c.box_w : 0.0;
+    m.xr = (all || f == 11) ? c.xr : xr_zero;
+    return m;
+}
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void cost_terms_kernel(ConstsArg<Tab...> consts, const double* __restrict__ xr_zero, int N, int first,
+                                                            int count, const double* __restrict__ x, const double* __restrict__ u, int xoff,
+                                                            const double* __restrict__ P, double* __restrict__ out,
+                                                            double* __restrict__ nodes) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NCOL = kCostTermsCols;
+    constexpr bool PW = M::P_WEIGHT >= 0;
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    double* tile = s;                                      // [N + 1][NCOL] the addends
+    double* sums = tile + size_t(N + 1) * NCOL;            // [NCOL] their sums
+    double* sp = sums + NCOL;                              // PW: [2][N + 1][NP] the parameters | with column P_WEIGHT = 0.0
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
+    const double* ub = u + size_t(xoff + i) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    const int items = (N + 1) * NCOL;
+    if constexpr (PW) {
+        for (int e = lane; e < (N + 1) * NP; e += kWave) {
+            const double v = Pb[e];
+            sp[e] = v;
+            sp[(N + 1) * NP + e] = e % NP == M::P_WEIGHT ? 0.0 : v;
+        }
+        wave_sync();
+    }
+    for (int e = lane; e < items; e += kWave) {
+        const int k = e / NCOL, col = e % NCOL;
+        const DevConsts m = cost_terms_consts(c, col, xr_zero);
+        const double* pk = Pb + size_t(k) * NP;
+        if constexpr (PW) {
+            const bool as_is = col == 0 || col == NCOL - 1 || (M::HAS_UR && col == NCOL - 2);
+            pk = sp + (as_is ? 0 : (N + 1) * NP) + k * NP;
+        }
+        const double* xk = xb + size_t(k) * NX;
+        double v;
+        if (k == N) {
+            v = M::term_cost(m, xk, pk);
+        } else {
+            double xn[NX];
+            v = M::step(m, xk, ub + size_t(k) * NU, pk, k, xn);
+        }
+        tile[e] = v;
+    }
+    wave_sync();
+    if constexpr (M::HAS_UR && PW) {
+        for (int k = lane; k <= N; k += kWave) tile[k * NCOL + NCOL - 2] -= tile[k * NCOL + NCOL - 1];
+        wave_sync();
+    }
+    if (nodes) {
+        double* no = nodes + size_t(i) * items;
+        for (int e = lane; e < items; e += kWave) no[e] = tile[e];
+    }
+    if (lane < NCOL) {
+        double acc = 0.0;
+        for (int k = 0; k <= N; ++k) acc += tile[k * NCOL + lane];
+        sums[lane] = acc;
+        out[size_t(i) * kCostTermsWords + lane] = acc;
+    }
+    wave_sync();
+    if (lane == 0) {
+        int best = 0;
+        bool nan = false;
+        for (int f = 0; f < kCostTermsFamilies - 1; ++f) {
+            const double v = sums[1 + f];
+            nan = nan || v != v;
+            if (v > sums[1 + best]) best = f;
+        }
+        out[size_t(i) * kCostTermsWords + 14] = nan ? -1.0 : double(best);
+        out[size_t(i) * kCostTermsWords + 15] = double(N);
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------------------
 // one wavefront per knot: lane 0 runs the scalar model code, all lanes expand the dense tiles
 template <class M>
 __global__ __launch_bounds__(kWave) void eval_knots_kernel(DevConsts c, int N, int nk, const int* __restrict__ kk,

@@ -248,6 +248,23 @@ int launch_stationarity(sddp_handle* h, int first, int count, const double* dx, 
     });
 }
 
+// the cost breakdown (cost_terms_kernel): one wavefront per instance of the range, dynamic LDS sized from N (cost_terms_lds: the tile of
+// addends and, where a parameter is a weight, two copies of the instance's parameter rows) -- no kernel_slots entry, no work buffer.
+// A horizon whose LDS exceeds the 64 KB a kernel has without an attribute is refused, there is no chunked path.  Every build has it.
+// own: as launch_stationarity.  xr_zero: the user rows' table with zero weights (null: the build has no such table).
+template <class M>
+int launch_cost_terms(sddp_handle* h, int first, int count, const double* dx, const double* du, bool own, const double* xr_zero, double* dout,
+                      double* dnodes) {
+    const size_t lds = cost_terms_lds<M>(h->N);
+    if (lds > size_t(64) * 1024)
+        return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: the horizon's tile of addends needs " + std::to_string(lds) +
+                                         " bytes of LDS, more than the 65536 one workgroup has here");
+    return with_table<M>(h, [&](auto... tab) {
+        return launch(h, cost_terms_kernel<M, decltype(tab)...>, count, kWave, lds, consts_arg(h, tab...), xr_zero, h->N, first, count, dx, du,
+                      own ? first : 0, h->last_params, dout, dnodes);
+    });
+}
+
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
     return with_table<M>(h, [&](auto... tab) {
@@ -281,6 +298,7 @@ ModelOps make_ops(const char* name) {
     if constexpr (has_policy<M>()) { o.launch_policy = launch_policy<M>; o.launch_policy_rollout = launch_policy_rollout<M>; }
     o.launch_audit = launch_audit<M>;
     o.launch_stationarity = launch_stationarity<M>;
+    o.launch_cost_terms = launch_cost_terms<M>;
     o.launch_model_step = launch_model_step<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
     return o;

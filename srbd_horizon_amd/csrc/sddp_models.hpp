@@ -345,6 +345,9 @@ struct SrbdModel {
     // what the class label reads (sddp.h sddp_enable_auto_classes; ModelOps::col_cmd / col_sw): the commanded velocity rdot_ref x, y and
     // the switch of the first contact of the left and of the right foot, p_sw(p, 0) and p_sw(p, CM)
     static constexpr int P_CMD0 = 0, P_CMD1 = 1, P_SW_L = CS ? 8 : 17, P_SW_R = CS ? 8 + 2 * (NC / 2) : 18;
+    // the one weight that is a parameter, not a constant: orientation_tracking_gain (p_otg).  The cost breakdown (cost_terms_kernel)
+    // zeroes this column where it zeroes the weights of DevConsts; what it multiplies is the breakdown's family `unweighted`
+    static constexpr int P_WEIGHT = 6;
     // the bound barrier's masks and bound arrays (sddp_model_consts.lower / upper) cover 64 entries of z: models with more
     // (srbd61: 109) take the friction-cone barrier only -- sddp_create refuses bound_barrier_weight > 0 for them, as the oracle does
     static constexpr bool BOX = BAR_ && (CS_ ? 13 + 12 * NC_ : 13 + 3 * NC_) <= 64;
@@ -1428,6 +1431,7 @@ struct LipModel {
     template <class QM> __device__ __forceinline__ static void add_const_rows(const DevConsts&, QM, int, int) {}   // (one Q block per thread: unused)
     static constexpr int NX = 30, NU = 15, NZ = 45, NPB = 11, NP = NPB + NXR;
     static constexpr int P_CMD0 = 0, P_CMD1 = 1, P_SW_L = 4, P_SW_R = 8;      // the class label's columns (see SrbdModel): p_sw(p, 0), p_sw(p, 2)
+    static constexpr int P_WEIGHT = -1;                                        // no parameter is a weight (see SrbdModel)
     static constexpr int XR = 0, XC = 3, XRD = 15, XCD = 18;
     static constexpr int REC_G = 0, NREC = NZ, NSO2T = 0, NSO2L = 0;
     static constexpr bool SO2 = false;

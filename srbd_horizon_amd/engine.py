@@ -269,6 +269,43 @@ class DdpEngine:
         self.synchronize()
         return out.cpu().numpy(), lam.cpu().numpy(), grad.cpu().numpy()
 
+    # ---- cost breakdown: the cost of a plan family by family, computed on the device (include/sddp.h) ----------------------------------
+    def cost_terms_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, nodes=None):
+        """The cost-breakdown records of the instances [first, first + count) into the device tensor out [count, 16]: total | the 13
+        families of _lib.COST_TERM_NAMES | the largest of the families 0 .. 11 | N.  x, u None: the handle's own plan; else device
+        tensors x [count, N + 1, nx], u [count, N, nu], a caller's whole-horizon trajectory.  nodes [count, N + 1, 14]: a device tensor
+        for the per-node addends (column 0 the total, column 1 + f family f), or None.  Every build has it; asynchronous, behind the
+        solve."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_cost_terms_range_device(self.h, int(first), n, self._dev_or_null(x, (n, self.N + 1, self.nx)),
+                                                        self._dev_or_null(u, (n, self.N, self.nu)), self._dev(out, (n, _lib.COST_TERMS_WORDS)),
+                                                        self._dev_or_null(nodes, (n, self.N + 1, _lib.COST_TERMS_COLS))))
+        return out
+
+    def cost_terms(self, first: int = 0, count: int | None = None, nodes: bool = False):
+        """The cost breakdown of the handle's own plan as a dict of numpy arrays: "total" [count], one entry [count] per family name
+        of _lib.COST_TERM_NAMES, "largest" [count] (the name of the largest of the families 0 .. 11, "" where one of them is NaN) and
+        "record" [count, 16], the raw records; nodes: also "nodes" [count, N + 1, 14], the per-node addends.  Waits for the stream."""
+        n = self._count(first, count)
+        if not nodes:
+            rec = np.empty((max(n, 0), _lib.COST_TERMS_WORDS))
+            self._chk(self.lib.sddp_cost_terms(self.h, int(first), n, _lib.ptr(rec)))
+            per_node = None
+        else:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out = torch.empty((max(n, 0), _lib.COST_TERMS_WORDS), dtype=torch.float64, device=dev)
+            nd = torch.empty((max(n, 0), self.N + 1, _lib.COST_TERMS_COLS), dtype=torch.float64, device=dev)
+            self.cost_terms_device(out, first, n, nodes=nd)
+            self.synchronize()
+            rec, per_node = out.cpu().numpy(), nd.cpu().numpy()
+        names = _lib.COST_TERM_NAMES
+        res = {"total": rec[:, 0].copy(), **{name: rec[:, 1 + f].copy() for f, name in enumerate(names)},
+               "largest": np.array([names[int(i)] if i >= 0 else "" for i in rec[:, 14]], dtype=object), "record": rec}
+        if per_node is not None:
+            res["nodes"] = per_node
+        return res
+
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
         self._chk(self.lib.sddp_is_converged(self.h, _lib.ptr(f)))

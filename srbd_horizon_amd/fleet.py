@@ -142,6 +142,17 @@ class FleetQueue:
         self.eng.stationarity_device(out[:n], 0, n, lam=None if lam is None else lam[:n], grad=None if grad is None else grad[:n])
         return n
 
+    def cost_terms(self, out, nodes=None):
+        """The cost-breakdown records (DdpEngine.cost_terms_device) of the instances the last flush / solve_sliced / solve_within
+        solved, into the first n rows of the device tensor out [>= n, 16] (nodes [>= n, N + 1, 14]: likewise, or None); launched behind
+        whatever that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet server which gain a
+        fleet's cost is made of before it turns one."""
+        n = self.solved
+        if n == 0:
+            return 0
+        self.eng.cost_terms_device(out[:n], 0, n, nodes=None if nodes is None else nodes[:n])
+        return n
+
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
         `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the
