@@ -412,6 +412,58 @@ int validate_options(sddp_handle* h, const sddp_options& o) {
     return SDDP_OK;
 }
 
+// device->host on the handle's stream, waited for (sddp_synchronize: the timing events of the launches in front are read as well)
+int download(sddp_handle* h, void* dst, const void* src, size_t bytes) {
+    HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    return sddp_synchronize(h);
+}
+
+// The plan inspectors (sddp_handle.hpp PlanSource): what every <fn> = sddp_*_range_device of theirs checks first, and the trajectory
+// it reads: the handle's own plan (d_x and d_u both NULL) or the caller's.
+int plan_source(sddp_handle* h, const char* fn, int first, int count, const double* d_x, const double* d_u, const double* d_out, PlanSource* s) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, std::string(fn) + ": no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if ((d_x == nullptr) != (d_u == nullptr))
+        return fail(h, SDDP_ERR_ARG, std::string(fn) + ": d_x and d_u are both NULL (the handle's own plan) or both given");
+    *s = d_x ? PlanSource{d_x, d_u, 0} : PlanSource{h->xs, h->us, first};
+    return SDDP_OK;
+}
+// ... and their host-array twins: range_device(d_out) on the handle's own plan into a scratch buffer of `words` doubles per instance,
+// made and freed by the call, and that buffer into out
+template <class F>
+int inspect_to_host(sddp_handle* h, int first, int count, int words, double* out, F range_device) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t bytes = size_t(count) * words * sizeof(double);
+    double* d_out = nullptr;
+    HIP_TRY(h, hipMalloc(&d_out, bytes));
+    int rc = range_device(d_out);
+    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+// h->xr_zero, made by the first cost breakdown of a handle with user rows: their table once more, its weight words (state rows | stage
+// rows) zero: a group of one buffer
+int make_xr_zero(sddp_handle* h) {
+    if (!h->xr_dev || h->xr_zero) return SDDP_OK;
+    GroupBuf g[] = {{kXrWords * sizeof(double)}};
+    if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_cost_terms_range_device: out of device memory");
+    double t[kXrWords];
+    fill_extra_table(h->consts, t);
+    for (int j = kXrWS; j < kXrC; ++j) t[j] = 0.0;
+    double* z = g[0];
+    if (const hipError_t e = hipMemcpy(z, t, sizeof(t), hipMemcpyHostToDevice); e != hipSuccess) {
+        release(h, z);
+        return fail(h, SDDP_ERR_HIP, std::string("hipMemcpy(xr_zero, t, sizeof(t), hipMemcpyHostToDevice): ") + hipGetErrorString(e));
+    }
+    h->xr_zero = z;
+    return SDDP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -671,11 +723,6 @@ static int upload(sddp_handle* h, void* dst, const void* src, size_t bytes) {
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->stage.up_off = 0;
     return SDDP_OK;
-}
-// the counterpart: device->host, waited for (sddp_synchronize: the timing events of the launches in front are read as well)
-static int download(sddp_handle* h, void* dst, const void* src, size_t bytes) {
-    HIP_TRY(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    return sddp_synchronize(h);
 }
 
 // ---- host-pointer setters -------------------------------------------------------------------------------------------
@@ -1287,32 +1334,21 @@ int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, 
 
 int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
                             double friction_coefficient, double* d_out) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: no solve has run on this handle");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if ((d_x == nullptr) != (d_u == nullptr)) return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
-    const bool own = d_x == nullptr;
-    if (own && (start != 0 || steps != h->N))
+    PlanSource src;
+    if (const int rc = plan_source(h, "sddp_audit_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
+    if (!d_x && (start != 0 || steps != h->N))
         return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: the handle's own plan is audited whole, start = 0 and steps = " + std::to_string(h->N));
     if (start < 0 || steps < 1 || start > h->N - steps)
         return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->N));
     // the call's coefficient, or the handle's: linearised as DevConsts::mu_lin is
     const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
-    return h->ops->launch_audit(h, first, count, start, steps, own ? h->xs : d_x, own ? h->us : d_u, own, mu / sqrt(2.0), d_out);
+    return h->ops->launch_audit(h, first, count, start, steps, src, mu / sqrt(2.0), d_out);
 }
 
 int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    const size_t bytes = size_t(count) * SDDP_AUDIT_WORDS * sizeof(double);
-    double* d_out = nullptr;
-    HIP_TRY(h, hipMalloc(&d_out, bytes));
-    int rc = sddp_audit_range_device(h, first, count, 0, h->N, nullptr, nullptr, friction_coefficient, d_out);
-    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
-    (void)hipFree(d_out);
-    return rc;
+    return inspect_to_host(h, first, count, SDDP_AUDIT_WORDS, out, [&](double* d_out) {
+        return sddp_audit_range_device(h, first, count, 0, h->N, nullptr, nullptr, friction_coefficient, d_out);
+    });
 }
 
 int sddp_stationarity_words(sddp_handle* h, int* words) {
@@ -1324,27 +1360,15 @@ int sddp_stationarity_words(sddp_handle* h, int* words) {
 
 int sddp_stationarity_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out,
                                    double* d_lambda, double* d_grad) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_stationarity_range_device: no solve has run on this handle");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if ((d_x == nullptr) != (d_u == nullptr))
-        return fail(h, SDDP_ERR_ARG, "sddp_stationarity_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
-    const bool own = d_x == nullptr;
-    return h->ops->launch_stationarity(h, first, count, own ? h->xs : d_x, own ? h->us : d_u, own, d_out, d_lambda, d_grad);
+    PlanSource src;
+    if (const int rc = plan_source(h, "sddp_stationarity_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
+    return h->ops->launch_stationarity(h, first, count, src, d_out, d_lambda, d_grad);
 }
 
 int sddp_stationarity(sddp_handle* h, int first, int count, double* out) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    const size_t bytes = size_t(count) * kStationarityWords * sizeof(double);
-    double* d_out = nullptr;
-    HIP_TRY(h, hipMalloc(&d_out, bytes));
-    int rc = sddp_stationarity_range_device(h, first, count, nullptr, nullptr, d_out, nullptr, nullptr);
-    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
-    (void)hipFree(d_out);
-    return rc;
+    return inspect_to_host(h, first, count, kStationarityWords, out, [&](double* d_out) {
+        return sddp_stationarity_range_device(h, first, count, nullptr, nullptr, d_out, nullptr, nullptr);
+    });
 }
 
 int sddp_cost_terms_words(sddp_handle* h, int* words, int* families) {
@@ -1367,40 +1391,16 @@ int sddp_cost_terms_name(int family, const char** name) {
 }
 
 int sddp_cost_terms_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out, double* d_nodes) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: no solve has run on this handle");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (!d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if ((d_x == nullptr) != (d_u == nullptr))
-        return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: d_x and d_u are both NULL (the handle's own plan) or both given");
-    if (h->xr_dev && !h->xr_zero) {      // the user rows' table once more, its weight words (state rows | stage rows) zero: a group of one buffer
-        GroupBuf g[] = {{kXrWords * sizeof(double)}};
-        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_cost_terms_range_device: out of device memory");
-        double t[kXrWords];
-        fill_extra_table(h->consts, t);
-        for (int j = kXrWS; j < kXrC; ++j) t[j] = 0.0;
-        double* z = g[0];
-        if (const hipError_t e = hipMemcpy(z, t, sizeof(t), hipMemcpyHostToDevice); e != hipSuccess) {
-            release(h, z);
-            return fail(h, SDDP_ERR_HIP, std::string("hipMemcpy(xr_zero, t, sizeof(t), hipMemcpyHostToDevice): ") + hipGetErrorString(e));
-        }
-        h->xr_zero = z;
-    }
-    const bool own = d_x == nullptr;
-    return h->ops->launch_cost_terms(h, first, count, own ? h->xs : d_x, own ? h->us : d_u, own, h->xr_zero, d_out, d_nodes);
+    PlanSource src;
+    if (const int rc = plan_source(h, "sddp_cost_terms_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
+    if (const int rc = make_xr_zero(h); rc != SDDP_OK) return rc;
+    return h->ops->launch_cost_terms(h, first, count, src, h->xr_zero, d_out, d_nodes);
 }
 
 int sddp_cost_terms(sddp_handle* h, int first, int count, double* out) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    const size_t bytes = size_t(count) * kCostTermsWords * sizeof(double);
-    double* d_out = nullptr;
-    HIP_TRY(h, hipMalloc(&d_out, bytes));
-    int rc = sddp_cost_terms_range_device(h, first, count, nullptr, nullptr, d_out, nullptr);
-    if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
-    (void)hipFree(d_out);
-    return rc;
+    return inspect_to_host(h, first, count, kCostTermsWords, out, [&](double* d_out) {
+        return sddp_cost_terms_range_device(h, first, count, nullptr, nullptr, d_out, nullptr);
+    });
 }
 
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {

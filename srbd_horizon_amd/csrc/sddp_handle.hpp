@@ -47,6 +47,16 @@ struct SolveChoice {
     size_t lds;
 };
 
+// The trajectory a plan inspector reads (plan audit, stationarity certificate, cost breakdown: sddp_api.hip plan_source).  An inspector
+// runs one wavefront per instance of a range [first, first + count) of a handle that has solved at least once; instance first + i reads
+// trajectory block xoff + i of x / u -- the handle's own plan {h->xs, h->us, first} or a caller's trajectory {d_x, d_u, 0}, whose block
+// i belongs to instance first + i --, row first + i of the last solve's parameters and its own constants, and stores to nothing but
+// the caller's outputs.
+struct PlanSource {
+    const double *x, *u;
+    int xoff;
+};
+
 // what a model build is and provides (sddp_launch.hpp: make_ops<M>)
 struct ModelOps {
     // the build's key: a handle's build is the one whose model and traits are the ones asked for (sddp_api.hip model_ops)
@@ -77,13 +87,12 @@ struct ModelOps {
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
     // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
     int (*launch_policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
-    // the plan audit: first, count, start, steps, x, u, own (the handle's xs / us) or the caller's, linearised friction coefficient, out
-    int (*launch_audit)(sddp_handle*, int, int, int, int, const double*, const double*, bool, double, double*) = nullptr;
-    // the stationarity certificate: first, count, x, u, own (the handle's xs / us) or the caller's, out, lambda or null, reduced gradient or null
-    int (*launch_stationarity)(sddp_handle*, int, int, const double*, const double*, bool, double*, double*, double*) = nullptr;
-    // the cost breakdown: first, count, x, u, own (the handle's xs / us) or the caller's, the user rows' table with zero weights or null, out,
-    // the per-node addends or null
-    int (*launch_cost_terms)(sddp_handle*, int, int, const double*, const double*, bool, const double*, double*, double*) = nullptr;
+    // the plan inspectors (PlanSource): first, count, [audit: start, steps,] the trajectory, then the inspector's own arguments --
+    // audit: linearised friction coefficient, out; stationarity: out, lambda or null, reduced gradient or null; cost breakdown: the
+    // user rows' table with zero weights or null, out, the per-node addends or null
+    int (*launch_audit)(sddp_handle*, int, int, int, int, PlanSource, double, double*) = nullptr;
+    int (*launch_stationarity)(sddp_handle*, int, int, PlanSource, double*, double*, double*) = nullptr;
+    int (*launch_cost_terms)(sddp_handle*, int, int, PlanSource, const double*, double*, double*) = nullptr;
     int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);

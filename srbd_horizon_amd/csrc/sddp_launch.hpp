@@ -115,13 +115,20 @@ int kernel_slots(sddp_handle* h, Fn kern, int cap, int* slots) {
 template <class M>
 constexpr int solve_cap(int wps) { return use_mw<M>() ? 0 : 4 * (wps >= 2 ? 2 : 1); }
 
+// A kernel that takes the constants first (ConstsArg<Tab...>) on `grid` workgroups of one wavefront: pick(tab...) names its
+// instantiation, and the handle's constants, or its table in their place, go in front of args..., which are the kernel's remaining
+// parameters in its own order.  No kernel_slots entry (at most 64 KB of LDS, no attribute) and no work buffer.
+template <class M, class Pick, class... A>
+int launch_waves(sddp_handle* h, Pick pick, int grid, size_t lds, const A&... args) {
+    return with_table<M>(h, [&](auto... tab) { return launch(h, pick(tab...), grid, kWave, lds, consts_arg(h, tab...), args...); });
+}
+// the pick of a kernel template <M, Tab...>
+#define SDDP_PICK(kernel) [](auto... tab) { return kernel<M, decltype(tab)...>; }
+
 // the queue_order 2 / 3 pre-pass: the initial cost of every instance of the launch, into h->cold.qkey / h->cold.order_in
 template <class M>
 int launch_cost_keys(sddp_handle* h, const SolveArgs& a, int first, int count) {
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, queue_cost_key_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), a.N, first, count, a.x0, a.P, a.xs, a.us,
-                      h->cold.qkey, h->cold.order_in);
-    });
+    return launch_waves<M>(h, SDDP_PICK(queue_cost_key_kernel), count, 0, a.N, first, count, a.x0, a.P, a.xs, a.us, h->cold.qkey, h->cold.order_in);
 }
 
 // The solve kernels of variant V as the handle launches them: f(pick, extra...), with pick(w) the kernel of the build for w wavefronts
@@ -218,58 +225,40 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
     });
 }
 
-// the exported policy rolled out through the model from a measured state (policy_rollout_kernel): one wavefront per instance of
-// the range, static LDS only -- no kernel_slots entry, no work buffer.  has_policy<M>() builds only, like launch_policy.
+// the exported policy rolled out through the model from a measured state: one wavefront per instance of the range, static LDS only.
+// has_policy<M>() builds only, like launch_policy.
 template <class M>
 int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int steps, const double* dxm, double* dx, double* du, double* dcost) {
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, policy_rollout_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, start, steps, h->xs,
-                      h->us, h->last_params, (const double*)h->pol.policy, h->policy_words(), dxm, dx, du, dcost);
-    });
+    return launch_waves<M>(h, SDDP_PICK(policy_rollout_kernel), count, 0, h->N, first, count, start, steps, h->xs, h->us, h->last_params,
+                           (const double*)h->pol.policy, h->policy_words(), dxm, dx, du, dcost);
 }
 
-// the plan audit (plan_audit_kernel): one wavefront per instance of the range, nothing but registers -- no kernel_slots entry, no work
-// buffer.  Every build has it.  own: the handle's xs / us (block first + i), else the caller's trajectory (block i).
+// The plan inspectors (sddp_handle.hpp PlanSource): one wavefront per instance of the range.  Every build has them.
+// the plan audit: nothing but registers
 template <class M>
-int launch_audit(sddp_handle* h, int first, int count, int start, int steps, const double* dx, const double* du, bool own, double ml, double* dout) {
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, plan_audit_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, start, steps, dx, du,
-                      own ? first : 0, h->last_params, ml, dout);
-    });
+int launch_audit(sddp_handle* h, int first, int count, int start, int steps, PlanSource s, double ml, double* dout) {
+    return launch_waves<M>(h, SDDP_PICK(plan_audit_kernel), count, 0, h->N, first, count, start, steps, s.x, s.u, s.xoff, h->last_params, ml, dout);
 }
-
-// the stationarity certificate (stationarity_kernel): one wavefront per instance of the range, static LDS only -- no kernel_slots entry,
-// no work buffer.  Every build has it.  own: the handle's xs / us (block first + i), else the caller's whole-horizon trajectory (block i).
+// the stationarity certificate: static LDS only
 template <class M>
-int launch_stationarity(sddp_handle* h, int first, int count, const double* dx, const double* du, bool own, double* dout, double* dlam, double* dgrad) {
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, stationarity_kernel<M, decltype(tab)...>, count, kWave, 0, consts_arg(h, tab...), h->N, first, count, dx, du, own ? first : 0,
-                      h->last_params, dout, dlam, dgrad);
-    });
+int launch_stationarity(sddp_handle* h, int first, int count, PlanSource s, double* dout, double* dlam, double* dgrad) {
+    return launch_waves<M>(h, SDDP_PICK(stationarity_kernel), count, 0, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dout, dlam, dgrad);
 }
-
-// the cost breakdown (cost_terms_kernel): one wavefront per instance of the range, dynamic LDS sized from N (cost_terms_lds: the tile of
-// addends and, where a parameter is a weight, two copies of the instance's parameter rows) -- no kernel_slots entry, no work buffer.
-// A horizon whose LDS exceeds the 64 KB a kernel has without an attribute is refused, there is no chunked path.  Every build has it.
-// own: as launch_stationarity.  xr_zero: the user rows' table with zero weights (null: the build has no such table).
+// the cost breakdown: dynamic LDS sized from N (cost_terms_lds: the tile of addends and, where a parameter is a weight, two copies of
+// the instance's parameter rows).  A horizon whose LDS exceeds the 64 KB a kernel has without an attribute is refused, there is no
+// chunked path.  xr_zero: the user rows' table with zero weights (null: the build has no such table).
 template <class M>
-int launch_cost_terms(sddp_handle* h, int first, int count, const double* dx, const double* du, bool own, const double* xr_zero, double* dout,
-                      double* dnodes) {
+int launch_cost_terms(sddp_handle* h, int first, int count, PlanSource s, const double* xr_zero, double* dout, double* dnodes) {
     const size_t lds = cost_terms_lds<M>(h->N);
     if (lds > size_t(64) * 1024)
         return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: the horizon's tile of addends needs " + std::to_string(lds) +
                                          " bytes of LDS, more than the 65536 one workgroup has here");
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, cost_terms_kernel<M, decltype(tab)...>, count, kWave, lds, consts_arg(h, tab...), xr_zero, h->N, first, count, dx, du,
-                      own ? first : 0, h->last_params, dout, dnodes);
-    });
+    return launch_waves<M>(h, SDDP_PICK(cost_terms_kernel), count, lds, xr_zero, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dout, dnodes);
 }
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
-    return with_table<M>(h, [&](auto... tab) {
-        return launch(h, model_step_kernel<M, decltype(tab)...>, (h->B + kWave - 1) / kWave, kWave, 0, consts_arg(h, tab...), h->B, k, dx, du, dp, dxn);
-    });
+    return launch_waves<M>(h, SDDP_PICK(model_step_kernel), (h->B + kWave - 1) / kWave, 0, h->B, k, dx, du, dp, dxn);
 }
 
 template <class M>

@@ -208,77 +208,79 @@ class DdpEngine:
         import torch
         n = self._count(first, count)
         s = int(self.policy_words()[1] - start if steps is None else steps)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        xm = torch.from_numpy(self._c(x_meas, (n, self.nx))).to(dev)
-        x = torch.empty((n, max(s, 0) + 1, self.nx), dtype=torch.float64, device=dev)
-        u = torch.empty((n, max(s, 0), self.nu), dtype=torch.float64, device=dev)
-        cost = torch.empty((n,), dtype=torch.float64, device=dev)
-        self.policy_rollout_device(xm, x, u, cost, first, n, start, s)
-        self.synchronize()
-        return x.cpu().numpy(), u.cpu().numpy(), cost.cpu().numpy()
+        xm = torch.from_numpy(self._c(x_meas, (n, self.nx))).cuda()
+        return self._to_numpy(n, [(max(s, 0) + 1, self.nx), (max(s, 0), self.nu), ()],
+                              lambda x, u, cost: self.policy_rollout_device(xm, x, u, cost, first, n, start, s))
 
-    # ---- plan audit: constraint violations of a plan, computed on the device (include/sddp.h) -----------------------------------
+    # ---- the plan inspectors: audit, stationarity certificate, cost breakdown ("Plan inspectors") ----------------
+    # Each reads the instances [first, first + count) of a handle that has solved: the handle's own plan (x, u None) or the caller's
+    # device tensors, whose block i belongs to instance first + i.  Every build has them; the *_device forms are asynchronous,
+    # behind the solve, and store to nothing but their outputs.
+    def _plan(self, n, x, u, steps=None):
+        """the trajectory pointers of an inspector: x [n, steps + 1, nx], u [n, steps, nu] (steps None: N), or None: NULL"""
+        if x is None and u is None:
+            return None, None                  # the handle's own plan
+        steps = self.N if steps is None else max(steps, 0)      # (a refused steps < 1 reaches the library, which says what is allowed)
+        return self._dev_or_null(x, (n, steps + 1, self.nx)), self._dev_or_null(u, (n, steps, self.nu))
+
+    def _to_numpy(self, n, shapes, run):
+        """run(*t) on fresh float64 CUDA tensors t[j] of shape [max(n, 0), *shapes[j]]; waits for the stream -> them as numpy arrays"""
+        import torch
+        ts = [torch.empty((max(n, 0), *shape), dtype=torch.float64, device="cuda") for shape in shapes]
+        run(*ts)
+        self.synchronize()
+        return tuple(t.cpu().numpy() for t in ts)
+
+    def _own_records(self, fn, first, count, words, *args):
+        """the host-array twin `fn` of an inspector: the records [count, words] of the handle's own plan; waits for the stream"""
+        n = self._count(first, count)
+        out = np.empty((max(n, 0), words))
+        self._chk(fn(self.h, int(first), n, *args, _lib.ptr(out)))
+        return out
+
     def audit_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, start: int = 0, steps: int | None = None,
                      friction: float = 0.0):
         """The audit records (_lib.AUDIT_* words) of the instances [first, first + count) into the device tensor out
         [count, AUDIT_WORDS].  x, u None: the handle's own plan; else device tensors x [count, steps + 1, nx], u [count, steps, nu]
         whose row j sits at node start + j (the outputs of policy_rollout_device); steps None: to node N.  friction > 0: the ground's
-        coefficient for this call, else the handle's friction_cone_coefficient.  Every build has it; asynchronous, behind the solve."""
+        coefficient for this call, else the handle's friction_cone_coefficient."""
         n = self._count(first, count)
         s = int(self.N - start if steps is None else steps)
-        rows = max(s, 0)                      # (a refused steps < 1 reaches the library, which says what is allowed)
-        self._chk(self.lib.sddp_audit_range_device(self.h, int(first), n, int(start), s, self._dev_or_null(x, (n, rows + 1, self.nx)),
-                                                   self._dev_or_null(u, (n, rows, self.nu)), float(friction),
+        self._chk(self.lib.sddp_audit_range_device(self.h, int(first), n, int(start), s, *self._plan(n, x, u, s), float(friction),
                                                    self._dev(out, (n, _lib.AUDIT_WORDS))))
         return out
 
     def audit(self, first: int = 0, count: int | None = None, friction: float = 0.0):
         """The audit records [count, AUDIT_WORDS] of the handle's own plan as a numpy array; waits for the stream."""
-        n = self._count(first, count)
-        out = np.empty((max(n, 0), _lib.AUDIT_WORDS))
-        self._chk(self.lib.sddp_audit(self.h, int(first), n, float(friction), _lib.ptr(out)))
-        return out
+        return self._own_records(self.lib.sddp_audit, first, count, _lib.AUDIT_WORDS, float(friction))
 
-    # ---- stationarity certificate: reduced gradient and costates of a plan, computed on the device (include/sddp.h) ------------------
     def stationarity_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, lam=None, grad=None):
         """The stationarity records (_lib.STATIONARITY_FIELDS) of the instances [first, first + count) into the device tensor out
         [count, 8].  x, u None: the handle's own plan; else device tensors x [count, N + 1, nx], u [count, N, nu], a caller's
         whole-horizon trajectory.  lam [count, N + 1, nx] / grad [count, N, nu]: device tensors for every costate / reduced gradient,
-        or None.  Every build has it; asynchronous, behind the solve."""
+        or None."""
         n = self._count(first, count)
-        self._chk(self.lib.sddp_stationarity_range_device(self.h, int(first), n, self._dev_or_null(x, (n, self.N + 1, self.nx)),
-                                                          self._dev_or_null(u, (n, self.N, self.nu)),
-                                                          self._dev(out, (n, len(_lib.STATIONARITY_FIELDS))),
-                                                          self._dev_or_null(lam, (n, self.N + 1, self.nx)),
-                                                          self._dev_or_null(grad, (n, self.N, self.nu))))
+        self._chk(self.lib.sddp_stationarity_range_device(self.h, int(first), n, *self._plan(n, x, u),
+                                                          self._dev(out, (n, len(_lib.STATIONARITY_FIELDS))), *self._plan(n, lam, grad)))
         return out
 
     def stationarity(self, first: int = 0, count: int | None = None, full: bool = False):
         """The stationarity records [count, 8] of the handle's own plan as a numpy array; full: -> (records, lambda [count, N + 1, nx],
         s [count, N, nu]).  Waits for the stream."""
-        n = self._count(first, count)
+        words = len(_lib.STATIONARITY_FIELDS)
         if not full:
-            out = np.empty((max(n, 0), len(_lib.STATIONARITY_FIELDS)))
-            self._chk(self.lib.sddp_stationarity(self.h, int(first), n, _lib.ptr(out)))
-            return out
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        mk = lambda *shape: torch.empty((max(n, 0), *shape), dtype=torch.float64, device=dev)
-        out, lam, grad = mk(len(_lib.STATIONARITY_FIELDS)), mk(self.N + 1, self.nx), mk(self.N, self.nu)
-        self.stationarity_device(out, first, n, lam=lam, grad=grad)
-        self.synchronize()
-        return out.cpu().numpy(), lam.cpu().numpy(), grad.cpu().numpy()
+            return self._own_records(self.lib.sddp_stationarity, first, count, words)
+        n = self._count(first, count)
+        return self._to_numpy(n, [(words,), (self.N + 1, self.nx), (self.N, self.nu)],
+                              lambda out, lam, grad: self.stationarity_device(out, first, n, lam=lam, grad=grad))
 
-    # ---- cost breakdown: the cost of a plan family by family, computed on the device (include/sddp.h) ----------------------------------
     def cost_terms_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, nodes=None):
         """The cost-breakdown records of the instances [first, first + count) into the device tensor out [count, 16]: total | the 13
         families of _lib.COST_TERM_NAMES | the largest of the families 0 .. 11 | N.  x, u None: the handle's own plan; else device
         tensors x [count, N + 1, nx], u [count, N, nu], a caller's whole-horizon trajectory.  nodes [count, N + 1, 14]: a device tensor
-        for the per-node addends (column 0 the total, column 1 + f family f), or None.  Every build has it; asynchronous, behind the
-        solve."""
+        for the per-node addends (column 0 the total, column 1 + f family f), or None."""
         n = self._count(first, count)
-        self._chk(self.lib.sddp_cost_terms_range_device(self.h, int(first), n, self._dev_or_null(x, (n, self.N + 1, self.nx)),
-                                                        self._dev_or_null(u, (n, self.N, self.nu)), self._dev(out, (n, _lib.COST_TERMS_WORDS)),
+        self._chk(self.lib.sddp_cost_terms_range_device(self.h, int(first), n, *self._plan(n, x, u), self._dev(out, (n, _lib.COST_TERMS_WORDS)),
                                                         self._dev_or_null(nodes, (n, self.N + 1, _lib.COST_TERMS_COLS))))
         return out
 
@@ -286,25 +288,15 @@ class DdpEngine:
         """The cost breakdown of the handle's own plan as a dict of numpy arrays: "total" [count], one entry [count] per family name
         of _lib.COST_TERM_NAMES, "largest" [count] (the name of the largest of the families 0 .. 11, "" where one of them is NaN) and
         "record" [count, 16], the raw records; nodes: also "nodes" [count, N + 1, 14], the per-node addends.  Waits for the stream."""
-        n = self._count(first, count)
+        names, per_node = _lib.COST_TERM_NAMES, {}
         if not nodes:
-            rec = np.empty((max(n, 0), _lib.COST_TERMS_WORDS))
-            self._chk(self.lib.sddp_cost_terms(self.h, int(first), n, _lib.ptr(rec)))
-            per_node = None
+            rec = self._own_records(self.lib.sddp_cost_terms, first, count, _lib.COST_TERMS_WORDS)
         else:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            out = torch.empty((max(n, 0), _lib.COST_TERMS_WORDS), dtype=torch.float64, device=dev)
-            nd = torch.empty((max(n, 0), self.N + 1, _lib.COST_TERMS_COLS), dtype=torch.float64, device=dev)
-            self.cost_terms_device(out, first, n, nodes=nd)
-            self.synchronize()
-            rec, per_node = out.cpu().numpy(), nd.cpu().numpy()
-        names = _lib.COST_TERM_NAMES
-        res = {"total": rec[:, 0].copy(), **{name: rec[:, 1 + f].copy() for f, name in enumerate(names)},
-               "largest": np.array([names[int(i)] if i >= 0 else "" for i in rec[:, 14]], dtype=object), "record": rec}
-        if per_node is not None:
-            res["nodes"] = per_node
-        return res
+            n = self._count(first, count)
+            rec, per_node["nodes"] = self._to_numpy(n, [(_lib.COST_TERMS_WORDS,), (self.N + 1, _lib.COST_TERMS_COLS)],
+                                                    lambda out, nd: self.cost_terms_device(out, first, n, nodes=nd))
+        return {"total": rec[:, 0].copy(), **{name: rec[:, 1 + f].copy() for f, name in enumerate(names)},
+                "largest": np.array([names[int(i)] if i >= 0 else "" for i in rec[:, 14]], dtype=object), "record": rec, **per_node}
 
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)

@@ -109,8 +109,9 @@ class FleetQueue:
         self.eng.solve_range_device(self.P, 0, n)
         if self.policy:
             self.eng.policy_range_device(0, n)                               # one sweep per instance at the returned iterate
+        self.solved = n
         if audit_out is not None:
-            self.eng.audit_device(audit_out[:n], 0, n)
+            self._inspect(self.eng.audit_device, audit_out)
         self.launches += 1
         if self.collective:
             import torch.distributed as dist
@@ -128,7 +129,14 @@ class FleetQueue:
             self._last = k
             self._k ^= 1
         self.pending = 0
-        self.solved = n
+        return n
+
+    def _inspect(self, launch, out, **optional):
+        """launch (an inspector's *_device method of the engine) on the instances the most recent solving call covered, into the
+        first n rows of out and of every optional output that is not None -> n; 0, and nothing launched, before the first such call"""
+        n = self.solved
+        if n:
+            launch(out[:n], 0, n, **{k: None if t is None else t[:n] for k, t in optional.items()})
         return n
 
     def stationarity(self, out, lam=None, grad=None):
@@ -136,22 +144,14 @@ class FleetQueue:
         solved, into the first n rows of the device tensor out [>= n, 8] (lam, grad: likewise, or None); launched behind whatever
         that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet server whether a cut robot is
         worth a second slice: word 0 / word 3 of its record."""
-        n = self.solved
-        if n == 0:
-            return 0
-        self.eng.stationarity_device(out[:n], 0, n, lam=None if lam is None else lam[:n], grad=None if grad is None else grad[:n])
-        return n
+        return self._inspect(self.eng.stationarity_device, out, lam=lam, grad=grad)
 
     def cost_terms(self, out, nodes=None):
         """The cost-breakdown records (DdpEngine.cost_terms_device) of the instances the last flush / solve_sliced / solve_within
         solved, into the first n rows of the device tensor out [>= n, 16] (nodes [>= n, N + 1, 14]: likewise, or None); launched behind
         whatever that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet server which gain a
         fleet's cost is made of before it turns one."""
-        n = self.solved
-        if n == 0:
-            return 0
-        self.eng.cost_terms_device(out[:n], 0, n, nodes=None if nodes is None else nodes[:n])
-        return n
+        return self._inspect(self.eng.cost_terms_device, out, nodes=nodes)
 
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most

@@ -32,19 +32,24 @@ OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 # (model, N, B, kind): "plain"; "x": the _x build (tests/variant_cases.py rows); "bar": friction barrier on; "so2": second_order = 2
 CASES = (("srbd13", 6, 5, "plain"), ("srbd37", 6, 3, "plain"), ("lip30", 6, 3, "plain"), ("srbd61", 4, 2, "plain"), ("srbd13", 6, 3, "x"),
          ("srbd13", 6, 5, "bar"), ("srbd13", 6, 5, "so2"))
-BARRIER = dict(friction_barrier_weight=1e-3, friction_barrier_sharpness=5.0)
 
 
-def problem(model, N, B, kind):
-    """-> (batch, P, consts, opts) of a case: seeds 3 .. B + 2 of srbd_horizon_amd.workload"""
+def problem(model, N, B, kind, seeds=None):
+    """-> (batch, P, consts, opts) of a case of the plan inspectors' tests (audit, stationarity, cost breakdown) on `seeds` of
+    srbd_horizon_amd.workload, None: 3 .. B + 2.  Beyond the kinds of CASES, "lin" and "box": the _x build on the rows, the bound
+    barrier on the band of tests/cost_terms_cases.py."""
     from srbd_horizon_amd import workload
-    from tests.variant_cases import extra_rows_problem
-    seeds = np.arange(B) + 3
-    if kind == "x":
-        batch, P, consts = extra_rows_problem(model, N, seeds)
-    else:
-        batch = workload.make_batch(model, N, seeds)
-        P, consts = batch["params"], dict(batch["consts"], **(BARRIER if kind == "bar" else {}))
+    from tests import cost_terms_cases as cc
+    from tests.variant_cases import extra_rows
+    seeds = np.arange(B) + 3 if seeds is None else np.asarray(seeds)
+    assert len(seeds) == B
+    batch = workload.make_batch(model, N, seeds)
+    P = batch["params"]
+    consts = dict(batch["consts"], **(dict(extra_rows=extra_rows(model)) if kind == "x" else cc.consts_of(model, "x" if kind == "lin" else kind)))
+    if kind in ("x", "lin"):      # the rows' per-knot references: eight more parameter columns, two of them in use
+        P = np.concatenate([P, np.zeros((B, N + 1, 8))], axis=2)
+        P[:, :, P.shape[2] - 8] = 0.02 * np.sin(np.arange(N + 1) / 5.0)[None]
+        P[:, :, P.shape[2] - (5 if kind == "x" else 6)] = 0.1 * np.cos(np.arange(N + 1) / 3.0)[None]
     return batch, P, consts, dict(OPTS, **(dict(second_order=2) if kind == "so2" else {}))
 
 

@@ -36,16 +36,7 @@ SEEDS = {("srbd13", "plain"): (3, 4, 5, 6, 7), ("srbd37", "plain"): (3, 8, 14), 
 
 def problem(model, N, B, kind):
     """-> (batch, P, consts, opts) of a case (tests/plan_audit_cases.py problem, on SEEDS)"""
-    from srbd_horizon_amd import workload
-    from tests.variant_cases import extra_rows_problem
-    seeds = np.asarray(SEEDS[model, kind])
-    assert len(seeds) == B
-    if kind == "x":
-        batch, P, consts = extra_rows_problem(model, N, seeds)
-    else:
-        batch = workload.make_batch(model, N, seeds)
-        P, consts = batch["params"], dict(batch["consts"], **(pac.BARRIER if kind == "bar" else {}))
-    return batch, P, consts, dict(OPTS, **(dict(second_order=2) if kind == "so2" else {}))
+    return pac.problem(model, N, B, kind, SEEDS[model, kind])
 
 
 # ---- the two CPU statements of the derivatives ---------------------------------------------------------------------------------------------

@@ -8,21 +8,18 @@ one rounding (they share the rows' values sqrt(w) e and differ in the order of o
 w e^2 where both of them form (sqrt(w) e)^2.  Every test prints its worst |difference| / tolerance.
 """
 import ctypes as C
-import dataclasses
-import functools
 import json
 import os
 
 import numpy as np
 import pytest
-import torch
 
 from oracle import models as omodels
 from srbd_horizon_amd import _lib, workload
 from srbd_horizon_amd.engine import DdpEngine
-from srbd_horizon_amd.fleet import FleetQueue
 from tests import cost_terms_cases as cc
-from tests.gpu_support import BUILDS, solve
+from tests.gpu_support import (BUILDS, COST_TERMS, assert_common_refusals, assert_fleet_queue_follows_the_last_flush,
+                               assert_nothing_else_moves, solve, solved, touch_with)
 from tests.variant_cases import SRBD13_FIELDS, draw
 
 pytestmark = pytest.mark.gpu
@@ -34,41 +31,14 @@ with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 FAM = slice(1, 1 + cc.FAMILIES)
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a, dtype=np.float64)).to("cuda")
-
-
 def _run(eng, first=0, count=None, x=None, u=None, nodes=True):
     """cost_terms_device on fresh device tensors -> numpy (record [n, 16], addends [n, N + 1, 14] or None)"""
-    n = eng.B - first if count is None else count
-    out = torch.full((n, cc.WORDS), 7.0, dtype=torch.float64, device="cuda")
-    nd = torch.full((n, eng.N + 1, cc.COLS), 7.0, dtype=torch.float64, device="cuda") if nodes else None
-    eng.cost_terms_device(out, first, n, x=None if x is None else _dev(x), u=None if u is None else _dev(u), nodes=nd)
-    eng.synchronize()
-    return out.cpu().numpy(), (nd.cpu().numpy() if nodes else None)
+    return COST_TERMS.device(eng, first, count, x, u, optional=nodes)
 
 
-def _problem(model, N, kind, nb=B):
-    """-> (batch, P, consts dict, opts) of a case: seeds 3 .. of srbd_horizon_amd.workload"""
-    batch = workload.make_batch(model, N, np.arange(nb) + 3)
-    P = batch["params"]
-    consts = dict(batch["consts"], **cc.consts_of(model, kind))
-    if kind == "x":
-        P = np.concatenate([P, np.zeros((nb, N + 1, 8))], axis=2)
-        P[:, :, P.shape[2] - 8] = 0.02 * np.sin(np.arange(N + 1) / 5.0)[None]
-        P[:, :, P.shape[2] - 6] = 0.1 * np.cos(np.arange(N + 1) / 3.0)[None]
-    return batch, P, consts, dict(OPTS, **(dict(second_order=2) if kind == "so2" else {}))
-
-
-@functools.lru_cache(maxsize=None)
-def _solved(model, N, wps=1, kind="plain", nb=B):
-    """a handle with its solve done, and what it gave: computed once, arrays read-only"""
-    batch, P, consts, opts = _problem(model, N, kind, nb)
-    eng = DdpEngine(model, N, nb, opts=dict(opts, waves_per_simd=wps), consts=consts)
-    x, u, st = solve(eng, batch, P)
-    for a in (x, u, st, P):
-        a.setflags(write=False)
-    return eng, omodels.RobotConsts(**consts), batch, x, u, st, P
+def _solved(model, N, wps=1, kind="plain"):
+    """the case on the seeds 3 .. B + 2; "x" here: the rows of tests/cost_terms_cases.py ("lin" of plan_audit_cases.problem)"""
+    return solved(model, N, B, "lin" if kind == "x" else kind, wps=wps)
 
 
 def _random_plan(batch, seed=11):
@@ -254,98 +224,19 @@ def test_a_nan_stays_on_its_instance():
 
 
 def test_nothing_else_moves():
-    model, N, nb, M = "srbd13", 6, 5, 4
-    batch = workload.make_batch(model, N, np.arange(nb) + 3)
-    eng = DdpEngine(model, N, nb, opts=dict(OPTS, max_iters=2), consts=batch["consts"])
-    eng.enable_resume()
-    eng.enable_iteration_log(8)
-    eng.enable_policy(M)
-    solve(eng, batch)
-    eng.policy_range_device()
-    assert eng.unfinished() > 0                                                     # a cut solve: there are resume flags to keep
-
-    def state():
-        xs, us, stats = eng.fetch()
-        rec, n = eng.iteration_log()
-        return (xs.tobytes(), us.tobytes(), stats.tobytes(), eng.fetch_policy().tobytes(), eng.unfinished(), eng.unfinished(1, 3),
-                rec.tobytes(), n.tobytes(), eng.queue_info(), eng.kernel_info())
-
-    before = state()
-    eng.cost_terms()
-    _run(eng, 1, 3)
-    _run(eng, x=batch["xs"], u=batch["us"])
-    assert state() == before
-    eng.close()
-    # the class labels and their history of a handle that labels its instances itself
-    eng = DdpEngine(model, N, nb, opts=dict(OPTS, queue_order=3), consts=batch["consts"])
-    eng.enable_auto_classes()
-    solve(eng, batch)
-    labels = lambda: (eng._host_copy(_lib.BUF_CLASSES, "<i4").tobytes(), eng.auto_classes_info())      # noqa: E731
-    before = labels()
-    eng.cost_terms()
-    _run(eng, x=batch["xs"], u=batch["us"])
-    assert labels() == before
-    eng.close()
-    # the slots' work buffers: a forward after a backward, with and without the call between them
-    eng = DdpEngine(model, N, nb, opts=dict(OPTS, max_iters=2), consts=batch["consts"])
-    solve(eng, batch)
-    eng.backward(batch["params"], 1e-6)
-    ref = eng.forward(batch["params"], 0.5)
-    eng.backward(batch["params"], 1e-6)
-    eng.cost_terms()
-    _run(eng, x=batch["xs"], u=batch["us"])
-    got = eng.forward(batch["params"], 0.5)
-    assert all(a.tobytes() == b_.tobytes() for a, b_ in zip(got, ref))
-    eng.close()
-    # a cut solve continued after the call is the one continued without it
-    ends = []
-    for call in (False, True):
-        e = DdpEngine(model, N, nb, opts=dict(OPTS, max_iters=2), consts=batch["consts"])
-        e.enable_resume()
-        solve(e, batch)
-        if call:
-            e.cost_terms()
-            _run(e, x=batch["xs"], u=batch["us"])
-        e.set_options(max_iters=100)
-        e.continue_solve()
-        ends.append(tuple(a.tobytes() for a in e.fetch()))
-        e.close()
-    assert ends[0] == ends[1]
+    assert_nothing_else_moves(touch_with(COST_TERMS), OPTS)
 
 
 def test_refusals():
-    model, N, nb = "srbd13", 6, 2
-    batch = workload.make_batch(model, N, [0, 1])
-    eng = DdpEngine(model, N, nb, opts=OPTS)
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        eng.cost_terms()
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        _run(eng)
-    x, u, _ = solve(eng, batch)
-    gx, gu = _dev(x), _dev(u)
-    out = torch.zeros((nb, cc.WORDS), dtype=torch.float64, device="cuda")
-    vp = eng._dev
-    for dx, du in ((vp(gx, gx.shape), None), (None, vp(gu, gu.shape))):             # one of d_x / d_u NULL
-        with pytest.raises(RuntimeError, match="both NULL"):
-            eng._chk(eng.lib.sddp_cost_terms_range_device(eng.h, 0, nb, dx, du, vp(out, out.shape), None))
-    with pytest.raises(RuntimeError, match="NULL argument"):
-        eng._chk(eng.lib.sddp_cost_terms_range_device(eng.h, 0, nb, None, None, None, None))
-    for call in (lambda: _run(eng, 1, 2), lambda: eng.cost_terms(1, 2), lambda: eng.cost_terms(-1, 1), lambda: eng.cost_terms(0, 0)):
-        with pytest.raises(RuntimeError, match="range outside"):
-            call()
-    assert eng.lib.sddp_cost_terms_range_device(eng.h, 1, 2, None, None, vp(out, out.shape), None) == -1      # SDDP_ERR_ARG
-    name = C.c_char_p()
+    assert_common_refusals(COST_TERMS, OPTS)
+    lib, name = _lib.load(), C.c_char_p()
     for family in (-1, cc.FAMILIES):
-        assert eng.lib.sddp_cost_terms_name(family, C.byref(name)) == -1
-        assert b"family must be 0 .. 12" in eng.lib.sddp_last_error(None)
-    assert eng.cost_terms()["record"].shape == (nb, cc.WORDS)                       # and the handle still works
-    eng.close()
+        assert lib.sddp_cost_terms_name(family, C.byref(name)) == -1
+        assert b"family must be 0 .. 12" in lib.sddp_last_error(None)
 
 
 def test_surface_and_fleet_queue():
-    model, N, batch_n, depth = "srbd13", 6, 4, 2
-    batch = workload.make_batch(model, N, np.arange(batch_n) + 3)
-    eng = DdpEngine(model, N, batch_n * depth, opts=OPTS, consts=batch["consts"])
+    eng = DdpEngine("srbd13", 6, 2, opts=OPTS)
     words, families, name = C.c_int(), C.c_int(), C.c_char_p()
     eng._chk(eng.lib.sddp_cost_terms_words(eng.h, C.byref(words), C.byref(families)))
     assert (words.value, families.value) == (16, 13) == (cc.WORDS, cc.FAMILIES) == (_lib.COST_TERMS_WORDS, len(_lib.COST_TERM_NAMES))
@@ -354,22 +245,5 @@ def test_surface_and_fleet_queue():
         assert eng.lib.sddp_cost_terms_name(f, C.byref(name)) == 0
         names.append(name.value.decode())
     assert tuple(names) == _lib.COST_TERM_NAMES == cc.NAMES and len(set(names)) == 13
-    t = {k: _dev(batch[k]) for k in ("x0", "xs", "us", "params")}
-    fleet = FleetQueue(eng, t["params"].repeat(depth, 1, 1).contiguous(), batch_n, depth)
-    out = torch.full((batch_n * depth + 1, cc.WORDS), 7.0, dtype=torch.float64, device="cuda")
-    assert fleet.cost_terms(out) == 0                                               # nothing flushed yet: nothing launched
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    assert fleet.flush() == batch_n and fleet.cost_terms(out) == batch_n            # a partial handle: the first block alone
-    eng.synchronize()
-    got = out.cpu().numpy()
-    assert got[:batch_n].tobytes() == eng.cost_terms(0, batch_n)["record"].tobytes() and np.all(got[batch_n:] == 7.0)
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    nd = torch.full((batch_n * depth, N + 1, cc.COLS), 7.0, dtype=torch.float64, device="cuda")
-    assert fleet.flush() == batch_n * depth and fleet.cost_terms(out, nodes=nd) == batch_n * depth
-    eng.synchronize()
-    got = out.cpu().numpy()
-    full = eng.cost_terms(nodes=True)
-    assert got[:-1].tobytes() == full["record"].tobytes() and np.all(got[-1] == 7.0) and nd.cpu().numpy().tobytes() == full["nodes"].tobytes()
-    assert got[:batch_n].tobytes() == got[batch_n:2 * batch_n].tobytes()            # the same robots in both blocks
     eng.close()
+    assert_fleet_queue_follows_the_last_flush(COST_TERMS, OPTS, "nodes")[0].close()

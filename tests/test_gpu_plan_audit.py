@@ -11,7 +11,6 @@ Tolerances (tests/plan_audit_cases.py assert_record):
   * words 12 - 15 exactly.
 """
 import dataclasses
-import functools
 
 import numpy as np
 import pytest
@@ -20,9 +19,9 @@ import torch
 from oracle import models as omodels
 from srbd_horizon_amd import _lib, workload
 from srbd_horizon_amd.engine import DdpEngine
-from srbd_horizon_amd.fleet import FleetQueue
 from tests import plan_audit_cases as pac
-from tests.gpu_support import solve
+from tests.gpu_support import (AUDIT, assert_common_refusals, assert_fleet_queue_follows_the_last_flush, assert_nothing_else_moves, dev,
+                               solve, solved, touch_with)
 from tests.variant_cases import TRACKING, draw
 
 pytestmark = pytest.mark.gpu
@@ -31,32 +30,14 @@ A = _lib
 W = _lib.AUDIT_WORDS
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
-
-
 def _audit_dev(eng, first=0, count=None, **kw):
     """audit_device on a fresh device tensor -> numpy [count, 16]"""
-    n = eng.B - first if count is None else count
-    out = torch.full((n, W), 7.0, dtype=torch.float64, device="cuda")
-    eng.audit_device(out, first, n, **kw)
-    eng.synchronize()
-    return out.cpu().numpy()
+    return AUDIT.device(eng, first, count, **kw)[0]
 
 
-@functools.lru_cache(maxsize=None)
 def _solved(model, N, B, kind, knots=0):
-    """a handle with its solve (and, knots > 0, its policy launch) done, and what it gave: computed once, arrays read-only"""
-    batch, P, consts, opts = pac.problem(model, N, B, kind)
-    eng = DdpEngine(model, N, B, opts=opts, consts=consts)
-    if knots:
-        eng.enable_policy(knots)
-    x, u, st = solve(eng, batch, P)
-    if knots:
-        eng.policy_range_device()
-    for a in (x, u, P):
-        a.setflags(write=False)
-    return eng, omodels.RobotConsts(**consts), x, u, P
+    eng, cst, batch, x, u, st, P = solved(model, N, B, kind, knots=knots)
+    return eng, cst, x, u, P
 
 
 def _check(model, cst, got, x, u, P, start, friction, label):
@@ -97,7 +78,7 @@ def _pushed_rollout(eng, x, M, steps):
     xm = x[:, 1] + 1e-2 * np.random.default_rng(7).standard_normal(x[:, 1].shape)
     gx = torch.empty((eng.B, steps + 1, eng.nx), dtype=torch.float64, device="cuda")
     gu = torch.empty((eng.B, steps, eng.nu), dtype=torch.float64, device="cuda")
-    eng.policy_rollout_device(_dev(xm), gx, gu, None, 0, eng.B, 1, steps)
+    eng.policy_rollout_device(dev(xm), gx, gu, None, 0, eng.B, 1, steps)
     return gx, gu
 
 
@@ -156,58 +137,31 @@ def test_each_instance_is_stepped_through_its_own_robot():
 
 
 def test_nothing_else_moves():
-    model, N, B, M = "srbd13", 6, 5, 4
-    batch = workload.make_batch(model, N, np.arange(B) + 3)
-    eng = DdpEngine(model, N, B, opts=dict(pac.OPTS, max_iters=2), consts=batch["consts"])
-    eng.enable_resume()
-    eng.enable_iteration_log(8)
-    eng.enable_policy(M)
-    x, u, st = solve(eng, batch)
-    eng.policy_range_device()
-    assert eng.unfinished() > 0                                                  # a cut solve: there are resume flags to keep
+    sub_range_and_warm_start = touch_with(AUDIT, friction=0.3)
 
-    def state():
-        xs, us, stats = eng.fetch()
-        rec, n = eng.iteration_log()
-        return (xs.tobytes(), us.tobytes(), stats.tobytes(), eng.fetch_policy().tobytes(), eng.unfinished(), eng.unfinished(1, 3),
-                rec.tobytes(), n.tobytes(), eng.queue_info(), eng.kernel_info())
+    def touch(eng, batch, x):
+        got = sub_range_and_warm_start(eng, batch, x)
+        M = eng.knots
+        if M:                                                                    # and a rollout of the handle's policy, audited where it sits
+            gx, gu = _pushed_rollout(eng, x, M, M - 1)
+            got += (_audit_dev(eng, x=gx, u=gu, start=1, steps=M - 1).tobytes(),)
+        return got
 
-    before = state()
-    eng.audit()
-    _audit_dev(eng, 1, 3, friction=0.3)
-    gx, gu = _pushed_rollout(eng, x, M, M - 1)
-    _audit_dev(eng, x=gx, u=gu, start=1, steps=M - 1)
-    assert state() == before
-    # the slots' work buffers: a forward after a backward, with and without audits between them
-    eng.backward(batch["params"], 1e-6)
-    ref = eng.forward(batch["params"], 0.5)
-    eng.backward(batch["params"], 1e-6)
-    eng.audit()
-    _audit_dev(eng, x=gx, u=gu, start=1, steps=M - 1)
-    got = eng.forward(batch["params"], 0.5)
-    for a, b_ in zip(got, ref):
-        assert a.tobytes() == b_.tobytes()
-    eng.close()
+    assert_nothing_else_moves(touch, pac.OPTS)
 
 
 def test_audit_refusals():
-    model, N, B = "srbd13", 6, 2
-    batch = workload.make_batch(model, N, [0, 1])
-    eng = DdpEngine(model, N, B, opts=pac.OPTS)
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        eng.audit()
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        _audit_dev(eng)
-    x, u, _ = solve(eng, batch)
-    gx, gu = _dev(x[:, 1:4]), _dev(u[:, 1:3])                                   # rows at the nodes 1 .. 3: start = 1, steps = 2
+    batch, x, u = assert_common_refusals(AUDIT, pac.OPTS)
+    N, B = 6, 2
+    eng = DdpEngine("srbd13", N, B, opts=pac.OPTS)
+    solve(eng, batch)
+    gx, gu = dev(x[:, 1:4]), dev(u[:, 1:3])                                     # rows at the nodes 1 .. 3: start = 1, steps = 2
     assert _audit_dev(eng, x=gx, u=gu, start=1, steps=2).shape == (B, W)
     out = torch.zeros((B, W), dtype=torch.float64, device="cuda")
     vp = eng._dev
-    for dx, du in ((vp(gx, gx.shape), None), (None, vp(gu, gu.shape))):         # one of d_x / d_u NULL
+    for dx, du in ((vp(gx, gx.shape), None), (None, vp(gu, gu.shape))):         # one of d_x / d_u NULL, whatever start and steps
         with pytest.raises(RuntimeError, match="both NULL"):
             eng._chk(eng.lib.sddp_audit_range_device(eng.h, 0, B, 1, 2, dx, du, 0.0, vp(out, out.shape)))
-    with pytest.raises(RuntimeError, match="NULL argument"):
-        eng._chk(eng.lib.sddp_audit_range_device(eng.h, 0, B, 0, N, None, None, 0.0, None))
     big_x = torch.zeros((B, N + 2, eng.nx), dtype=torch.float64, device="cuda")
     big_u = torch.zeros((B, N + 1, eng.nu), dtype=torch.float64, device="cuda")
     for start, steps in ((0, N + 1), (1, N), (N, 1), (-1, 1), (0, 0)):          # (refused before anything is read: the tensors only have to exist)
@@ -216,32 +170,12 @@ def test_audit_refusals():
     for start, steps in ((0, N - 1), (1, N - 1), (1, N)):                       # the handle's own plan is audited whole
         with pytest.raises(RuntimeError, match="audited whole"):
             _audit_dev(eng, start=start, steps=steps)
-    for call in (lambda: _audit_dev(eng, 1, 2), lambda: eng.audit(1, 2), lambda: eng.audit(-1, 1), lambda: eng.audit(0, 0)):
-        with pytest.raises(RuntimeError, match="range outside"):
-            call()
     assert eng.audit().shape == (B, W)                                          # and the handle still works
     eng.close()
 
 
 def test_fleet_queue_flush_audits_the_solved_range():
-    model, N, batch_n, depth = "srbd13", 6, 4, 2
-    batch = workload.make_batch(model, N, np.arange(batch_n) + 3)
-    eng = DdpEngine(model, N, batch_n * depth, opts=pac.OPTS, consts=batch["consts"])
-    t = {k: _dev(batch[k]) for k in ("x0", "xs", "us", "params")}
-    fleet = FleetQueue(eng, t["params"].repeat(depth, 1, 1).contiguous(), batch_n, depth)
-    out = torch.full((batch_n * depth + 1, W), 7.0, dtype=torch.float64, device="cuda")
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    assert fleet.flush(audit_out=out) == batch_n                                # a partial handle: the first block alone
-    eng.synchronize()
-    got = out.cpu().numpy()
-    assert got[:batch_n].tobytes() == eng.audit(0, batch_n).tobytes() and np.all(got[batch_n:] == 7.0)
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    assert fleet.flush(out) == batch_n * depth
-    eng.synchronize()
-    got = out.cpu().numpy()
-    assert got[:-1].tobytes() == eng.audit().tobytes() and np.all(got[-1] == 7.0)
-    assert got[:batch_n].tobytes() == got[batch_n:2 * batch_n].tobytes()        # the same robots in both blocks
+    eng, batch, got = assert_fleet_queue_follows_the_last_flush(AUDIT, pac.OPTS)
     x, u, _ = eng.fetch()
-    _check(model, omodels.RobotConsts(**batch["consts"]), got[:batch_n], x[:batch_n], u[:batch_n], batch["params"], 0, 0.8, "fleet block 0")
+    _check("srbd13", omodels.RobotConsts(**batch["consts"]), got[:4], x[:4], u[:4], batch["params"], 0, 0.8, "fleet block 0")
     eng.close()

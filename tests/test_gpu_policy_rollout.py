@@ -12,16 +12,12 @@ from oracle import models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from tests import policy_rollout_cases as prc
-from tests.gpu_support import solve
+from tests.gpu_support import assert_nothing_else_moves, dev as _dev, solve
 from tests.variant_cases import TRACKING, draw, extra_rows_problem
 
 pytestmark = pytest.mark.gpu
 
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # tests/test_gpu_policy.py
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
 
 
 def _rollout_dev(eng, xm, first=0, count=None, start=0, steps=None, cost=True):
@@ -175,31 +171,12 @@ def test_without_a_policy_launch_the_rollout_is_open_loop():
 
 
 def test_nothing_else_moves():
-    model, N, B, M = "srbd13", 6, 5, 4
-    batch = workload.make_batch(model, N, np.arange(B) + 3)
-    eng = DdpEngine(model, N, B, opts=OPTS, consts=batch["consts"])
-    eng.enable_policy(M)
-    x, u, st = solve(eng, batch)
-    eng.policy_range_device()
-    pol, qi, ki = eng.fetch_policy(), eng.queue_info(), eng.kernel_info()
-    xm = _pushed(x, 0)
-    _rollout_dev(eng, xm)
-    _apply(eng, xm, knot=M - 1)
-    x2, u2, st2 = eng.fetch()
-    assert x2.tobytes() == x.tobytes() and u2.tobytes() == u.tobytes()
-    for f in st.dtype.names:
-        np.testing.assert_array_equal(st2[f], st[f], err_msg=f)
-    assert eng.fetch_policy().tobytes() == pol.tobytes()
-    assert eng.queue_info() == qi and eng.kernel_info() == ki
-    # the slots' work buffers: a forward after a backward, with and without a rollout between them
-    eng.backward(batch["params"], 1e-6)
-    ref = eng.forward(batch["params"], 0.5)
-    eng.backward(batch["params"], 1e-6)
-    _rollout_dev(eng, xm)
-    _apply(eng, xm, knot=1)
-    got = eng.forward(batch["params"], 0.5)
-    for a, b_ in zip(got, ref):
-        assert a.tobytes() == b_.tobytes()
+    def touch(eng, batch, x):
+        xm, M = _pushed(x, 0), eng.knots
+        got = (*_rollout_dev(eng, xm), _apply(eng, xm, knot=M - 1), _apply(eng, xm, knot=1))
+        return tuple(a.tobytes() for a in got)
+
+    assert_nothing_else_moves(touch, OPTS, policy=True)
 
 
 def test_rollout_refusals():

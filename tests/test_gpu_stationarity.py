@@ -12,18 +12,17 @@ The record has no word for the node of the defect, so "word 6 / node against aud
 and word 7 against the audit's node count (word 12).
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import models as omodels
-from srbd_horizon_amd import _lib, workload
+from srbd_horizon_amd import _lib
 from srbd_horizon_amd.engine import DdpEngine
-from srbd_horizon_amd.fleet import FleetQueue
 from tests import nlp_fixtures as nf, stationarity_cases as sc
-from tests.gpu_support import solve
+from tests.gpu_support import (AUDIT, STATIONARITY, assert_common_refusals, assert_fleet_queue_follows_the_last_flush,
+                               assert_nothing_else_moves, solve, solved, touch_with)
 from tests.variant_cases import TRACKING, draw
 
 pytestmark = pytest.mark.gpu
@@ -31,36 +30,17 @@ pytestmark = pytest.mark.gpu
 W = sc.W
 
 
-def _dev(a):
-    return torch.from_numpy(np.array(a, dtype=np.float64)).to("cuda")
-
-
 def _run(eng, first=0, count=None, x=None, u=None, full=True):
     """stationarity_device on fresh device tensors -> numpy (record [n, 8], lambda, s), the last two None without `full`"""
-    n = eng.B - first if count is None else count
-    mk = lambda *shape: torch.full((n, *shape), 7.0, dtype=torch.float64, device="cuda")
-    out, lam, grad = mk(W), (mk(eng.N + 1, eng.nx) if full else None), (mk(eng.N, eng.nu) if full else None)
-    eng.stationarity_device(out, first, n, x=None if x is None else _dev(x), u=None if u is None else _dev(u), lam=lam, grad=grad)
-    eng.synchronize()
-    return out.cpu().numpy(), (lam.cpu().numpy() if full else None), (grad.cpu().numpy() if full else None)
+    return STATIONARITY.device(eng, first, count, x, u, optional=full)
 
 
 def _audit(eng, x=None, u=None):
-    out = torch.empty((eng.B, _lib.AUDIT_WORDS), dtype=torch.float64, device="cuda")
-    eng.audit_device(out, x=None if x is None else _dev(x), u=None if u is None else _dev(u))
-    eng.synchronize()
-    return out.cpu().numpy()
+    return AUDIT.device(eng, x=x, u=u)[0]
 
 
-@functools.lru_cache(maxsize=None)
 def _solved(model, N, B, kind):
-    """a handle with its solve done, and what it gave: computed once, arrays read-only"""
-    batch, P, consts, opts = sc.problem(model, N, B, kind)
-    eng = DdpEngine(model, N, B, opts=opts, consts=consts)
-    x, u, st = solve(eng, batch, P)
-    for a in (x, u, st, P):
-        a.setflags(write=False)
-    return eng, omodels.RobotConsts(**consts), batch, x, u, st, P
+    return solved(model, N, B, kind, sc.SEEDS[model, kind])
 
 
 def _check(model, cst, got, x, u, P, label):
@@ -126,49 +106,7 @@ def test_same_bytes_whatever_the_source_the_range_and_the_optional_outputs():
 
 
 def test_nothing_else_moves():
-    model, N, B, M = "srbd13", 6, 5, 4
-    batch = workload.make_batch(model, N, np.arange(B) + 3)
-    eng = DdpEngine(model, N, B, opts=dict(sc.OPTS, max_iters=2), consts=batch["consts"])
-    eng.enable_resume()
-    eng.enable_iteration_log(8)
-    eng.enable_policy(M)
-    x, u, st = solve(eng, batch)
-    eng.policy_range_device()
-    assert eng.unfinished() > 0                                                  # a cut solve: there are resume flags to keep
-
-    def state():
-        xs, us, stats = eng.fetch()
-        rec, n = eng.iteration_log()
-        return (xs.tobytes(), us.tobytes(), stats.tobytes(), eng.fetch_policy().tobytes(), eng.unfinished(), eng.unfinished(1, 3),
-                rec.tobytes(), n.tobytes(), eng.queue_info(), eng.kernel_info())
-
-    before = state()
-    eng.stationarity()
-    _run(eng, 1, 3)
-    _run(eng, x=batch["xs"], u=batch["us"])
-    assert state() == before
-    # the slots' work buffers: a forward after a backward, with and without the call between them
-    eng.backward(batch["params"], 1e-6)
-    ref = eng.forward(batch["params"], 0.5)
-    eng.backward(batch["params"], 1e-6)
-    eng.stationarity()
-    _run(eng, x=batch["xs"], u=batch["us"])
-    got = eng.forward(batch["params"], 0.5)
-    for a, b_ in zip(got, ref):
-        assert a.tobytes() == b_.tobytes()
-    eng.close()
-    # a solve after the call is the solve of a fresh handle; two slots for five instances, so the queue and the slots' buffers are in play
-    opts = dict(sc.OPTS, max_slots=2)
-    used, fresh = (DdpEngine(model, N, B, opts=opts, consts=batch["consts"]) for _ in range(2))
-    assert used.queue_info()[0] == 2
-    solve(used, batch)
-    used.stationarity()
-    _run(used, x=batch["xs"], u=batch["us"])
-    after, ref = solve(used, batch), solve(fresh, batch)
-    assert all(a.tobytes() == b_.tobytes() for a, b_ in zip(after, ref))
-    assert all(a.tobytes() == b_.tobytes() for a, b_ in zip(_run(used), _run(fresh)))
-    used.close()
-    fresh.close()
+    assert_nothing_else_moves(touch_with(STATIONARITY), sc.OPTS)
 
 
 def test_instance_constants():
@@ -213,28 +151,7 @@ def test_a_nan_stays_on_its_instance():
 
 
 def test_refusals():
-    model, N, B = "srbd13", 6, 2
-    batch = workload.make_batch(model, N, [0, 1])
-    eng = DdpEngine(model, N, B, opts=sc.OPTS)
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        eng.stationarity()
-    with pytest.raises(RuntimeError, match="no solve has run"):
-        _run(eng)
-    x, u, _ = solve(eng, batch)
-    gx, gu = _dev(x), _dev(u)
-    out = torch.zeros((B, W), dtype=torch.float64, device="cuda")
-    vp = eng._dev
-    for dx, du in ((vp(gx, gx.shape), None), (None, vp(gu, gu.shape))):         # one of d_x / d_u NULL
-        with pytest.raises(RuntimeError, match="both NULL"):
-            eng._chk(eng.lib.sddp_stationarity_range_device(eng.h, 0, B, dx, du, vp(out, out.shape), None, None))
-    with pytest.raises(RuntimeError, match="NULL argument"):
-        eng._chk(eng.lib.sddp_stationarity_range_device(eng.h, 0, B, None, None, None, None, None))
-    for call in (lambda: _run(eng, 1, 2), lambda: eng.stationarity(1, 2), lambda: eng.stationarity(-1, 1), lambda: eng.stationarity(0, 0)):
-        with pytest.raises(RuntimeError, match="range outside"):
-            call()
-    assert eng.lib.sddp_stationarity_range_device(eng.h, 1, 2, None, None, vp(out, out.shape), None, None) == -1      # SDDP_ERR_ARG
-    assert eng.stationarity().shape == (B, W)                                   # and the handle still works
-    eng.close()
+    assert_common_refusals(STATIONARITY, sc.OPTS)
 
 
 FIXTURES = nf.load_all()
@@ -272,25 +189,4 @@ def test_progress_of_the_solves_that_end_with_status_0():
 
 
 def test_fleet_queue_certifies_the_last_flushed_range():
-    model, N, batch_n, depth = "srbd13", 6, 4, 2
-    batch = workload.make_batch(model, N, np.arange(batch_n) + 3)
-    eng = DdpEngine(model, N, batch_n * depth, opts=sc.OPTS, consts=batch["consts"])
-    t = {k: _dev(batch[k]) for k in ("x0", "xs", "us", "params")}
-    fleet = FleetQueue(eng, t["params"].repeat(depth, 1, 1).contiguous(), batch_n, depth)
-    out = torch.full((batch_n * depth + 1, W), 7.0, dtype=torch.float64, device="cuda")
-    assert fleet.stationarity(out) == 0                                         # nothing flushed yet: nothing launched
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    assert fleet.flush() == batch_n and fleet.stationarity(out) == batch_n      # a partial handle: the first block alone
-    eng.synchronize()
-    got = out.cpu().numpy()
-    assert got[:batch_n].tobytes() == eng.stationarity(0, batch_n).tobytes() and np.all(got[batch_n:] == 7.0)
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    fleet.submit(t["x0"], t["xs"], t["us"])
-    lam = torch.full((batch_n * depth, N + 1, eng.nx), 7.0, dtype=torch.float64, device="cuda")
-    assert fleet.flush() == batch_n * depth and fleet.stationarity(out, lam=lam) == batch_n * depth
-    eng.synchronize()
-    got = out.cpu().numpy()
-    rec, flam, _ = eng.stationarity(full=True)
-    assert got[:-1].tobytes() == rec.tobytes() and np.all(got[-1] == 7.0) and lam.cpu().numpy().tobytes() == flam.tobytes()
-    assert got[:batch_n].tobytes() == got[batch_n:2 * batch_n].tobytes()        # the same robots in both blocks
-    eng.close()
+    assert_fleet_queue_follows_the_last_flush(STATIONARITY, sc.OPTS, "lam")[0].close()
