@@ -83,7 +83,13 @@ typedef struct sddp_options {
 } sddp_options;
 
 /* replaces what the reference bakes into the CasADi graphs from the URDF and the rosparam server
- * (prb.py:92-99 mass/inertia, prb.py:130-139 feet/com, prb.py:142-150 and :358-362 gains) */
+ * (prb.py:92-99 mass/inertia, prb.py:130-139 feet/com, prb.py:142-150 and :358-362 gains).
+ * Refused with SDDP_ERR_ARG and a message that names the field, before a device is looked for, by sddp_create, sddp_eval_knots and
+ * every entry of sddp_set_instance_consts: m, dt, force_scaling or lip_height not finite and > 0; a gain or weight (the *_gain
+ * fields, force_switch_weight) NaN, infinite or negative; a non-finite entry of I, com or feet; lever_sign other than +-1;
+ * inertia_mode other than 0 or 1.
+ * Of com only com[2] and of feet only the x / y offsets feet[2] - feet[0] and feet[3] - feet[1] enter the problem (the z tracking
+ * target, d_initial_1/2); com[0], com[1] and the z of the feet are inert in the kernels: they only enter x0 / c_ref, host side. */
 typedef struct sddp_model_consts {
     double m;              /* kg                                   prb.py:92    */
     double I[9];           /* kg m^2, row major                    prb.py:94-95 */

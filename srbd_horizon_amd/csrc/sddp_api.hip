@@ -572,6 +572,27 @@ int sddp_default_consts_for(int model_id, sddp_model_consts* c) {
 
 const char* sddp_last_error(const sddp_handle* h) { return h ? h->err.c_str() : create_error().c_str(); }
 
+// What make_dev_consts divides by, and what no robot has: "" for constants it may take, else the refusal, which names the field
+// (sddp.h: sddp_create, sddp_eval_knots and every entry of sddp_set_instance_consts).  Needs no device.
+static std::string check_consts(const sddp_model_consts& c) {
+    const struct { const char* name; double v; } positive[] = {{"m", c.m}, {"dt", c.dt}, {"force_scaling", c.force_scaling}, {"lip_height", c.lip_height}};
+    for (const auto& f : positive)
+        if (!(std::isfinite(f.v) && f.v > 0.0)) return std::string(f.name) + " must be finite and > 0";
+    const struct { const char* name; double v; } gains[] = {
+        {"r_tracking_gain", c.r_tracking_gain}, {"rdot_tracking_gain", c.rdot_tracking_gain}, {"w_tracking_gain", c.w_tracking_gain},
+        {"rel_pos_gain", c.rel_pos_gain}, {"force_switch_weight", c.force_switch_weight}, {"min_qddot_gain", c.min_qddot_gain},
+        {"min_f_gain", c.min_f_gain}, {"zmp_tracking_gain", c.zmp_tracking_gain}};
+    for (const auto& f : gains)
+        if (!(std::isfinite(f.v) && f.v >= 0.0)) return std::string(f.name) + " must be finite and >= 0";
+    const struct { const char* name; const double* v; int n; } vectors[] = {{"I", c.I, 9}, {"com", c.com, 3}, {"feet", c.feet, 12}};
+    for (const auto& f : vectors)
+        for (int i = 0; i < f.n; ++i)
+            if (!std::isfinite(f.v[i])) return std::string(f.name) + " holds a non-finite value";
+    if (c.lever_sign != 1.0 && c.lever_sign != -1.0) return "lever_sign must be +1 or -1";
+    if (c.inertia_mode != 0 && c.inertia_mode != 1) return "inertia_mode must be 0 or 1";
+    return "";
+}
+
 int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_options* opts, const sddp_model_consts* consts) {
     if (!out) return fail(nullptr, SDDP_ERR_ARG, "out is NULL");
     *out = nullptr;
@@ -588,6 +609,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
                                                     : "this model has no such build (srbd61: no second_order = 2 build)");
     const Dims d = ops->dims;
     if (N < 1 || batch < 1) return fail(nullptr, SDDP_ERR_ARG, "N and batch must be >= 1");
+    if (consts) { const std::string msg = check_consts(*consts); if (!msg.empty()) return fail(nullptr, SDDP_ERR_ARG, msg); }
     if (const char* msg = check_user_rows(model_id, consts)) return fail(nullptr, SDDP_ERR_ARG, msg);
     if (xr) { const char* msg = check_extra(*consts, d.nx, d.nu); if (msg) return fail(nullptr, SDDP_ERR_ARG, msg); }
     if (consts && (consts->friction_barrier_weight < 0.0 || (consts->friction_barrier_weight > 0.0 && !(consts->friction_cone_coefficient > 0.0))))
@@ -1209,6 +1231,8 @@ int sddp_set_instance_consts(sddp_handle* h, int first, int count, const sddp_mo
         if (c.n_extra != 0) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: n_extra must be 0 in every entry");
         if (c.friction_barrier_weight != 0.0 || c.bound_barrier_weight != 0.0)
             return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: friction_barrier_weight and bound_barrier_weight must be 0 in every entry");
+        const std::string msg = check_consts(c);
+        if (!msg.empty()) return fail(h, SDDP_ERR_ARG, "sddp_set_instance_consts: entry " + std::to_string(i) + ": " + msg);
     }
     const size_t B = size_t(h->B), n = size_t(count);
     host_buf rows(std::max(h->table.on() ? n : B, n) * sizeof(DevConsts));
@@ -1514,6 +1538,10 @@ int sddp_eval_knots(int model_id, const sddp_model_consts* consts, int N, int nk
     if (const char* msg = check_user_rows(model_id, &cc)) return fail(nullptr, SDDP_ERR_ARG, msg);
     if (nk < 1 || !k || !x || !u || !p) return fail(nullptr, SDDP_ERR_ARG, "bad argument");
     if (xr) { const char* msg = check_extra(cc, d.nx, d.nu); if (msg) return fail(nullptr, SDDP_ERR_ARG, msg); }
+    if (const std::string msg = check_consts(cc); !msg.empty()) return fail(nullptr, SDDP_ERR_ARG, msg);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return fail(nullptr, SDDP_ERR_HIP, "no HIP device visible: the SDDP engine has no CPU fallback");
     DevConsts dc = make_dev_consts(cc);
     const int nz = d.nx + d.nu;
     const size_t D = sizeof(double);

@@ -331,10 +331,11 @@ def assert_fleet_queue_follows_the_last_flush(insp, opts, optional=None):
 
 
 # ---- another iteration count than the oracle ---------------------------------------------------------------------------------------------
-def explain(c, s, opts, engine_over, idx):
-    """the instances on another iteration count than the oracle: one-step shadowing of the GPU path (tests/shadow.py)"""
+def explain(c, s, opts, engine_over, idx, cst=None):
+    """the instances on another iteration count than the oracle: one-step shadowing of the GPU path (tests/shadow.py).  cst: the
+    oracle's constants where they are not RobotConsts(**s["consts"]) (srbd61 with other feet: tests/consts_cases.py oracle_consts)"""
     from tests import shadow
-    recs = shadow.explain_divergent(c.model, c.N, opts, engine_over, s["consts"], omodels.RobotConsts(**s["consts"]), s, idx)
+    recs = shadow.explain_divergent(c.model, c.N, opts, engine_over, s["consts"], omodels.RobotConsts(**s["consts"]) if cst is None else cst, s, idx)
     out = []
     for r in recs:
         try:

@@ -99,8 +99,14 @@ def test_bit_identities_among_the_device_entry_points(model, N, B, M):
         xm = _pushed(x, s)
         gx, gu, gc = _rollout_dev(eng, xm, start=s)
         assert gu[:, 0].tobytes() == _apply(eng, xm, knot=s).tobytes(), f"start {s}"
-        same = gx[:, 1].tobytes() == eng.model_step(xm, gu[:, 0], P[:, s], s).tobytes()
-        print(f"{model} start {s}: x_out[:, 1] bit-equal to model_step: {same}")          # reported, not asserted
+        # Both kernels inline the same M::step on the same operands, but not provably as the same instruction sequence: model_step_kernel
+        # discards the stage cost that policy_rollout_kernel accumulates, and the cost shares products with the dynamics (wdot), so
+        # under the compiler's free contraction a product may be fused into an FMA in one kernel and kept apart in the other.  Bit
+        # equality is therefore reported; asserted is agreement within one rounding of each component: one unit in its last place.
+        step = eng.model_step(xm, gu[:, 0], P[:, s], s)
+        ulps = float(np.max(np.abs(gx[:, 1] - step) / np.spacing(np.abs(step))))
+        print(f"{model} start {s}: x_out[:, 1] bit-equal to model_step: {gx[:, 1].tobytes() == step.tobytes()}; worst difference {ulps:.0f} ulp")
+        assert ulps <= 1.0, (model, s, ulps)
     # ranges: the result of an instance does not depend on the range it was part of
     xm = _pushed(x, 0)
     whole = _rollout_dev(eng, xm)
