@@ -102,8 +102,16 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+STAT_FIELDS = ("cost", "iters", "converged", "alpha", "gap", "mu", "status", "rho")      # the stats columns of solve_batch / solve_trace
+
+
+def stat(stats, field):
+    """the column `field` of a stats array: [B] of solve_batch's [B, 8], a scalar of solve_trace's [8]"""
+    return stats[..., STAT_FIELDS.index(field)]
+
+
 def solve_batch(cst, opts, x0, P, xs, us, threads=1, model="srbd13", variant=None):
-    """-> xs [B,N+1,nx], us [B,N,nu], stats [B,8] = cost, iters, converged, alpha, gap, mu, status, rho"""
+    """-> xs [B,N+1,nx], us [B,N,nu], stats [B,8]: one column per STAT_FIELDS, read with stat()"""
     lib = load(variant)
     B, N = us.shape[0], us.shape[1]
     nx, nu, npar = DIMS[model]
@@ -138,7 +146,7 @@ TRACE_FIELDS = ("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_new", "th
 
 
 def solve_trace(cst, opts, x0, P, xs, us, model="srbd13", variant=None, cap=256, resume=None):
-    """One instance with its line-search record -> xs, us, stats[8], list of dicts (one per line search: TRACE_FIELDS plus
+    """One instance with its line-search record -> xs, us, stats [8] (STAT_FIELDS), list of dicts (one per line search: TRACE_FIELDS plus
     "margin" / "J_cand", the Armijo margin  dphi - (beta pred + slack)  and the cost of every candidate tried, largest step first;
     a candidate is accepted iff its margin <= 0)."""
     lib = load(variant)

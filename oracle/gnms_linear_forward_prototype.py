@@ -53,14 +53,15 @@ if __name__=="__main__":
     gap_tol=float(sys.argv[2]) if len(sys.argv)>2 else 1e-9
     o=oddp.DdpOptions(**dict(OPTS,gap_tol=gap_tol))
     xo,uo,so=cport.solve_batch(cst,oddp.DdpOptions(**OPTS),batch["x0"],batch["params"],batch["xs"],batch["us"],threads=8)
+    Jo,it_o,conv_o=(cport.stat(so,f) for f in ("cost","iters","converged"))
     t=time.time(); res=[]
     for b in range(len(seeds)):
         it,cv,st,J,xs,us,ev=solve_gnms(m,batch["x0"][b],batch["params"][b],batch["xs"][b],batch["us"][b],o)
-        res.append((it,cv,st,J,ev,np.max(np.abs(xs-xo[b])),abs(J-so[b,0])/so[b,0]))
+        res.append((it,cv,st,J,ev,np.max(np.abs(xs-xo[b])),abs(J-Jo[b])/Jo[b]))
     r=np.array([(a,b,c,e) for a,b,c,_,e,_,_ in res],float)
     print("time",time.time()-t)
-    print("DDP  : mean iters",so[:,1].mean(),"max",so[:,1].max(),"conv",so[:,2].mean())
+    print("DDP  : mean iters",it_o.mean(),"max",it_o.max(),"conv",conv_o.mean())
     print("GNMS : mean iters",r[:,0].mean(),"max",r[:,0].max(),"conv",r[:,1].mean(),"status",np.unique(r[:,2],return_counts=True),"merit evals per iter",r[:,3].sum()/max(r[:,0].sum(),1))
-    both=(so[:,2]==1)&(r[:,1]==1)
+    both=(conv_o==1)&(r[:,1]==1)
     print("same optimum: max linf x",max(x[5] for x,bb in zip(res,both) if bb),"max rel cost",max(x[6] for x,bb in zip(res,both) if bb))
-    print("iters DDP vs GNMS (first 30):",list(zip(so[:30,1].astype(int),r[:30,0].astype(int))))
+    print("iters DDP vs GNMS (first 30):",list(zip(it_o[:30].astype(int),r[:30,0].astype(int))))

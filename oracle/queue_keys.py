@@ -31,10 +31,10 @@ def collect(blocks):
     thr = min(16, os.cpu_count() or 1)
     out = {}
     _, _, s = cport.solve_batch(cst, oddp.DdpOptions(**OPTS), *a, threads=thr)
-    out["iters"] = s[:, 1].astype(int)
+    out["iters"] = cport.stat(s, "iters").astype(int)
     for k in (0, 1, 3):                                   # what a probe of k iterations would know
         _, _, s = cport.solve_batch(cst, oddp.DdpOptions(**dict(OPTS, max_iters=k)), *a, threads=thr)
-        out[f"J{k}"], out[f"a{k}"], out[f"gap{k}"] = s[:, 0], s[:, 3], s[:, 4]
+        out[f"J{k}"], out[f"a{k}"], out[f"gap{k}"] = cport.stat(s, "cost"), cport.stat(s, "alpha"), cport.stat(s, "gap")
     out["labels"], out["n_classes"] = workload.srbd13_schedule_classes(batch["params"])
     out["labels_unsigned"], _ = workload.srbd13_schedule_classes(batch["params"], signed=False)
     out["rdref"] = np.linalg.norm(batch["params"][:, N, 0:3], axis=1)

@@ -21,6 +21,7 @@ import functools
 import numpy as np
 
 from srbd_horizon_amd import workload
+from tests import oracle_refs as refs
 
 NAN = float("nan")
 CMDS = (0.0, -0.0, 1e-12, -1e-12, 2e-12, -2e-12, 0.5, -0.5)
@@ -87,7 +88,6 @@ def build(model, N, B, extra=0):
         labels[b] = ((s0 * (N + 2) + fc) * 3 + CMD_CLASS[ix]) * 3 + CMD_CLASS[iy]
         stance[b], change[b] = s0, fc
     out = dict(x0=batch["x0"], xs=batch["xs"], us=batch["us"], params=P, labels=labels, stance0=stance, first_change=change)
-    for a in out.values():
-        a.setflags(write=False)
+    refs.frozen(out.values())
     out.update(consts=batch["consts"], n_classes=36 * (N + 2))
     return out

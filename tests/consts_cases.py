@@ -24,12 +24,11 @@ draw_all  every field of _lib.INSTANCE_CONST_FIELDS drawn per instance from one 
 srbd61: the library's `feet` are contact points 0..3 of the eight-point model, the oracle's RobotConsts.feet8[:4] (oracle_consts).
 """
 import dataclasses
-import functools
 
 import numpy as np
 
 from oracle import models as omodels
-from srbd_horizon_amd import workload
+from tests import oracle_refs as refs
 
 MODELS = ("srbd13", "srbd37", "lip30", "srbd61")
 
@@ -56,14 +55,9 @@ APPLIES = {"srbd13": frozenset(_SRBD),
 COMPONENTS = {"com": np.array([False, False, True]), "feet": np.tile([True, True, False], (4, 1))}
 
 
-@functools.lru_cache(maxsize=None)
-def _workload_consts(model):
-    return dict(workload.make_batch(model, 1, [0])["consts"])
-
-
 def defaults(model):
     """the workload's constants of `model` (the library's defaults, written out): a fresh dict"""
-    return {k: (np.array(v, dtype=float) if np.ndim(v) else v) for k, v in _workload_consts(model).items()}
+    return {k: (np.array(v, dtype=float) if np.ndim(v) else v) for k, v in refs.batch(model, 1, [0])["consts"].items()}
 
 
 def off_value(model, field, base=None):
@@ -171,7 +165,7 @@ def knot_excess(got, ref):
 
 
 # ---- one sweep, one rollout and whole solves with ALL_OFF ---------------------------------------------------------------------------------
-BASE = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
+BASE = refs.BASE
 # (model, N, waves_per_simd builds): the smallest shapes tests/sweep_cases.py uses per family; theta = 1, mu = 1e-6, open gaps
 SWEEPS = (("srbd13", 3, (1, 2)), ("srbd37", 2, (1,)), ("lip30", 2, (2,)), ("srbd61", 1, (1,)))
 SO2_SWEEPS = (("srbd13", 3), ("srbd37", 2))      # the second_order = 2 builds: the same shapes, mode 2
@@ -188,16 +182,13 @@ SOLVE_OPTS = {"lip30": dict(alpha_0=0.5)}
 
 
 def solve_options(model):
-    return dict(BASE, **SOLVE_OPTS.get(model, {}))
+    return refs.options(SOLVE_OPTS.get(model, {}))
 
 
 def problem(model, N, seeds, consts=None):
     """the workload's batch of `seeds` for the robot `consts` (default ALL_OFF): the start is the workload's (the default robot's
     stance), the constants the solver and the oracle get are `consts` -> dict(x0, params, xs, us, consts)"""
-    b = workload.make_batch(model, N, list(seeds))
-    out = {k: b[k] for k in ("x0", "params", "xs", "us")}
-    out["consts"] = dict(ALL_OFF[model] if consts is None else consts)
-    return out
+    return dict(refs.batch(model, N, seeds), consts=dict(ALL_OFF[model] if consts is None else consts))
 
 
 def sweep_start(model, N, consts=None, mode=1):

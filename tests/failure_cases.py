@@ -43,11 +43,9 @@ from collections import namedtuple
 
 import numpy as np
 
-from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-from tests import options_cases as oc
+from tests import oracle_refs as refs
 
-BASE = oc.BASE
+BASE = refs.BASE
 SHAPES = {"srbd13": (30, 12), "srbd37": (20, 6), "lip30": (20, 6), "srbd61": (20, 4)}      # model -> (N, B)
 MODELS = tuple(SHAPES)
 FAIL = {"srbd13": (0, 4, 5, 11), "srbd37": (0, 2, 3, 5), "lip30": (0, 2, 3, 5), "srbd61": (0, 1, 3)}
@@ -83,41 +81,21 @@ def cases():
 
 CASES = {c.name: c for c in cases()}
 MIXED = tuple(n for n, c in CASES.items() if c.kind != "S2")
-
-
-def options(case, **more):
-    """the case's option dictionary (both sides: DdpEngine(opts=...) and oddp.DdpOptions(**...))"""
-    return dict(BASE, **case.over, **more)
+options = refs.case_options      # (case, **more) -> the case's option dictionary, both sides
 
 
 def healthy_idx(case):
     return np.array([b for b in range(len(case.seeds)) if b not in case.fail], dtype=int)
 
 
-def _frozen(d):
-    for k in ("x0", "params", "xs", "us"):
-        d[k].setflags(write=False)
-    return d
-
-
-@functools.lru_cache(maxsize=None)
-def _optimum(model):
-    """the optimum the C oracle (`off`) reaches under BASE from the warm start of seeds 0..B-1"""
-    N, B = SHAPES[model]
-    b = workload.make_batch(model, N, list(range(B)))
-    xs, us, st = cport.solve_batch(omodels.RobotConsts(**b["consts"]), oddp.DdpOptions(**BASE), b["x0"], b["params"], b["xs"], b["us"], model=model)
-    assert (st[:, 2] == 1).all() and (st[:, 6] == 0).all(), st
-    return xs, us
-
-
 def _make(c, seeds, fail):
     """the batch of `seeds` with the case's fault put on the instances `fail`"""
-    b = workload.make_batch(c.model, c.N, list(seeds))
-    out = {k: b[k].copy() for k in ("x0", "params", "xs", "us")}
-    out["consts"] = b["consts"]
+    out = refs.batch(c.model, c.N, seeds)
+    out.update({k: out[k].copy() for k in refs.ARRAYS})
     f = list(fail)
+    optimum = functools.partial(refs.optimum, c.model, c.N, tuple(range(len(seeds))))      # the C oracle's under BASE, seeds 0..B-1
     if c.kind == "S3e":                               # single shooting: the workload's constant input does not roll out to a finite cost
-        out["us"][:] = _optimum(c.model)[1]           # on every model; the optimum's inputs do
+        out["us"][:] = optimum()[1]                   # on every model; the optimum's inputs do
     if c.kind in ("S3a", "S3e"):
         out["x0"][f, 3:7] = np.nan
         out["xs"][f, :, 3:7] = np.nan
@@ -128,10 +106,10 @@ def _make(c, seeds, fail):
     elif c.kind == "S3d":
         out["x0"][f, 0] = HUGE_X0
     elif c.kind == "S40":                             # healthy instances: at the optimum; failing ones: the cold start
-        xs, us = _optimum(c.model)
+        xs, us = optimum()
         h = [i for i in range(len(seeds)) if i not in f]
         out["xs"][h], out["us"][h] = xs[h], us[h]
-    return _frozen(out)
+    return refs.frozen(out)
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,27 +131,21 @@ def healthy(name):
 
 
 def consts(name):
-    return omodels.RobotConsts(**start(name)["consts"])
+    return refs.consts(start(name))
 
 
 @functools.lru_cache(maxsize=None)
 def oracle(name, variant="off", twin=False):
     """-> (xs, us, stats [B,8]) of the C oracle build `variant` on the case's batch (twin: on its all-healthy twin), read-only"""
-    c, s = CASES[name], (healthy(name) if twin else start(name))
-    with np.errstate(all="ignore"):
-        out = cport.solve_batch(consts(name), oddp.DdpOptions(**options(c)), s["x0"], s["params"], s["xs"], s["us"], threads=4, model=c.model,
-                                variant=variant)
-    for a in out:
-        a.setflags(write=False)
-    return out
+    c = CASES[name]
+    return refs.c_oracle(c.model, healthy(name) if twin else start(name), options(c), variant)
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_trace(name, b, variant="off"):
     """-> the line-search records (cport.solve_trace) of instance b of the case"""
-    c, s = CASES[name], start(name)
-    return tuple(cport.solve_trace(consts(name), oddp.DdpOptions(**options(c)), s["x0"][b], s["params"][b], s["xs"][b], s["us"][b],
-                                   model=c.model, variant=variant)[3])
+    c = CASES[name]
+    return tuple(refs.c_trace(c.model, start(name), options(c), b, variant)[3])
 
 
 def expected_status(case):

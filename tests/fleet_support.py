@@ -5,8 +5,9 @@ import socket
 import numpy as np
 import torch
 
-from oracle import cport, ddp as oddp, models as omodels
+from oracle import cport
 from srbd_horizon_amd import _lib
+from tests import oracle_refs as refs
 
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 N, NX, NU, NP = 30, 13, 6, 19
@@ -32,12 +33,12 @@ class OracleEngine:
 
     def solve_range_device(self, params, first, count):
         s = slice(first, first + count)
-        xo, uo, so = cport.solve_batch(omodels.RobotConsts(), oddp.DdpOptions(**OPTS), self.x0[s].numpy(), params[s].numpy(),
-                                       self.x[s].numpy(), self.u[s].numpy(), threads=2)
-        self.x[s] = torch.from_numpy(xo)
-        self.u[s] = torch.from_numpy(uo)
-        self.stats["cost"][s] = so[:, 0]
-        self.stats["iters"][s] = so[:, 1].astype(np.int32)
+        start = dict(x0=self.x0[s].numpy(), params=params[s].numpy(), xs=self.x[s].numpy(), us=self.u[s].numpy(), consts={})      # the default robot
+        xo, uo, so = refs.c_oracle("srbd13", start, OPTS, threads=2)
+        self.x[s] = torch.from_numpy(xo.copy())
+        self.u[s] = torch.from_numpy(uo.copy())
+        self.stats["cost"][s] = cport.stat(so, "cost")
+        self.stats["iters"][s] = cport.stat(so, "iters").astype(np.int32)
 
     def fetch_device_views(self):
         return self.x, self.u, self.sf, self.si

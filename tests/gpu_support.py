@@ -1,7 +1,8 @@
-"""What the GPU tests share: loading and solving a batch on a handle, cutting and continuing a solve, the byte comparison of two
-results, the references several modules compare against (computed once per key, read-only), what the plan inspectors' modules share
-(the contract of DESIGN.md section 5, "Plan inspectors", as three routines), and the explanation of an instance on another iteration
-count than the oracle.  Plain functions, no fixtures; no test module imports another."""
+"""What the GPU tests share: loading and solving a batch on a handle, a whole solve compared with the C oracle's (the cases of
+tests/whole_solve_cases.py), cutting and continuing a solve, the byte comparison of two results, the references several modules
+compare against (computed once per key, read-only), what the plan inspectors' modules share (the contract of DESIGN.md section 5,
+"Plan inspectors", as three routines), and the explanation of an instance on another iteration count than the oracle.  Plain
+functions, no fixtures; no test module imports another."""
 import functools
 from typing import Callable, NamedTuple
 
@@ -13,16 +14,10 @@ from oracle import models as omodels
 from srbd_horizon_amd import _lib, workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
-from tests import iteration_log_cases as lc, plan_audit_cases as pac, resume_cases as rc
+from tests import iteration_log_cases as lc, parity, plan_audit_cases as pac, resume_cases as rc, whole_solve_cases as wc
+from tests.oracle_refs import frozen      # noqa: F401  (a cached reference: the same arrays, read-only)
 
 BUILDS = {"srbd13": (1, 2), "srbd37": (1, 2), "lip30": (2,), "srbd61": (1,)}          # waves_per_simd per model
-
-
-def frozen(arrays):
-    """a cached reference: the same arrays, read-only"""
-    for a in arrays:
-        a.setflags(write=False)
-    return arrays
 
 
 def dev(a):
@@ -64,6 +59,19 @@ def same_bytes(got, ref, sel=slice(None), msg=""):
         for f in ref[2].dtype.names:
             np.testing.assert_array_equal(got[2][f][sel], ref[2][f][sel], err_msg=f"stats.{f} {msg}")
         raise AssertionError(f"stats differ in their padding {msg}")
+
+
+def whole_solve(name, default_consts=False, check_handle=None, **engine_over):
+    """the case of tests/whole_solve_cases.py on a fresh handle (default_consts: one created without constants; check_handle(eng)
+    before the solve), compared with the C oracle's solve field by field (parity.assert_matches_c_oracle) -> (x, u, stats)"""
+    c, s = wc.CASES[name], wc.start(name)
+    eng = DdpEngine(c.model, c.N, len(c.seeds), opts=dict(wc.options(c), **engine_over), consts=None if default_consts else s["consts"])
+    if check_handle is not None:
+        check_handle(eng)
+    x, u, st = solve(eng, s)
+    eng.close()
+    parity.assert_matches_c_oracle(x, u, st, *wc.oracle(name), explain=lambda idx: explain(c, s, wc.options(c), engine_over, idx))
+    return x, u, st
 
 
 # ---- the handles and references of tests/resume_cases.py -------------------------------------------------------------------------------

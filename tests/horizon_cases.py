@@ -39,8 +39,7 @@ from collections import namedtuple
 import numpy as np
 
 from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-from tests import options_cases as oc, parity
+from tests import options_cases as oc, oracle_refs as refs, parity
 
 BASE = oc.BASE
 SEEDS = tuple(range(8))
@@ -90,34 +89,25 @@ ADVANCE_WORDS = 4096                                # sddp_advance shifts arrays
 
 def options(case, **more):
     """the case's option dictionary (both sides: DdpEngine(opts=...) and oddp.DdpOptions(**...))"""
-    return dict(BASE, **case.over, second_order=case.so, **more)
+    return refs.case_options(case, second_order=case.so, **more)
 
 
 @functools.lru_cache(maxsize=None)
 def start(name):
     """-> dict(x0, params, xs, us, consts) of the case: the workload's warm start, read-only"""
     c = CASES[name]
-    b = workload.make_batch(c.model, c.N, list(c.seeds))
-    out = {k: b[k] for k in ("x0", "params", "xs", "us")}
-    for a in out.values():
-        a.setflags(write=False)
-    out["consts"] = b["consts"]
-    return out
+    return refs.batch(c.model, c.N, c.seeds)
 
 
 def consts(name):
-    return omodels.RobotConsts(**start(name)["consts"])
+    return refs.consts(start(name))
 
 
 @functools.lru_cache(maxsize=None)
 def oracle(name, variant="off", max_iters=None):
     """-> (xs [B,N+1,nx], us [B,N,nu], stats [B,8]) of the C oracle build `variant` on the case, computed once, read-only"""
-    c, s = CASES[name], start(name)
-    o = options(c) if max_iters is None else options(c, max_iters=max_iters)
-    out = cport.solve_batch(consts(name), oddp.DdpOptions(**o), s["x0"], s["params"], s["xs"], s["us"], threads=4, model=c.model, variant=variant)
-    for a in out:
-        a.setflags(write=False)
-    return out
+    c = CASES[name]
+    return refs.c_oracle(c.model, start(name), options(c) if max_iters is None else options(c, max_iters=max_iters), variant)
 
 
 @functools.lru_cache(maxsize=None)
@@ -129,10 +119,9 @@ def oracle_truncated(name):
         m = omodels.make_model(c.model, consts(name))
         cost = np.array([oddp.total_cost(m, s["x0"][b][None], np.zeros((0, m.nu)), s["params"][b, :1]) for b in range(len(c.seeds))])
         return s["x0"][:, None, :].copy(), cost
-    xs, _, st = cport.solve_batch(consts(name), oddp.DdpOptions(**options(c)), s["x0"], s["params"][:, :c.N], s["xs"][:, :c.N], s["us"][:, :c.N - 1],
-                                  threads=4, model=c.model)
-    assert (oc.stat(st, "status") == 0).all(), (name, st)
-    return xs, oc.stat(st, "cost").copy()
+    xs, _, st = refs.c_oracle(c.model, s, options(c), params=s["params"][:, :c.N], xs=s["xs"][:, :c.N], us=s["us"][:, :c.N - 1])
+    assert (cport.stat(st, "status") == 0).all(), (name, st)
+    return xs, cport.stat(st, "cost").copy()
 
 
 def case_of(model, N):

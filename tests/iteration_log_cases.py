@@ -21,9 +21,8 @@ import functools
 
 import numpy as np
 
-from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-from tests import options_cases as oc, parity, resume_cases as rc
+from oracle import cport
+from tests import options_cases as oc, oracle_refs as refs, parity, resume_cases as rc
 
 SETTINGS = ("base", "A", "E", "so0", "ir1", "T", "Z")
 EXTRA = {"T": dict(alpha_converge_threshold=0.9), "Z": dict(initial_rollout=1)}
@@ -52,32 +51,26 @@ def options(case, **more):
 @functools.lru_cache(maxsize=None)
 def batch(model, case="base"):
     """the start of (model, setting), read-only: resume_cases' batch; srbd13 "ir1" on IR1_SEEDS; "Z" restarted from the oracle's optimum"""
+    N, B = rc.SHAPES[model]
     if model == "srbd13" and case == "ir1":
-        b = workload.make_batch(model, rc.SHAPES[model][0], list(IR1_SEEDS))
-        assert len(IR1_SEEDS) == rc.SHAPES[model][1]
-    elif case == "Z":
-        b = dict(rc.batch(model))
-        xo, uo, _ = rc.oracle(model, "base")
-        b["xs"], b["us"] = xo.copy(), uo.copy()
-    else:
-        return rc.batch(model)
-    for k in ("x0", "params", "xs", "us"):
-        b[k].setflags(write=False)
-    return b
+        assert len(IR1_SEEDS) == B
+        return refs.batch(model, N, IR1_SEEDS)
+    if case == "Z":
+        xs, us = refs.optimum(model, N, tuple(range(B)))
+        return dict(rc.batch(model), xs=xs, us=us)
+    return rc.batch(model)
 
 
 @functools.lru_cache(maxsize=None)
 def traces(model, case, variant="off"):
     """-> (list over the instances of [n, 12] arrays: the oracle's records, stats [B, 8]) of the uncut solve"""
     s = batch(model, case)
-    cst, opt = omodels.RobotConsts(**s["consts"]), oddp.DdpOptions(**options(case))
     recs, stats = [], []
     for b in range(len(s["x0"])):
-        _, _, st, tr = cport.solve_trace(cst, opt, s["x0"][b], s["params"][b], s["xs"][b], s["us"][b], model=model, variant=variant, cap=256)
-        a = np.array([[r[k] for k in cport.TRACE_FIELDS] for r in tr]).reshape(len(tr), 12)
-        a.setflags(write=False)
-        recs.append(a); stats.append(st)
-    return recs, np.array(stats)
+        _, _, st, tr = refs.c_trace(model, s, options(case), b, variant)
+        recs.append(np.array([[r[k] for k in cport.TRACE_FIELDS] for r in tr]).reshape(len(tr), 12))
+        stats.append(st)
+    return refs.frozen(recs), np.array(stats)
 
 
 @functools.lru_cache(maxsize=None)

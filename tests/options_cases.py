@@ -48,12 +48,10 @@ D..G but lip30's G, where they agree to the bit).  RHO_SPREAD is that figure; th
 import functools
 from collections import namedtuple
 
-import numpy as np
+from oracle import cport
+from tests import oracle_refs as refs
 
-from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-
-BASE = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
+BASE = refs.BASE
 HORIZON = {"srbd13": 30, "srbd37": 20, "lip30": 20, "srbd61": 20}
 MODELS = tuple(HORIZON)
 
@@ -94,71 +92,45 @@ def cases():
 
 
 CASES = {c.name: c for c in cases()}
-
-
-def options(case, **more):
-    """the case's option dictionary (both sides: DdpEngine(opts=...) and oddp.DdpOptions(**...))"""
-    o = dict(BASE)
-    o.update(case.over)
-    o.update(more)
-    return o
+options = refs.case_options      # (case, **more) -> the case's option dictionary, both sides
 
 
 @functools.lru_cache(maxsize=None)
 def start(name):
     """-> dict(x0, params, xs, us, consts) of the case, read-only; "restart": xs, us = the C oracle's (`off`) optimum under BASE"""
     c = CASES[name]
-    b = workload.make_batch(c.model, c.N, list(c.seeds))
-    out = {k: b[k] for k in ("x0", "params", "xs", "us")}
-    out["consts"] = b["consts"]
+    out = refs.batch(c.model, c.N, c.seeds)
     if c.start == "restart":
-        xs, us, st = cport.solve_batch(consts(name, b["consts"]), oddp.DdpOptions(**BASE), b["x0"], b["params"], b["xs"], b["us"], model=c.model)
-        assert (st[:, 2] == 1).all() and (st[:, 6] == 0).all(), st
+        xs, us = refs.optimum(c.model, c.N, c.seeds)
         out["xs"], out["us"] = xs, us + G_U_SHIFT.get(c.model, 0.0)
-    for k in ("x0", "params", "xs", "us"):
-        out[k].setflags(write=False)
-    return out
+    return refs.frozen(out)
 
 
-def consts(name, c=None):
-    return omodels.RobotConsts(**(start(name)["consts"] if c is None else c))
-
-
-STAT_FIELDS = ("cost", "iters", "converged", "alpha", "gap", "mu", "status", "rho")      # cport.solve_batch's stats columns
+def consts(name):
+    return refs.consts(start(name))
 
 
 @functools.lru_cache(maxsize=None)
 def oracle(name, variant="off", second_order=1):
     """-> (xs [B,N+1,nx], us [B,N,nu], stats [B,8]) of the C oracle build `variant` on the case, computed once, read-only"""
-    c, s = CASES[name], start(name)
-    out = cport.solve_batch(consts(name), oddp.DdpOptions(**options(c, second_order=second_order)), s["x0"], s["params"], s["xs"], s["us"], threads=4, model=c.model,
-                            variant=variant)
-    for a in out:
-        a.setflags(write=False)
-    return out
+    c = CASES[name]
+    return refs.c_oracle(c.model, start(name), options(c, second_order=second_order), variant)
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_start_stats(name):
     """-> stats [B,8] of the start itself (max_iters = 0): its cost and defect norm"""
-    c, s = CASES[name], start(name)
-    st = cport.solve_batch(consts(name), oddp.DdpOptions(**options(c, max_iters=0)), s["x0"], s["params"], s["xs"], s["us"], model=c.model)[2]
-    st.setflags(write=False)
-    return st
+    c = CASES[name]
+    return refs.c_oracle(c.model, start(name), options(c, max_iters=0))[2]
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_tried(name, variant="off"):
     """-> per instance the tuple of `tried` (candidates rolled out) of every line search of the solve, from cport.solve_trace"""
-    c, s = CASES[name], start(name)
+    c = CASES[name]
     out = []
     for b in range(len(c.seeds)):
-        _, _, st, tr = cport.solve_trace(consts(name), oddp.DdpOptions(**options(c)), s["x0"][b], s["params"][b], s["xs"][b], s["us"][b],
-                                         model=c.model, variant=variant)
-        assert st[1] == oracle(name, variant)[2][b, 1]
+        _, _, st, tr = refs.c_trace(c.model, start(name), options(c), b, variant)
+        assert cport.stat(st, "iters") == cport.stat(oracle(name, variant)[2], "iters")[b]
         out.append(tuple(int(r["tried"]) for r in tr))
     return tuple(out)
-
-
-def stat(stats, field):
-    return stats[:, STAT_FIELDS.index(field)]

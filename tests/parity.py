@@ -2,7 +2,7 @@
 only (tests/options_cases.py, which holds RHO_RTOL beside the figure it is derived from, needs no GPU either): CPU tests import this
 module, tests/test_parity_helper_cpu.py pins every bound below.
 
-Against the C oracle (cport.solve_batch: stats [B, 8] = options_cases.STAT_FIELDS): iters, status, converged and alpha exact (alpha:
+Against the C oracle (cport.solve_batch: stats [B, 8] = cport.STAT_FIELDS): iters, status, converged and alpha exact (alpha:
 the same double); mu rel 1e-12 (regularisation bump: exact factors of ten); l-inf of x and of u 1e-6 and cost rel 1e-9 (a converged
 solve, fp64 on both sides); gap rel 1e-9 (the start's defect norm times exact factors 1 - alpha); rho within RHO_RTOL, ten times the
 spread of the oracle's own two builds.
@@ -14,7 +14,8 @@ deviations() divides by the cost: failed instances go through failed_deviations(
 import numpy as np
 import pytest
 
-from tests.options_cases import RHO_RTOL, stat
+from oracle.cport import stat
+from tests.options_cases import RHO_RTOL
 
 X_TOL = 1e-6             # l-inf of x and of u
 COST_RTOL = 1e-9

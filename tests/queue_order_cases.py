@@ -8,7 +8,7 @@ The order changes no byte of any result, so no parity test sees it; here it is t
   order 3   descending  mean + 1e-3 j0 / (|j0| + 1e9),  mean = the class's iterations / solves so far, 1e6 for label -1 and
             for a class without history; a non-finite j0 stays the key                                    order3_keys
   order 1   descending  min(iterations of the previous solve, 256),  257 for "never solved"               order1_keys
-J0 comes from the C oracle (cport.solve_batch at max_iters = 0, stats[:, 0]) with the case's model, constants and parameter rows,
+J0 comes from the C oracle (cport.solve_batch at max_iters = 0, the stats' "cost") with the case's model, constants and parameter rows,
 instance by instance where the instances have constants of their own.  The one exception is the user build: its rows are
 non-linear, which the C oracle does not have, so its J0 is oracle.ddp.total_cost of the numpy oracle wrapped with the same rows
 (tests/user_terms_oracle.py); test_queue_order_cases_cpu.py asserts that this sum and the C oracle agree to 1e-12 on the same batch
@@ -102,10 +102,10 @@ import numpy as np
 
 from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
-from tests import failure_cases as fc, options_cases as oc, user_terms_defs as defs, variant_cases
+from tests import failure_cases as fc, oracle_refs as refs, user_terms_defs as defs, variant_cases
 from tests.user_terms_oracle import WithUserRows
 
-BASE = oc.BASE
+BASE = refs.BASE
 KEY_RTOL = 1e-9
 SEPARATION = 1e-6                     # relative to max |J0|: no two finite reference keys of a case are closer
 MUTATION_SHARE = 0.25                  # of the queue positions: what every mutation of a case's key must move
@@ -263,13 +263,6 @@ def order1_ties(keys):
 
 
 # ---- the key cases: inputs and references -------------------------------------------------------------------------------------------
-def _frozen(d):
-    for k in ("x0", "params", "xs", "us"):
-        d[k] = np.ascontiguousarray(d[k])
-        d[k].setflags(write=False)
-    return d
-
-
 @functools.lru_cache(maxsize=None)
 def user_spec(N):
     return defs.spec_of(defs.srbd13_terrain(N, gain=USER_GAIN)[1])
@@ -281,7 +274,7 @@ NOISE_V, NOISE_R, NOISE_U, NOISE_SEED = 3.0, 0.3, 0.05, 20260
 def _noisy_batch(model, N, seeds, inputs=False, position=False):
     """workload.make_batch with seeded noise on the warm start: NOISE_V N(0, 1) on the CoM velocity of the knots 1 .. N and, with
     `inputs`, NOISE_U N(0, 1) on every input (module docstring)"""
-    b = workload.make_batch(model, N, list(seeds))
+    b = refs.batch(model, N, seeds)
     rng = np.random.default_rng(NOISE_SEED + int(seeds[0]))
     xs, us = b["xs"].copy(), b["us"].copy()
     rd = omodels.make_model(model).RD_
@@ -326,19 +319,18 @@ def start(name):
             assert fc.CASES[f"{kind}-{c.model}"].N == c.N and 0 in fc.CASES[f"{kind}-{c.model}"].fail
             for k in ("x0", "xs", "us", "params"):
                 out[k][at] = f[k][0]
-    out = _frozen(out)
+    out = refs.frozen(out)
     out.update(consts=consts, plain=plain, table=table, csts=csts, opts=opts)
     return out
 
 
 def _c_costs(model, csts, s, P, variant):
     """J0 of every instance from the C oracle: one call where the instances share their constants, else instance by instance"""
-    o = oddp.DdpOptions(**dict(BASE, max_iters=0))
-    with np.errstate(all="ignore"):
-        if all(c is csts[0] for c in csts):
-            return cport.solve_batch(csts[0], o, s["x0"], P, s["xs"], s["us"], model=model, variant=variant)[2][:, 0].copy()
-        return np.array([cport.solve_batch(c, o, s["x0"][b:b + 1], P[b:b + 1], s["xs"][b:b + 1], s["us"][b:b + 1], model=model,
-                                           variant=variant)[2][0, 0] for b, c in enumerate(csts)])
+    def cost(c, sel):
+        return cport.stat(refs.c_oracle(model, s, refs.options({}, max_iters=0), variant, cst=c, sel=sel, params=P)[2], "cost")
+    if all(c is csts[0] for c in csts):
+        return cost(csts[0], slice(None)).copy()
+    return np.array([cost(c, [b])[0] for b, c in enumerate(csts)])
 
 
 def _user_model(name):
@@ -356,8 +348,7 @@ def initial_costs(name, variant="off"):
         J = np.array([oddp.total_cost(m, xs[b], s["us"][b], s["params"][b]) for b in range(c.B)])
     else:
         J = _c_costs(c.model, s["csts"], s, s["params"], variant)
-    J.setflags(write=False)
-    return J
+    return refs.frozen(J)
 
 
 def _knot_cost(name, b, k):
@@ -406,39 +397,33 @@ def mutants(name):
 
 # ---- order 1, case (c), and the order 3 shapes -------------------------------------------------------------------------------------
 def c_options(**more):
-    return dict(BASE, alpha_0=C_ALPHA0, **more)
+    return refs.options(dict(alpha_0=C_ALPHA0), **more)
 
 
 @functools.lru_cache(maxsize=None)
 def c_start():
-    b = workload.make_batch(C_MODEL, C_N, list(range(C_SEED0, C_SEED0 + B)))
-    return _frozen({k: b[k] for k in ("x0", "params", "xs", "us")} | {"consts": b["consts"]})
+    return refs.batch(C_MODEL, C_N, range(C_SEED0, C_SEED0 + B))
 
 
 @functools.lru_cache(maxsize=None)
 def c_oracle_iters(max_iters, variant="off", first=0, count=B):
     """-> the C oracle's iteration counts [count] of case (c) at that cap"""
-    s = c_start()
-    r = slice(first, first + count)
-    st = cport.solve_batch(omodels.RobotConsts(**s["consts"]), oddp.DdpOptions(**c_options(max_iters=max_iters)), s["x0"][r], s["params"][r],
-                           s["xs"][r], s["us"][r], threads=4, model=C_MODEL, variant=variant)[2]
-    return st[:, 1].astype(int)
+    st = refs.c_oracle(C_MODEL, c_start(), c_options(max_iters=max_iters), variant, sel=slice(first, first + count))[2]
+    return cport.stat(st, "iters").astype(int)
 
 
 @functools.lru_cache(maxsize=None)
 def stride_start():
-    b = workload.make_batch(STRIDE["model"], STRIDE["N"], list(range(STRIDE["seed0"], STRIDE["seed0"] + STRIDE["B"])))
-    return _frozen({k: b[k] for k in ("x0", "params", "xs", "us")} | {"consts": b["consts"]})
+    return refs.batch(STRIDE["model"], STRIDE["N"], range(STRIDE["seed0"], STRIDE["seed0"] + STRIDE["B"]))
 
 
 @functools.lru_cache(maxsize=None)
 def order3_start(model):
     """-> dict(x0, params, xs, us, consts, labels, n_classes, J0) of the order 3 shape of `model`, read-only"""
     N, B3, _, _, seed0 = ORDER3[model]
-    b = workload.make_batch(model, N, list(range(seed0, seed0 + B3)))
-    out = _frozen({k: b[k] for k in ("x0", "params", "xs", "us")} | {"consts": b["consts"]})
-    out["labels"], out["n_classes"] = (workload.srbd13_schedule_classes if model == "srbd13" else functools.partial(workload.schedule_classes, model))(b["params"])
-    out["J0"] = _c_costs(model, [omodels.RobotConsts(**b["consts"])] * B3, out, out["params"], "off")
+    out = refs.batch(model, N, range(seed0, seed0 + B3))
+    out["labels"], out["n_classes"] = (workload.srbd13_schedule_classes if model == "srbd13" else functools.partial(workload.schedule_classes, model))(out["params"])
+    out["J0"] = _c_costs(model, [refs.consts(out)] * B3, out, out["params"], "off")
     return out
 
 

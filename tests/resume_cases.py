@@ -19,11 +19,7 @@ would pass -- and where the workload seeds 0..47 at N = 10 show them on the C or
 """
 import functools
 
-import numpy as np
-
-from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-from tests import options_cases as oc
+from tests import options_cases as oc, oracle_refs as refs
 
 SHAPES = {"srbd13": (10, 48), "srbd37": (8, 8), "lip30": (8, 8), "srbd61": (6, 4)}      # model -> (N, B); seeds 0 .. B - 1
 MAX_SLOTS = {"srbd13": 4, "srbd37": 2, "lip30": 2, "srbd61": 2}
@@ -39,24 +35,16 @@ IDENTITY = [("srbd13", "base", 1), ("srbd13", "base", 2), ("srbd13", "ir1", 2), 
 
 
 def options(case, **more):
-    return dict(oc.BASE, **OVER[case], **more)
+    return refs.options(OVER[case], **more)
 
 
 @functools.lru_cache(maxsize=None)
 def batch(model):
     N, B = SHAPES[model]
-    b = workload.make_batch(model, N, list(range(B)))
-    for k in ("x0", "params", "xs", "us"):
-        b[k].setflags(write=False)
-    return b
+    return refs.batch(model, N, range(B))
 
 
 @functools.lru_cache(maxsize=None)
 def oracle(model, case, max_iters=TOTAL):
-    """-> (xs, us, stats [B, 8] = cost, iters, converged, alpha, gap, mu, status, rho) of the C oracle, read-only"""
-    b = batch(model)
-    out = cport.solve_batch(omodels.RobotConsts(**b["consts"]), oddp.DdpOptions(**options(case, max_iters=max_iters)), b["x0"], b["params"],
-                            b["xs"], b["us"], threads=4, model=model)
-    for a in out:
-        a.setflags(write=False)
-    return out
+    """-> (xs, us, stats [B, 8]: cport.STAT_FIELDS) of the C oracle, read-only"""
+    return refs.c_oracle(model, batch(model), options(case, max_iters=max_iters))

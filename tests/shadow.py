@@ -15,6 +15,8 @@ import os
 import numpy as np
 
 from oracle import cport, ddp as oddp
+from oracle.cport import stat
+from tests import oracle_refs as refs
 
 
 PROBE_REL = 1e-12      # relative size (per entry) of the perturbations of the iterate
@@ -29,7 +31,7 @@ ONE_STEP_MEDIAN_RTOL = 1e-7    # and the median step of an instance by no more t
 
 def _one_step(cst, o1, x0, P, x, u, resume, model, variant=None):
     xo, uo, st, tr = cport.solve_trace(cst, o1, x0, P, x, u, model=model, variant=variant, resume=resume)
-    return xo, uo, st, tr, (float(st[3]) if int(st[1]) == 1 else 0.0)      # step length taken (0.0: line search exhausted)
+    return xo, uo, st, tr, (float(stat(st, "alpha")) if int(stat(st, "iters")) == 1 else 0.0)      # step length taken (0.0: line search exhausted)
 
 
 def _max_cond_quu(cst, model, x0, P, xs, us, mu):
@@ -76,7 +78,7 @@ def shadow_one_instance(cst, opts: dict, x0, P, states, model="srbd13", variant=
                       mu=s["mu"])
         xo, uo, st, tr, a_o = _one_step(cst, o1, x0, P, s["x"], s["u"], resume, model, variant)
         J = max(abs(t["cost"]), 1e-300)
-        rec = dict(k=k + 1, alpha_engine=float(t["alpha"]), alpha_oracle=a_o, rel_cost=abs(st[0] - t["cost"]) / J,
+        rec = dict(k=k + 1, alpha_engine=float(t["alpha"]), alpha_oracle=a_o, rel_cost=abs(stat(st, "cost") - t["cost"]) / J,
                    rel_x=float(np.max(np.abs(xo - t["x"])) / max(np.max(np.abs(t["x"])), 1e-300)),
                    rel_u=float(np.max(np.abs(uo - t["u"])) / max(np.max(np.abs(t["u"])), 1e-300)))
         # the oracle against itself, from perturbed copies of the same iterate
@@ -91,7 +93,7 @@ def shadow_one_instance(cst, opts: dict, x0, P, states, model="srbd13", variant=
             _, _, sp, _, a_p = _one_step(cst, o1, x0, P, *perturbed(), resume, model, variant)
             alphas.add(a_p)
             if a_p == a_o:
-                sens = max(sens, abs(sp[0] - st[0]) / max(abs(st[0]), 1e-300))
+                sens = max(sens, abs(stat(sp, "cost") - stat(st, "cost")) / max(abs(stat(st, "cost")), 1e-300))
         rec["noise_explained"] = False
         if rec["alpha_engine"] != a_o:           # different step lengths from the same iterate: look harder
             alphas.add(_one_step(cst, o1, x0, P, s["x"], s["u"], resume, model, "fast" if variant != "fast" else "off")[4])
@@ -139,8 +141,8 @@ def engine_states_from_oracle(cst, opts: dict, x0, P, xs, us, model="srbd13", va
     for k in range(kmax + 1):
         o = oddp.DdpOptions(**dict(opts, max_iters=k))
         x, u, st = cport.solve_batch(cst, o, x0[None], P[None], xs[None], us[None], model=model, variant=variant)
-        states.append(dict(x=x[0], u=u[0], cost=st[0, 0], iters=int(st[0, 1]), converged=int(st[0, 2]), alpha=st[0, 3], gap=st[0, 4],
-                           mu=st[0, 5], status=int(st[0, 6]), rho=st[0, 7]))
+        rec = {f: stat(st, f)[0] for f in cport.STAT_FIELDS}
+        states.append(dict(rec, x=x[0], u=u[0], iters=int(rec["iters"]), converged=int(rec["converged"]), status=int(rec["status"])))
         if states[-1]["iters"] < k:
             break
     return states
@@ -231,17 +233,16 @@ def explain_divergent(model, N, opts, engine_over, consts, cst, batch, idx):
     gs = engine_states(model, N, dict(opts, **engine_over), consts, sub["x0"], sub["params"], sub["xs"], sub["us"], kmax)
     out = []
     for j, b in enumerate(idx):
-        a = (cst, oddp.DdpOptions(**opts), sub["x0"][j], sub["params"][j], sub["xs"][j], sub["us"][j])
-        xo, uo, so, tr_off = cport.solve_trace(*a, model=model)
-        xf, uf, sf, tr_fast = cport.solve_trace(*a, model=model, variant="fast")
+        xo, uo, so, tr_off = refs.c_trace(model, sub, opts, j, cst=cst)
+        xf, uf, sf, tr_fast = refs.c_trace(model, sub, opts, j, "fast", cst=cst)
         steps = shadow_one_instance(cst, opts, sub["x0"][j], sub["params"][j], gs[j], model=model)
         end = gs[j][kmax]
-        rec = dict(instance=int(b), gpu_iters=end["iters"], oracle_iters=int(so[1]), oracle_fast_iters=int(sf[1]),
-                   gpu_status=end["status"], oracle_status=int(so[6]),
+        rec = dict(instance=int(b), gpu_iters=end["iters"], oracle_iters=int(stat(so, "iters")), oracle_fast_iters=int(stat(sf, "iters")),
+                   gpu_status=end["status"], oracle_status=int(stat(so, "status")),
                    shadow=summarize(steps),
                    split_gpu=first_split(gs[j], tr_off), split_cpu_fast=first_split(tr_fast, tr_off),
                    end_linf=float(max(np.max(np.abs(end["x"] - xo)), np.max(np.abs(end["u"] - uo)))),
-                   end_rel_cost=float(abs(end["cost"] - so[0]) / max(abs(so[0]), 1e-300)))
+                   end_rel_cost=float(abs(end["cost"] - stat(so, "cost")) / max(abs(stat(so, "cost")), 1e-300)))
         out.append(rec)
     return out
 
@@ -277,16 +278,14 @@ def check_batch(model, N, batch, opts, engine_over, cst, threads=16):
 def compare_batch(model, N, batch, opts, engine_over, cst, x, u, st, threads=16, queue_info=None):
     """The oracle side of check_batch for results (x, u, st) the engine has already produced from `batch` (x0, params, xs, us,
     consts) -- e.g. one tick of a device-resident receding-horizon loop, whose inputs the caller has rebuilt on the host."""
-    o = oddp.DdpOptions(**opts)
-    xo, uo, so = cport.solve_batch(cst, o, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=threads, model=model)
-    _, _, sf = cport.solve_batch(cst, o, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=threads, model=model,
-                                 variant="fast")
-    it_o = so[:, 1].astype(int)
+    xo, uo, so = refs.c_oracle(model, batch, opts, cst=cst, threads=threads)
+    sf = refs.c_oracle(model, batch, opts, "fast", cst=cst, threads=threads)[2]
+    it_o = stat(so, "iters").astype(int)
     same = st["iters"] == it_o
     idx = np.nonzero(~same)[0]
     explained = explain_divergent(model, N, opts, engine_over, batch["consts"], cst, batch, idx) if idx.size else []
     return dict(x=x, u=u, st=st, xo=xo, uo=uo, so=so, same=same, explained=explained, queue_info=queue_info,
-                n_cpu_pair=int((sf[:, 1] != so[:, 1]).sum()), cpu_pair_idx=np.nonzero(sf[:, 1] != so[:, 1])[0])
+                n_cpu_pair=int((stat(sf, "iters") != stat(so, "iters")).sum()), cpu_pair_idx=np.nonzero(stat(sf, "iters") != stat(so, "iters"))[0])
 
 
 def parity_record(res):
@@ -317,11 +316,11 @@ def assert_batch(res, key, record_property, tripwire=True, same_optimum=True):
     x, u, st, xo, uo, so, same = (res[k] for k in ("x", "u", "st", "xo", "uo", "so", "same"))
     report_parity(record_property, key, **parity_record(res))
     # ---- same path: end-to-end parity at the north_star tolerance
-    np.testing.assert_array_equal(st["status"][same], so[same, 6].astype(int))
-    np.testing.assert_array_equal(st["converged"][same], so[same, 2].astype(int))
-    conv = same & (so[:, 2] == 1)
+    np.testing.assert_array_equal(st["status"][same], stat(so, "status")[same].astype(int))
+    np.testing.assert_array_equal(st["converged"][same], stat(so, "converged")[same].astype(int))
+    conv = same & (stat(so, "converged") == 1)
     assert np.max(np.abs(x[conv] - xo[conv])) <= 1e-4 and np.max(np.abs(u[conv] - uo[conv])) <= 1e-4
-    np.testing.assert_allclose(st["cost"][conv], so[conv, 0], rtol=1e-8)
+    np.testing.assert_allclose(st["cost"][conv], stat(so, "cost")[conv], rtol=1e-8)
     assert np.all(np.isfinite(x)) and np.all(np.isfinite(u)) and np.all(np.isfinite(st["cost"]))
     # ---- another path: every accepted GPU step is the oracle's step from the same iterate
     for rec in res["explained"]:

@@ -15,9 +15,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from oracle import cport, ddp as oddp, models as omodels  # noqa: E402
+from oracle import cport, models as omodels  # noqa: E402
 from srbd_horizon_amd import workload  # noqa: E402
-from tests import shadow  # noqa: E402
+from tests import oracle_refs as refs, shadow  # noqa: E402
 from tests.shadow import OPTS, THREADS, assert_batch  # noqa: E402
 
 
@@ -42,21 +42,19 @@ def main(first, chunks, per, model="srbd13", N=30, over=None):
         other_rec = []
         for r in other:
             i = r["instance"]
-            a = [batch[k][i:i + 1] for k in ("x0", "params", "xs", "us")]
-            cst = omodels.RobotConsts(**batch["consts"])
-            xf, uf, sf = cport.solve_batch(cst, oddp.DdpOptions(**OPTS), *a, threads=1, variant="fast", model=model)
+            xf, uf, sf = refs.c_oracle(model, batch, OPTS, "fast", sel=[i], threads=1)
             sp = r["split_gpu"] or {}
             other_rec.append(dict(seed=int(seeds[i]), it=(r["gpu_iters"], r["oracle_iters"], r["oracle_fast_iters"]), end_linf=r["end_linf"],
                                   end_rel_cost=r["end_rel_cost"], split_step=sp.get("step"), drift_before=sp.get("drift_before"),
                                   shadow_max_rel_cost=float(r["shadow"]["max_rel_cost"]), shadow_violations=len(r["shadow"]["violations"]),
-                                  cpu_builds_end_linf=float(np.max(np.abs(xf[0] - res["xo"][i]))), cpu_fast_status=int(sf[0, 6])))
+                                  cpu_builds_end_linf=float(np.max(np.abs(xf[0] - res["xo"][i]))), cpu_fast_status=int(cport.stat(sf, "status")[0])))
             # the split must come after a visible drift, with every GPU step shadowed (assert_batch has checked the latter)
             if not (sp.get("drift_before") is not None and sp["drift_before"] >= 1e-9):
                 failed = (failed or "") + f" | other optimum without a visible drift before the split: {r}"[:2000]
         same, so, st = res["same"], res["so"], res["st"]
-        conv = same & (so[:, 2] == 1)
+        conv = same & (cport.stat(so, "converged") == 1)
         rec = dict(blocks=[blocks[0], blocks[-1]], instances=len(seeds), other_path=len(res["explained"]), cpu_pair=int(res["n_cpu_pair"]),
-                   both=len(set(r["instance"] for r in res["explained"]) & set(res["cpu_pair_idx"].tolist())), unconverged_oracle=int((so[:, 2] == 0).sum()), unconverged_gpu=int((st["converged"] == 0).sum()),
+                   both=len(set(r["instance"] for r in res["explained"]) & set(res["cpu_pair_idx"].tolist())), unconverged_oracle=int((cport.stat(so, "converged") == 0).sum()), unconverged_gpu=int((st["converged"] == 0).sum()),
                    worst_same_linf=float(max(np.max(np.abs(res["x"][conv] - res["xo"][conv])), np.max(np.abs(res["u"][conv] - res["uo"][conv])))),
                    worst_end_linf=float(max([r["end_linf"] for r in res["explained"] if r["gpu_status"] == 0 and r["oracle_status"] == 0
                                              and r["end_linf"] <= 1e-4] or [0.0])),

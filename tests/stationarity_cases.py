@@ -16,9 +16,9 @@ import functools
 
 import numpy as np
 
-from oracle import cport, ddp as oddp, models as omodels
+from oracle import cport, models as omodels
 from srbd_horizon_amd import _lib
-from tests import plan_audit_cases as pac
+from tests import oracle_refs as refs, plan_audit_cases as pac
 
 W = len(_lib.STATIONARITY_FIELDS)
 STAT, NODE, INPUT, SCALE, LAM0, LAM_MAX, DEFECT, NODES = range(8)
@@ -117,10 +117,8 @@ def oracle_plans(model, N, B, kind):
     """(batch, P, RobotConsts, xs, us, stats) of a case: the plans the C oracle returns at the case's options; read-only"""
     batch, P, consts, opts = problem(model, N, B, kind)
     cst = omodels.RobotConsts(**consts)
-    xs, us, st = cport.solve_batch(cst, oddp.DdpOptions(**opts), batch["x0"], P, batch["xs"], batch["us"], model=model)
-    for a in (xs, us, st, P):
-        a.setflags(write=False)
-    return batch, P, cst, xs, us, st
+    xs, us, st = refs.c_oracle(model, batch, opts, cst=cst, params=P)
+    return batch, refs.frozen(P), cst, xs, us, st
 
 
 def measure():

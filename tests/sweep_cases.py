@@ -36,10 +36,9 @@ from collections import namedtuple
 import numpy as np
 
 from oracle import ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
-from tests import variant_cases
+from tests import oracle_refs as refs, variant_cases
 
-BASE = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
+BASE = refs.BASE
 CUT = 2
 NOISE = 1e-3
 ALPHAS = (1.0, 0.25, 2.0 ** -10)
@@ -101,7 +100,7 @@ def _start(model, build, N, seeds, cut):
     models: one oracle model per instance); read-only"""
     so2, extra = BUILDS[build]
     B = len(seeds)
-    batch = workload.make_batch(model, N, list(seeds))
+    batch = refs.batch(model, N, seeds)
     P, consts, table = batch["params"], dict(batch["consts"]), None
     if extra == "rows":                                   # the four user rows of tests/test_gpu_extra_rows.py
         _, P, consts = variant_cases.extra_rows_problem(model, N, list(seeds))
@@ -116,11 +115,8 @@ def _start(model, build, N, seeds, cut):
     models = [omodels.make_model(model, c) for c in csts]
     opt = oddp.DdpOptions(**dict(BASE, second_order=2 if so2 else 1, max_iters=cut))
     res = [oddp.solve(models[b], batch["x0"][b], P[b], batch["xs"][b], batch["us"][b], opt) for b in range(B)]
-    out = dict(x0=batch["x0"], params=np.ascontiguousarray(P), xs=np.stack([r.xs for r in res]), us=np.stack([r.us for r in res]))
-    for a in out.values():
-        a.setflags(write=False)
-    out.update(consts=consts, table=table, models=models)
-    return out
+    return refs.frozen(dict(x0=batch["x0"], params=np.ascontiguousarray(P), xs=np.stack([r.xs for r in res]), us=np.stack([r.us for r in res]),
+                            consts=consts, table=table, models=models))
 
 
 def start(case):
@@ -136,8 +132,7 @@ def _trajectory(model, build, N, seeds, cut, noise):
         xs += noise * rng.standard_normal(xs.shape)
         us += noise * rng.standard_normal(us.shape)
         xs[:, 0] = s["x0"]
-    xs.setflags(write=False); us.setflags(write=False)
-    return xs, us
+    return refs.frozen((xs, us))
 
 
 def trajectory(case):

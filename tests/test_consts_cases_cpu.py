@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import cport, ddp as oddp
-from tests import consts_cases as cc, sweep_cases as sc
+from tests import consts_cases as cc, oracle_refs as refs, sweep_cases as sc
 
 PAIRS = [(m, f) for m in cc.MODELS for f in cc.FIELDS]
 LISTED = [(m, f) for m, f in PAIRS if f in cc.APPLIES[m]]
@@ -81,18 +81,17 @@ def test_both_builds_of_the_c_oracle_take_the_same_iterations(model):
     N, seeds = cc.SOLVES[model]
     s = cc.problem(model, N, seeds)
     cst = cc.oracle_consts(model, s["consts"])
-    opts = oddp.DdpOptions(**cc.solve_options(model))
-    st = {v: cport.solve_batch(cst, opts, s["x0"], s["params"], s["xs"], s["us"], model=model, variant=v)[2]
-          for v in ("off", "fast")}
-    print(f"{model} N {N} seeds {seeds}: iterations off {st['off'][:, 1].astype(int).tolist()} fast {st['fast'][:, 1].astype(int).tolist()}; "
-          f"status {st['off'][:, 6].astype(int).tolist()}")
-    np.testing.assert_array_equal(st["off"][:, 1], st["fast"][:, 1])
-    np.testing.assert_array_equal(st["off"][:, 6], st["fast"][:, 6])
-    assert (st["off"][:, 2] == 1).all() and (st["off"][:, 1] >= 1).all(), "a whole-solve case that does not converge, or has nothing to do"
+    st = {v: refs.c_oracle(model, s, cc.solve_options(model), v, cst=cst)[2] for v in ("off", "fast")}
+    it, status = ({v: cport.stat(st[v], f).astype(int) for v in st} for f in ("iters", "status"))
+    print(f"{model} N {N} seeds {seeds}: iterations off {it['off'].tolist()} fast {it['fast'].tolist()}; status {status['off'].tolist()}")
+    np.testing.assert_array_equal(it["off"], it["fast"])
+    np.testing.assert_array_equal(status["off"], status["fast"])
+    assert (cport.stat(st["off"], "converged") == 1).all() and (it["off"] >= 1).all(), "a whole-solve case that does not converge, or has nothing to do"
     m = cc.oracle_model(model, s["consts"])      # and the numpy oracle, which the GPU test compares with, is on that count too
+    opts = oddp.DdpOptions(**cc.solve_options(model))
     for b in range(len(seeds)):
         r = oddp.solve(m, s["x0"][b], s["params"][b], s["xs"][b], s["us"][b], opts)
-        assert r.iters == int(st["off"][b, 1]) and r.converged, (model, b, r.iters)
+        assert r.iters == it["off"][b] and r.converged, (model, b, r.iters)
 
 
 @pytest.mark.parametrize("model,N,mode", [(m, N, 1) for m, N, _ in cc.SWEEPS] + [(m, N, 2) for m, N in cc.SO2_SWEEPS])

@@ -7,16 +7,16 @@ the pin of tests/test_oracle_c.py to the failure exits and to the pivot's upper 
 import numpy as np
 import pytest
 
-from oracle import ddp as oddp, models as omodels
-from tests import failure_cases as fc, options_cases as oc, parity
+from oracle import cport, ddp as oddp, models as omodels
+from tests import failure_cases as fc, parity
 
 NAMES = list(fc.CASES)
 
 
 def _same_decisions(a, b):
     for f in ("iters", "status", "converged"):
-        np.testing.assert_array_equal(oc.stat(a, f), oc.stat(b, f), err_msg=f)
-    assert oc.stat(a, "alpha").tobytes() == oc.stat(b, "alpha").tobytes()
+        np.testing.assert_array_equal(cport.stat(a, f), cport.stat(b, f), err_msg=f)
+    assert cport.stat(a, "alpha").tobytes() == cport.stat(b, "alpha").tobytes()
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -26,16 +26,16 @@ def test_case_ends_the_way_the_table_says_on_both_builds(name):
     fail = list(c.fail)
     for variant in ("off", "fast"):
         st = fc.oracle(name, variant)[2]
-        np.testing.assert_array_equal(oc.stat(st, "status"), want)
-        np.testing.assert_array_equal(oc.stat(st, "converged"), (want == 0).astype(float))
-        assert (oc.stat(st, "alpha")[fail] == 0.0).all()
+        np.testing.assert_array_equal(cport.stat(st, "status"), want)
+        np.testing.assert_array_equal(cport.stat(st, "converged"), (want == 0).astype(float))
+        assert (cport.stat(st, "alpha")[fail] == 0.0).all()
         if c.kind == "S4m":
-            np.testing.assert_array_equal(oc.stat(st, "iters")[fail], fc.MID_ITERS[name])
+            np.testing.assert_array_equal(cport.stat(st, "iters")[fail], fc.MID_ITERS[name])
         else:
-            assert (oc.stat(st, "iters")[fail] == 0).all()
-        cost = oc.stat(st, "cost")[fail]
+            assert (cport.stat(st, "iters")[fail] == 0).all()
+        cost = cport.stat(st, "cost")[fail]
         if c.kind.startswith("S3"):
-            assert not np.isfinite(cost).any() and (oc.stat(st, "mu")[fail] == 0.0).all()
+            assert not np.isfinite(cost).any() and (cport.stat(st, "mu")[fail] == 0.0).all()
         else:
             assert (np.abs(cost) < 1e290).all()                          # the kernels test |J| < 1e300, the oracle isfinite
     _same_decisions(fc.oracle(name, "off")[2], fc.oracle(name, "fast")[2])
@@ -52,7 +52,7 @@ def test_healthy_instances_are_their_solves_in_the_all_healthy_batch(name):
         assert s[k][h].tobytes() == t[k][h].tobytes(), k
     for variant in ("off", "fast"):
         mixed, twin = fc.oracle(name, variant), fc.oracle(name, variant, True)
-        assert (oc.stat(twin[2], "status") == 0).all() and (oc.stat(twin[2], "converged") == 1).all()
+        assert (cport.stat(twin[2], "status") == 0).all() and (cport.stat(twin[2], "converged") == 1).all()
         for a, b in zip(mixed, twin):
             assert a[h].tobytes() == b[h].tobytes()
     _same_decisions(fc.oracle(name, "off", True)[2], fc.oracle(name, "fast", True)[2])
@@ -66,11 +66,11 @@ def test_status_2_ends_after_one_bump_with_the_start_returned(model):
     assert 10.0 * fc.MU0_S2 + opt.mu_min > opt.mu_max and np.isfinite(10.0 * fc.MU0_S2)
     for variant in ("off", "fast"):
         xs, us, st = fc.oracle(name, variant)
-        assert (oc.stat(st, "mu") == 10.0 * fc.MU0_S2 + opt.mu_min).all()
+        assert (cport.stat(st, "mu") == 10.0 * fc.MU0_S2 + opt.mu_min).all()
         want = s["xs"].copy()
         want[:, 0] = s["x0"]
         assert xs.tobytes() == want.tobytes() and us.tobytes() == s["us"].tobytes()
-    start_cost = fc.oracle(name)[2][:, 0]
+    start_cost = cport.stat(fc.oracle(name)[2], "cost")
     assert np.isfinite(start_cost).all()
 
 
@@ -86,9 +86,9 @@ def test_numpy_oracle_agrees_with_the_c_oracle(name):
 def _numpy_agrees(c, s, m, xo, uo, so, b):
     with np.errstate(all="ignore"):
         r = oddp.solve(m, s["x0"][b], s["params"][b], s["xs"][b], s["us"][b], oddp.DdpOptions(**fc.options(c)))
-    assert (r.status, r.iters, int(r.converged)) == tuple(int(oc.stat(so, f)[b]) for f in ("status", "iters", "converged"))
-    assert r.alpha == oc.stat(so, "alpha")[b] and r.mu == pytest.approx(oc.stat(so, "mu")[b], rel=parity.MU_RTOL)
-    cost = oc.stat(so, "cost")[b]
+    assert (r.status, r.iters, int(r.converged)) == tuple(int(cport.stat(so, f)[b]) for f in ("status", "iters", "converged"))
+    assert r.alpha == cport.stat(so, "alpha")[b] and r.mu == pytest.approx(cport.stat(so, "mu")[b], rel=parity.MU_RTOL)
+    cost = cport.stat(so, "cost")[b]
     if np.isfinite(cost):
         assert abs(r.cost - cost) <= parity.COST_RTOL * abs(cost)
         assert np.max(np.abs(r.xs - xo[b])) <= parity.X_TOL and np.max(np.abs(r.us - uo[b])) <= parity.X_TOL
@@ -120,7 +120,7 @@ def test_the_policy_rule_gives_no_policy_behind_status_2_and_3(model):
         opt = oddp.DdpOptions(**fc.options(c))
         xo, uo, so = fc.oracle(name)
         b = c.fail[0]
-        stats = {f: oc.stat(so, f)[b] for f in oc.STAT_FIELDS}
+        stats = {f: cport.stat(so, f)[b] for f in cport.STAT_FIELDS}
         with np.errstate(all="ignore"):
             kff, K, info = pc.oracle_policy(m, xo[b], uo[b], s["params"][b], stats, opt, 3)
             if kind == "S3c":

@@ -10,9 +10,10 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from oracle import cport, ddp as oddp, models as omodels
+from oracle import cport
 from srbd_horizon_amd import dist as sdist, workload
 from srbd_horizon_amd.fleet import FleetQueue
+from tests import oracle_refs
 from tests.fleet_support import N, NP, NU, NX, OPTS, OracleEngine, free_port as _free_port, seeds_of as _seeds
 
 
@@ -65,9 +66,7 @@ def test_fleet_step_world2_gathers_every_ranks_records(gather):
     refs = []
     for st in launches:
         seeds = np.concatenate([_seeds(r, steps, s, B) for r in range(world) for s in st])
-        batch = workload.make_batch("srbd13", N, seeds)
-        xo, uo, so = cport.solve_batch(omodels.RobotConsts(), oddp.DdpOptions(**OPTS), batch["x0"], batch["params"], batch["xs"], batch["us"])
-        refs.append((xo, uo, so))
+        refs.append(oracle_refs.c_oracle("srbd13", dict(workload.make_batch("srbd13", N, seeds), consts={}), OPTS))      # the default robot
     for rank, n_launch, gbytes, out in res:
         assert n_launch == 3
         assert gbytes == steps * B * W * 8                             # every record leaves the rank exactly once
@@ -89,7 +88,7 @@ def test_fleet_step_world2_gathers_every_ranks_records(gather):
                 np.testing.assert_array_equal(rec[:, :NU], uo[:, 0])
                 np.testing.assert_array_equal(rec[:, NU:NU + NX], xo[:, 1])
                 cost, iters = rec[:, NU + NX], rec[:, NU + NX + 1]
-            np.testing.assert_array_equal(cost, so[:, 0])
-            np.testing.assert_array_equal(iters, so[:, 1])
+            np.testing.assert_array_equal(cost, cport.stat(so, "cost"))
+            np.testing.assert_array_equal(iters, cport.stat(so, "iters"))
     for a, b in zip(res[0][3], res[1][3]):
         np.testing.assert_array_equal(a[1], b[1])                      # every rank ends with the same gathered tensors

@@ -266,7 +266,7 @@ def test_fleet_tick_of_1024_robots_matches_the_c_oracle_tick_by_tick(record_prop
         res = shadow.compare_batch("srbd13", N, dict(x0=x0, params=P, xs=xs_ws, us=us_ws, consts=b["consts"]), OPTS, dict(waves_per_simd=1),
                                    cst, x, u, st, threads=min(16, os.cpu_count() or 1))
         assert_batch(res, f"fleet_tick_{t}", record_property)
-        assert (res["so"][:, 2] == 1).mean() >= 0.98
+        assert (cport.stat(res["so"], "converged") == 1).mean() >= 0.98
     assert eng.stats["iters"].mean() < 8                          # warm-started ticks, not cold solves
 
 

@@ -13,6 +13,7 @@ from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
 from tests import auto_class_cases as acc
+from tests.gpu_support import solve as _solve
 
 pytestmark = pytest.mark.gpu
 
@@ -22,12 +23,6 @@ QUEUE3 = dict(OPTS, max_slots=16, waves_per_simd=2, queue_order=3)         # the
 
 def _load(eng, b):
     eng.load(b["x0"], b["xs"], b["us"])
-
-
-def _solve(eng, b):
-    _load(eng, b)
-    x, u = eng.solve(b["params"])
-    return x.copy(), u.copy(), eng.stats.copy()
 
 
 def _dev(a, dtype=torch.float64):

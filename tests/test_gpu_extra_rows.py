@@ -9,6 +9,8 @@ from srbd_horizon_amd.ddp import DDPSolver
 from srbd_horizon_amd.engine import DdpEngine, eval_knots
 from srbd_horizon_amd.prb import SRBDProblem
 from srbd_horizon_amd.problem import LinearTerm
+from tests import whole_solve_cases as wc
+from tests.gpu_support import solve, whole_solve
 from tests.variant_cases import extra_rows_problem as _problem
 
 pytestmark = pytest.mark.gpu
@@ -41,21 +43,16 @@ def test_knots_with_extra_rows(model):
 
 @pytest.mark.parametrize("model,N,B,wps", [("srbd13", 30, 48, 1), ("srbd13", 30, 48, 2), ("srbd37", 20, 16, 2), ("srbd37", 60, 4, 1), ("lip30", 20, 12, 1), ("srbd61", 20, 6, 1)])
 def test_solves_with_extra_rows_match_the_c_oracle(model, N, B, wps):
-    batch, P, consts = _problem(model, N, np.arange(B) + 1)
-    eng = DdpEngine(model, N, B, opts=dict(OPTS, waves_per_simd=wps), consts=consts)
-    assert eng.np_ == cport.DIMS[model][2] + 8
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(P)
-    xo, uo, so = cport.solve_batch(omodels.RobotConsts(**consts), oddp.DdpOptions(**OPTS), batch["x0"], P, batch["xs"], batch["us"],
-                                   threads=4, model=model)
-    np.testing.assert_array_equal(eng.stats["iters"], so[:, 1].astype(int))
-    assert eng.stats["converged"].all()
-    assert np.max(np.abs(x - xo)) <= 1e-6 and np.max(np.abs(u - uo)) <= 1e-6
-    np.testing.assert_allclose(eng.stats["cost"], so[:, 0], rtol=1e-9)
+    c, batch = wc.CASES[f"rows-{model}-N{N}"], wc.start(f"rows-{model}-N{N}")
+    assert len(c.seeds) == B
+
+    def carries_the_reference_columns(eng):
+        assert eng.np_ == cport.DIMS[model][2] + 8
+    x, u, st = whole_solve(c.name, check_handle=carries_the_reference_columns, waves_per_simd=wps)
+    assert st["converged"].all()
     # the rows act: the solution differs from the plain model's
-    e0 = DdpEngine(model, N, B, opts=OPTS, consts=batch["consts"])
-    e0.load(batch["x0"], batch["xs"], batch["us"])
-    x0, u0 = e0.solve(batch["params"])
+    params, consts = batch["plain"]
+    x0, _, _ = solve(DdpEngine(model, N, B, opts=OPTS, consts=consts), batch, params)
     assert np.max(np.abs(x - x0)) > 1e-4
 
 

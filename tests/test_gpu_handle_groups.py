@@ -11,8 +11,8 @@ import functools
 import numpy as np
 import pytest
 
-from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
+from tests import oracle_refs as refs
 from tests.gpu_support import frozen, same_bytes, solve
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +26,7 @@ N_CLASSES = 36 * (N + 2)                                         # the library's
 
 @functools.lru_cache(maxsize=None)
 def batch(model):
-    b = workload.make_batch(model, N, list(range(B)))
-    for k in ("x0", "params", "xs", "us"):
-        b[k].setflags(write=False)
-    return b
+    return refs.batch(model, N, range(B))
 
 
 def engine(model, wps):

@@ -31,7 +31,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ddp as oddp, models as omodels
+from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from tests import horizon_cases as hc, options_cases as oc, parity, policy_cases as pc
@@ -56,7 +56,7 @@ def test_case_matches_the_c_oracle(name, wps, slots):
     assert info["wavefronts_per_instance"] == (1 if c.model == "srbd13" else 4)
     assert queue[1:] == ((2, B) if slots else (B, 0))
     xo, uo, so = hc.oracle(name, "off")
-    it_o = oc.stat(so, "iters").astype(int)
+    it_o = cport.stat(so, "iters").astype(int)
     d = parity.deviations(x, u, st, xo, uo, so)
     for k in WORST:
         if np.isfinite(d[k]):
@@ -83,7 +83,7 @@ def test_cut_and_continued_is_the_uncut_solve_byte_for_byte(model, N, cuts):
         at_cut = cut(eng, s, k)
         n_cut = int((at_cut[2]["status"] == 1).sum())
         print(f"{name}: uncut iterations {ref[2]['iters'].tolist()}, unfinished at {k}: {n_cut}")
-        assert n_cut == int((oc.stat(hc.oracle(name, "off", k)[2], "status") == 1).sum()) == eng.unfinished()
+        assert n_cut == int((cport.stat(hc.oracle(name, "off", k)[2], "status") == 1).sum()) == eng.unfinished()
         same_bytes(continue_to(eng, TOTAL), ref, msg=f"(cut at {k}, continued)")
     if len(cuts) > 1:
         cut(eng, s, cuts[0])

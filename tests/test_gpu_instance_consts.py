@@ -11,25 +11,18 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import cport, ddp as oddp, models as omodels
+from oracle import ddp as oddp, models as omodels
+from oracle.cport import stat
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
+from tests import oracle_refs as refs
+from tests.gpu_support import solve as _solve
 from tests.variant_cases import SRBD13_FIELDS, TRACKING, draw
 
 pytestmark = pytest.mark.gpu
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
 SMALL = {"srbd13": (30, 40), "srbd37": (20, 6), "lip30": (20, 6), "srbd61": (20, 4)}      # model -> (N, B) of the bit-equality tests
-
-
-def _load(eng, batch):
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-
-
-def _solve(eng, batch):
-    _load(eng, batch)
-    x, u = eng.solve(batch["params"])
-    return x.copy(), u.copy(), eng.stats.copy()
 
 
 def _same(got, ref):
@@ -39,13 +32,9 @@ def _same(got, ref):
 
 
 def _oracle(model, csts, batch, opts=None):
-    o = oddp.DdpOptions(**(opts or OPTS))
-    xo, uo, so = [], [], []
-    for b, c in enumerate(csts):
-        s = slice(b, b + 1)
-        x, u, st = cport.solve_batch(c, o, batch["x0"][s], batch["params"][s], batch["xs"][s], batch["us"][s], model=model)
-        xo.append(x[0]); uo.append(u[0]); so.append(st[0])
-    return np.array(xo), np.array(uo), np.array(so)
+    """the C oracle instance by instance, each with its own constants -> (xs, us, stats [B, 8])"""
+    out = [refs.c_oracle(model, batch, opts or OPTS, cst=c, sel=[b]) for b, c in enumerate(csts)]
+    return tuple(np.concatenate(a) for a in zip(*out))
 
 
 # ---- 1. identity ---------------------------------------------------------------------------------------------------------------
@@ -79,7 +68,7 @@ def _parity(model, N, B, fields, long_cap):
     eng.set_instance_consts(over)
     x, u, st = _solve(eng, batch)
     xo, uo, so = _oracle(model, csts, batch)
-    it_o = so[:, 1].astype(int)
+    it_o = stat(so, "iters").astype(int)
     long_ = it_o >= 50                  # long crawls: where GPU and oracle legitimately part
     same = ~long_
     print(f"{model}: oracle iterations mean {it_o.mean():.2f}, {int(long_.sum())} of {B} with >= 50; GPU iterations mean {st['iters'].mean():.2f}; "
@@ -87,9 +76,9 @@ def _parity(model, N, B, fields, long_cap):
     assert long_.sum() <= long_cap
     assert np.all(np.isfinite(x)) and np.all(np.isfinite(u)) and np.all(np.isfinite(st["cost"]))
     np.testing.assert_array_equal(st["iters"][same], it_o[same])
-    np.testing.assert_array_equal(st["status"][same], so[same, 6].astype(int))
-    np.testing.assert_allclose(st["cost"][same], so[same, 0], rtol=1e-8)
-    conv = same & (so[:, 2] == 1)
+    np.testing.assert_array_equal(st["status"][same], stat(so, "status")[same].astype(int))
+    np.testing.assert_allclose(st["cost"][same], stat(so, "cost")[same], rtol=1e-8)
+    conv = same & (stat(so, "converged") == 1)
     ex, eu = np.max(np.abs(x[conv] - xo[conv])), np.max(np.abs(u[conv] - uo[conv]))
     print(f"{model}: converged {int(conv.sum())}, linf x {ex:.2e} u {eu:.2e}")
     assert ex <= 1e-6 and eu <= 1e-6
@@ -97,7 +86,7 @@ def _parity(model, N, B, fields, long_cap):
         idx = np.flatnonzero(long_)
         sub = {k: batch[k][idx] for k in ("x0", "params", "xs", "us")}
         _, _, s0 = _oracle(model, [csts[i] for i in idx], sub, dict(OPTS, max_iters=0))
-        assert np.all(st["cost"][idx] <= s0[:, 0])
+        assert np.all(st["cost"][idx] <= stat(s0, "cost"))
     return batch, over, csts, st, it_o
 
 
@@ -106,9 +95,8 @@ def test_heterogeneous_srbd13_batch_matches_the_oracle_instance_by_instance():
     17.8 iterations, and 200 of 256 instances change their iteration count against the common constants."""
     N, B = 30, 256
     batch, over, csts, st, it_o = _parity("srbd13", N, B, SRBD13_FIELDS, long_cap=(6 * B) // 100)
-    _, _, s_common = cport.solve_batch(omodels.RobotConsts(**batch["consts"]), oddp.DdpOptions(**OPTS), batch["x0"], batch["params"],
-                                       batch["xs"], batch["us"], threads=min(16, os.cpu_count() or 1))
-    assert (it_o != s_common[:, 1].astype(int)).sum() >= B // 2      # the table matters: ignoring it cannot pass
+    s_common = refs.c_oracle("srbd13", batch, OPTS, threads=min(16, os.cpu_count() or 1))[2]
+    assert (it_o != stat(s_common, "iters").astype(int)).sum() >= B // 2      # the table matters: ignoring it cannot pass
 
 
 @pytest.mark.parametrize("model,N,B", [("srbd37", 20, 64), ("lip30", 20, 32), ("srbd61", 20, 32)])
@@ -131,7 +119,7 @@ def test_heterogeneous_results_do_not_depend_on_range_order_or_slot():
     # three ranges of one handle
     P = torch.from_numpy(batch["params"]).to("cuda:0")
     torch.cuda.synchronize()
-    _load(one, batch)
+    one.load(batch["x0"], batch["xs"], batch["us"])
     for lo in (0, 64, 128):
         one.solve_range_device(P, lo, 64)
     _same(one.fetch(), ref)

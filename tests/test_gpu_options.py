@@ -32,7 +32,7 @@ import math
 import numpy as np
 import pytest
 
-from oracle import ddp as oddp, models as omodels
+from oracle import cport, ddp as oddp, models as omodels
 from srbd_horizon_amd.engine import DdpEngine
 from tests import options_cases as oc, parity, policy_cases as pc
 from tests.gpu_support import BUILDS, explain, solve as _solve
@@ -53,7 +53,7 @@ def test_case_matches_the_c_oracle(name, wps, so):
     eng.close()
     assert info["wavefronts_per_instance"] == (1 if c.model == "srbd13" else 4)
     xo, uo, so_ = oc.oracle(name, "off", so)
-    it_o = oc.stat(so_, "iters").astype(int)
+    it_o = cport.stat(so_, "iters").astype(int)
     print(f"{name} {info['kernel']}: iterations GPU {st['iters'].tolist()} oracle {it_o.tolist()}; rollouts {st['rollouts'].tolist()}; "
           f"{parity.summary(parity.deviations(x, u, st, xo, uo, so_))}")
     # gap: the start's defect norm times exact factors 1 - alpha.  A restart (G) begins at a trajectory that closes its gaps in
@@ -84,7 +84,7 @@ def test_options_changed_on_a_live_handle_solve_like_a_fresh_one(model):
     for f in st2.dtype.names:
         np.testing.assert_array_equal(st1[f], st2[f], err_msg=f)
     assert (st1["alpha"] == 0.8).all() and (st0["alpha"] == 1.0).all()                      # the options did change
-    np.testing.assert_array_equal(st1["iters"], oc.stat(oc.oracle(name)[2], "iters")[:B].astype(int))
+    np.testing.assert_array_equal(st1["iters"], cport.stat(oc.oracle(name)[2], "iters")[:B].astype(int))
 
 
 @pytest.mark.parametrize("model", ["srbd13", "srbd37"])

@@ -4,11 +4,12 @@ converged solves, the builder surface."""
 import numpy as np
 import pytest
 
-from oracle import cport, ddp as oddp, models as omodels
-from srbd_horizon_amd import workload
+from oracle import ddp as oddp, models as omodels
 from srbd_horizon_amd.ddp import DDPSolver
-from srbd_horizon_amd.engine import DdpEngine, eval_knots
+from srbd_horizon_amd.engine import eval_knots
 from srbd_horizon_amd.prb import SRBDProblem
+from tests import whole_solve_cases as wc
+from tests.gpu_support import whole_solve
 
 pytestmark = pytest.mark.gpu
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
@@ -43,17 +44,10 @@ def test_knots_without_relative_velocity_rows(model):
 
 @pytest.mark.parametrize("model,N,B", [("srbd37", 20, 24), ("srbd37", 60, 6), ("lip30", 20, 16)])
 def test_solves_without_relative_velocity_rows_match_the_c_oracle(model, N, B):
-    batch = workload.make_batch(model, N, np.arange(B) + 3)
-    consts = dict(batch["consts"], relative_velocity_constraints=0)
-    eng = DdpEngine(model, N, B, opts=OPTS, consts=consts)
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(batch["params"])
-    xo, uo, so = cport.solve_batch(omodels.RobotConsts(**consts), oddp.DdpOptions(**OPTS), batch["x0"], batch["params"], batch["xs"],
-                                   batch["us"], threads=4, model=model)
-    np.testing.assert_array_equal(eng.stats["iters"], so[:, 1].astype(int))
-    assert eng.stats["converged"].all()
-    assert np.max(np.abs(x - xo)) <= 1e-6 and np.max(np.abs(u - uo)) <= 1e-6
-    np.testing.assert_allclose(eng.stats["cost"], so[:, 0], rtol=1e-9)
+    c = wc.CASES[f"pointfeet-{model}-N{N}"]
+    assert len(c.seeds) == B and wc.start(c.name)["consts"]["relative_velocity_constraints"] == 0
+    x, u, st = whole_solve(c.name)
+    assert st["converged"].all()
 
 
 def test_builder_surface_with_four_point_feet():

@@ -12,18 +12,13 @@ from srbd_horizon_amd import dist as sdist, workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.mpc import MpcLoop
 from tests import policy_cases as pc
+from tests.gpu_support import solve as _solve
 from tests.variant_cases import extra_rows_problem
 
 pytestmark = pytest.mark.gpu
 
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)      # dsrbd_example.py:55-58
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _solve(eng, batch, params=None):
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(batch["params"] if params is None else params)
-    return x.copy(), u.copy(), eng.stats.copy()
 
 
 def _x_problem(model, N, seeds):

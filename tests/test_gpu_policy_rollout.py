@@ -12,7 +12,7 @@ from oracle import models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from tests import policy_rollout_cases as prc
-from tests.gpu_support import assert_nothing_else_moves, dev as _dev, solve
+from tests.gpu_support import assert_nothing_else_moves, dev as _dev, frozen, solve
 from tests.variant_cases import TRACKING, draw, extra_rows_problem
 
 pytestmark = pytest.mark.gpu
@@ -55,9 +55,7 @@ def _solved(model, N, B, M, xr=False, policy=True):
     if policy:
         eng.policy_range_device()
     _, K, info = eng.policy()
-    for a in (x, u, P, K, info):
-        a.setflags(write=False)
-    return eng, consts, x, u, P, K, info
+    return (eng, consts, *frozen((x, u, P, K, info)))
 
 
 def _pushed(x, start, seed=7, size=1e-2):

@@ -14,6 +14,8 @@ from oracle import cport, ddp as oddp, models as omodels  # noqa: F401
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
+from tests import oracle_refs as refs
+from tests.gpu_support import solve as _solve
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +26,6 @@ def _engine(model, N, B, max_slots=None, **over):
     if max_slots is not None:
         over = dict(over, max_slots=max_slots)
     return DdpEngine(model, N, B, opts=dict(OPTS, **over))
-
-
-def _solve(eng, batch):
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(batch["params"])
-    return x.copy(), u.copy(), eng.stats.copy()
 
 
 @pytest.mark.parametrize("model,N,B,slots,wps", [("srbd13", 30, 300, 48, 1), ("srbd13", 30, 300, 37, 2), ("srbd37", 20, 7, 2, 1),
@@ -131,7 +127,7 @@ def test_configs3_all_eight_rank_shards_match_the_c_oracle(record_property):
     print(f"configs[3]: {len(res['explained'])} of {R * B} instances on another path, per rank shard {per_shard}; the two CPU builds "
           f"of the oracle split on {res['n_cpu_pair']}; slots {slots}; iterations mean {st['iters'].mean():.2f} max {st['iters'].max()}")
     assert_batch(res, "configs3_8192", record_property)
-    assert int((so[:, 2] == 0).sum()) <= R * B // 500            # a handful of instances (of 8192) crawl past 100 iterations
+    assert int((cport.stat(so, "converged") == 0).sum()) <= R * B // 500            # a handful of instances (of 8192) crawl past 100 iterations
 
 
 def test_cold_queue_order_starts_the_costliest_warm_starts_first():
@@ -141,9 +137,7 @@ def test_cold_queue_order_starts_the_costliest_warm_starts_first():
     per-slot gains buffer is overwritten -- here simply checked through results (bit-exact, above) plus the key itself."""
     N, B = 30, 96
     batch = workload.make_batch("srbd13", N, np.arange(B) + 4000)
-    cst, o0 = omodels.RobotConsts(**batch["consts"]), oddp.DdpOptions(**dict(OPTS, max_iters=0))
-    _, _, so = cport.solve_batch(cst, o0, batch["x0"], batch["params"], batch["xs"], batch["us"])
-    J0 = so[:, 0]
+    J0 = cport.stat(refs.c_oracle("srbd13", batch, dict(OPTS, max_iters=0))[2], "cost")
     eng = _engine("srbd13", N, B, max_slots=8, queue_order=2, max_iters=0)       # max_iters = 0: stats.cost = the initial cost
     x, u, st = _solve(eng, batch)
     np.testing.assert_allclose(st["cost"], J0, rtol=1e-12)

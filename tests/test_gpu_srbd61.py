@@ -6,12 +6,10 @@ model beside the others.  The kernel is the 4-wavefront one in its W-free layout
 import numpy as np
 import pytest
 
-from oracle import cport
-from oracle import ddp as oddp
-from oracle import models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
-from tests import options_cases as oc
+from tests import options_cases as oc, whole_solve_cases as wc
+from tests.gpu_support import solve, whole_solve
 
 pytestmark = pytest.mark.gpu
 NAME = "srbd61"
@@ -21,20 +19,11 @@ def test_default_constants_are_the_eight_point_robot():
     """sddp_create(consts = NULL) / DdpEngine("srbd61") without constants must solve the problem its own workload and oracle
     describe: contact points 0..3 = the first four sole corners of the eight-point model (sddp_default_consts_for, ABI v9), not the
     line feet of srbd37 (the rel_pos targets d_initial_1/2 silently differed)."""
-    N, seeds = 20, np.arange(6)
-    batch = workload.make_batch(NAME, N, seeds)
-    eng = DdpEngine(NAME, N, len(seeds), opts=oc.BASE)                       # no consts
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(batch["params"])
-    xo, uo, so = cport.solve_batch(omodels.make_model(NAME).cst, oddp.DdpOptions(**oc.BASE), batch["x0"], batch["params"], batch["xs"],
-                                   batch["us"], threads=4, model=NAME)
-    np.testing.assert_array_equal(eng.stats["iters"], so[:, 1].astype(int))
-    assert eng.stats["converged"].all()
-    assert np.max(np.abs(x - xo)) <= 1e-6 and np.max(np.abs(u - uo)) <= 1e-6
-    np.testing.assert_allclose(eng.stats["cost"], so[:, 0], rtol=1e-9)
-    ex = DdpEngine(NAME, N, len(seeds), opts=oc.BASE, consts=batch["consts"])      # the builder's explicit constants: the same problem
-    ex.load(batch["x0"], batch["xs"], batch["us"])
-    x2, u2 = ex.solve(batch["params"])
+    c, batch = wc.CASES["srbd61-default"], wc.start("srbd61-default")
+    x, u, st = whole_solve(c.name, default_consts=True)                      # no consts
+    assert st["converged"].all()
+    ex = DdpEngine(NAME, c.N, len(c.seeds), opts=oc.BASE, consts=batch["consts"])      # the builder's explicit constants: the same problem
+    x2, u2, _ = solve(ex, batch)
     np.testing.assert_array_equal(x2, x); np.testing.assert_array_equal(u2, u)
 
 
@@ -42,38 +31,16 @@ def test_default_constants_are_the_eight_point_robot():
 def test_solved_to_convergence_matches_the_c_oracle(N, nseeds):
     """whole solves against the plain-C oracle: N = 60 with every node's defect open (configs[4]'s shape on this model), and
     N = 20 (the horizon dsrbd_example.py runs) over 40 seeds."""
-    seeds = np.arange(nseeds) + 20
-    batch = workload.make_batch(NAME, N, seeds)
-    rng = np.random.default_rng(9)
-    xs = batch["xs"] + (1e-3 * rng.standard_normal(batch["xs"].shape) if N == 60 else 0.0)
-    xs[:, 0] = batch["x0"]
-    eng = DdpEngine(NAME, N, len(seeds), opts=oc.BASE, consts=batch["consts"])
-    eng.load(batch["x0"], xs, batch["us"])
-    x, u = eng.solve(batch["params"])
-    st = eng.stats.copy()
-    xo, uo, so = cport.solve_batch(omodels.make_model(NAME).cst, oddp.DdpOptions(**oc.BASE), batch["x0"], batch["params"], xs, batch["us"],
-                                   threads=4, model=NAME)
-    print(f"srbd61 N={N}: iterations GPU", st["iters"].tolist(), "oracle", so[:, 1].astype(int).tolist(),
-          "linf x", float(np.max(np.abs(x - xo))), "linf u", float(np.max(np.abs(u - uo))))
-    np.testing.assert_array_equal(st["iters"], so[:, 1].astype(int))
-    np.testing.assert_array_equal(st["status"], so[:, 6].astype(int))
-    np.testing.assert_array_equal(st["converged"], so[:, 2].astype(int))
+    assert len(wc.CASES[f"srbd61-N{N}"].seeds) == nseeds
+    x, u, st = whole_solve(f"srbd61-N{N}")
+    print(f"srbd61 N={N}: iterations GPU", st["iters"].tolist())
     assert st["converged"].all() and np.all(st["gap"] <= 1e-9) and st["iters"].min() >= 3
-    assert np.max(np.abs(x - xo)) <= 1e-6 and np.max(np.abs(u - uo)) <= 1e-6
-    np.testing.assert_allclose(st["cost"], so[:, 0], rtol=1e-9)
 
 
 @pytest.mark.parametrize("N,B", [(1, 2), (2, 3), (70, 1)])
 def test_extreme_horizons(N, B):
-    seeds = list(range(B))
-    batch = workload.make_batch(NAME, N, seeds)
-    eng = DdpEngine(NAME, N, B, opts=oc.BASE, consts=batch["consts"])
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    x, u = eng.solve(batch["params"])
-    xo, uo, so = cport.solve_batch(omodels.make_model(NAME).cst, oddp.DdpOptions(**oc.BASE), batch["x0"], batch["params"], batch["xs"],
-                                   batch["us"], model=NAME)
-    np.testing.assert_array_equal(eng.stats["iters"], so[:, 1].astype(int))
-    assert np.max(np.abs(x - xo)) <= 1e-6 and np.max(np.abs(u - uo)) <= 1e-6
+    assert len(wc.CASES[f"srbd61-N{N}"].seeds) == B
+    whole_solve(f"srbd61-N{N}")
 
 
 def test_queue_of_more_instances_than_slots_is_bit_identical():

@@ -4,6 +4,7 @@ has drifted shows here first."""
 import numpy as np
 import pytest
 
+from oracle import cport
 from tests import horizon_cases as hc, options_cases as oc
 
 ALL = [c.name for c in hc.cases()]
@@ -22,19 +23,19 @@ def test_the_table_is_the_one_the_kernels_need():
 def test_both_oracle_builds_agree_and_the_case_converges_in_the_recorded_iterations(name):
     c = hc.CASES[name]
     (xo, _, so), (xf, _, sf) = hc.oracle(name, "off"), hc.oracle(name, "fast")
-    it = oc.stat(so, "iters").astype(int)
-    print(f"{name}: iterations {it.tolist()} alpha {sorted(set(oc.stat(so, 'alpha').tolist()))} gap {oc.stat(so, 'gap').max():.3e} "
+    it = cport.stat(so, "iters").astype(int)
+    print(f"{name}: iterations {it.tolist()} alpha {sorted(set(cport.stat(so, 'alpha').tolist()))} gap {cport.stat(so, 'gap').max():.3e} "
           f"l-inf between the builds' x {np.max(np.abs(xo - xf)):.3e}")
     for f in ("iters", "status", "converged", "alpha"):                                    # alpha: the same double
-        np.testing.assert_array_equal(oc.stat(so, f), oc.stat(sf, f), err_msg=f)
-    assert (oc.stat(so, "status") == 0).all() and (oc.stat(so, "converged") == 1).all()
+        np.testing.assert_array_equal(cport.stat(so, f), cport.stat(sf, f), err_msg=f)
+    assert (cport.stat(so, "status") == 0).all() and (cport.stat(so, "converged") == 1).all()
     assert tuple(it.tolist()) == hc.ITERS[name]
-    assert (oc.stat(so, "alpha") == hc.LAST_ALPHA[c.kind]).all()
+    assert (cport.stat(so, "alpha") == hc.LAST_ALPHA[c.kind]).all()
     assert np.max(np.abs(xo - xf)) <= hc.BUILDS_LINF
-    ro, rf = oc.stat(so, "rho"), oc.stat(sf, "rho")
+    ro, rf = cport.stat(so, "rho"), cport.stat(sf, "rho")
     assert ((ro == 0) == (rf == 0)).all() and np.max(np.abs(ro - rf) / np.maximum(np.abs(ro), 1e-300)) <= oc.RHO_SPREAD
     if c.kind == "a05":                                                                     # the loop and the gap_tol exit did run
-        assert (it >= 24).all() and (oc.stat(so, "gap") > 0).all() and (oc.stat(so, "gap") <= 1e-9).all()
+        assert (it >= 24).all() and (cport.stat(so, "gap") > 0).all() and (cport.stat(so, "gap") <= 1e-9).all()
     if c.kind == "so2" and c.N > 1:                                                         # the second-order term acts
         assert tuple(it.tolist()) != hc.ITERS[f"{c.model}-N{c.N}"]
 
@@ -48,7 +49,7 @@ def test_a_forgotten_last_knot_would_show(name):
     xt, Jt = hc.oracle_truncated(name)
     assert xt.shape == xo[:, :c.N].shape
     dx = np.max(np.abs(xo[:, :c.N] - xt), axis=(1, 2))
-    J = oc.stat(so, "cost")
+    J = cport.stat(so, "cost")
     dJ = np.abs(J - Jt) / np.abs(J)
     print(f"{name}: x[:N] differs by {dx.min():.3e} .. {dx.max():.3e}, the cost by {dJ.min():.3e} .. {dJ.max():.3e} relative")
     assert ((dx >= hc.MARGIN_X) | (dJ >= hc.MARGIN_COST)).all(), (dx, dJ)
@@ -61,7 +62,7 @@ def test_the_resume_cuts_do_cut(model, N, cuts):
     name = hc.case_of(model, N).name
     for k in cuts:
         st = hc.oracle(name, "off", k)[2]
-        n_cut = int((oc.stat(st, "status") == 1).sum())
+        n_cut = int((cport.stat(st, "status") == 1).sum())
         print(f"{name} cut at {k}: {n_cut} unfinished")
         assert n_cut == sum(i >= k for i in hc.ITERS[name]) and n_cut >= 1
 

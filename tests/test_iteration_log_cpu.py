@@ -5,8 +5,9 @@ import ctypes as C
 
 import numpy as np
 
+from oracle import cport
 from srbd_horizon_amd import _lib
-from tests import iteration_log_cases as lc, options_cases as oc, resume_cases as rc
+from tests import iteration_log_cases as lc, resume_cases as rc
 
 F = lc.F
 
@@ -65,7 +66,7 @@ def test_the_settings_show_every_kind_of_record_on_the_c_oracle():
         mu0 = lc.options("E")["mu0"]
         assert all(len(tr) and tr[0, F["mu"]] > max(mu0, 0.0) for tr in e), model             # (2) the first sweep bumps, every instance
         z = lc.traces(model, "Z")
-        assert all(len(tr) == 0 for tr in z[0]) and (oc.stat(z[1], "status") == 0).all(), model      # (4)
+        assert all(len(tr) == 0 for tr in z[0]) and (cport.stat(z[1], "status") == 0).all(), model      # (4)
     for model in ("srbd13", "srbd37", "lip30"):
         a = lc.traces(model, "A")[0]
         assert any(((tr[:, F["gap"]] > 0.0) & (tr[:, F["rho"]] > 0.0)).any() for tr in a), model     # (3)

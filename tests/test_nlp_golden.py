@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import cport, ddp as oddp, models as omodels
-from tests import nlp_fixtures as nf
+from tests import nlp_fixtures as nf, oracle_refs as refs
 
 FIXTURES = nf.load_all()
 
@@ -21,12 +21,11 @@ def test_fixture_set_is_what_the_design_lists():
 
 @pytest.mark.parametrize("fx", FIXTURES, ids=[f["name"] for f in FIXTURES])
 def test_c_oracle_lands_on_the_nlp_optimum(fx):
-    cst = omodels.RobotConsts(**fx["consts"])
-    x, u, st = cport.solve_batch(cst, oddp.DdpOptions(**nf.OPTS), fx["x0"][None], fx["params"][None], fx["xs0"][None], fx["us0"][None],
-                                 model=fx["model"])
-    assert int(st[0, 2]) == 1
-    ex, eu, rc = nf.check(fx, x[0], u[0], st[0, 0])
-    print(f"{fx['name']}: C oracle {int(st[0, 1])} iterations, linf x {ex:.1e} u {eu:.1e}, cost rel {rc:.1e}")
+    start = dict(x0=fx["x0"][None], params=fx["params"][None], xs=fx["xs0"][None], us=fx["us0"][None], consts=fx["consts"])
+    x, u, st = refs.c_oracle(fx["model"], start, nf.OPTS)
+    assert int(cport.stat(st, "converged")[0]) == 1
+    ex, eu, rc = nf.check(fx, x[0], u[0], cport.stat(st, "cost")[0])
+    print(f"{fx['name']}: C oracle {int(cport.stat(st, 'iters')[0])} iterations, linf x {ex:.1e} u {eu:.1e}, cost rel {rc:.1e}")
 
 
 @pytest.mark.parametrize("fx", [f for f in FIXTURES if f["model"] != "srbd37" or f["seed"] == 0], ids=lambda f: f["name"])

@@ -4,7 +4,7 @@ asserted here are the ones the module docstring of tests/options_cases.py states
 import numpy as np
 import pytest
 
-from oracle import ddp as oddp, models as omodels
+from oracle import cport, ddp as oddp, models as omodels
 from tests import options_cases as oc
 
 ALL = [c.name for c in oc.cases()]
@@ -14,21 +14,21 @@ ALL = [c.name for c in oc.cases()]
 def test_both_oracle_builds_agree_and_the_case_shows_its_facts(name):
     c = oc.CASES[name]
     so, sf = oc.oracle(name, "off")[2], oc.oracle(name, "fast")[2]
-    it, alpha, status, gap, mu = (oc.stat(so, f) for f in ("iters", "alpha", "status", "gap", "mu"))
+    it, alpha, status, gap, mu = (cport.stat(so, f) for f in ("iters", "alpha", "status", "gap", "mu"))
     print(f"{name}: iterations {it.astype(int).tolist()} alpha {sorted(set(alpha.tolist()))} status {sorted(set(status.astype(int).tolist()))} "
           f"gap {gap.min():.3e}..{gap.max():.3e} mu {mu.min():.3e}..{mu.max():.3e}")
     # the two builds: same iteration count, same step length to the bit, same status -- every instance
-    np.testing.assert_array_equal(it, oc.stat(sf, "iters"))
-    np.testing.assert_array_equal(alpha, oc.stat(sf, "alpha"))
-    np.testing.assert_array_equal(status, oc.stat(sf, "status"))
+    np.testing.assert_array_equal(it, cport.stat(sf, "iters"))
+    np.testing.assert_array_equal(alpha, cport.stat(sf, "alpha"))
+    np.testing.assert_array_equal(status, cport.stat(sf, "status"))
     if c.kind in oc.SETS:
-        assert (status == 0).all() and (oc.stat(so, "converged") == 1).all() and (it < oc.options(c)["max_iters"]).all()
+        assert (status == 0).all() and (cport.stat(so, "converged") == 1).all() and (it < oc.options(c)["max_iters"]).all()
         assert (alpha == oc.LAST_ALPHA[c.kind]).all()
     if c.kind in oc.ITERS:
         lo, hi = oc.ITERS[c.kind][c.model]
         assert it.min() == lo and it.max() == hi, (it.min(), it.max())
     if c.kind in "AB":
-        start_gap = oc.stat(oc.oracle_start_stats(name), "gap")
+        start_gap = cport.stat(oc.oracle_start_stats(name), "gap")
         assert (gap >= start_gap * 0.5 ** it * (1 - 1e-12)).all()                   # at best halved by every step: never an exact zero
         assert (np.abs(gap / (start_gap * 0.5 ** it) - 1) <= 1e-12).sum() >= 5      # (a few instances backtrack below 0.5 on the way)
     if c.kind == "A":
@@ -36,7 +36,7 @@ def test_both_oracle_builds_agree_and_the_case_shows_its_facts(name):
     if c.kind == "B":
         assert (gap > 0).all() and (gap <= 1e-3).all()
         assert (gap > 1e-9).sum() >= len(c.seeds) - 2                               # ... and would not have let these through
-        assert (it <= oc.stat(oc.oracle(f"A-{c.model}")[2], "iters")).all() and (it < oc.stat(oc.oracle(f"A-{c.model}")[2], "iters")).any()
+        assert (it <= cport.stat(oc.oracle(f"A-{c.model}")[2], "iters")).all() and (it < cport.stat(oc.oracle(f"A-{c.model}")[2], "iters")).any()
     if c.kind == "D":
         assert (mu == 1e-3).all()
     if c.kind == "E":
@@ -61,10 +61,10 @@ def test_both_oracle_builds_agree_and_the_case_shows_its_facts(name):
 def test_both_oracle_builds_agree_in_the_other_second_order_modes(name, so):
     so_, sf = oc.oracle(name, "off", so)[2], oc.oracle(name, "fast", so)[2]
     for f in ("iters", "alpha", "status"):
-        np.testing.assert_array_equal(oc.stat(so_, f), oc.stat(sf, f), err_msg=f)
-    assert (oc.stat(so_, "status") == 0).all() and (oc.stat(so_, "alpha") == oc.LAST_ALPHA[oc.CASES[name].kind]).all()
-    rho = np.abs(oc.stat(so_, "rho") - oc.stat(sf, "rho")) / np.maximum(np.abs(oc.stat(so_, "rho")), 1e-300)
-    print(f"{name} second_order={so}: iterations {oc.stat(so_, 'iters').astype(int).tolist()}, rho differs by {rho.max():.3e}")
+        np.testing.assert_array_equal(cport.stat(so_, f), cport.stat(sf, f), err_msg=f)
+    assert (cport.stat(so_, "status") == 0).all() and (cport.stat(so_, "alpha") == oc.LAST_ALPHA[oc.CASES[name].kind]).all()
+    rho = np.abs(cport.stat(so_, "rho") - cport.stat(sf, "rho")) / np.maximum(np.abs(cport.stat(so_, "rho")), 1e-300)
+    print(f"{name} second_order={so}: iterations {cport.stat(so_, 'iters').astype(int).tolist()}, rho differs by {rho.max():.3e}")
     assert rho.max() <= oc.RHO_SPREAD
 
 
@@ -78,7 +78,7 @@ def test_rho_differs_between_the_builds_by_no_more_than_the_stated_spread():
     """the figure tests/test_gpu_options.py derives its tolerance for rho from (ten times RHO_SPREAD)"""
     worst = 0.0
     for name in ALL:
-        ro, rf = oc.stat(oc.oracle(name, "off")[2], "rho"), oc.stat(oc.oracle(name, "fast")[2], "rho")
+        ro, rf = cport.stat(oc.oracle(name, "off")[2], "rho"), cport.stat(oc.oracle(name, "fast")[2], "rho")
         assert ((ro == 0) == (rf == 0)).all()
         rel = np.max(np.abs(ro - rf) / np.maximum(np.abs(ro), 1e-300))
         worst = max(worst, rel)
@@ -92,6 +92,6 @@ def test_numpy_oracle_agrees_with_the_c_oracle(name, b):
     m = omodels.make_model(c.model, oc.consts(name))
     r = oddp.solve(m, s["x0"][b], s["params"][b], s["xs"][b], s["us"][b], oddp.DdpOptions(**oc.options(c)))
     xo, uo, so = oc.oracle(name)
-    assert r.iters == so[b, 1] and r.alpha == so[b, 3] and r.status == so[b, 6] and int(r.converged) == so[b, 2]
-    assert r.mu == pytest.approx(so[b, 5], rel=1e-12) and r.gap == pytest.approx(so[b, 4], rel=1e-9)
+    assert r.iters == cport.stat(so, "iters")[b] and r.alpha == cport.stat(so, "alpha")[b] and r.status == cport.stat(so, "status")[b] and int(r.converged) == cport.stat(so, "converged")[b]
+    assert r.mu == pytest.approx(cport.stat(so, "mu")[b], rel=1e-12) and r.gap == pytest.approx(cport.stat(so, "gap")[b], rel=1e-9)
     assert np.max(np.abs(r.xs - xo[b])) <= 1e-8 and np.max(np.abs(r.us - uo[b])) <= 1e-8

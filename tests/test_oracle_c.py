@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import cport, ddp as oddp, models as omodels
+from oracle.cport import stat
 from srbd_horizon_amd import workload
 
 
@@ -39,9 +40,9 @@ def test_c_solve_matches_numpy_solve(barrier):
     xs, us, st = cport.solve_batch(cst, opts, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=2)
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], opts)
-        assert int(st[b, 1]) == r.iters and bool(st[b, 2]) == r.converged and st[b, 3] == r.alpha
+        assert int(stat(st, "iters")[b]) == r.iters and bool(stat(st, "converged")[b]) == r.converged and stat(st, "alpha")[b] == r.alpha
         assert np.max(np.abs(xs[b] - r.xs)) <= 1e-8 and np.max(np.abs(us[b] - r.us)) <= 1e-8
-        assert abs(st[b, 0] - r.cost) <= 1e-10 * abs(r.cost)
+        assert abs(stat(st, "cost")[b] - r.cost) <= 1e-10 * abs(r.cost)
 
 
 def test_exhausted_line_search_is_a_stall_not_convergence_in_both_oracles():
@@ -55,7 +56,7 @@ def test_exhausted_line_search_is_a_stall_not_convergence_in_both_oracles():
     r = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0], opts)
     _, _, st = cport.solve_batch(cst, opts, batch["x0"], batch["params"], batch["xs"], batch["us"])
     assert r.status == 4 and not r.converged and r.iters == 0 and r.gap > opts.gap_tol
-    assert int(st[0, 6]) == 4 and int(st[0, 2]) == 0 and int(st[0, 1]) == 0
+    assert int(stat(st, "status")[0]) == 4 and int(stat(st, "converged")[0]) == 0 and int(stat(st, "iters")[0]) == 0
     # restart from the optimum with an impossible Armijo fraction: nothing is accepted, but the point is optimal
     full = oddp.DdpOptions(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
     opt = oddp.solve(m, batch["x0"][0], batch["params"][0], batch["xs"][0], batch["us"][0], full)
@@ -63,13 +64,13 @@ def test_exhausted_line_search_is_a_stall_not_convergence_in_both_oracles():
     hard = oddp.DdpOptions(max_iters=5, alpha_converge_threshold=0.5, beta=1e6, cost_reduction_ths=1e-12)
     r2 = oddp.solve(m, batch["x0"][0], batch["params"][0], opt.xs, opt.us, hard)
     _, _, st2 = cport.solve_batch(cst, hard, batch["x0"], batch["params"], opt.xs[None], opt.us[None])
-    assert r2.status == 0 and r2.converged and r2.iters == 0 and int(st2[0, 2]) == 1 and int(st2[0, 6]) == 0      # converged <=> status 0
+    assert r2.status == 0 and r2.converged and r2.iters == 0 and int(stat(st2, "converged")[0]) == 1 and int(stat(st2, "status")[0]) == 0      # converged <=> status 0
     # the same restart with a threshold no sweep can meet: the line search is exhausted and the point does NOT pass the
     # (relative) optimality test any more -> status 4, not converged
     harder = oddp.DdpOptions(max_iters=5, alpha_converge_threshold=0.5, beta=1e6, cost_reduction_ths=1e-30)
     r3 = oddp.solve(m, batch["x0"][0], batch["params"][0], opt.xs, opt.us, harder)
     _, _, st3 = cport.solve_batch(cst, harder, batch["x0"], batch["params"], opt.xs[None], opt.us[None])
-    assert r3.status == 4 and not r3.converged and int(st3[0, 6]) == 4 and int(st3[0, 2]) == 0
+    assert r3.status == 4 and not r3.converged and int(stat(st3, "status")[0]) == 4 and int(stat(st3, "converged")[0]) == 0
 
 
 @pytest.mark.parametrize("name,barrier", [("srbd37", 0.0), ("srbd37", 6.0), ("lip30", 0.0), ("srbd61", 0.0), ("srbd61", 6.0)])
@@ -105,9 +106,9 @@ def test_c_solve_matches_numpy_solve_reference_models(name, N, seeds):
     xs, us, st = cport.solve_batch(cst, opts, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=2, model=name)
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], opts)
-        assert int(st[b, 1]) == r.iters and bool(st[b, 2]) == r.converged and st[b, 3] == r.alpha and int(st[b, 6]) == r.status
+        assert int(stat(st, "iters")[b]) == r.iters and bool(stat(st, "converged")[b]) == r.converged and stat(st, "alpha")[b] == r.alpha and int(stat(st, "status")[b]) == r.status
         assert np.max(np.abs(xs[b] - r.xs)) <= 1e-7 and np.max(np.abs(us[b] - r.us)) <= 1e-7
-        assert abs(st[b, 0] - r.cost) <= 1e-9 * abs(r.cost)
+        assert abs(stat(st, "cost")[b] - r.cost) <= 1e-9 * abs(r.cost)
 
 
 @pytest.mark.parametrize("name,N,seeds,bar", [("srbd13", 30, [1, 2, 4], 0.0), ("srbd37", 12, [3], 0.0), ("srbd13", 30, [2], 2.0), ("srbd61", 10, [4], 0.0)])
@@ -122,10 +123,10 @@ def test_c_full_second_order_solve_matches_numpy(name, N, seeds, bar):
     _, _, st1 = cport.solve_batch(cst, o1, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=2, model=name)
     for b in range(len(seeds)):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], opts)
-        assert int(st[b, 1]) == r.iters and bool(st[b, 2]) == r.converged and st[b, 3] == r.alpha
+        assert int(stat(st, "iters")[b]) == r.iters and bool(stat(st, "converged")[b]) == r.converged and stat(st, "alpha")[b] == r.alpha
         assert np.max(np.abs(xs[b] - r.xs)) <= 1e-7 and np.max(np.abs(us[b] - r.us)) <= 1e-7
-        assert abs(st[b, 0] - r.cost) <= 1e-9 * abs(r.cost)
-        assert abs(st[b, 0] - st1[b, 0]) <= 1e-6 * abs(st1[b, 0])          # the same optimum as the default mode
+        assert abs(stat(st, "cost")[b] - r.cost) <= 1e-9 * abs(r.cost)
+        assert abs(stat(st, "cost")[b] - stat(st1, "cost")[b]) <= 1e-6 * abs(stat(st1, "cost")[b])          # the same optimum as the default mode
 
 
 def test_two_cpu_builds_of_the_oracle_shadow_each_other_step_by_step():
@@ -167,11 +168,11 @@ def test_resumed_oracle_solve_continues_the_same_path():
     a = (batch["x0"], batch["params"], batch["xs"], batch["us"])
     xf, uf, sf = cport.solve_batch(cst, oddp.DdpOptions(**opts), *a)
     k = 3
-    assert sf[0, 1] > k + 1
+    assert stat(sf, "iters")[0] > k + 1
     xk, uk, sk = cport.solve_batch(cst, oddp.DdpOptions(**dict(opts, max_iters=k)), *a)
-    resume = dict(rho=sk[0, 7], theta=1.0 if sk[0, 3] == 1.0 else 0.0, closed=sk[0, 4] == 0.0, mu=sk[0, 5])
+    resume = dict(rho=stat(sk, "rho")[0], theta=1.0 if stat(sk, "alpha")[0] == 1.0 else 0.0, closed=stat(sk, "gap")[0] == 0.0, mu=stat(sk, "mu")[0])
     xr, ur, sr, _ = cport.solve_trace(cst, oddp.DdpOptions(**opts), batch["x0"][0], batch["params"][0], xk[0], uk[0], resume=resume)
-    assert int(sr[1]) + k == int(sf[0, 1]) and int(sr[2]) == 1
+    assert int(stat(sr, "iters")) + k == int(stat(sf, "iters")[0]) and int(stat(sr, "converged")) == 1
     assert np.max(np.abs(xr - xf[0])) <= 1e-9 and np.max(np.abs(ur - uf[0])) <= 1e-9
 
 
@@ -186,7 +187,7 @@ def test_c_oracle_without_relative_velocity_constraints_matches_numpy(model, N):
     xs1, us1, st1 = cport.solve_batch(omodels.RobotConsts(**batch["consts"]), opts, batch["x0"], batch["params"], batch["xs"], batch["us"], model=model)
     for b in range(2):
         r = oddp.solve(m, batch["x0"][b], batch["params"][b], batch["xs"][b], batch["us"][b], opts)
-        assert int(st[b, 1]) == r.iters and bool(st[b, 2]) == r.converged
+        assert int(stat(st, "iters")[b]) == r.iters and bool(stat(st, "converged")[b]) == r.converged
         assert np.max(np.abs(xs[b] - r.xs)) <= 1e-8 and np.max(np.abs(us[b] - r.us)) <= 1e-8
     if model == "srbd37":
         assert np.max(np.abs(xs - xs1)) > 1e-6          # and it is another problem than the one with the constraints
@@ -209,7 +210,31 @@ def test_c_oracle_with_user_rows_matches_numpy(model, N):
     o = oddp.DdpOptions(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
     r = oddp.solve(omodels.make_model(model, cst), batch["x0"][0], P[0], batch["xs"][0], batch["us"][0], o)
     xo, uo, so = cport.solve_batch(cst, o, batch["x0"], P, batch["xs"], batch["us"], threads=1, model=model)
-    assert r.converged and int(so[0, 1]) == r.iters and int(so[0, 2]) == 1
-    assert np.max(np.abs(r.xs - xo[0])) <= 1e-9 and np.max(np.abs(r.us - uo[0])) <= 1e-9 and abs(r.cost - so[0, 0]) <= 1e-11 * abs(r.cost)
+    assert r.converged and int(stat(so, "iters")[0]) == r.iters and int(stat(so, "converged")[0]) == 1
+    assert np.max(np.abs(r.xs - xo[0])) <= 1e-9 and np.max(np.abs(r.us - uo[0])) <= 1e-9 and abs(r.cost - stat(so, "cost")[0]) <= 1e-11 * abs(r.cost)
     plain = cport.solve_batch(omodels.RobotConsts(**batch["consts"]), o, batch["x0"], batch["params"], batch["xs"], batch["us"], threads=1, model=model)
     assert np.max(np.abs(plain[0][0] - xo[0])) > 1e-5            # the rows act
+
+
+def test_stats_columns_carry_the_names_of_stat_fields():
+    """cport.STAT_FIELDS names the columns of solve_batch's [B, 8] and solve_trace's [8]: every field the numpy oracle's result carries
+    is that result's attribute.  One lip30 instance at N = 2 with alpha_0 = 0.5 and mu0 = 1e-3, where no two fields hold the same
+    value (26 iterations, converged 1, last step 0.5, gap 5e-10, mu 1e-3, status 0), so a column under another name cannot pass.
+    Exact but for cost and gap, sums that the two oracles round differently (1e-9 relative, the bounds of tests/parity.py); rho, which
+    the result object lacks, is the merit weight of the last line search of the trace."""
+    batch = workload.make_batch("lip30", 2, [0])
+    cst, opts = omodels.RobotConsts(**batch["consts"]), oddp.DdpOptions(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3, alpha_0=0.5, mu0=1e-3)
+    a = (batch["x0"], batch["params"], batch["xs"], batch["us"])
+    so = cport.solve_batch(cst, opts, *a, model="lip30")[2]
+    _, _, s1, tr = cport.solve_trace(cst, opts, *(v[0] for v in a), model="lip30")
+    r = oddp.solve(omodels.make_model("lip30", cst), *(v[0] for v in a), opts)
+    assert so.shape == (1, len(cport.STAT_FIELDS)) and s1.shape == (len(cport.STAT_FIELDS),)
+    values = {f: float(stat(so, f)[0]) for f in cport.STAT_FIELDS}
+    assert len(set(values.values())) == len(values), values
+    for f, v in values.items():
+        assert stat(s1, f) == v, f                                     # the same layout on solve_trace's [8]
+        if f in ("cost", "gap"):
+            assert abs(v - getattr(r, f)) <= 1e-9 * abs(getattr(r, f)), (f, v, getattr(r, f))
+        elif f != "rho":
+            assert v == getattr(r, f), (f, v, getattr(r, f))
+    assert values["status"] == 0 and values["rho"] == tr[-1]["rho"]

@@ -3,6 +3,7 @@ each quantity passes at half its bound and fails at twice it, the exact ones fai
 import numpy as np
 import pytest
 
+from oracle import cport
 from srbd_horizon_amd import _lib
 from tests import options_cases as oc, parity
 
@@ -13,17 +14,17 @@ def _oracle():
     """finite, non-zero everywhere; mu of instance 2 above 1, where the relative bound is the one that binds (parity.MU_RTOL)"""
     rng = np.random.default_rng(0)
     xo, uo = rng.uniform(0.5, 2.0, (B, N + 1, NX)), rng.uniform(0.5, 2.0, (B, N, NU))
-    so = np.zeros((B, len(oc.STAT_FIELDS)))
+    so = np.zeros((B, len(cport.STAT_FIELDS)))
     for f, v in dict(cost=(3.5e4, 12.0, 0.7), iters=(7, 12, 3), converged=(1, 0, 1), alpha=(1.0, 0.5, 0.8 ** 3), gap=(2e-4, 3.0, 5e-9),
                      mu=(3e-8, 1e-3, 30.0), status=(0, 1, 0), rho=(40.0, 2.5e3, 0.3)).items():
-        so[:, oc.STAT_FIELDS.index(f)] = v
+        so[:, cport.STAT_FIELDS.index(f)] = v
     return xo, uo, so
 
 
 def _gpu(xo, uo, so):
     st = np.zeros(B, dtype=_lib.STATS_DTYPE)
-    for f in oc.STAT_FIELDS:
-        st[f] = oc.stat(so, f)
+    for f in cport.STAT_FIELDS:
+        st[f] = cport.stat(so, f)
     return xo.copy(), uo.copy(), st
 
 
@@ -119,12 +120,12 @@ def test_the_numpy_oracle_comparison_of_one_instance():
     xo, uo, so = _oracle()
     x, u, st = _gpu(xo, uo, so)
     st["gap"][0] = 0.5 * parity.GAP_CLOSED
-    r = SimpleNamespace(xs=xo[0], us=uo[0], iters=7, cost=so[0, 0])
+    r = SimpleNamespace(xs=xo[0], us=uo[0], iters=7, cost=cport.stat(so, "cost")[0])
     parity.assert_matches_numpy_oracle(x[0], u[0], st[0], r)
     x[0, 1, 1] += 0.5 * parity.X_TOL
     st["cost"][0] *= 1.0 + 0.5 * parity.COST_RTOL
     parity.assert_matches_numpy_oracle(x[0], u[0], st[0], r)
-    for field, value in (("iters", 8), ("cost", so[0, 0] * (1.0 + 2 * parity.COST_RTOL)), ("gap", 2 * parity.GAP_CLOSED)):
+    for field, value in (("iters", 8), ("cost", cport.stat(so, "cost")[0] * (1.0 + 2 * parity.COST_RTOL)), ("gap", 2 * parity.GAP_CLOSED)):
         bad = st[0].copy()
         bad[field] = value
         with pytest.raises(AssertionError):
@@ -138,7 +139,7 @@ def test_the_numpy_oracle_comparison_of_one_instance():
 def _failed(status=4, cost=12.0, gap=3.0):
     xo, uo, so = _oracle()
     for f, v in dict(status=status, converged=0, iters=2, alpha=0.0, cost=cost, gap=gap, mu=30.0).items():
-        so[1, oc.STAT_FIELDS.index(f)] = v
+        so[1, cport.STAT_FIELDS.index(f)] = v
     return xo, uo, so
 
 

@@ -9,6 +9,7 @@ from oracle import ddp as oddp, models as omodels
 from srbd_horizon_amd import workload
 from srbd_horizon_amd.engine import DdpEngine
 from tests import abi_header, policy_cases as pc, policy_rollout_cases as prc
+from tests.oracle_refs import frozen
 
 OPTS = dict(max_iters=100, alpha_converge_threshold=1e-12, beta=1e-3)
 M = 4
@@ -42,9 +43,7 @@ def _plan():
     r = oddp.solve(m, b["x0"][0], P, b["xs"][0], b["us"][0], opt)
     _, K, info = pc.oracle_policy(m, r.xs, r.us, P, dict(gap=r.gap, mu=r.mu, alpha=r.alpha, status=r.status), opt, M)
     assert info[3] == 1.0
-    for a in (r.xs, r.us, P, K):
-        a.setflags(write=False)
-    return m, r.xs, r.us, P, K
+    return (m, *frozen((r.xs, r.us, P, K)))
 
 
 def _open_loop(m, us, P, x_meas, start, steps):

@@ -1,14 +1,12 @@
 """Resumable solves without a GPU: the fixture selection of tests/test_gpu_resume.py on the C oracle."""
 import numpy as np
 
-from oracle import cport, ddp as oddp, models as omodels
-from tests import options_cases as oc, resume_cases as rc
+from oracle import cport, ddp as oddp
+from tests import oracle_refs as refs, resume_cases as rc
 
 
 def _trace(model, case, b):
-    s = rc.batch(model)
-    return cport.solve_trace(omodels.RobotConsts(**s["consts"]), oddp.DdpOptions(**rc.options(case)), s["x0"][b], s["params"][b],
-                             s["xs"][b], s["us"][b], model=model)
+    return refs.c_trace(model, rc.batch(model), rc.options(case), b)
 
 
 def test_the_cut_points_show_every_kind_of_carried_state_on_the_c_oracle():
@@ -19,7 +17,7 @@ def test_the_cut_points_show_every_kind_of_carried_state_on_the_c_oracle():
     state at the cut is the C oracle's own at max_iters = k."""
     N, B = rc.SHAPES["srbd13"]
     k = rc.CUT["srbd13"]
-    stat = oc.stat
+    stat = cport.stat
     # uncut traces: iteration counts, first accepted step, the largest mu any line search ran with
     first_alpha, mu_max, iters = {}, {}, {}
     for case in ("base", "A", "E"):
@@ -27,8 +25,8 @@ def test_the_cut_points_show_every_kind_of_carried_state_on_the_c_oracle():
         for b in range(B):
             _, _, st, tr = _trace("srbd13", case, b)
             acc = [r for r in tr if r["alpha"] > 0.0]
-            fa.append(acc[0]["alpha"] if acc else 0.0); mm.append(max(r["mu"] for r in tr)); it.append(int(st[1]))
-            assert int(st[1]) == int(stat(rc.oracle("srbd13", case)[2], "iters")[b])
+            fa.append(acc[0]["alpha"] if acc else 0.0); mm.append(max(r["mu"] for r in tr)); it.append(int(stat(st, "iters")))
+            assert int(stat(st, "iters")) == int(stat(rc.oracle("srbd13", case)[2], "iters")[b])
         first_alpha[case], mu_max[case], iters[case] = np.array(fa), np.array(mm), np.array(it)
     cut = {case: rc.oracle("srbd13", case, k)[2] for case in ("base", "A", "E")}
     unfinished = {case: stat(cut[case], "status") == 1 for case in cut}
@@ -62,5 +60,5 @@ def test_every_model_has_something_to_continue_at_its_cut():
         for case in ("base", "ir1"):
             for k in (rc.CUT[model], *rc.CUTS3[model]):
                 st = rc.oracle(model, case, k)[2]
-                assert (oc.stat(st, "status") == 1).any(), (model, case, k)
+                assert (cport.stat(st, "status") == 1).any(), (model, case, k)
             assert rc.CUTS3[model][0] < rc.CUTS3[model][1]

@@ -6,7 +6,7 @@ import inspect
 import numpy as np
 import pytest
 
-from oracle import models as omodels
+from oracle import cport, models as omodels
 from srbd_horizon_amd import _lib, workload
 from srbd_horizon_amd.engine import DdpEngine
 from srbd_horizon_amd.fleet import FleetQueue
@@ -105,7 +105,7 @@ def test_progress_on_the_c_oracles_plans():
         model, N, B, kind = case
         batch, P, cst, xs, us, st = sc.oracle_plans(*case)
         m = omodels.make_model(model, cst)
-        for b in np.flatnonzero(st[:, 6] == 0):
+        for b in np.flatnonzero(cport.stat(st, "status") == 0):
             total += 1
             taking_part += sc.relative(sc.model_reference(m, xs[b], us[b], P[b])[0]) < sc.relative(sc.model_reference(m, batch["xs"][b], batch["us"][b], P[b])[0])
     assert (total, taking_part) == (13, 13)
