@@ -172,7 +172,7 @@ _lib = None
 
 
 class Build(NamedTuple):
-    """One model build of the library: one translation unit (csrc/sddp_inst.hip) that defines the accessor sddp::ops_<fn>()."""
+    """One model build of the library: the units of csrc/sddp_inst.hip (translation_units) behind the accessor sddp::ops_<fn>()."""
     fn: str                 # accessor suffix
     type: str               # device model type (csrc/sddp_models.hpp)
     model: str              # model name, a key of MODEL_IDS
@@ -188,8 +188,8 @@ _SINK = ("-mllvm", "-sink-insts-to-avoid-spills")
 # THE list of model builds: what build() compiles and hands to csrc/sddp_api.hip, which finds a handle's build in it by
 # (model, traits); no two entries share that key (build() checks).  The builds without traits are the plain builds: they alone have
 # table kernels (sddp_set_instance_consts) and the solve kernels' further variants (VARIANTS: sddp_enable_resume,
-# sddp_enable_iteration_log), each compiled in a translation unit of its own (translation_units).  A new build: its alias in
-# csrc/sddp_models.hpp and one entry here.
+# sddp_enable_iteration_log), each compiled in a translation unit of its own; every build has one more unit for the kernels that only
+# read a plan (translation_units).  A new build: its alias in csrc/sddp_models.hpp and one entry here.
 INSTANCES = [
     Build("srbd13", "Srbd13", "srbd13"), Build("srbd13_b", "Srbd13B", "srbd13", ("bar",)),
     Build("srbd13_s", "Srbd13S", "srbd13", ("so2",)), Build("srbd13_bs", "Srbd13BS", "srbd13", ("bar", "so2")),
@@ -199,7 +199,8 @@ INSTANCES = [
     Build("srbd13_x", "Srbd13X", "srbd13", ("xr",)), Build("srbd37_x", "Srbd37X", "srbd37", ("xr",)), Build("lip30_x", "Lip30X", "lip30", ("xr",)),
     Build("srbd61_x", "Srbd61X", "srbd61", ("xr",), _SINK), Build("srbd61_b", "Srbd61B", "srbd61", ("bar",), _SINK),
 ]
-HEADERS = ["sddp_kernels.hpp", "sddp_kernels_mw.hpp", "sddp_models.hpp", "sddp_sort.hpp", "sddp_handle.hpp", "sddp_launch.hpp", "sddp_kernels_host.hpp"]
+HEADERS = ["sddp_kernels.hpp", "sddp_kernels_mw.hpp", "sddp_models.hpp", "sddp_sort.hpp", "sddp_handle.hpp", "sddp_launch.hpp", "sddp_kernels_host.hpp",
+           "sddp_inspect.hpp", "sddp_launch_inspect.hpp"]
 
 
 def header_stamp(root: str = ROOT) -> str:
@@ -214,6 +215,17 @@ def header_stamp(root: str = ROOT) -> str:
 
 # the solve variants, in the order of csrc/sddp_handle.hpp SolveVariant: the suffix of a variant's translation units
 VARIANTS = ("", "resume", "log")
+# the one definition that makes csrc/sddp_inst.hip a build's inspect unit
+INSPECT_DEF = "-DSDDP_INST_INSPECT"
+
+
+def build_jobs() -> int:
+    """How many compilers run at once: the first of SDDP_BUILD_JOBS, MAX_JOBS, CMAKE_BUILD_PARALLEL_LEVEL that is set, else the CPUs
+    the host reports, at most 16 (a shared machine reports hundreds and allows far fewer)."""
+    for var in ("SDDP_BUILD_JOBS", "MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        if os.environ.get(var):
+            return max(1, int(os.environ[var]))
+    return min(os.cpu_count() or 4, 16)
 
 
 def translation_units():
@@ -221,11 +233,14 @@ def translation_units():
     unit of every entry of INSTANCES, named by its accessor suffix, and for every build without traits one side unit
     <suffix>_<variant> per further entry of VARIANTS: that variant's solve kernels and their launcher (-DSDDP_INST_VARIANT=<index>),
     which the main unit enters in its table.  A side unit is its main unit's command line plus that one definition; a build with
-    traits that asked for one would not compile (csrc/sddp_launch.hpp launch_solve_variant)."""
-    return [(b.fn + ("_" + suffix if v else ""),
-             ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
-             + (["-DSDDP_INST_VARIANT=%d" % v] if v else []))
-            for b in INSTANCES for v, suffix in enumerate(VARIANTS) if v == 0 or not b.traits]
+    traits that asked for one would not compile (csrc/sddp_launch.hpp launch_solve_variant).  Behind them, for every entry of
+    INSTANCES, its inspect unit <suffix>_inspect (INSPECT_DEF): the kernels that only read a plan (csrc/sddp_inspect.hpp), kept out
+    of the device modules of the solve kernels; again its main unit's command line plus the one definition."""
+    def main(b):
+        return ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
+    return ([(b.fn + ("_" + suffix if v else ""), main(b) + (["-DSDDP_INST_VARIANT=%d" % v] if v else []))
+             for b in INSTANCES for v, suffix in enumerate(VARIANTS) if v == 0 or not b.traits]
+            + [(b.fn + "_inspect", main(b) + [INSPECT_DEF]) for b in INSTANCES])
 
 
 def compile_command(unit: str | None = None, root: str = ROOT) -> list:
@@ -256,8 +271,8 @@ def _fresh(obj: str, deps, cmd) -> bool:
 
 def build(force: bool = False, verbose: bool = False, only=None) -> str:
     """Compile the HIP library for gfx950 into libsddp_hip.so (in-tree, so it travels to the GPU box): the host API
-    (csrc/sddp_api.hip), the queue sort (csrc/sddp_sort.hip) and one object per model build (csrc/sddp_inst.hip x INSTANCES),
-    compiled in parallel and linked.  Objects live in build/obj (git-ignored), each beside a stamp of the command line that
+    (csrc/sddp_api.hip), the queue sort (csrc/sddp_sort.hip) and one object per unit of the model builds (csrc/sddp_inst.hip x
+    translation_units()), compiled in parallel (build_jobs) and linked.  Objects live in build/obj (git-ignored), each beside a stamp of the command line that
     made it; stale ones (older than a source or header, or made by another command line) are recompiled.
     only: recompile just these model builds (development); refuses to link while another object is stale."""
     import hashlib
@@ -309,7 +324,7 @@ def build(force: bool = False, verbose: bool = False, only=None) -> str:
         with open(_cmd_stamp(obj), "w") as f:
             f.write(" ".join(cmd))
 
-    workers = max(1, min(len(todo), int(os.environ.get("SDDP_BUILD_JOBS", str(os.cpu_count() or 4)))))
+    workers = max(1, min(len(todo), build_jobs()))
     if todo:
         with ThreadPoolExecutor(max_workers=workers) as ex:
             list(ex.map(compile_one, todo))

@@ -1353,7 +1353,7 @@ int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, 
         return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->pol.policy_knots) +
                                          " (the knots of sddp_enable_policy)");
     if (!d_x_meas || !d_x_out || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
-    return h->ops->launch_policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
+    return h->ops->inspect.policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
 }
 
 int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
@@ -1366,7 +1366,7 @@ int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int
         return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->N));
     // the call's coefficient, or the handle's: linearised as DevConsts::mu_lin is
     const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
-    return h->ops->launch_audit(h, first, count, start, steps, src, mu / sqrt(2.0), d_out);
+    return h->ops->inspect.audit(h, first, count, start, steps, src, mu / sqrt(2.0), d_out);
 }
 
 int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out) {
@@ -1386,7 +1386,7 @@ int sddp_stationarity_range_device(sddp_handle* h, int first, int count, const d
                                    double* d_lambda, double* d_grad) {
     PlanSource src;
     if (const int rc = plan_source(h, "sddp_stationarity_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
-    return h->ops->launch_stationarity(h, first, count, src, d_out, d_lambda, d_grad);
+    return h->ops->inspect.stationarity(h, first, count, src, d_out, d_lambda, d_grad);
 }
 
 int sddp_stationarity(sddp_handle* h, int first, int count, double* out) {
@@ -1418,7 +1418,7 @@ int sddp_cost_terms_range_device(sddp_handle* h, int first, int count, const dou
     PlanSource src;
     if (const int rc = plan_source(h, "sddp_cost_terms_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
     if (const int rc = make_xr_zero(h); rc != SDDP_OK) return rc;
-    return h->ops->launch_cost_terms(h, first, count, src, h->xr_zero, d_out, d_nodes);
+    return h->ops->inspect.cost_terms(h, first, count, src, h->xr_zero, d_out, d_nodes);
 }
 
 int sddp_cost_terms(sddp_handle* h, int first, int count, double* out) {
@@ -1440,7 +1440,7 @@ int sddp_model_step(sddp_handle* h, const double* x, const double* u, const doub
         std::memcpy(hp + B * nx, u, B * nu * D);
         std::memcpy(hp + B * (nx + nu), p, B * np * D);
         HIP_TRY(h, hipMemcpyAsync(dx, hp, B * (nx + nu + np) * D, hipMemcpyHostToDevice, h->stream));
-        rc = h->ops->launch_model_step(h, k, dx, du, dp, dxn);
+        rc = h->ops->inspect.model_step(h, k, dx, du, dp, dxn);
         if (rc != SDDP_OK) return rc;
         rc = download(h, hp + B * (nx + nu + np), dxn, B * nx * D);
         if (rc == SDDP_OK) std::memcpy(x_next, hp + B * (nx + nu + np), B * nx * D);
@@ -1449,7 +1449,7 @@ int sddp_model_step(sddp_handle* h, const double* x, const double* u, const doub
     HIP_TRY(h, hipMemcpyAsync(dx, x, B * nx * D, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(du, u, B * nu * D, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(dp, p, B * np * D, hipMemcpyHostToDevice, h->stream));
-    rc = h->ops->launch_model_step(h, k, dx, du, dp, dxn);
+    rc = h->ops->inspect.model_step(h, k, dx, du, dp, dxn);
     if (rc != SDDP_OK) return rc;
     return download(h, x_next, dxn, B * nx * D);
 }

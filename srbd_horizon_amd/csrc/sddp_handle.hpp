@@ -1,7 +1,8 @@
 // sddp_handle.hpp -- the handle behind include/sddp.h and the per-model operation table.
 //
-// The library is built from one translation unit per model build (sddp_inst.hip, compiled once per entry of
-// srbd_horizon_amd/_lib.py INSTANCES, in parallel) plus the model-independent host code (sddp_api.hip).  A model build reaches
+// The library is built from the translation units of the model builds (sddp_inst.hip, compiled per entry of
+// srbd_horizon_amd/_lib.py INSTANCES as its main unit, its inspect unit and, for a plain build, one unit per further solve variant:
+// _lib.translation_units, in parallel) plus the model-independent host code (sddp_api.hip).  A model build reaches
 // the API through a ModelOps table: what the build is (model, traits), and plain function pointers to what it can do.  Nothing
 // templated crosses a translation unit, and sddp_api.hip asks the table instead of knowing the builds.
 #pragma once
@@ -85,17 +86,23 @@ struct ModelOps {
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
     int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
-    // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
-    int (*launch_policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
-    // the plan inspectors (PlanSource): first, count, [audit: start, steps,] the trajectory, then the inspector's own arguments --
-    // audit: linearised friction coefficient, out; stationarity: out, lambda or null, reduced gradient or null; cost breakdown: the
-    // user rows' table with zero weights or null, out, the per-node addends or null
-    int (*launch_audit)(sddp_handle*, int, int, int, int, PlanSource, double, double*) = nullptr;
-    int (*launch_stationarity)(sddp_handle*, int, int, PlanSource, double*, double*, double*) = nullptr;
-    int (*launch_cost_terms)(sddp_handle*, int, int, PlanSource, const double*, double*, double*) = nullptr;
-    int (*launch_model_step)(sddp_handle*, int, const double*, const double*, const double*, double*);
+    // the knot evaluation of the parity tests (sddp_eval_knots; main unit, on purpose: sddp_kernels.hpp eval_knots_kernel)
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);
+    // The other kernels that only read (sddp_inspect.hpp), of every build.  They are compiled in a translation unit of their own, the
+    // build's inspect unit (sddp_inst.hip with -DSDDP_INST_INSPECT; a user build: one unit holds both), so that they share no device
+    // module with the solve kernels; the main unit enters the table whole (sddp_launch.hpp side_inspect_ops).
+    struct InspectOps {
+        // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
+        int (*policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
+        // the plan inspectors (PlanSource): first, count, [audit: start, steps,] the trajectory, then the inspector's own arguments --
+        // audit: linearised friction coefficient, out; stationarity: out, lambda or null, reduced gradient or null; cost breakdown: the
+        // user rows' table with zero weights or null, out, the per-node addends or null
+        int (*audit)(sddp_handle*, int, int, int, int, PlanSource, double, double*) = nullptr;
+        int (*stationarity)(sddp_handle*, int, int, PlanSource, double*, double*, double*) = nullptr;
+        int (*cost_terms)(sddp_handle*, int, int, PlanSource, const double*, double*, double*) = nullptr;
+        int (*model_step)(sddp_handle*, int, const double*, const double*, const double*, double*) = nullptr;
+    } inspect;
 };
 
 }  // namespace sddp

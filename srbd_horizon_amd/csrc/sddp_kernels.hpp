@@ -28,7 +28,9 @@ namespace sddp {
 constexpr int kWave = 64;
 constexpr int kSlots = 6;   // line-search candidates whose trajectories are kept per pass (one-wave kernel)
 constexpr int kScal = 24;  // doubles per instance in the scratch `scal` record (test kernels / diagnostic stamps)
+// the record sizes of the kernels of sddp_inspect.hpp that sddp_api.hip reports, here so that it needs none of that file:
 constexpr int kStationarityWords = 8;      // doubles per record of the stationarity certificate (sddp.h sddp_stationarity_words)
+constexpr int kCostTermsWords = 16, kCostTermsFamilies = 13;   // ... of the cost breakdown, and its families (sddp.h sddp_cost_terms_words)
 
 // Diagnostic build only (-DSDDP_STAMPS): per-phase shader-cycle sums, written to `scal`; never in the shipped library.
 #ifdef SDDP_STAMPS
@@ -1369,439 +1371,12 @@ __global__ __launch_bounds__(kWave) void queue_cost_key_kernel(ConstsArg<Tab...>
 }
 
 // -----------------------------------------------------------------------------------------------------------------
-// single-phase kernels for the parity tests (same device code as the fused kernel)
-// -----------------------------------------------------------------------------------------------------------------
-// one model step per instance, x+ = f(x, u, p_k) (ddp.py:228-230): the closed-loop simulator step of the examples
-// (dsrbd_example.py:158-159) through the same device model code as the solver.  One thread per instance.
-// -----------------------------------------------------------------------------------------------------------------
-// One thread per instance: b is not wave-uniform, so with a table every lane loads its own row (vector loads), not consts_of's.
-__device__ __forceinline__ const DevConsts& lane_consts_of(const DevConsts& c, const int) { return c; }
-__device__ __forceinline__ DevConsts lane_consts_of(const DevConsts* __restrict__ ctab, const int b) { return ctab[b]; }
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void model_step_kernel(ConstsArg<Tab...> consts, int B, int k, const double* __restrict__ x,
-                                                           const double* __restrict__ u, const double* __restrict__ p,
-                                                           double* __restrict__ xn) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    const int b = blockIdx.x * kWave + threadIdx.x;
-    if (b >= B) return;
-    const DevConsts& c = lane_consts_of(consts, b);
-    double xv[NX], uv[NU], pv[NP], xo[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xv[i] = x[size_t(b) * NX + i];
-#pragma unroll
-    for (int i = 0; i < NU; ++i) uv[i] = u[size_t(b) * NU + i];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) pv[i] = p[size_t(b) * NP + i];
-    (void)M::step(c, xv, uv, pv, k, xo);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xn[size_t(b) * NX + i] = xo[i];
-}
-
-// -----------------------------------------------------------------------------------------------------------------
-// Closed-loop rollout of the exported policy from a measured state (sddp_policy_rollout_device): for the instances b = first + i,
-//   x_0' = x_meas[i];  u_j' = u_k[b] + K_k[b] (x_j' - x_k[b]);  x_{j+1}' = f(x_j', u_j'; P[b][k], k),  k = start + j,  j < steps,
-// through M::step, the model code of the solve's own rollout: its prediction, no renormalisation.  cost (may be null): the sum of
-// the stage costs L_k(x_j', u_j') in knot order.  ok = 0 in the policy record `pol` [B][pol_words]: K is not multiplied (0 x NaN is
-// not 0), the open-loop rollout of u_k from x_meas.
-// One wavefront per instance.  Per knot, lane r < NU owns row r of K_k with apply_policy_kernel's FMA chain (u' at start = 0 is
-// bit-equal to it), reading x_j' from LDS (every lane the same word: a broadcast, no conflict); lane 0 then runs the scalar model
-// code as eval_knots_kernel does and leaves x_{j+1}' in LDS, from where the wave stores it.  Static LDS only, nothing of the
-// slots' work buffers, plain vector stores to the caller's outputs alone.
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void policy_rollout_kernel(ConstsArg<Tab...> consts, int N, int first, int count, int start, int steps,
-                                                               const double* __restrict__ xs, const double* __restrict__ us,
-                                                               const double* __restrict__ P, const double* __restrict__ pol, int pol_words,
-                                                               const double* __restrict__ x_meas, double* __restrict__ x_out,
-                                                               double* __restrict__ u_out, double* __restrict__ cost_out) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    static_assert(NU <= kWave, "one lane per row of K_k");
-    __shared__ double sz[NX + NU];                         // x_j' | u_j'
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= count) return;
-    const int b = first + i;
-    const DevConsts& c = consts_of(consts, b);
-    const double* xb = xs + size_t(b) * (N + 1) * NX;
-    const double* ub = us + size_t(b) * N * NU;
-    const double* Pb = P + size_t(b) * (N + 1) * NP;
-    const double* rec = pol + size_t(b) * pol_words;
-    const bool feedback = rec[pol_words - 1] != 0.0;
-    double* xo = x_out + size_t(i) * (steps + 1) * NX;
-    double* uo = u_out + size_t(i) * steps * NU;
-    for (int e = lane; e < NX; e += kWave) {
-        const double v = x_meas[size_t(i) * NX + e];
-        sz[e] = v;
-        xo[e] = v;
-    }
-    wave_sync();
-    double J = 0.0;
-    for (int j = 0; j < steps; ++j) {
-        const int k = start + j;
-        if (lane < NU) {
-            const double* K = rec + size_t(k) * NU * (NX + 1) + NU + size_t(lane) * NX;
-            const double* xk = xb + k * NX;
-            double acc = ub[k * NU + lane];
-            if (feedback)
-                for (int t = 0; t < NX; ++t) acc = fma(K[t], sz[t] - xk[t], acc);
-            sz[NX + lane] = acc;
-            uo[j * NU + lane] = acc;
-        }
-        wave_sync();
-        if (lane == 0) {
-            double xl[NX], ul[NU], xn[NX];
-#pragma unroll
-            for (int t = 0; t < NX; ++t) xl[t] = sz[t];
-#pragma unroll
-            for (int t = 0; t < NU; ++t) ul[t] = sz[NX + t];
-            J += M::step(c, xl, ul, Pb + k * NP, k, xn);
-#pragma unroll
-            for (int t = 0; t < NX; ++t) sz[t] = xn[t];
-        }
-        wave_sync();
-        for (int e = lane; e < NX; e += kWave) xo[(j + 1) * NX + e] = sz[e];
-    }
-    if (lane == 0 && cost_out) cost_out[i] = J;
-}
-
-// -----------------------------------------------------------------------------------------------------------------
-// Plan audit (sddp_audit_range_device): how far a trajectory is from what the solver only penalises -- friction cone, unilateral
-// force, load on a swing foot, quaternion norm, foot height, slip, rigid foot, dynamics defect -- as SDDP_AUDIT_WORDS maxima per
-// instance (include/sddp.h has the table).  x [..][steps + 1][NX], u [..][steps][NU]: row j sits at node start + j; instance
-// b = first + i reads block xoff + i of them (the handle's own xs / us: xoff = first, steps = N; a caller's: xoff = 0) and row b of P.
-// ml: the linearised friction coefficient of the call.
-// One wavefront per instance; lane l audits the nodes j = l, l + 64, ... on its own (one M::step per stage node, the model code of
-// the solve's rollout) into private maxima, one butterfly of shuffles merges them, lane 0 stores the record.  Read-only but for
-// `out`: no LDS, no atomics, no work buffer.
-// Every maximum propagates NaN (fmax would drop it), and a NaN maximum has no index.
-__device__ __forceinline__ double nan_max(const double a, const double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-// a maximum with the place it was found at: key = node * NC + contact, smaller key on ties (first in node-major order)
-struct AuditMax {
-    double v;
-    int key;
-};
-constexpr int kAuditNoKey = 0x7fffffff;
-__device__ __forceinline__ void audit_take(AuditMax& m, const double v, const int key) {
-    if (m.v != m.v) return;
-    if (v != v) { m.v = v; m.key = kAuditNoKey; }
-    else if (v > m.v || (v == m.v && key < m.key)) { m.v = v; m.key = key; }
-}
-__device__ __forceinline__ void audit_merge(AuditMax& m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double v = __shfl_xor(m.v, o, kWave);
-        const int key = __shfl_xor(m.key, o, kWave);
-        audit_take(m, v, key);
-    }
-}
-__device__ __forceinline__ double audit_merge(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, kWave));
-    return v;
-}
-__device__ __forceinline__ double audit_index(const AuditMax& m, const int div, const bool rem) {
-    if (m.v != m.v || m.key == kAuditNoKey) return -1.0;
-    return double(rem ? m.key % div : m.key / div);
-}
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void plan_audit_kernel(ConstsArg<Tab...> consts, int N, int first, int count, int start, int steps,
-                                                            const double* __restrict__ x, const double* __restrict__ u, int xoff,
-                                                            const double* __restrict__ P, double ml, double* __restrict__ out) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NC = M::NC;
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= count) return;
-    const int b = first + i;
-    const DevConsts& c = consts_of(consts, b);
-    const double* xb = x + size_t(xoff + i) * (steps + 1) * NX;
-    const double* ub = u + size_t(xoff + i) * steps * NU;
-    const double* Pb = P + (size_t(b) * (N + 1) + start) * NP;
-    const double inf = __builtin_huge_val();
-    AuditMax cone{-inf, kAuditNoKey}, pull{-inf, kAuditNoKey}, defect{0.0, kAuditNoKey};
-    double swing = 0.0, drift = 0.0, height = 0.0, slip = 0.0, rigid = 0.0;
-    int stance_pairs = 0;
-    for (int j = lane; j <= steps; j += kWave) {
-        const double* xj = xb + size_t(j) * NX;
-        if constexpr (M::AUDIT_QUAT) {
-            const double* o = xj + M::XO;
-            drift = nan_max(drift, fabs(sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3]) - 1.0));
-        }
-        if (j == steps) break;
-        const int k = start + j;
-        const double* uj = ub + size_t(j) * NU;
-        const double* pj = Pb + size_t(j) * NP;
-#pragma unroll
-        for (int n = 0; n < NC; ++n) {
-            const bool stance = M::p_sw(pj, n) > 0.5;
-            if constexpr (M::AUDIT_FORCES) {
-                const double* f = uj + M::uf(n);
-                const double side = nan_max(fabs(f[0]), fabs(f[1]));
-                if (stance) {
-                    audit_take(cone, side - ml * f[2], k * NC + n);
-                    audit_take(pull, -f[2], k * NC + n);
-                    ++stance_pairs;
-                } else {
-                    swing = nan_max(swing, nan_max(side, fabs(f[2])));
-                }
-            }
-            if constexpr (M::AUDIT_CONTACT_STATES) {
-                height = nan_max(height, fabs(xj[M::XC + 3 * n + 2] - M::p_cref(pj, n)));
-                if (stance) slip = nan_max(slip, nan_max(fabs(xj[M::XCD + 3 * n]), fabs(xj[M::XCD + 3 * n + 1])));
-            }
-        }
-        if constexpr (M::AUDIT_CONTACT_STATES) {
-            if (c.w_rv != 0.0) {
-#pragma unroll
-                for (int q = 0; q < M::NRV; ++q)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e)
-                        rigid = nan_max(rigid, fabs(xj[M::XCD + 3 * M::rv_a(q) + e] - xj[M::XCD + 3 * M::rv_b(q) + e]));
-            }
-        }
-        double xn[NX];
-        (void)M::step(c, xj, uj, pj, k, xn);
-        double d = 0.0;
-#pragma unroll
-        for (int e = 0; e < NX; ++e) d = nan_max(d, fabs(xj[NX + e] - xn[e]));
-        audit_take(defect, d, k);
-    }
-    audit_merge(cone);
-    audit_merge(pull);
-    audit_merge(defect);
-    swing = audit_merge(swing);
-    drift = audit_merge(drift);
-    height = audit_merge(height);
-    slip = audit_merge(slip);
-    rigid = audit_merge(rigid);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) stance_pairs += __shfl_xor(stance_pairs, o, kWave);
-    if (lane == 0) {
-        double* r = out + size_t(i) * SDDP_AUDIT_WORDS;
-        r[0] = cone.v;  r[1] = audit_index(cone, NC, false);  r[2] = audit_index(cone, NC, true);
-        r[3] = pull.v;  r[4] = audit_index(pull, NC, false);
-        r[5] = swing;   r[6] = drift;  r[7] = height;  r[8] = slip;  r[9] = rigid;
-        r[10] = defect.v;  r[11] = audit_index(defect, 1, false);
-        r[12] = double(steps);  r[13] = double(stance_pairs);
-        r[14] = 0.0;  r[15] = 0.0;
-    }
-}
-
-// -----------------------------------------------------------------------------------------------------------------
-// Stationarity certificate (sddp_stationarity_range_device): the costates and the reduced gradient of a whole-horizon trajectory,
-//   lambda_N = l_x,N;   q_k = [l_x,k ; l_u,k] + F_k^T lambda_{k+1},  F_k = [f_x f_u] at (x_k, u_k, p_k);   lambda_k = q_k[0:NX],  s_k = q_k[NX:NZ],
-// k = N - 1 .. 0, every derivative at the STORED (x_k, u_k) whatever the gaps (the multiple-shooting linearisation), and 8 doubles per
-// instance (include/sddp.h has the table).  x [..][N + 1][NX], u [..][N][NU]; instance b = first + i reads block xoff + i of them
-// (the handle's own xs / us: xoff = first; a caller's: xoff = 0) and row b of P.
-// One wavefront per instance, the knots backward.  Per knot, lane 0 runs the scalar model code as eval_knots_kernel does -- M::derivs
-// into a knot record in LDS, with a zero input vector at the terminal knot -- and M::step on the operands plan_audit_kernel gives it
-// (word 6 is its word 10); the wave then expands F_k into an LDS tile through M::F_entry exactly as eval_knots_kernel does, and lane
-// z < NZ, two passes where NZ > 64, forms q[z] = g[z] + sum_j F[j][z] lambda_{k+1}[j] as one FMA chain over j = 0 .. NX - 1, lambda_{k+1}
-// read from LDS (every lane the same word: a broadcast; F[j][.]: consecutive words).  The tile is not a convenience: calling M::F_entry
-// with any other index expressions than eval_knots_kernel's changes what the compiler knows about its arguments over the whole
-// translation unit, and with it the instruction streams of the srbd13 solve, backward and policy kernels (profiles/stationarity).
-// lambda ping-pongs between two LDS vectors, so a pass never reads what it writes.  The maxima are the audit's: NaN propagates, a NaN
-// maximum has no index, the smaller key = node * NU + input wins a tie.  Static LDS only (NREC + 2 NX + NX NZ doubles: 56.7 KB for
-// srbd61), nothing of the slots' work buffers, plain vector stores to the caller's outputs alone (lam / grad may be null).
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void stationarity_kernel(ConstsArg<Tab...> consts, int N, int first, int count,
-                                                              const double* __restrict__ x, const double* __restrict__ u, int xoff,
-                                                              const double* __restrict__ P, double* __restrict__ out,
-                                                              double* __restrict__ lam_out, double* __restrict__ grad_out) {
-    constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NP = M::NP, NREC = M::NREC;
-    __shared__ double srec[NREC];                          // the record of knot k
-    __shared__ double slam[2][NX];                         // lambda_{k+1} | lambda_k, swapping
-    __shared__ double sF[NX * NZ];                         // F_k, row-major
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= count) return;
-    const int b = first + i;
-    const DevConsts& c = consts_of(consts, b);
-    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
-    const double* ub = u + size_t(xoff + i) * N * NU;
-    const double* Pb = P + size_t(b) * (N + 1) * NP;
-    double* lo = lam_out ? lam_out + size_t(i) * (N + 1) * NX : nullptr;
-    double* go = grad_out ? grad_out + size_t(i) * N * NU : nullptr;
-    AuditMax stat{0.0, kAuditNoKey}, defect{0.0, kAuditNoKey};
-    double scale = 0.0, lam0 = 0.0, lam_rest = 0.0;
-    int cur = 0;
-    for (int k = N; k >= 0; --k) {
-        const double* xk = xb + size_t(k) * NX;
-        const double* pk = Pb + size_t(k) * NP;
-        if (lane == 0) {
-            double xl[NX], ul[NU];
-#pragma unroll
-            for (int t = 0; t < NX; ++t) xl[t] = xk[t];
-#pragma unroll
-            for (int t = 0; t < NU; ++t) ul[t] = k < N ? ub[size_t(k) * NU + t] : 0.0;
-            M::derivs(c, xl, ul, pk, k, N, srec);
-            if (k < N) {
-                double xn[NX];
-                (void)M::step(c, xk, ub + size_t(k) * NU, pk, k, xn);
-                double d = 0.0;
-#pragma unroll
-                for (int e = 0; e < NX; ++e) d = nan_max(d, fabs(xk[NX + e] - xn[e]));
-                audit_take(defect, d, k);
-            }
-        }
-        wave_sync();
-        if (k == N) {
-            for (int z = lane; z < NX; z += kWave) {
-                const double v = srec[M::REC_G + z];
-                slam[cur][z] = v;
-                if (lo) lo[size_t(k) * NX + z] = v;
-                lam_rest = nan_max(lam_rest, fabs(v));
-            }
-        } else {
-            const double* ln = slam[cur];
-            for (int e = lane; e < NX * NZ; e += kWave) sF[e] = M::F_entry(c, srec, e / NZ, e % NZ);
-            wave_sync();
-            for (int z = lane; z < NZ; z += kWave) {
-                const double g = srec[M::REC_G + z];
-                double acc = g, mag = fabs(g);
-                for (int j = 0; j < NX; ++j) {
-                    const double f = sF[j * NZ + z], l = ln[j];
-                    acc = fma(f, l, acc);
-                    mag = fma(fabs(f), fabs(l), mag);
-                }
-                if (z < NX) {
-                    slam[cur ^ 1][z] = acc;
-                    if (lo) lo[size_t(k) * NX + z] = acc;
-                    if (k == 0) lam0 = nan_max(lam0, fabs(acc));
-                    else lam_rest = nan_max(lam_rest, fabs(acc));
-                } else {
-                    if (go) go[size_t(k) * NU + (z - NX)] = acc;
-                    audit_take(stat, fabs(acc), k * NU + (z - NX));
-                    scale = nan_max(scale, mag);
-                }
-            }
-            cur ^= 1;
-        }
-        wave_sync();                                       // lambda_k is in LDS, and the record is free for knot k - 1
-    }
-    audit_merge(stat);
-    scale = audit_merge(scale);
-    lam0 = audit_merge(lam0);
-    lam_rest = audit_merge(lam_rest);
-    if (lane == 0) {
-        double* r = out + size_t(i) * kStationarityWords;
-        r[0] = stat.v;  r[1] = audit_index(stat, NU, false);  r[2] = audit_index(stat, NU, true);
-        r[3] = scale;  r[4] = lam0;  r[5] = lam_rest;
-        r[6] = defect.v;  r[7] = double(N);
-    }
-}
-
-// -----------------------------------------------------------------------------------------------------------------
-// Cost breakdown (sddp_cost_terms_range_device): the cost of a whole-horizon trajectory family by family, kCostTermsWords doubles per
-// instance (include/sddp.h has the table).  No model code of its own: column 0 of a node is M::step / M::term_cost on the instance's
-// constants as they are, column 1 + f the same code on a copy that keeps family f's weights and has 0.0 in every other one, so the
-// terms of a family are formed and added exactly as inside the full cost.  The copy is made BY DATA (w' = keep ? w : 0.0, a pointer
-// select for the user rows' table, whose second copy `xr_zero` has zero weights), so the wave runs one instruction stream whatever
-// families its lanes hold; what diverges is k == N (term_cost) and what the model branches on itself.  One weight is no constant but
-// a parameter (M::P_WEIGHT, orientation_tracking_gain): the instance's parameter rows are staged in LDS twice, as they are and with
-// that column 0.0, and a column reads the second copy unless it is the total or `unweighted` -- the family of what is left when every
-// weight of DevConsts is 0.0.  A user build's rows may read any parameter, so there family 11 is evaluated on the rows as they are
-// and the node's `unweighted` is taken off it afterwards (the one place a family is a difference).
-// x [..][N + 1][NX], u [..][N][NU]; instance b = first + i reads block xoff + i of them (the handle's own xs / us: xoff = first; a
-// caller's: xoff = 0) and row b of P.  One wavefront per instance; the work items are the (node, column) pairs e = k * 14 + col,
-// strided over the lanes; M::step's next state is discarded.  The addends go to a tile [N + 1][14] in dynamic LDS (the launcher
-// refuses horizons whose tile and parameter copies exceed it) and from there to `nodes` when given; then lane col < 14 adds its
-// column in node order, which is the record: no lane mapping enters a sum.  Plain vector stores to out / nodes alone.
-constexpr int kCostTermsWords = 16, kCostTermsFamilies = 13, kCostTermsCols = kCostTermsFamilies + 1;
-template <class M>
-constexpr size_t cost_terms_lds(int N) {
-    return sizeof(double) * (size_t(N + 1) * (kCostTermsCols + (M::P_WEIGHT >= 0 ? 2 * M::NP : 0)) + kCostTermsCols);
-}
-// the constants of column col: the total (0) keeps everything, family f = col - 1 what include/sddp.h's table says
-__device__ __forceinline__ DevConsts cost_terms_consts(const DevConsts& c, const int col, const double* xr_zero) {
-    const int f = col - 1;
-    const bool all = col == 0;
-    DevConsts m = c;
-    m.w_rz = (all || f == 0) ? c.w_rz : 0.0;
-    m.w_rxy = (all || f == 0) ? c.w_rxy : 0.0;
-    m.w_rd = (all || f == 1) ? c.w_rd : 0.0;
-    m.w_w = (all || f == 2) ? c.w_w : 0.0;
-    m.w_rel = (all || f == 3) ? c.w_rel : 0.0;
-    m.w_f = (all || f == 4) ? c.w_f : 0.0;
-    m.w_sw = (all || f == 5) ? c.w_sw : 0.0;
-    m.gq = (all || f == 6) ? c.gq : 0.0;
-    m.w_zmp = (all || f == 7) ? c.w_zmp : 0.0;
-    m.w_pen = (all || f == 8) ? c.w_pen : 0.0;
-    m.w_rv = (all || f == 8) ? c.w_rv : 0.0;
-    m.bar_w = (all || f == 9) ? c.bar_w : 0.0;
-    m.box_w = (all || f == 10) ? c.box_w : 0.0;
-    m.xr = (all || f == 11) ? c.xr : xr_zero;
-    return m;
-}
-template <class M, class... Tab>
-__global__ __launch_bounds__(kWave) void cost_terms_kernel(ConstsArg<Tab...> consts, const double* __restrict__ xr_zero, int N, int first,
-                                                            int count, const double* __restrict__ x, const double* __restrict__ u, int xoff,
-                                                            const double* __restrict__ P, double* __restrict__ out,
-                                                            double* __restrict__ nodes) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NCOL = kCostTermsCols;
-    constexpr bool PW = M::P_WEIGHT >= 0;
-    extern __shared__ __attribute__((aligned(16))) double s[];
-    double* tile = s;                                      // [N + 1][NCOL] the addends
-    double* sums = tile + size_t(N + 1) * NCOL;            // [NCOL] their sums
-    double* sp = sums + NCOL;                              // PW: [2][N + 1][NP] the parameters | with column P_WEIGHT = 0.0
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= count) return;
-    const int b = first + i;
-    const DevConsts& c = consts_of(consts, b);
-    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
-    const double* ub = u + size_t(xoff + i) * N * NU;
-    const double* Pb = P + size_t(b) * (N + 1) * NP;
-    const int items = (N + 1) * NCOL;
-    if constexpr (PW) {
-        for (int e = lane; e < (N + 1) * NP; e += kWave) {
-            const double v = Pb[e];
-            sp[e] = v;
-            sp[(N + 1) * NP + e] = e % NP == M::P_WEIGHT ? 0.0 : v;
-        }
-        wave_sync();
-    }
-    for (int e = lane; e < items; e += kWave) {
-        const int k = e / NCOL, col = e % NCOL;
-        const DevConsts m = cost_terms_consts(c, col, xr_zero);
-        const double* pk = Pb + size_t(k) * NP;
-        if constexpr (PW) {
-            const bool as_is = col == 0 || col == NCOL - 1 || (M::HAS_UR && col == NCOL - 2);
-            pk = sp + (as_is ? 0 : (N + 1) * NP) + k * NP;
-        }
-        const double* xk = xb + size_t(k) * NX;
-        double v;
-        if (k == N) {
-            v = M::term_cost(m, xk, pk);
-        } else {
-            double xn[NX];
-            v = M::step(m, xk, ub + size_t(k) * NU, pk, k, xn);
-        }
-        tile[e] = v;
-    }
-    wave_sync();
-    if constexpr (M::HAS_UR && PW) {
-        for (int k = lane; k <= N; k += kWave) tile[k * NCOL + NCOL - 2] -= tile[k * NCOL + NCOL - 1];
-        wave_sync();
-    }
-    if (nodes) {
-        double* no = nodes + size_t(i) * items;
-        for (int e = lane; e < items; e += kWave) no[e] = tile[e];
-    }
-    if (lane < NCOL) {
-        double acc = 0.0;
-        for (int k = 0; k <= N; ++k) acc += tile[k * NCOL + lane];
-        sums[lane] = acc;
-        out[size_t(i) * kCostTermsWords + lane] = acc;
-    }
-    wave_sync();
-    if (lane == 0) {
-        int best = 0;
-        bool nan = false;
-        for (int f = 0; f < kCostTermsFamilies - 1; ++f) {
-            const double v = sums[1 + f];
-            nan = nan || v != v;
-            if (v > sums[1 + best]) best = f;
-        }
-        out[size_t(i) * kCostTermsWords + 14] = nan ? -1.0 : double(best);
-        out[size_t(i) * kCostTermsWords + 15] = double(N);
-    }
-}
-
+// single-phase kernels for the parity tests (same device code as the fused kernel): the knot evaluation, one backward sweep, one
+// forward rollout.  The other kernels that only read -- model step, policy rollout, the plan inspectors -- are in sddp_inspect.hpp,
+// which a unit of its own instantiates.  eval_knots_kernel reads only as well and stays here, in the main unit, on purpose: it is the
+// second caller of M::F_entry beside the sweeps, and without it in their module six of the eight 4-wave main units come out with
+// reordered address arithmetic in their solve, backward and policy kernels (profiles/inspect_unit/README.md).  It has one
+// instantiation per build and no table form.
 // -----------------------------------------------------------------------------------------------------------------
 // one wavefront per knot: lane 0 runs the scalar model code, all lanes expand the dense tiles
 template <class M>

@@ -1,5 +1,7 @@
 // sddp_launch.hpp -- host-side launchers of one model build (templates on the device model), collected into a ModelOps table.
-// Included by sddp_inst.hip only: one translation unit per model build.
+// Included by sddp_inst.hip (and by a user build's generated unit).  What a unit instantiates of it decides which kernels its
+// device module holds: the main unit make_ops<M> -- the solve, policy, backward / forward and cost-key kernels --, a variant unit
+// solve_ops<M, V> alone, the inspect unit (sddp_launch_inspect.hpp, which includes this file) the kernels that only read.
 #pragma once
 #include <algorithm>
 #include <tuple>
@@ -225,47 +227,20 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
     });
 }
 
-// the exported policy rolled out through the model from a measured state: one wavefront per instance of the range, static LDS only.
-// has_policy<M>() builds only, like launch_policy.
-template <class M>
-int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int steps, const double* dxm, double* dx, double* du, double* dcost) {
-    return launch_waves<M>(h, SDDP_PICK(policy_rollout_kernel), count, 0, h->N, first, count, start, steps, h->xs, h->us, h->last_params,
-                           (const double*)h->pol.policy, h->policy_words(), dxm, dx, du, dcost);
-}
-
-// The plan inspectors (sddp_handle.hpp PlanSource): one wavefront per instance of the range.  Every build has them.
-// the plan audit: nothing but registers
-template <class M>
-int launch_audit(sddp_handle* h, int first, int count, int start, int steps, PlanSource s, double ml, double* dout) {
-    return launch_waves<M>(h, SDDP_PICK(plan_audit_kernel), count, 0, h->N, first, count, start, steps, s.x, s.u, s.xoff, h->last_params, ml, dout);
-}
-// the stationarity certificate: static LDS only
-template <class M>
-int launch_stationarity(sddp_handle* h, int first, int count, PlanSource s, double* dout, double* dlam, double* dgrad) {
-    return launch_waves<M>(h, SDDP_PICK(stationarity_kernel), count, 0, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dout, dlam, dgrad);
-}
-// the cost breakdown: dynamic LDS sized from N (cost_terms_lds: the tile of addends and, where a parameter is a weight, two copies of
-// the instance's parameter rows).  A horizon whose LDS exceeds the 64 KB a kernel has without an attribute is refused, there is no
-// chunked path.  xr_zero: the user rows' table with zero weights (null: the build has no such table).
-template <class M>
-int launch_cost_terms(sddp_handle* h, int first, int count, PlanSource s, const double* xr_zero, double* dout, double* dnodes) {
-    const size_t lds = cost_terms_lds<M>(h->N);
-    if (lds > size_t(64) * 1024)
-        return fail(h, SDDP_ERR_ARG, "sddp_cost_terms_range_device: the horizon's tile of addends needs " + std::to_string(lds) +
-                                         " bytes of LDS, more than the 65536 one workgroup has here");
-    return launch_waves<M>(h, SDDP_PICK(cost_terms_kernel), count, lds, xr_zero, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dout, dnodes);
-}
-
-template <class M>
-int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
-    return launch_waves<M>(h, SDDP_PICK(model_step_kernel), (h->B + kWave - 1) / kWave, 0, h->B, k, dx, du, dp, dxn);
-}
-
+// the knot evaluation of the parity tests: the one kernel that only reads and stays in the main unit (sddp_kernels.hpp says why)
 template <class M>
 void launch_eval_knots(const DevConsts& dc, int N, int nk, const int* dk, const double* dx, const double* du, const double* dp, double* drec,
                        double* df, double* dF, double* dH, double* dg, double* dL) {
     hipLaunchKernelGGL(eval_knots_kernel<M>, dim3(nk), dim3(kWave), 0, 0, dc, N, nk, dk, dx, du, dp, drec, df, dF, dH, dg, dL);
 }
+
+// The launchers of the kernels that only read (ModelOps::InspectOps) as the build's main unit names them without instantiating a
+// kernel of theirs: declared here, defined (an explicit specialisation, SDDP_DEFINE_INSPECT_OPS of sddp_launch_inspect.hpp) by the
+// build's inspect unit alone, or by a user build's one unit in front of its make_ops.  This is side_solve_ops' mechanism for every
+// build: what those kernels are, and what is done to them later, cannot reach the code generation of the solve kernels of this
+// unit.  A build whose inspect unit is missing does not load.
+template <class M>
+ModelOps::InspectOps side_inspect_ops();
 
 template <class M>
 ModelOps make_ops(const char* name) {
@@ -284,12 +259,9 @@ ModelOps make_ops(const char* name) {
     o.launch_cost_keys = launch_cost_keys<M>;
     o.launch_backward = launch_backward<M>;
     o.launch_forward = launch_forward<M>;
-    if constexpr (has_policy<M>()) { o.launch_policy = launch_policy<M>; o.launch_policy_rollout = launch_policy_rollout<M>; }
-    o.launch_audit = launch_audit<M>;
-    o.launch_stationarity = launch_stationarity<M>;
-    o.launch_cost_terms = launch_cost_terms<M>;
-    o.launch_model_step = launch_model_step<M>;
+    if constexpr (has_policy<M>()) o.launch_policy = launch_policy<M>;
     o.launch_eval_knots = launch_eval_knots<M>;
+    o.inspect = side_inspect_ops<M>();
     return o;
 }
 

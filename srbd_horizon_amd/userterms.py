@@ -301,12 +301,15 @@ using std::sqrt; using std::pow; using std::exp; using std::log; using std::sin;
 
 
 def source(spec: UserSpec) -> str:
-    """The translation unit of a user build (the form of csrc/sddp_inst.hip)."""
+    """The translation unit of a user build (the form of csrc/sddp_inst.hip).  One unit, one shared object: it is the build's main
+    unit and its inspect unit at once, and defines side_inspect_ops for its model, with csrc/sddp_inst.hip's own macro, in front of the
+    make_ops that enters it."""
     npb, targs = MODELS[spec.model]
     mw_check = ("static_assert(!use_mw<SddpUserModel>(), \"srbd13's user build stays on the one-wave kernel (LDS under the 48 KB switch)\");"
                 if spec.model == "srbd13" else "")
     return f"""// user build of {spec.model} -- generated by srbd_horizon_amd/userterms.py; loaded by sddp_register_user_build (include/sddp.h)
 #include "sddp_launch.hpp"
+#include "sddp_launch_inspect.hpp"
 
 {HOST_PRELUDE}
 {generate(spec)}
@@ -314,6 +317,7 @@ namespace sddp {{
 using SddpUserModel = SrbdModel<{targs}, false, false, kXrRows, ::SddpUserRows>;
 static_assert(SddpUserModel::NPB == {npb}, "parameter layout of the generated rows");
 {mw_check}
+SDDP_DEFINE_INSPECT_OPS(SddpUserModel)
 }}  // namespace sddp
 
 #define SDDP_USER_EXPORT extern "C" __attribute__((visibility("default")))

@@ -123,8 +123,18 @@ def _variant_defs(defs):
     return [d for d in defs if d.startswith("-DSDDP_INST_VARIANT")]
 
 
+def _inspect_defs(defs):
+    return [d for d in defs if d.startswith("-DSDDP_INST_INSPECT")]
+
+
+def _solve_units():
+    """the units of the solve kernels: every unit but the builds' inspect units"""
+    return [(name, defs) for name, defs in _lib.translation_units() if not name.endswith("_inspect")]
+
+
 def test_the_resume_units_are_exactly_the_builds_without_traits():
-    units = _lib.translation_units()
+    assert len(_lib.translation_units()) == len(set(dict(_lib.translation_units()))) == 38
+    units = _solve_units()
     names = [name for name, _ in units]
     plain = sorted(b.fn for b in _lib.INSTANCES if not b.traits)
     assert _lib.VARIANTS == ("", "resume", "log")                # the order of csrc/sddp_handle.hpp SolveVariant
@@ -141,3 +151,59 @@ def test_the_resume_units_are_exactly_the_builds_without_traits():
         if name.endswith("_resume"):      # a resume unit is compiled as its build's main unit but for that definition
             assert [d for d in defs if d not in _variant_defs(defs)] == by_name[name[:-len("_resume")]], name
     assert sorted(n for n, defs in units if not _variant_defs(defs)) == sorted(b.fn for b in _lib.INSTANCES)
+
+
+def test_every_build_has_exactly_one_inspect_unit_its_main_unit_plus_one_definition():
+    units = _lib.translation_units()
+    by_name = dict(units)
+    inspect = [name for name, _ in units if name.endswith("_inspect")]
+    assert sorted(inspect) == sorted(b.fn + "_inspect" for b in _lib.INSTANCES) and len(inspect) == len(set(inspect)) == 15
+    assert _lib.INSPECT_DEF == "-DSDDP_INST_INSPECT"
+    for name, defs in units:
+        # the one definition that makes a unit the inspect unit: on the inspect units alone, once, and with no variant beside it
+        assert _inspect_defs(defs) == ([_lib.INSPECT_DEF] if name in inspect else []), name
+        if name in inspect:
+            main = by_name[name[:-len("_inspect")]]
+            assert [d for d in defs if d != _lib.INSPECT_DEF] == main and len(defs) == len(main) + 1 and not _variant_defs(defs), name
+    assert _lib.compile_command("srbd61_inspect")[-3:] == ["-mllvm", "-sink-insts-to-avoid-spills", _lib.INSPECT_DEF]
+
+
+def test_the_units_of_the_solve_kernels_and_their_definitions_are_what_they_were():
+    """the 23 units from before the inspect units, as literals: names in build order, the definitions of one of each kind"""
+    units = _solve_units()
+    assert [name for name, _ in units] == [
+        "srbd13", "srbd13_resume", "srbd13_log", "srbd13_b", "srbd13_s", "srbd13_bs", "srbd37", "srbd37_resume", "srbd37_log", "srbd37_b",
+        "srbd37_s", "srbd37_bs", "lip30", "lip30_resume", "lip30_log", "srbd61", "srbd61_resume", "srbd61_log", "srbd13_x", "srbd37_x",
+        "lip30_x", "srbd61_x", "srbd61_b"]
+    by_name = dict(units)
+    assert by_name["srbd13"] == ["-DSDDP_INST_MODEL=Srbd13", "-DSDDP_INST_FN=ops_srbd13", '-DSDDP_INST_NAME="srbd13"']
+    assert by_name["srbd37_bs"] == ["-DSDDP_INST_MODEL=Srbd37BS", "-DSDDP_INST_FN=ops_srbd37_bs", '-DSDDP_INST_NAME="srbd37"']
+    assert by_name["lip30_resume"] == ["-DSDDP_INST_MODEL=Lip30", "-DSDDP_INST_FN=ops_lip30", '-DSDDP_INST_NAME="lip30"', "-DSDDP_INST_VARIANT=1"]
+    assert by_name["srbd61_log"] == ["-DSDDP_INST_MODEL=Srbd61", "-DSDDP_INST_FN=ops_srbd61", '-DSDDP_INST_NAME="srbd61"', "-mllvm",
+                                     "-sink-insts-to-avoid-spills", "-DSDDP_INST_VARIANT=2"]
+    for b in _lib.INSTANCES:      # every main unit: the build's three definitions and its own flags, nothing else
+        assert by_name[b.fn] == ["-DSDDP_INST_MODEL=" + b.type, "-DSDDP_INST_FN=ops_" + b.fn, '-DSDDP_INST_NAME="' + b.model + '"', *b.flags]
+    # the units behind them are the inspect units, so the objects of the solve kernels keep their place on the link line
+    assert [name for name, _ in _lib.translation_units()][:23] == [name for name, _ in units]
+
+
+def test_a_user_build_is_its_own_inspect_unit():
+    """text only: the generated unit includes the inspectors' launchers and defines side_inspect_ops for its model with the macro
+    csrc/sddp_inst.hip uses, in front of the make_ops that enters it"""
+    import os
+    import numpy as np
+    from srbd_horizon_amd import userterms
+    nx, nu = DIMS["srbd13"][:2]
+    a = np.zeros(nx + nu)
+    a[2] = 1.0
+    spec = userterms.UserSpec("srbd13", nx, nu, [userterms.UserRow("state", 2.0, a=a)], [])
+    src = userterms.source(spec)
+    macro = "SDDP_DEFINE_INSPECT_OPS"
+    assert '#include "sddp_launch_inspect.hpp"' in src and src.count(macro + "(SddpUserModel)") == 1
+    assert src.index("using SddpUserModel") < src.index(macro + "(SddpUserModel)") < src.index("make_ops<sddp::SddpUserModel>")
+    inst = open(os.path.join(_lib.CSRC, "sddp_inst.hip")).read()
+    hdr = open(os.path.join(_lib.CSRC, "sddp_launch_inspect.hpp")).read()
+    assert macro + "(SDDP_INST_MODEL)" in inst and "#define " + macro + "(M)" in hdr
+    # ... and nobody writes the specialisation out by hand
+    assert "side_inspect_ops<" not in src and "side_inspect_ops<SDDP" not in inst
+    assert {"sddp_inspect.hpp", "sddp_launch_inspect.hpp"} <= set(_lib.HEADERS)

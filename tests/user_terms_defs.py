@@ -112,6 +112,7 @@ def prebuild(verbose=False):
     """Compile every user build the tests and the example use (in parallel; existing builds are kept)."""
     from concurrent.futures import ThreadPoolExecutor
     specs = {userterms.build_path(s): s for s in all_specs()}
-    workers = max(1, min(len(specs), int(os.environ.get("SDDP_BUILD_JOBS", str(os.cpu_count() or 4)))))
+    from srbd_horizon_amd import _lib
+    workers = max(1, min(len(specs), _lib.build_jobs()))
     with ThreadPoolExecutor(max_workers=workers) as ex:
         return list(ex.map(lambda s: userterms.ensure_build(s, verbose), specs.values()))

@@ -7,8 +7,10 @@ comparison between two trees, kernel by kernel: the proof that a refactor left t
 
 dump compiles csrc/sddp_inst.hip of TREE (default: this tree) by TREE's own _lib: its unit list and its command line, so two
 trees whose unit recipes differ are each compiled exactly as their own build() compiles them.  diff drops comments, takes the
-function number out of the basic-block labels and compares what is left of every kernel line by line; it exits 1 if the two
-directories hold different units, a unit holds different kernel names, or a kernel differs."""
+function number out of the basic-block labels and compares what is left of every kernel line by line.  Kernels are matched by name:
+in their own unit where both trees have them there, else wherever the other tree holds them, reported under the branch's unit as
+"moved <from> -> <to>: same | differing".  The two trees need not hold the same units.  It exits 1 if a kernel differs, is gone
+from the branch, or is in the branch alone."""
 import argparse
 import difflib
 import importlib.util
@@ -49,7 +51,8 @@ def kernels(path):
         i = j = start[name]
         while not lines[j].startswith(".Lfunc_end"):
             j += 1
-        body = (re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*$", "", l).rstrip()) for l in lines[i + 1:j])
+        # (.Lpost_getpc<n>, the label of a long branch, is numbered through the module like the functions)
+        body = (re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*$", "", l).rstrip())) for l in lines[i + 1:j])
         out[name] = [l for l in body if l.strip()]
     return out
 
@@ -79,22 +82,43 @@ def main():
     up, ub = units_in(args.parent), units_in(args.branch)
     for unit in sorted(up ^ ub):
         print(f"{unit:<14} only in {args.parent if unit in up else args.branch}")
-    total = differing = 0
-    for unit in sorted(up & ub):
-        kp, kb = kernels(os.path.join(args.parent, unit + ".s")), kernels(os.path.join(args.branch, unit + ".s"))
-        bad = sorted(set(kp) ^ set(kb))
-        lines = 0
-        for name in sorted(set(kp) & set(kb)):
+    parent = {u: kernels(os.path.join(args.parent, u + ".s")) for u in up}
+    branch = {u: kernels(os.path.join(args.branch, u + ".s")) for u in ub}
+    # a kernel that its own unit no longer holds is looked for in the rest of the other tree: (name, parent unit) <-> (name, branch unit)
+    left = {(n, u) for u in up for n in parent[u] if n not in branch.get(u, {})}
+    came_from = {}
+    for u in sorted(ub):
+        for n in sorted(set(branch[u]) - set(parent.get(u, {}))):
+            src = min((pu for pn, pu in left if pn == n), default=None)
+            if src is not None:
+                left.discard((n, src))
+                came_from[(n, u)] = src
+    total = differing = moved = 0
+    for unit in sorted(up | ub):
+        kp, kb = parent.get(unit, {}), branch.get(unit, {})
+        bad = sorted([n for n in kp if (n, unit) in left] + [n for n in kb if n not in kp and (n, unit) not in came_from])      # gone, new
+        notes, lines = [], 0
+        for name in sorted(kb):
+            src = unit if name in kp else came_from.get((name, unit))
+            if src is None:
+                continue
             lines += len(kb[name])
-            if kp[name] != kb[name]:
+            same = parent[src][name] == kb[name]
+            if not same:
                 bad.append(name)
-                for x in list(difflib.unified_diff(kp[name], kb[name], lineterm="", n=0))[:8]:
+                for x in list(difflib.unified_diff(parent[src][name], kb[name], lineterm="", n=0))[:8]:
                     print("   ", x)
+            if src != unit:
+                moved += 1
+                notes.append(f"{name}  moved {src} -> {unit}: {'same' if same else 'differing'}")
         total += len(kb)
         differing += len(bad)
-        print(f"{unit:<14} {len(kb):>3} kernels, {lines:>8} instructions and labels, differing kernels: {len(bad)}" + "".join("\n    " + b for b in bad))
-    print(f"{len(up & ub)} units in both, {len(up ^ ub)} in one only, {total} kernels, differing kernels: {differing}")
-    return 1 if differing or up ^ ub else 0
+        if unit in ub or bad:
+            print(f"{unit:<14} {len(kb):>3} kernels, {lines:>8} instructions and labels, differing kernels: {len(bad)}"
+                  + "".join("\n    " + b for b in bad + notes))
+    print(f"{len(up & ub)} units in both, {len(up ^ ub)} in one only, {total} kernels, differing kernels: {differing}"
+          + (f", moved: {moved}" if moved else ""))
+    return 1 if differing else 0
 
 
 if __name__ == "__main__":

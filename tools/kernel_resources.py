@@ -1,6 +1,6 @@
 """Code-object resources of every kernel of every translation unit of the model builds (srbd_horizon_amd/_lib.py translation_units:
-one unit per entry of INSTANCES, and the side units `<build>_resume` and `<build>_log` of the plain builds' further solve variants,
-_lib.VARIANTS): SGPRs, VGPRs, AGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports
+one unit per entry of INSTANCES, the side units `<build>_resume` and `<build>_log` of the plain builds' further solve variants,
+_lib.VARIANTS, and every build's `<build>_inspect` unit of the kernels that only read a plan): SGPRs, VGPRs, AGPRs, scratch bytes per lane, occupancy (waves per SIMD) and static LDS, as the compiler reports
 them for gfx950.
 
     python tools/kernel_resources.py [-j JOBS] [--only srbd13,srbd13_resume] [--root OTHER_TREE] > resources.txt
