@@ -365,6 +365,44 @@ int  sddp_cost_terms_name(int family, const char** name);
 int  sddp_cost_terms_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
                                   double* d_out /*[count][16]*/, double* d_nodes /*[count][N + 1][14] or NULL*/);
 int  sddp_cost_terms(sddp_handle* h, int first, int count, double* out /*[count][16], host*/);
+/* ---- parameter sensitivities (v9): the gradient of a plan's cost in its per-knot parameters, computed on the device ----------------
+ * The audit, the certificate and the breakdown describe a plan; none says how its cost would change with what the caller feeds the
+ * solver every tick, the parameter tensor P [B][N + 1][np]: commanded velocities, the orientation reference and its gain, contact
+ * switches and c_ref and, on srbd13, the footholds.  For the Lagrangian of the stationarity section and the costates it defines,
+ *       G_k[j] = dL_k/dp_k[j] + sum_i lambda_{k+1}[i] df_k[i]/dp_k[j]   (k < N),        G_N[j] = dL_N/dp_N[j],
+ * every derivative at the STORED (x_k, u_k, p_k), analytic device model code beside the one sddp_eval_knots returns (input residuals
+ * and penalties on the nodes 0 .. N - 1, state residuals on 1 .. N, the terminal node without inputs).  At a converged plan with
+ * closed gaps G is the gradient of the optimal cost in P (envelope theorem); elsewhere it is the gradient of the Lagrangian, and
+ * words 5 and 6 say how far from that the plan is.  lambda_0 (d_lambda row 0) is the other half: the gradient in x_0.
+ * df/dp is non-zero only on srbd13, whose contact points (columns 11 .. 16) are the lever arms of wdot; on the other models no
+ * parameter enters the dynamics.  Neither barrier reads a parameter and second_order plays no part, so the barrier and second_order = 2
+ * builds differ only through their plans.  With user rows (n_extra > 0) a row is np + 8 wide, sddp_handle_dims' width, and the rows'
+ * reference columns np + j hold -2 w_j e_j, e_j = a_j . z - (p[np + j] + const_j), where the row's kind is active.  A user build
+ * (non-linear rows) has no derivative code in the parameters: SDDP_ERR_ARG.
+ * Entry j starts at dL/dp[j] and adds fma(df[i]/dp[j], lambda_{k+1}[i], .) for i = 0 .. nx - 1 in this order, structural zeros skipped.
+ * One record is sddp_param_gradient_words() = 8 doubles per instance (np: the width of a row of d_grad):
+ *    0  max over k, j of |G_k[j]|
+ *    1, 2  its node and column (the first in node-major order on ties; -1 where word 0 is NaN)
+ *    3  scale: max over k, j of |dL/dp[j]| + sum_i |df[i]/dp[j]| |lambda_{k+1}[i]|
+ *    4  || lambda_0 ||_inf, the bits of stationarity word 4
+ *    5  stationarity word 0: how far from stationary the plan is, and so how far G is from the gradient of the optimal cost
+ *    6  stationarity word 6, the defect          7  N
+ * A maximum whose operands include a NaN is NaN.
+ * sddp_param_gradient_range_device: d_x == NULL and d_u == NULL take the handle's own xs / us; both given take a caller's trajectory,
+ *   d_x [count][N + 1][nx] and d_u [count][N][nu], block i for instance first + i.  d_grad [count][N + 1][np] receives every G_k,
+ *   d_lambda [count][N + 1][nx] every costate; either may be NULL.  The costates are not recomputed by other code: the call first runs
+ *   the launch of sddp_stationarity_range_device into a buffer the handle owns (made by the first call, freed with the handle), so
+ *   d_lambda and words 4 - 6 have the bits that call gives.  The parameters are those of the last sddp_solve* launch (SDDP_ERR_ARG
+ *   if no solve ran, if only one of d_x / d_u is given, for a range outside the handle, or on a user build); with per-instance
+ *   constants instance b is differentiated through its own robot.  Asynchronous on the handle's stream, behind the solve; it writes
+ *   nothing but d_out, d_grad and d_lambda and uses none of the slots' work buffers: no solve result, policy record, resume flag, log
+ *   record or class table changes, and the result of an instance does not depend on the range it was part of.
+ * sddp_param_gradient: the records (and, grad != NULL, the gradients) of the handle's own plan into host arrays; waits for the stream. */
+int  sddp_param_gradient_words(sddp_handle* h, int* words, int* np);
+int  sddp_param_gradient_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
+                                      double* d_out /*[count][8]*/, double* d_grad /*[count][N + 1][np] or NULL*/,
+                                      double* d_lambda /*[count][N + 1][nx] or NULL*/);
+int  sddp_param_gradient(sddp_handle* h, int first, int count, double* out /*[count][8], host*/, double* grad /*[count][N + 1][np] or NULL, host*/);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

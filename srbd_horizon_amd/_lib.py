@@ -71,6 +71,8 @@ STATIONARITY_FIELDS = ("stationarity", "node", "input", "scale", "lambda_0", "la
 # names are the library's (sddp_cost_terms_name): load() reads them into COST_TERM_NAMES, empty until then
 COST_TERMS_WORDS, COST_TERMS_COLS = 16, 14
 COST_TERM_NAMES = ()
+# the words of one record of the parameter sensitivities (include/sddp.h sddp_param_gradient_range_device), by name
+PARAM_GRADIENT_FIELDS = ("gradient", "node", "column", "scale", "lambda_0", "stationarity", "defect", "nodes")
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = C.sizeof(SddpStats) // 8, C.sizeof(SddpStats) // 4
 STATS_F64_COST = SddpStats.cost.offset // 8
@@ -127,6 +129,9 @@ SYMBOLS = {
     "sddp_cost_terms_name": (C.c_int, [C.c_int, _P(C.c_char_p)]),
     "sddp_cost_terms_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sddp_cost_terms": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_param_gradient_words": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_param_gradient_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "sddp_param_gradient": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),

@@ -431,16 +431,18 @@ int plan_source(sddp_handle* h, const char* fn, int first, int count, const doub
     return SDDP_OK;
 }
 // ... and their host-array twins: range_device(d_out) on the handle's own plan into a scratch buffer of `words` doubles per instance,
-// made and freed by the call, and that buffer into out
+// made and freed by the call, and that buffer into out.  extra != NULL: the scratch buffer holds `extra_words` more doubles per
+// instance behind the records (range_device finds them at d_out + count * words), which go into extra
 template <class F>
-int inspect_to_host(sddp_handle* h, int first, int count, int words, double* out, F range_device) {
+int inspect_to_host(sddp_handle* h, int first, int count, int words, double* out, F range_device, size_t extra_words = 0, double* extra = nullptr) {
     if (!h) return SDDP_ERR_ARG;
     if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    const size_t bytes = size_t(count) * words * sizeof(double);
+    const size_t bytes = size_t(count) * words * sizeof(double), more = extra ? size_t(count) * extra_words * sizeof(double) : 0;
     double* d_out = nullptr;
-    HIP_TRY(h, hipMalloc(&d_out, bytes));
+    HIP_TRY(h, hipMalloc(&d_out, bytes + more));
     int rc = range_device(d_out);
+    if (rc == SDDP_OK && more) rc = download(h, extra, d_out + size_t(count) * words, more);
     if (rc == SDDP_OK) rc = download(h, out, d_out, bytes);
     (void)hipFree(d_out);
     return rc;
@@ -1425,6 +1427,40 @@ int sddp_cost_terms(sddp_handle* h, int first, int count, double* out) {
     return inspect_to_host(h, first, count, kCostTermsWords, out, [&](double* d_out) {
         return sddp_cost_terms_range_device(h, first, count, nullptr, nullptr, d_out, nullptr);
     });
+}
+
+int sddp_param_gradient_words(sddp_handle* h, int* words, int* np) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!words || !np) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    *words = kParamGradientWords;
+    *np = h->d.np;
+    return SDDP_OK;
+}
+
+int sddp_param_gradient_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out, double* d_grad,
+                                     double* d_lambda) {
+    PlanSource src;
+    if (const int rc = plan_source(h, "sddp_param_gradient_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
+    if (!h->ops->inspect.param_gradient)
+        return fail(h, SDDP_ERR_ARG, "sddp_param_gradient_range_device: a user build's non-linear rows have no derivative in the parameters");
+    if (!h->pgrad.on()) {      // the costates and the stationarity record of a call, for the kernel behind them
+        GroupBuf g[] = {{h->n_x() * sizeof(double)}, {size_t(h->B) * kStationarityWords * sizeof(double)}};
+        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_param_gradient_range_device: out of device memory");
+        h->pgrad = {g[0], g[1]};
+    }
+    // the costates are the stationarity certificate's, by its own launch: lambda has the bits it writes to d_lambda
+    if (const int rc = h->ops->inspect.stationarity(h, first, count, src, h->pgrad.stat, h->pgrad.lam, nullptr); rc != SDDP_OK) return rc;
+    if (d_lambda)
+        HIP_TRY(h, hipMemcpyAsync(d_lambda, h->pgrad.lam, size_t(count) * (h->N + 1) * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return h->ops->inspect.param_gradient(h, first, count, src, h->pgrad.lam, h->pgrad.stat, d_out, d_grad);
+}
+
+int sddp_param_gradient(sddp_handle* h, int first, int count, double* out, double* grad) {
+    const size_t row = h ? size_t(h->N + 1) * h->d.np : 0;      // the gradient of an instance, behind the records in the scratch buffer
+    return inspect_to_host(h, first, count, kParamGradientWords, out, [&](double* d_out) {
+        return sddp_param_gradient_range_device(h, first, count, nullptr, nullptr, d_out,
+                                                grad ? d_out + size_t(count) * kParamGradientWords : nullptr, nullptr);
+    }, row, grad);
 }
 
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {

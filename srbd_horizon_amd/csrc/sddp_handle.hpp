@@ -101,6 +101,9 @@ struct ModelOps {
         int (*audit)(sddp_handle*, int, int, int, int, PlanSource, double, double*) = nullptr;
         int (*stationarity)(sddp_handle*, int, int, PlanSource, double*, double*, double*) = nullptr;
         int (*cost_terms)(sddp_handle*, int, int, PlanSource, const double*, double*, double*) = nullptr;
+        // parameter sensitivities: the costates and the record the stationarity launch stored for the range, out, the gradient or
+        // null; null: a user build (its rows have no d/dp code)
+        int (*param_gradient)(sddp_handle*, int, int, PlanSource, const double*, const double*, double*, double*) = nullptr;
         int (*model_step)(sddp_handle*, int, const double*, const double*, const double*, double*) = nullptr;
     } inspect;
 };
@@ -202,6 +205,13 @@ struct sddp_handle {
         sddp::DevConsts* ctab = nullptr;   // [B]
         bool on() const { return ctab != nullptr; }
     } table;
+    // parameter sensitivities (sddp_param_gradient_range_device): where the stationarity launch of a call leaves the costates and its
+    // record for the kernel behind it; made by the first call, for the handle's life.  Block i belongs to instance first + i of the call
+    struct ParamGradient {
+        double* lam = nullptr;          // [B][N + 1][nx]
+        double* stat = nullptr;         // [B][kStationarityWords]
+        bool on() const { return lam != nullptr; }
+    } pgrad;
     // host staging: each buffer is made by the first call that uses it and kept for the handle's life, so there is nothing to switch
     // and no on(); a pinned buffer that could not be had stays null and its caller takes the pageable path (sddp_api.hip staging)
     struct Staging {

@@ -1,12 +1,13 @@
 // sddp_inspect.hpp -- the kernels that only read: one model step, the policy rolled out and the plan inspectors (audit, stationarity
-// certificate, cost breakdown).  They run the same device model code as the solve (M::step, M::derivs, M::F_entry, ...) on one
-// wavefront per instance, and store to nothing but the caller's outputs.  (The knot evaluation of the parity tests reads only as
+// certificate, cost breakdown, parameter sensitivities).  They run the same device model code as the solve (M::step, M::derivs,
+// M::F_entry, ...; the sensitivities M::param_grad, which the solve has no use for) on one wavefront per instance, and store to
+// nothing but the caller's outputs.  (The knot evaluation of the parity tests reads only as
 // well and stays in sddp_kernels.hpp, which says why.)
 //
 // Instantiated by the inspect unit of a model build alone (sddp_launch_inspect.hpp, sddp_inst.hip with -DSDDP_INST_INSPECT): a device
 // module of their own, so that nothing written here can reach the code generation of the solve kernels (sddp_kernels.hpp,
 // sddp_kernels_mw.hpp), which no longer share a module with them.  The record sizes that sddp_api.hip reports (kStationarityWords,
-// kCostTermsWords, kCostTermsFamilies) are in sddp_kernels.hpp, where it finds them without this file.
+// kCostTermsWords, kCostTermsFamilies, kParamGradientWords) are in sddp_kernels.hpp, where it finds them without this file.
 #pragma once
 #include "sddp_kernels.hpp"
 
@@ -444,6 +445,63 @@ __global__ __launch_bounds__(kWave) void cost_terms_kernel(ConstsArg<Tab...> con
         }
         out[size_t(i) * kCostTermsWords + 14] = nan ? -1.0 : double(best);
         out[size_t(i) * kCostTermsWords + 15] = double(N);
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------------------
+// Parameter sensitivities (sddp_param_gradient_range_device): the gradient of the Lagrangian of a whole-horizon trajectory in the
+// per-knot parameters,
+//   G_k[j] = dL_k/dp_k[j] + sum_i lambda_{k+1}[i] df_k[i]/dp_k[j]  (k < N),    G_N[j] = dL_N/dp_N[j],
+// through M::param_grad, and kParamGradientWords doubles per instance (include/sddp.h has the table).  The costates are not formed
+// here: lam [count][N + 1][NX] and stat [count][kStationarityWords] are what stationarity_kernel stored for the same range just
+// before on the same stream (sddp_api.hip), block i for instance first + i, and words 4 - 6 of the record are words 4, 0, 6 of stat as
+// they are.  x [..][N + 1][NX], u [..][N][NU]; instance b = first + i reads block xoff + i of them and row b of P.
+// With lambda given the nodes are independent.  One wavefront per instance, lane l on the nodes k = l, l + 64, ..., as
+// plan_audit_kernel does it, rather than a flat grid over count (N + 1) nodes: the record is a maximum over the nodes of one instance
+// with its place, which one butterfly of shuffles merges inside the wave; a flat grid would split an instance across wavefronts and
+// need a second pass or atomics for it.  A lane keeps G_k and its magnitudes (2 NP doubles: 70 on srbd61_x) and what M::param_grad
+// needs of the knot: on the models with contact states (srbd37, srbd61, lip30) no parameter enters f, so that is a handful of state
+// entries and no model core; on srbd13 the core of one knot (the solve's rollout keeps the same).  x and u are read in place, not
+// copied to per-lane arrays: no LDS, no scratch (profiles/param_gradient has the compiler's figures per build).
+// Read-only but for out / grad: plain vector stores to the caller's outputs alone, no atomics, no work buffer.  The maxima are the
+// audit's: NaN propagates, a NaN maximum has no place, the smaller key = node * NP + column wins a tie.
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void param_gradient_kernel(ConstsArg<Tab...> consts, int N, int first, int count,
+                                                                const double* __restrict__ x, const double* __restrict__ u, int xoff,
+                                                                const double* __restrict__ P, const double* __restrict__ lam,
+                                                                const double* __restrict__ stat, double* __restrict__ out,
+                                                                double* __restrict__ grad) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
+    const double* ub = u + size_t(xoff + i) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    const double* lb = lam + size_t(i) * (N + 1) * NX;
+    double* go = grad ? grad + size_t(i) * (N + 1) * NP : nullptr;
+    AuditMax top{0.0, kAuditNoKey};
+    double scale = 0.0;
+    for (int k = lane; k <= N; k += kWave) {
+        double g[NP], m[NP];
+        // (k == N: no input and no next costate; param_grad reads neither there, the pointers stay inside the buffers)
+        M::param_grad(c, xb + size_t(k) * NX, ub + size_t(k < N ? k : 0) * NU, Pb + size_t(k) * NP, k, N,
+                      lb + size_t(k < N ? k + 1 : k) * NX, g, m);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            if (go) go[size_t(k) * NP + j] = g[j];
+            audit_take(top, fabs(g[j]), k * NP + j);
+            scale = nan_max(scale, m[j]);
+        }
+    }
+    audit_merge(top);
+    scale = audit_merge(scale);
+    if (lane == 0) {
+        const double* s = stat + size_t(i) * kStationarityWords;
+        double* r = out + size_t(i) * kParamGradientWords;
+        r[0] = top.v;  r[1] = audit_index(top, NP, false);  r[2] = audit_index(top, NP, true);
+        r[3] = scale;  r[4] = s[4];  r[5] = s[0];  r[6] = s[6];  r[7] = double(N);
     }
 }
 

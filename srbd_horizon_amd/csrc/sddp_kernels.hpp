@@ -31,6 +31,7 @@ constexpr int kScal = 24;  // doubles per instance in the scratch `scal` record 
 // the record sizes of the kernels of sddp_inspect.hpp that sddp_api.hip reports, here so that it needs none of that file:
 constexpr int kStationarityWords = 8;      // doubles per record of the stationarity certificate (sddp.h sddp_stationarity_words)
 constexpr int kCostTermsWords = 16, kCostTermsFamilies = 13;   // ... of the cost breakdown, and its families (sddp.h sddp_cost_terms_words)
+constexpr int kParamGradientWords = 8;     // ... of the parameter sensitivities (sddp.h sddp_param_gradient_words)
 
 // Diagnostic build only (-DSDDP_STAMPS): per-phase shader-cycle sums, written to `scal`; never in the shipped library.
 #ifdef SDDP_STAMPS

@@ -38,6 +38,13 @@ int launch_cost_terms(sddp_handle* h, int first, int count, PlanSource s, const 
                                          " bytes of LDS, more than the 65536 one workgroup has here");
     return launch_waves<M>(h, SDDP_PICK(cost_terms_kernel), count, lds, xr_zero, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dout, dnodes);
 }
+// the parameter sensitivities: nothing but registers.  dlam / dstat: what launch_stationarity stored for the same range just before
+// (sddp_api.hip).  Not on a user build, whose rows have no d/dp code (SrbdModel::param_grad)
+template <class M>
+int launch_param_gradient(sddp_handle* h, int first, int count, PlanSource s, const double* dlam, const double* dstat, double* dout, double* dgrad) {
+    return launch_waves<M>(h, SDDP_PICK(param_gradient_kernel), count, 0, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dlam, dstat, dout,
+                           dgrad);
+}
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
@@ -51,6 +58,7 @@ ModelOps::InspectOps inspect_ops() {
     o.audit = launch_audit<M>;
     o.stationarity = launch_stationarity<M>;
     o.cost_terms = launch_cost_terms<M>;
+    if constexpr (!M::HAS_UR) o.param_gradient = launch_param_gradient<M>;
     o.model_step = launch_model_step<M>;
     return o;
 }

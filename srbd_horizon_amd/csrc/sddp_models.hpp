@@ -812,6 +812,114 @@ struct SrbdModel {
         for (int i = 0; i < NZ; ++i) rec[REC_G + i] = g[i];
     }
 
+    // Parameter sensitivities of knot k (param_gradient_kernel; sddp.h sddp_param_gradient_range_device): for every parameter column j
+    //   out[j] = dL_k/dp[j] + sum_i df[i]/dp[j] lam_next[i]   (k < N; lam_next is not read at k == N, where out[j] = dL_N/dp[j]),
+    // entry j starting at dL/dp[j] and adding fma(df[i]/dp[j], lam_next[i], .) for i = 0 .. NX - 1 in this order, the structural zeros
+    // skipped.  The node classes are derivs': state residuals on k >= 1, input residuals and penalties on k < N.  mag (may be null):
+    // |dL/dp[j]| + sum_i |df[i]/dp[j]| |lam_next[i]|, the size of what cancels in out[j].
+    // Where a parameter enters f: only on srbd13 (!CS), whose contact points p[11 .. 16] are the lever arms of wdot, so rows XW .. XW + 2
+    // of f read them; on srbd37 / srbd61 the contact points are states and step() reads p for the cost alone.
+    // The user rows of an _x build read their reference columns p[NPB + j] only.  A user build's rows (HAS_UR) may read any parameter
+    // and userterms.py writes no d/dp code: no such build instantiates this (sddp_launch_inspect.hpp inspect_ops).
+    __device__ __forceinline__ static void param_grad(const DevConsts& c, const double* x, const double* u, const double* p, int k, int N,
+                                                      const double* lam_next, double* out, double* mag = nullptr) {
+        static_assert(!HAS_UR, "a user build has no d/dp code");
+        constexpr int PO = CS ? 7 + 2 * NC : 7;            // p_oref
+        double g[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) g[j] = 0.0;
+        if (k >= 1) {  // state residuals: rdot_ref, w_ref, orientation_tracking_gain, oref
+            const double* o = x + XO;
+            const double qx = p_oref(p, 0), qy = p_oref(p, 1), qz = p_oref(p, 2), qw = p_oref(p, 3);
+            const double e0 = o[3] * qx + qw * o[0] + (o[1] * qz - o[2] * qy);
+            const double e1 = o[3] * qy + qw * o[1] + (o[2] * qx - o[0] * qz);
+            const double e2 = o[3] * qz + qw * o[2] + (o[0] * qy - o[1] * qx);
+            const double e3 = o[3] * qw - (o[0] * qx + o[1] * qy + o[2] * qz) - 1.0;
+            const double otg = p_otg(p);
+            const double s2 = 2 * otg * otg;
+            g[6] += 2 * otg * (e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3);
+            g[PO + 0] += s2 * (e0 * o[3] + e1 * o[2] - e2 * o[1] - e3 * o[0]);
+            g[PO + 1] += s2 * (-e0 * o[2] + e1 * o[3] + e2 * o[0] - e3 * o[1]);
+            g[PO + 2] += s2 * (e0 * o[1] - e1 * o[0] + e2 * o[3] - e3 * o[2]);
+            g[PO + 3] += s2 * (e0 * o[0] + e1 * o[1] + e2 * o[2] + e3 * o[3]);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                g[a] -= 2 * c.w_rd * (x[XRD + a] - p_rdref(p, a));
+                g[3 + a] -= 2 * c.w_w * (x[XW + a] - p_wref(p, a));
+            }
+        }
+        double T[NC][9];                                   // !CS, k < N: d wdot / d c_i
+        double wd[3] = {0.0, 0.0, 0.0};
+        if (k < N) {  // input residuals and penalties: the switches, c_ref; srbd13: the contact points through wdot
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const int psw = CS ? 8 + 2 * i : 17 + i;
+                const double* f = u + uf(i);
+                const double sw = p_sw(p, i);
+                g[psw] -= 2 * c.w_sw * (1.0 - sw) * (f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+                if (CS) {
+                    const double vx = x[XCD + 3 * i], vy = x[XCD + 3 * i + 1];
+                    g[psw] += 2 * c.w_pen * sw * (vx * vx + vy * vy);
+                    g[7 + 2 * i] -= 2 * c.w_pen * (x[XC + 3 * i + 2] - p_cref(p, i));
+                }
+            }
+            // (BAR builds: the friction-cone barrier reads the forces and the bound barrier z and the bounds; neither reads a parameter.
+            //  SO2 builds: second_order changes the sweep, not L or f.)
+            if (!CS) {
+                double cp[NC][3], f[NC][3];
+                load_contacts(x, u, p, cp, f);
+                Core q;
+                core(c, x + XR, x + XO, x + XW, cp, f, q);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) wd[a] = q.wdot[a];
+                const double s = 2 * c.gq;
+#pragma unroll
+                for (int i = 0; i < NC; ++i) {
+                    const double mf[3] = {-c.lever * f[i][0], -c.lever * f[i][1], -c.lever * f[i][2]};
+                    mat_skew3(q.Mi, mf, T[i]);             // d wdot / d c_i = Mi * (-s skew(f_i)), derivs' column AC of the CS builds
+#pragma unroll
+                    for (int b = 0; b < 3; ++b)
+                        g[11 + 3 * i + b] += s * (T[i][b] * wd[0] + T[i][3 + b] * wd[1] + T[i][6 + b] * wd[2]);
+                }
+            }
+        }
+        // user rows of an _x build: e_j = a_j . z - (p[NPB + j] + const_j), cost w_j e_j^2 where the row's kind is active (xr_eval)
+        if constexpr (NXR > 0) {
+#pragma unroll
+            for (int j = 0; j < kXrRows; ++j) {
+                if (j < c.xr_n) {
+                    const double* a = c.xr + j * kXrStride;
+                    const double w = (k >= 1 ? c.xr[kXrWS + j] : 0.0) + (k < N ? c.xr[kXrWG + j] : 0.0);
+                    double e = -p[NPB + j] - c.xr[kXrC + j];
+                    for (int i = 0; i < NX; ++i) e = fma(a[i], x[i], e);
+                    if (k < N)
+                        for (int i = 0; i < NU; ++i) e = fma(a[NX + i], u[i], e);
+                    g[NPB + j] -= 2.0 * w * e;
+                }
+            }
+        }
+        double m[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) m[j] = fabs(g[j]);
+        if (!CS && k < N) {  // df[XW + a]/dc_i[b] = dt d wdot[a]/d c_i[b]: the only rows of f that read a parameter
+#pragma unroll
+            for (int i = 0; i < NC; ++i)
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        const double d = c.dt * T[i][3 * a + b], l = lam_next[XW + a];
+                        g[11 + 3 * i + b] = fma(d, l, g[11 + 3 * i + b]);
+                        m[11 + 3 * i + b] = fma(fabs(d), fabs(l), m[11 + 3 * i + b]);
+                    }
+        }
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            out[j] = g[j];
+            if (mag) mag[j] = m[j];
+        }
+    }
+
     // Full second-order builds: what the sweep needs to contract the second derivatives of wdot = I_w(o)^-1 n(z),
     // n = sum s (c_i - r) x f_i - w x I_w(o) w, with a multiplier it only knows then (add_second_order).  Differentiating
     // I_w wdot = n twice (oracle/models.py srbd_wdot_hess):
@@ -1566,6 +1674,47 @@ struct LipModel {
         if (NXR) (void)xr_eval<NX, NU>(c, x, u, k < N, p + NPB, k >= 1, k < N, g);     // user rows: their gradient
 #pragma unroll
         for (int i = 0; i < NZ; ++i) rec[REC_G + i] = g[i];
+    }
+
+    // Parameter sensitivities of knot k (see SrbdModel::param_grad).  The dynamics are linear in (x, u) and read no parameter: out is
+    // dL_k/dp alone and lam_next is not read.  rdot_ref enters the state residuals (k >= 1), c_ref and the switches the penalties
+    // (k < N), the user rows of the _x build their reference columns.
+    __device__ __forceinline__ static void param_grad(const DevConsts& c, const double* x, const double* u, const double* p, int k, int N,
+                                                      const double*, double* out, double* mag = nullptr) {
+        double g[NP];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) g[j] = 0.0;
+        if (k >= 1) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) g[a] -= 2 * c.w_rd * (x[XRD + a] - p[a]);
+        }
+        if (k < N) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const double sw = p_sw(p, i), vx = x[XCD + 3 * i], vy = x[XCD + 3 * i + 1];
+                g[3 + 2 * i] -= 2 * c.w_pen * (x[XC + 3 * i + 2] - p_cref(p, i));
+                g[4 + 2 * i] += 2 * c.w_pen * sw * (vx * vx + vy * vy);
+            }
+        }
+        if constexpr (NXR > 0) {
+#pragma unroll
+            for (int j = 0; j < kXrRows; ++j) {
+                if (j < c.xr_n) {
+                    const double* a = c.xr + j * kXrStride;
+                    const double w = (k >= 1 ? c.xr[kXrWS + j] : 0.0) + (k < N ? c.xr[kXrWG + j] : 0.0);
+                    double e = -p[NPB + j] - c.xr[kXrC + j];
+                    for (int i = 0; i < NX; ++i) e = fma(a[i], x[i], e);
+                    if (k < N)
+                        for (int i = 0; i < NU; ++i) e = fma(a[NX + i], u[i], e);
+                    g[NPB + j] -= 2.0 * w * e;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            out[j] = g[j];
+            if (mag) mag[j] = fabs(g[j]);
+        }
     }
 
     enum { V_R = 0, V_C, V_RD, V_CD, V_Z, V_CDD };

@@ -234,6 +234,40 @@ class DDPSolver:
         self.policy_info = dict(mu_used=info[0, 0], theta_used=info[0, 1], expected=info[0, 2], ok=bool(info[0, 3]))
         return [K[0, k] for k in range(M)]
 
+    def parameter_gradient(self):
+        """The gradient of the last solve's cost in the problem's parameters (sddp_param_gradient_range_device): a dict
+        from every Parameter's name -- rdot_ref, w_ref, orientation_tracking_gain, oref, c_ref<i>, cdot_switch<i>, on srbd13 c<i>, and
+        the references of declared LinearTerm residuals -- to an array [dim, nodes] in the layout of Parameter.getValues(), entry
+        (r, k) the derivative in row r of the parameter at node k; and "x0" -> lambda_0 [nx], the gradient in the initial state.  It is
+        the gradient of the optimal cost where the solve converged with closed gaps; `parameter_gradient_record` keeps the record
+        (_lib.PARAM_GRADIENT_FIELDS), whose words "stationarity" and "defect" say how far from that the plan is.  Waits for the stream."""
+        if self.var_solution is None:
+            raise RuntimeError("parameter_gradient(): no solve has run")
+        if self._user is not None:
+            raise NotImplementedError("non-linear residuals (problem.NonlinearTerm) have no derivative code in the parameters")
+        from . import _lib
+        eng = self.ddp_solver
+        grad, rec, lam = eng.param_gradient(0, 1, want_lambda=True)
+        eng.synchronize()
+        G, rec, lam = (np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=float) for t in (grad, rec, lam))
+        self.parameter_gradient_record = dict(zip(_lib.PARAM_GRADIENT_FIELDS, rec[0]))
+        return self._parameter_gradient_dict(G[0], lam[0, 0])
+
+    def _parameter_gradient_dict(self, G, lam0):
+        """G [nodes, np of the handle] -> the dictionary of parameter_gradient: the columns in the order of _parameter_matrix()"""
+        out, col = {}, 0
+        for name, p in self.param_var.items():
+            if col < self._np_model:                                        # the model's own parameters, in creation order
+                out[name] = np.ascontiguousarray(G[:, col:col + p.getDim()].T)
+                col += p.getDim()
+            else:                                                           # a reference of user rows: the rows that read it
+                out[name] = np.zeros((p.getDim(), G.shape[0]))
+        for j, ref in enumerate(self._extra_refs):
+            if ref is not None:
+                out[ref[0].getName()][ref[1], :] = G[:, self._np_model + j]
+        out["x0"] = np.array(lam0, dtype=float)
+        return out
+
     def is_equality_constraint(self, constr):                               # ddp.py:108-111
         upper = np.array(constr.getUpperBounds())
         lower = np.array(constr.getLowerBounds())

@@ -212,7 +212,7 @@ class DdpEngine:
         return self._to_numpy(n, [(max(s, 0) + 1, self.nx), (max(s, 0), self.nu), ()],
                               lambda x, u, cost: self.policy_rollout_device(xm, x, u, cost, first, n, start, s))
 
-    # ---- the plan inspectors: audit, stationarity certificate, cost breakdown ("Plan inspectors") ----------------
+    # ---- the plan inspectors: audit, stationarity certificate, cost breakdown, parameter sensitivities ("Plan inspectors") ----------------
     # Each reads the instances [first, first + count) of a handle that has solved: the handle's own plan (x, u None) or the caller's
     # device tensors, whose block i belongs to instance first + i.  Every build has them; the *_device forms are asynchronous,
     # behind the solve, and store to nothing but their outputs.
@@ -297,6 +297,32 @@ class DdpEngine:
                                                     lambda out, nd: self.cost_terms_device(out, first, n, nodes=nd))
         return {"total": rec[:, 0].copy(), **{name: rec[:, 1 + f].copy() for f, name in enumerate(names)},
                 "largest": np.array([names[int(i)] if i >= 0 else "" for i in rec[:, 14]], dtype=object), "record": rec, **per_node}
+
+    def param_gradient_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, grad=None, lam=None):
+        """The parameter-sensitivity records (_lib.PARAM_GRADIENT_FIELDS) of the instances [first, first + count) into the device
+        tensor out [count, 8].  x, u None: the handle's own plan; else device tensors x [count, N + 1, nx], u [count, N, nu], a caller's
+        whole-horizon trajectory.  grad [count, N + 1, np]: a device tensor for every G_k = dL_k/dp_k + (df_k/dp_k)^T lambda_{k+1}, np
+        the handle's parameter width; lam [count, N + 1, nx]: one for the costates, the bits of stationarity_device's; or None."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_param_gradient_range_device(self.h, int(first), n, *self._plan(n, x, u),
+                                                            self._dev(out, (n, len(_lib.PARAM_GRADIENT_FIELDS))),
+                                                            self._dev_or_null(grad, (n, self.N + 1, self.np_)),
+                                                            self._dev_or_null(lam, (n, self.N + 1, self.nx))))
+        return out
+
+    def param_gradient(self, first: int = 0, count: int | None = None, x=None, u=None, want_lambda: bool = False):
+        """The gradient of each plan's cost in its per-knot parameters, on the device: x, u None (the handle's own plan) or device
+        tensors as for param_gradient_device -> (grad [count, N + 1, np], record [count, 8]), with want_lambda also lambda
+        [count, N + 1, nx] whose row 0 is the gradient in x_0; fresh float64 CUDA tensors.  Asynchronous, behind the solve: synchronize()
+        (or a copy to the host) before reading.  At a converged plan with closed gaps grad is the gradient of the optimal cost in P;
+        record words "stationarity" and "defect" say how far from that the plan is."""
+        import torch
+        n = self._count(first, count)
+        mk = lambda *shape: torch.empty((max(n, 0), *shape), dtype=torch.float64, device="cuda")      # noqa: E731
+        rec, grad = mk(len(_lib.PARAM_GRADIENT_FIELDS)), mk(self.N + 1, self.np_)
+        lam = mk(self.N + 1, self.nx) if want_lambda else None
+        self.param_gradient_device(rec, first, n, x=x, u=u, grad=grad, lam=lam)
+        return (grad, rec, lam) if want_lambda else (grad, rec)
 
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)

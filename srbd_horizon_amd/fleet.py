@@ -153,6 +153,13 @@ class FleetQueue:
         fleet's cost is made of before it turns one."""
         return self._inspect(self.eng.cost_terms_device, out, nodes=nodes)
 
+    def param_gradient(self, out, grad=None):
+        """The parameter-sensitivity records (DdpEngine.param_gradient_device) of the instances the last flush / solve_sliced /
+        solve_within solved, into the first n rows of the device tensor out [>= n, 8] (grad [>= n, N + 1, np]: likewise, or None);
+        launched behind whatever that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet
+        server which way to move a reference or a foothold of each robot before the next tick."""
+        return self._inspect(self.eng.param_gradient_device, out, grad=grad)
+
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
         `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the

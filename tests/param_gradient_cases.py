@@ -1,0 +1,281 @@
+"""What the parameter-sensitivity tests share (tests/test_param_gradient_cpu.py, tests/test_gpu_param_gradient.py): the result of
+sddp_param_gradient_range_device (include/sddp.h) stated once in numpy over SYMBOLIC derivatives in the parameters, the comparison of a
+device result with it, and the cases.
+
+THE GRADIENT of one instance, from a trajectory x [N + 1, nx], u [N, nu], the parameters P [N + 1, np] and costates lam [N + 1, nx]:
+    G_k[j] = dL_k/dp_k[j] + sum_i lam_{k+1}[i] df_k[i]/dp_k[j]  (k < N),      G_N[j] = dL_N/dp_N[j],
+    dL/dp = 2 r^T dr/dp over the residual rows of the node class (input residuals on 0 .. N - 1, state residuals on 1 .. N),
+entry j starting at dL/dp[j] and adding df[i]/dp[j] lam_{k+1}[i] for i = 0 .. nx - 1 in this order.
+THE RECORD (8 doubles, _lib.PARAM_GRADIENT_FIELDS): 0 max |G_k[j]|, 1, 2 its node and column (first in node-major order; -1 where word 0
+is NaN), 3 max of |dL/dp[j]| + sum_i |df[i]/dp[j]| |lam_{k+1}[i]|, 4 - 6 words 4, 0, 6 of the stationarity record, 7 N.
+
+Where the symbols come from.  tests/sym_models.py symbolic(...)[0]["_sym"] holds f and the residual rows as sympy expressions, and
+jacobians() differentiates them in p.  symbolic() also differentiates and compiles everything in z, which takes 7 - 10 s per model at
+inertia_mode 0, about 4 minutes per model at inertia_mode 1, and it has no argument for the gains; so the expressions of a constant
+set are assembled here by assemble(), from the same building blocks of tests/sym_models.py (_srbd, _state_res, _force_res, _penalties,
+_relpos) in the order _build puts them together, and tests/test_param_gradient_cpu.py checks that assembly against symbolic()'s own
+"_sym" on the default constants of every model.
+"""
+import functools
+
+import numpy as np
+import sympy as sp
+
+from oracle import models as omodels
+from srbd_horizon_amd import _lib
+from tests import sym_models as sm
+
+W = len(_lib.PARAM_GRADIENT_FIELDS)
+GRAD, NODE, COLUMN, SCALE, LAM0, STAT, DEFECT, NODES = range(8)
+MODELS = ("srbd13", "srbd37", "lip30", "srbd61")
+DIMS = {"srbd13": (13, 6, 19), "srbd37": (37, 24, 19), "lip30": (30, 15, 11), "srbd61": (61, 48, 27)}
+RTOL = 1e-11      # tests/test_gpu_parity.py test_eval_knots_matches_oracle: the relative tolerance of g and F, here of word 3
+
+# the constant sets of the tests, by key: the defaults, and one set away from them (inertia_mode 1, lever_sign -1, no relative-velocity
+# constraints, other gains).  A key stands for keyword arguments of oracle.models.RobotConsts AND of the engine's consts.
+OFF = dict(inertia_mode=1, lever_sign=-1.0, relative_velocity_constraints=0, r_tracking_gain=700.0, rdot_tracking_gain=3.0e3,
+           w_tracking_gain=2.0e3, rel_pos_gain=4.0e3, force_switch_weight=30.0, min_qddot_gain=2.5, min_f_gain=0.05,
+           zmp_tracking_gain=600.0)
+CONSTS = {"default": {}, "off": OFF}
+
+
+def register(key, consts):
+    """a further constant set under `key` (a batch's robot, the rows of an _x build, a robot of a heterogeneous fleet): keyword
+    arguments, or a RobotConsts -> key"""
+    CONSTS[key] = consts if isinstance(consts, omodels.RobotConsts) else dict(consts)
+    return key
+
+
+def robot(name, key):
+    if isinstance(CONSTS[key], omodels.RobotConsts):
+        return CONSTS[key]
+    kw = dict(CONSTS[key])
+    if kw.get("extra_rows") is not None:
+        kw["extra_rows"] = tuple(kw["extra_rows"])
+    return omodels.RobotConsts(**kw)
+
+
+def assemble(name, cst):
+    """(x, u, p, f, ires, sres): the state, input and parameter symbols, the model step and the residual rows of the input and of the
+    state class, as tests/sym_models.py _build assembles them"""
+    nx, nu, npar = DIMS[name]
+    rows = list(getattr(cst, "extra_rows", None) or ())
+    npb = npar
+    if rows:
+        npar += 8
+    x, u, p = (sp.Matrix(sp.symbols(f"{s}0:{n}")) for s, n in (("x", nx), ("u", nu), ("p", npar)))
+    rel_vel = bool(getattr(cst, "relative_velocity_constraints", True))
+    if name == "srbd13":
+        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[7:10, 0], x[10:13, 0]
+        fs = [u[0:3, 0], u[3:6, 0]]
+        rddot, wdot, odot = sm._srbd(cst, r, o, w, [p[11:14, 0], p[14:17, 0]], fs)
+        xdot = sp.Matrix([*rd, *odot, *rddot, *wdot])
+        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7:11, 0])
+        ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot]))]
+        for i in range(2):
+            ires += sm._force_res(cst, fs[i], p[17 + i])
+    elif name in ("srbd37", "srbd61"):
+        nc = 4 if name == "srbd37" else 8
+        rd0 = 7 + 3 * nc
+        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[rd0:rd0 + 3, 0], x[rd0 + 3:rd0 + 6, 0]
+        cs = [x[7 + 3 * i:10 + 3 * i, 0] for i in range(nc)]
+        cds = [x[rd0 + 6 + 3 * i:rd0 + 9 + 3 * i, 0] for i in range(nc)]
+        cdd = [u[6 * i:6 * i + 3, 0] for i in range(nc)]
+        fs = [u[6 * i + 3:6 * i + 6, 0] for i in range(nc)]
+        rddot, wdot, odot = sm._srbd(cst, r, o, w, cs, fs)
+        xdot = sp.Matrix([*rd, *odot, *[e for c in cds for e in c], *rddot, *wdot, *[e for c in cdd for e in c]])
+        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7 + 2 * nc:11 + 2 * nc, 0]) + sm._relpos(cst, cs)
+        ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot, *[e for c in cdd for e in c]]))]
+        for i in range(nc):
+            ires += sm._force_res(cst, fs[i], p[8 + 2 * i])
+        ires += sm._penalties(cs, cds, [p[7 + 2 * i] for i in range(nc)], [p[8 + 2 * i] for i in range(nc)], rel_vel)
+    else:
+        r, rd = x[0:3, 0], x[15:18, 0]
+        cs = [x[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
+        cds = [x[18 + 3 * i:21 + 3 * i, 0] for i in range(4)]
+        z = u[0:3, 0]
+        cdd = [u[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
+        rddot = (9.81 / cst.lip_height) * (r - z) - sp.Matrix([0, 0, sm.G])
+        xdot = sp.Matrix([*rd, *cds[0], *cds[1], *cds[2], *cds[3], *rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]])
+        mean_c = (cs[0] + cs[1] + cs[2] + cs[3]) / 4
+        sres = [sp.sqrt(cst.r_tracking_gain) * (r[2] - cst.com[2]), *(sp.sqrt(cst.r_tracking_gain) * (r[0:2, 0] - mean_c[0:2, 0])),
+                *(sp.sqrt(cst.rdot_tracking_gain) * (rd - p[0:3, 0]))] + sm._relpos(cst, cs)
+        ires = [*(sp.sqrt(cst.zmp_tracking_gain) * (z - mean_c)),
+                *(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]]))]
+        ires += sm._penalties(cs, cds, [p[3 + 2 * i] for i in range(4)], [p[4 + 2 * i] for i in range(4)], rel_vel)
+    z_all = [*x, *u]
+    for j, row in enumerate(rows):
+        a = np.asarray(row["a"], dtype=float)
+        e = sp.sqrt(row["w"]) * (sum(float(a[i]) * z_all[i] for i in range(nx + nu) if a[i] != 0.0) - p[npb + j] - float(row.get("const", 0.0)))
+        (sres if row["kind"] == "state" else ires).append(e)
+    return x, u, p, x + cst.dt * xdot, sp.Matrix(ires), sp.Matrix(sres)
+
+
+@functools.lru_cache(maxsize=None)
+def jacobians(name, key="default"):
+    """the compiled residual rows and the SYMBOLIC Jacobians in p of f, ires and sres for the constant set `key`: a dict of functions
+    of (x, u, p): "f" [nx], "ires", "sres", "Fp" [nx, np], "Jip", "Jsp"; and "np", "nx", "nu"; computed once"""
+    x, u, p, f, ires, sres = assemble(name, robot(name, key))
+    args = (list(x), list(u), list(p))
+    lam = lambda e: sp.lambdify(args, e, "numpy", cse=True)      # noqa: E731
+    out = dict(f=lam(f), ires=lam(ires), sres=lam(sres), Fp=lam(f.jacobian(p)), Jip=lam(ires.jacobian(p)), Jsp=lam(sres.jacobian(p)))
+    out.update(np=len(p), nx=len(x), nu=len(u))
+    return out
+
+
+def _arr(v, shape=None):
+    a = np.asarray(v, dtype=float)
+    return a.reshape(-1) if shape is None else np.broadcast_to(a, shape).astype(float)
+
+
+def node_class(k, N):
+    return "N" if k == N else ("0" if k == 0 else "k")
+
+
+def cost(J, key, x, u, p):
+    """L of node class key in {'0', 'k', 'N'}: the squared residual rows (tests/sym_models.py cost_terms)"""
+    u = np.zeros(J["nu"]) if u is None else u
+    r = np.concatenate(([] if key == "N" else [_arr(J["ires"](x, u, p))]) + ([] if key == "0" else [_arr(J["sres"](x, u, p))]))
+    return float(r @ r)
+
+
+def dL_dp(J, key, x, u, p):
+    """dL/dp = 2 r^T dr/dp [np] of node class key, assembled numerically as tests/sym_models.py cost_terms does in z"""
+    u = np.zeros(J["nu"]) if u is None else u
+    g = np.zeros(J["np"])
+    if key != "N":
+        r = _arr(J["ires"](x, u, p))
+        g = g + 2.0 * r @ _arr(J["Jip"](x, u, p), (r.size, J["np"]))
+    if key != "0":
+        r = _arr(J["sres"](x, u, p))
+        g = g + 2.0 * r @ _arr(J["Jsp"](x, u, p), (r.size, J["np"]))
+    return g
+
+
+def node_gradient(J, k, N, x, u, p, lam_next):
+    """(G_k [np], magnitudes [np]) of node k"""
+    g = dL_dp(J, node_class(k, N), x, u, p)
+    m = np.abs(g)
+    if k < N:
+        Fp = _arr(J["Fp"](x, u, p), (J["nx"], J["np"]))
+        for i in range(J["nx"]):
+            g = g + Fp[i] * lam_next[i]
+            m = m + np.abs(Fp[i]) * abs(lam_next[i])
+    return g, m
+
+
+def reference(J, x, u, P, lam):
+    """-> (G [N + 1, np], words 0 .. 3 of the record) of one instance, with the costates lam [N + 1, nx] given"""
+    x, u, P, lam = (np.asarray(a, dtype=float) for a in (x, u, P, lam))
+    N = u.shape[0]
+    G, M = np.zeros((N + 1, J["np"])), np.zeros((N + 1, J["np"]))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(N + 1):
+            G[k], M[k] = node_gradient(J, k, N, x[k], u[k] if k < N else None, P[k], lam[k + 1] if k < N else None)
+    cand = np.abs(G)
+    top = np.max(cand)
+    at = -1 if np.isnan(top) else int(np.argmax(cand.reshape(-1) == top))
+    node, col = (-1, -1) if at < 0 else divmod(at, J["np"])
+    return G, np.array([top, node, col, np.max(M)])
+
+
+def assert_result(rec, G, ref, label=""):
+    """a device record and gradient of one instance against reference(): every entry within RTOL x word 3, words 0 and 3 likewise, the
+    place the reference's unless its two largest candidates lie within the tolerance of each other (then the reported place must hold
+    such a candidate) -> worst error / tolerance"""
+    Gr, rr = ref
+    if np.isnan(rr[GRAD]):
+        assert np.isnan(rec[GRAD]) and rec[NODE] == -1 and rec[COLUMN] == -1, label
+        assert np.array_equal(np.isnan(G), np.isnan(Gr)), label
+        ok = ~np.isnan(Gr)
+        return float(np.max(np.abs(G[ok] - Gr[ok]), initial=0.0) / (RTOL * np.nanmax(np.abs(Gr[ok]), initial=1.0)))
+    tol = RTOL * rr[SCALE]
+    err = float(np.max(np.abs(G - Gr)))
+    assert err <= tol, f"{label}: gradient off by {err:.3e}, tolerance {tol:.3e}"
+    assert abs(rec[GRAD] - rr[GRAD]) <= tol and abs(rec[SCALE] - rr[SCALE]) <= tol, f"{label}: words 0 / 3 {rec[[GRAD, SCALE]]} against {rr[[GRAD, SCALE]]}"
+    assert rec[GRAD].tobytes() == np.max(np.abs(G)).tobytes(), f"{label}: word 0 is not the maximum of the gradient it came with"
+    k, j = int(rec[NODE]), int(rec[COLUMN])
+    assert abs(G[k, j]) == rec[GRAD] and np.argmax(np.abs(G).reshape(-1)) == k * G.shape[1] + j, f"{label}: place {k, j}"
+    if (k, j) != (int(rr[NODE]), int(rr[COLUMN])):
+        assert abs(Gr[k, j]) >= rr[GRAD] - 2 * tol, f"{label}: place {k, j}, the reference's {rr[NODE], rr[COLUMN]}"
+    return err / tol
+
+
+# ---- random plans: a non-converged trajectory with open gaps, random parameters with switches at 0 and at 1 --------------------------------
+def random_plan(name, N, B, seed, consts=None, wide=False):
+    """-> (batch of srbd_horizon_amd.workload on seeds seed .. seed + B - 1, x [B, N + 1, nx], u [B, N, nu], P [B, N + 1, np (+ 8)]): the
+    batch's warm start and parameters pushed by 0.05 N(0, 1) per entry, every contact switch then set to 0 or 1 at random"""
+    from srbd_horizon_amd import workload
+    batch = workload.make_batch(name, N, np.arange(B) + seed)
+    rng = np.random.default_rng(100 + seed)
+    x = batch["xs"] + 0.05 * rng.standard_normal(batch["xs"].shape)
+    u = batch["us"] + 0.05 * rng.standard_normal(batch["us"].shape)
+    P = batch["params"] + 0.05 * rng.standard_normal(batch["params"].shape)
+    nc = {"srbd13": 2, "srbd37": 4, "lip30": 4, "srbd61": 8}[name]
+    cols = [17, 18] if name == "srbd13" else [(4 if name == "lip30" else 8) + 2 * i for i in range(nc)]
+    P[:, :, cols] = rng.integers(0, 2, size=(B, N + 1, len(cols))).astype(float)
+    if wide:
+        P = np.concatenate([P, 0.1 * rng.standard_normal((B, N + 1, 8))], axis=2)
+    return batch, x, u, P
+
+
+# ---- the envelope experiment: G against central differences of the OPTIMAL cost ------------------------------------------------------------
+# srbd13, N = 8, four robots, options tight enough that a solve ends at a stationary point with closed gaps.  dp is a fixed random
+# direction over rdot_ref (columns 0 .. 2) and the footholds (columns 11 .. 16) of every node; J*(p) is the cost the solver converges to
+# from the base optimum as its warm start.  The discrepancy of an instance is
+#     | sum G . dp  -  (J*(p + h dp) - J*(p - h dp)) / 2h |  /  sum |G . dp|    (entry by entry under the sum signs),
+# and the experiment's figure is its maximum over the four.  ENVELOPE_H and ENVELOPE_DISCREPANCY are what envelope_scan() measures on the
+# CPU with the C oracle's solves and the symbolic reference (tests/test_param_gradient_cpu.py asserts them again; they are recorded in
+# profiles/param_gradient/README.md): the h of the scan with the smallest figure, and that figure.  The GPU test uses this h and allows
+# 10 x the figure, because the GPU's end point differs from the oracle's by up to the parity tolerance of converged solves.
+ENVELOPE_MODEL, ENVELOPE_N = "srbd13", 8
+ENVELOPE_SEEDS = (3, 4, 5, 6)
+ENVELOPE_OPTS = dict(max_iters=400, alpha_converge_threshold=1e-12, beta=1e-3, cost_reduction_ths=1e-12, gap_tol=1e-12)
+ENVELOPE_STEPS = (1e-1, 3e-2, 1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 3e-5, 1e-5, 3e-6, 1e-6, 3e-7, 1e-7)
+ENVELOPE_GAP = 1e-10          # "closed gaps": the solver's gap statistic at the end of each of the three solves
+# measured: the figure falls as h^2 from 7.4e-2 at h = 1e-1 to 1.3e-8 at 3e-5 and then stays between 8.0e-9 and 8.5e-9 down to h = 1e-7 (what
+# the base solve's own distance from stationarity leaves); the smallest of the scan is at h = 1e-5
+ENVELOPE_H = 1e-5
+ENVELOPE_DISCREPANCY = 8.03e-9
+
+
+def envelope_problem():
+    """-> (batch, dP [B, N + 1, 19]): the start of the experiment and the direction"""
+    from tests import oracle_refs as refs
+    batch = refs.batch(ENVELOPE_MODEL, ENVELOPE_N, ENVELOPE_SEEDS)
+    rng = np.random.default_rng(2026)
+    dP = np.zeros(batch["params"].shape)
+    cols = [0, 1, 2, 11, 12, 13, 14, 15, 16]
+    dP[:, :, cols] = rng.standard_normal((dP.shape[0], dP.shape[1], len(cols)))
+    return batch, dP
+
+
+def envelope_discrepancy(G, dP, Jp, Jm, h):
+    """the figure of every instance: G [B, N + 1, np], the costs J*(p + h dp), J*(p - h dp) [B] -> [B]"""
+    pred = np.sum(G * dP, axis=(1, 2))
+    return np.abs(pred - (Jp - Jm) / (2.0 * h)) / np.sum(np.abs(G * dP), axis=(1, 2))
+
+
+def envelope_scan(steps=ENVELOPE_STEPS):
+    """the experiment on the CPU -> {h: the figure [B]}; asserts that all three solves of every instance converge with closed gaps"""
+    from oracle import cport
+    from tests import oracle_refs as refs, stationarity_cases as sc
+    batch, dP = envelope_problem()
+    cst = refs.consts(batch)
+
+    def solve(P, xs, us):
+        x, u, st = refs.c_oracle(ENVELOPE_MODEL, batch, ENVELOPE_OPTS, params=P, xs=xs, us=us)
+        assert (cport.stat(st, "converged") == 1).all() and (cport.stat(st, "status") == 0).all(), st
+        assert (cport.stat(st, "gap") <= ENVELOPE_GAP).all(), cport.stat(st, "gap")
+        return x, u, cport.stat(st, "cost").copy()
+
+    x, u, _ = solve(batch["params"], batch["xs"], batch["us"])
+    J = jacobians(ENVELOPE_MODEL, register("srbd13:envelope", batch["consts"]))
+    m = omodels.make_model(ENVELOPE_MODEL, cst)
+    G = np.stack([reference(J, x[b], u[b], batch["params"][b], sc.model_reference(m, x[b], u[b], batch["params"][b])[1])[0]
+                  for b in range(x.shape[0])])
+    out = {}
+    for h in steps:
+        Jp, Jm = (solve(batch["params"] + s * h * dP, x, u)[2] for s in (1.0, -1.0))
+        out[h] = envelope_discrepancy(G, dP, Jp, Jm, h)
+    return out
