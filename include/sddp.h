@@ -403,6 +403,67 @@ int  sddp_param_gradient_range_device(sddp_handle* h, int first, int count, cons
                                       double* d_out /*[count][8]*/, double* d_grad /*[count][N + 1][np] or NULL*/,
                                       double* d_lambda /*[count][N + 1][nx] or NULL*/);
 int  sddp_param_gradient(sddp_handle* h, int first, int count, double* out /*[count][8], host*/, double* grad /*[count][N + 1][np] or NULL, host*/);
+/* ---- constant sensitivities (v9): the gradient of a plan's cost in the robot's constants, computed on the device ---------------------
+ * The parameter sensitivities differentiate in what changes every tick; this call differentiates in the robot itself, sddp_model_consts:
+ * which robot's payload estimate matters, which gain to turn, and the raw material for fitting the model to a measured trajectory.
+ * With the Lagrangian and the costates of the stationarity section, every derivative at the STORED (x_k, u_k, p_k),
+ *       C[c] = sum_{k=0}^{N-1} ( dL_k/dtheta_c + sum_i lambda_{k+1}[i] df_k[i]/dtheta_c ) + dL_N/dtheta_c,
+ * theta the DERIVED constants the kernels read (what sddp_create makes of sddp_model_consts), in this fixed order of 32 columns:
+ *    0 dt         1 inv_ms = force_scaling / m          2 .. 10 Is[0 .. 8] = I / force_scaling (row-major)        11 com_z = com[2]
+ *   12 w_rz      13 w_rxy (both r_tracking_gain)       14 w_rd      15 w_w      16 w_rel
+ *   17 w_f = force_scaling^2 min_f_gain                18 w_sw = force_scaling^2 force_switch_weight
+ *   19 gq = min_qddot_gain        20 w_zmp             21 eta2 = g / lip_height
+ *   22 .. 25 d1x, d1y, d2x, d2y = feet[6] - feet[0], feet[7] - feet[1], feet[9] - feet[3], feet[10] - feet[4]
+ *   26 mu_lin = friction_cone_coefficient / sqrt(2)    27, 28 bar_w, bar_s (friction barrier weight, sharpness)
+ *   29, 30 box_w, box_s (bound barrier weight, sharpness)                   31 reserved, 0
+ * No column: the constraint weights (1e6: fixed numbers, no constants of a robot), inertia_mode, lever_sign,
+ * relative_velocity_constraints (they select code), the bounds lower / upper and the user rows' tables extra_*.
+ * A column whose constant the build's model does not read is an exact 0.0: eta2, w_zmp, w_rxy on the srbd models; inv_ms, Is, w_w, w_f,
+ * w_sw on lip30; w_rel and 22 .. 25 on srbd13; 26 .. 28 without the friction barrier on, 29, 30 without the bound barrier on.
+ * dL/dtheta uses the node classes of sddp_eval_knots (input residuals and penalties on the nodes 0 .. N - 1, state residuals on
+ * 1 .. N, the terminal node without inputs).  df/dtheta: dt enters every Euler row; inv_ms enters rddot; Is enters wdot through the
+ * model core in both inertia_modes; eta2 the LIP rows of rddot.  Analytic device code beside the solve's model code.  Per entry: start at
+ * dL/dtheta_c, then add fma(df[i]/dtheta_c, lambda_{k+1}[i], .) for i = 0 .. nx - 1 in this order, structural zeros skipped.
+ * At a converged plan with closed gaps C is the gradient of the optimal cost in theta (envelope theorem); elsewhere, and at a caller's
+ * measured trajectory, it is the gradient of the Lagrangian, and words 35, 36 say how far from stationary the plan is.
+ * One record is sddp_const_gradient_words() = 40 doubles per instance:
+ *    0 .. 31  C[c]
+ *   32  max over c of |C[c] theta_c|: the first-order cost change per unit RELATIVE change of a constant, comparable across units
+ *   33  its column (the first on ties; -1 where word 32 is NaN: a NaN among the operands propagates)
+ *   34  || lambda_0 ||_inf, the bits of stationarity word 4       35  stationarity word 0       36  stationarity word 6, the defect
+ *   37  N          38, 39  reserved, 0
+ * A column is a SUM over the nodes, so its order is fixed: the addends of node k are row k of a tile in LDS, and column c is added in
+ * node order.  d_nodes [count][N + 1][32] (may be NULL) receives the addends; words 0 .. 31 are the in-order sums of its rows bit for
+ * bit and depend on no lane mapping, range, slot or order.  A horizon whose tile does not fit the 64 KB of LDS a workgroup has
+ * ((N + 2) * 256 bytes: N > 254) is refused with SDDP_ERR_ARG; there is no chunked path.
+ * sddp_const_gradient_range_device: d_x / d_u, the range, asynchrony and what the call may write are those of
+ *   sddp_param_gradient_range_device: it runs the stationarity launch into the same handle-owned buffer first, so d_lambda
+ *   [count][N + 1][nx] (may be NULL) and words 34 - 36 have that call's bits; it writes nothing but d_out, d_nodes and d_lambda and uses
+ *   none of the slots' work buffers; with per-instance constants instance b is differentiated through its own row.  Every build has it
+ *   but a user build (non-linear rows), whose generated rows have no such code: SDDP_ERR_ARG.
+ * sddp_const_gradient: the records of the handle's own plan into a host array; waits for the stream.
+ * sddp_const_gradient_name: the name of a column, a static string ("dt", "inv_ms", "Is[0]", ...; SDDP_ERR_ARG outside 0 .. 31).
+ * sddp_const_gradient_fields: host code, no handle, no device: the chain rule of the table above from words 0 .. 31 of one record
+ *   (`derived`) to the fields of sddp_model_consts a user sets, for the constants `consts` the record was computed with (validated as
+ *   sddp_create validates them; the message through sddp_last_error(NULL)).  fields_out receives *n_fields = 41 doubles:
+ *    0 m   1 .. 9 I[0 .. 8]   10 .. 12 com   13 .. 24 feet[0 .. 11]   25 dt   26 force_scaling   27 r_tracking_gain   28 rdot_tracking_gain
+ *   29 w_tracking_gain   30 rel_pos_gain   31 force_switch_weight   32 min_qddot_gain   33 min_f_gain   34 zmp_tracking_gain   35 lip_height
+ *   36 friction_cone_coefficient   37 friction_barrier_weight   38 friction_barrier_sharpness   39 bound_barrier_weight
+ *   40 bound_barrier_sharpness
+ *   with  m: -force_scaling / m^2 C[inv_ms];  I[i]: C[Is[i]] / force_scaling;  force_scaling: C[inv_ms] / m - sum_i I[i] C[Is[i]] /
+ *   force_scaling^2 + 2 force_scaling (min_f_gain C[w_f] + force_switch_weight C[w_sw]);  r_tracking_gain: C[w_rz] + C[w_rxy];
+ *   min_f_gain, force_switch_weight: force_scaling^2 C[w_f], C[w_sw];  lip_height: -g / lip_height^2 C[eta2];  feet[0], feet[6]: -+C[d1x],
+ *   feet[1], feet[7]: -+C[d1y], feet[3], feet[9]: -+C[d2x], feet[4], feet[10]: -+C[d2y], every other entry of feet and com[0], com[1]: 0;
+ *   friction_cone_coefficient: C[mu_lin] / sqrt(2);  the other gains and the barrier constants one to one.
+ * sddp_const_gradient_field_name: the name of a field of that list ("m", "I[0]", ..., "feet[11]", "dt", ...). */
+int  sddp_const_gradient_words(sddp_handle* h, int* words, int* columns);
+int  sddp_const_gradient_name(int column, const char** name);
+int  sddp_const_gradient_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u,
+                                      double* d_out /*[count][40]*/, double* d_nodes /*[count][N + 1][32] or NULL*/,
+                                      double* d_lambda /*[count][N + 1][nx] or NULL*/);
+int  sddp_const_gradient(sddp_handle* h, int first, int count, double* out /*[count][40], host*/);
+int  sddp_const_gradient_fields(const sddp_model_consts* consts, const double* derived /*[32]*/, double* fields_out /*[41]*/, int* n_fields);
+int  sddp_const_gradient_field_name(int field, const char** name);
 /* ---- resumable solves: continue a solve that was cut at max_iters, bit for bit (opt-in; a handle that never calls
  * sddp_enable_resume launches exactly the kernels it always did) ------------------------------------------------------------------
  * A launch ends with its slowest instance.  With resumable solves a fleet server runs every robot for k iterations (max_iters = k),

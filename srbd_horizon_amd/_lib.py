@@ -73,6 +73,13 @@ COST_TERMS_WORDS, COST_TERMS_COLS = 16, 14
 COST_TERM_NAMES = ()
 # the words of one record of the parameter sensitivities (include/sddp.h sddp_param_gradient_range_device), by name
 PARAM_GRADIENT_FIELDS = ("gradient", "node", "column", "scale", "lambda_0", "stationarity", "defect", "nodes")
+# the constant sensitivities (include/sddp.h sddp_const_gradient_range_device): a record is the CONST_GRADIENT_COLS columns and the words
+# CONST_GRADIENT_TAIL behind them.  The columns' names (the derived constants) and the names of the sddp_model_consts fields
+# sddp_const_gradient_fields maps them to are the library's: load() reads them into CONST_GRADIENT_NAMES / CONST_GRADIENT_FIELD_NAMES
+CONST_GRADIENT_WORDS, CONST_GRADIENT_COLS = 40, 32
+CONST_GRADIENT_TAIL = ("relative", "column", "lambda_0", "stationarity", "defect", "nodes", "reserved0", "reserved1")
+CONST_GRADIENT_NAMES = ()
+CONST_GRADIENT_FIELD_NAMES = ()
 # one sddp_stats record seen as words (the zero-copy device views of engine.fetch_device_views)
 STATS_F64_WORDS, STATS_I32_WORDS = C.sizeof(SddpStats) // 8, C.sizeof(SddpStats) // 4
 STATS_F64_COST = SddpStats.cost.offset // 8
@@ -132,6 +139,12 @@ SYMBOLS = {
     "sddp_param_gradient_words": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
     "sddp_param_gradient_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "sddp_param_gradient": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "sddp_const_gradient_words": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_const_gradient_name": (C.c_int, [C.c_int, _P(C.c_char_p)]),
+    "sddp_const_gradient_range_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "sddp_const_gradient": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_const_gradient_fields": (C.c_int, [_P(SddpModelConsts), _vp, _vp, _P(C.c_int)]),
+    "sddp_const_gradient_field_name": (C.c_int, [C.c_int, _P(C.c_char_p)]),
     "sddp_enable_resume": (C.c_int, [_vp, C.c_int]),
     "sddp_continue_range_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "sddp_continue_device": (C.c_int, [_vp, _vp]),
@@ -367,6 +380,12 @@ def load():
     while lib.sddp_cost_terms_name(len(names), C.byref(name)) == 0:
         names.append(name.value.decode())
     COST_TERM_NAMES = tuple(names)
+    global CONST_GRADIENT_NAMES, CONST_GRADIENT_FIELD_NAMES
+    for fn, target in ((lib.sddp_const_gradient_name, "CONST_GRADIENT_NAMES"), (lib.sddp_const_gradient_field_name, "CONST_GRADIENT_FIELD_NAMES")):
+        names = []
+        while fn(len(names), C.byref(name)) == 0:
+            names.append(name.value.decode())
+        globals()[target] = tuple(names)
     _lib = lib
     return lib
 

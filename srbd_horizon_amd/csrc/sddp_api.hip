@@ -1463,6 +1463,106 @@ int sddp_param_gradient(sddp_handle* h, int first, int count, double* out, doubl
     }, row, grad);
 }
 
+// the columns of the constant sensitivities (sddp_models.hpp ConstCol) and the fields of sddp_model_consts their chain rule reaches
+static const char* const kConstGradientNames[kConstGradientCols] = {
+    "dt", "inv_ms", "Is[0]", "Is[1]", "Is[2]", "Is[3]", "Is[4]", "Is[5]", "Is[6]", "Is[7]", "Is[8]", "com_z", "w_rz", "w_rxy", "w_rd", "w_w",
+    "w_rel", "w_f", "w_sw", "gq", "w_zmp", "eta2", "d1x", "d1y", "d2x", "d2y", "mu_lin", "bar_w", "bar_s", "box_w", "box_s", "reserved"};
+enum { CF_M = 0, CF_I = 1, CF_COM = 10, CF_FEET = 13, CF_DT = 25, CF_FS, CF_R_GAIN, CF_RDOT_GAIN, CF_W_GAIN, CF_REL_GAIN, CF_SWITCH_WEIGHT,
+       CF_QDDOT_GAIN, CF_F_GAIN, CF_ZMP_GAIN, CF_LIP_HEIGHT, CF_MU, CF_BAR_W, CF_BAR_S, CF_BOX_W, CF_BOX_S, kConstGradientFields };
+static const char* const kConstGradientFieldNames[kConstGradientFields] = {
+    "m", "I[0]", "I[1]", "I[2]", "I[3]", "I[4]", "I[5]", "I[6]", "I[7]", "I[8]", "com[0]", "com[1]", "com[2]", "feet[0]", "feet[1]", "feet[2]",
+    "feet[3]", "feet[4]", "feet[5]", "feet[6]", "feet[7]", "feet[8]", "feet[9]", "feet[10]", "feet[11]", "dt", "force_scaling",
+    "r_tracking_gain", "rdot_tracking_gain", "w_tracking_gain", "rel_pos_gain", "force_switch_weight", "min_qddot_gain", "min_f_gain",
+    "zmp_tracking_gain", "lip_height", "friction_cone_coefficient", "friction_barrier_weight", "friction_barrier_sharpness",
+    "bound_barrier_weight", "bound_barrier_sharpness"};
+
+int sddp_const_gradient_words(sddp_handle* h, int* words, int* columns) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!words || !columns) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    *words = kConstGradientWords;
+    *columns = kConstGradientCols;
+    return SDDP_OK;
+}
+
+int sddp_const_gradient_name(int column, const char** name) {
+    if (!name || column < 0 || column >= kConstGradientCols) return SDDP_ERR_ARG;
+    *name = kConstGradientNames[column];
+    return SDDP_OK;
+}
+
+int sddp_const_gradient_field_name(int field, const char** name) {
+    if (!name || field < 0 || field >= kConstGradientFields) return SDDP_ERR_ARG;
+    *name = kConstGradientFieldNames[field];
+    return SDDP_OK;
+}
+
+int sddp_const_gradient_range_device(sddp_handle* h, int first, int count, const double* d_x, const double* d_u, double* d_out, double* d_nodes,
+                                     double* d_lambda) {
+    PlanSource src;
+    if (const int rc = plan_source(h, "sddp_const_gradient_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
+    if (!h->ops->inspect.const_gradient)
+        return fail(h, SDDP_ERR_ARG, "sddp_const_gradient_range_device: a user build's non-linear rows have no derivative code beside them");
+    if (const size_t lds = const_gradient_lds(h->N); lds > size_t(64) * 1024)      // before anything is launched
+        return fail(h, SDDP_ERR_ARG, "sddp_const_gradient_range_device: the horizon's tile of addends needs " + std::to_string(lds) +
+                                         " bytes of LDS, more than the 65536 one workgroup has here");
+    if (!h->pgrad.on()) {      // the costates and the stationarity record of a call (the parameter sensitivities' group)
+        GroupBuf g[] = {{h->n_x() * sizeof(double)}, {size_t(h->B) * kStationarityWords * sizeof(double)}};
+        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_const_gradient_range_device: out of device memory");
+        h->pgrad = {g[0], g[1]};
+    }
+    // the costates are the stationarity certificate's, by its own launch: lambda has the bits it writes to d_lambda
+    if (const int rc = h->ops->inspect.stationarity(h, first, count, src, h->pgrad.stat, h->pgrad.lam, nullptr); rc != SDDP_OK) return rc;
+    if (d_lambda)
+        HIP_TRY(h, hipMemcpyAsync(d_lambda, h->pgrad.lam, size_t(count) * (h->N + 1) * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return h->ops->inspect.const_gradient(h, first, count, src, h->pgrad.lam, h->pgrad.stat, d_out, d_nodes);
+}
+
+int sddp_const_gradient(sddp_handle* h, int first, int count, double* out) {
+    return inspect_to_host(h, first, count, kConstGradientWords, out, [&](double* d_out) {
+        return sddp_const_gradient_range_device(h, first, count, nullptr, nullptr, d_out, nullptr, nullptr);
+    });
+}
+
+// the chain rule of make_dev_consts (sddp_models.hpp), backwards: host code alone
+int sddp_const_gradient_fields(const sddp_model_consts* consts, const double* derived, double* fields_out, int* n_fields) {
+    if (n_fields) *n_fields = kConstGradientFields;
+    if (!consts || !derived || !fields_out) return fail(nullptr, SDDP_ERR_ARG, "sddp_const_gradient_fields: NULL argument");
+    if (const std::string msg = check_consts(*consts); !msg.empty()) return fail(nullptr, SDDP_ERR_ARG, msg);
+    const sddp_model_consts& c = *consts;
+    const double* C = derived;
+    const double fs = c.force_scaling;
+    double* o = fields_out;
+    for (int i = 0; i < kConstGradientFields; ++i) o[i] = 0.0;
+    o[CF_M] = -fs / (c.m * c.m) * C[CG_INV_MS];
+    double fs_is = 0.0;
+    for (int i = 0; i < 9; ++i) {
+        o[CF_I + i] = C[CG_IS + i] / fs;
+        fs_is += c.I[i] * C[CG_IS + i];
+    }
+    o[CF_COM + 2] = C[CG_COM_Z];
+    o[CF_FEET + 0] = -C[CG_D1X];  o[CF_FEET + 6] = C[CG_D1X];
+    o[CF_FEET + 1] = -C[CG_D1Y];  o[CF_FEET + 7] = C[CG_D1Y];
+    o[CF_FEET + 3] = -C[CG_D2X];  o[CF_FEET + 9] = C[CG_D2X];
+    o[CF_FEET + 4] = -C[CG_D2Y];  o[CF_FEET + 10] = C[CG_D2Y];
+    o[CF_DT] = C[CG_DT];
+    o[CF_FS] = C[CG_INV_MS] / c.m - fs_is / (fs * fs) + 2.0 * fs * (c.min_f_gain * C[CG_W_F] + c.force_switch_weight * C[CG_W_SW]);
+    o[CF_R_GAIN] = C[CG_W_RZ] + C[CG_W_RXY];
+    o[CF_RDOT_GAIN] = C[CG_W_RD];
+    o[CF_W_GAIN] = C[CG_W_W];
+    o[CF_REL_GAIN] = C[CG_W_REL];
+    o[CF_SWITCH_WEIGHT] = fs * fs * C[CG_W_SW];
+    o[CF_QDDOT_GAIN] = C[CG_GQ];
+    o[CF_F_GAIN] = fs * fs * C[CG_W_F];
+    o[CF_ZMP_GAIN] = C[CG_W_ZMP];
+    o[CF_LIP_HEIGHT] = -kGravity / (c.lip_height * c.lip_height) * C[CG_ETA2];
+    o[CF_MU] = C[CG_MU_LIN] / sqrt(2.0);
+    o[CF_BAR_W] = C[CG_BAR_W];
+    o[CF_BAR_S] = C[CG_BAR_S];
+    o[CF_BOX_W] = C[CG_BOX_W];
+    o[CF_BOX_S] = C[CG_BOX_S];
+    return SDDP_OK;
+}
+
 int sddp_model_step(sddp_handle* h, const double* x, const double* u, const double* p, int k, double* x_next) {
     if (!h || !x || !u || !p || !x_next) return SDDP_ERR_ARG;
     if (k < 0 || k >= h->N) return fail(h, SDDP_ERR_ARG, "sddp_model_step: k must be a stage node, 0 <= k < N");

@@ -104,6 +104,8 @@ struct ModelOps {
         // parameter sensitivities: the costates and the record the stationarity launch stored for the range, out, the gradient or
         // null; null: a user build (its rows have no d/dp code)
         int (*param_gradient)(sddp_handle*, int, int, PlanSource, const double*, const double*, double*, double*) = nullptr;
+        // constant sensitivities: the same inputs, out, the per-node addends or null; null: a user build
+        int (*const_gradient)(sddp_handle*, int, int, PlanSource, const double*, const double*, double*, double*) = nullptr;
         int (*model_step)(sddp_handle*, int, const double*, const double*, const double*, double*) = nullptr;
     } inspect;
 };

@@ -1,5 +1,5 @@
 // sddp_inspect.hpp -- the kernels that only read: one model step, the policy rolled out and the plan inspectors (audit, stationarity
-// certificate, cost breakdown, parameter sensitivities).  They run the same device model code as the solve (M::step, M::derivs,
+// certificate, cost breakdown, parameter and constant sensitivities).  They run the same device model code as the solve (M::step, M::derivs,
 // M::F_entry, ...; the sensitivities M::param_grad, which the solve has no use for) on one wavefront per instance, and store to
 // nothing but the caller's outputs.  (The knot evaluation of the parity tests reads only as
 // well and stays in sddp_kernels.hpp, which says why.)
@@ -7,7 +7,7 @@
 // Instantiated by the inspect unit of a model build alone (sddp_launch_inspect.hpp, sddp_inst.hip with -DSDDP_INST_INSPECT): a device
 // module of their own, so that nothing written here can reach the code generation of the solve kernels (sddp_kernels.hpp,
 // sddp_kernels_mw.hpp), which no longer share a module with them.  The record sizes that sddp_api.hip reports (kStationarityWords,
-// kCostTermsWords, kCostTermsFamilies, kParamGradientWords) are in sddp_kernels.hpp, where it finds them without this file.
+// kCostTermsWords, kCostTermsFamilies, kParamGradientWords, kConstGradientWords) are in sddp_kernels.hpp, where it finds them without this file.
 #pragma once
 #include "sddp_kernels.hpp"
 
@@ -502,6 +502,80 @@ __global__ __launch_bounds__(kWave) void param_gradient_kernel(ConstsArg<Tab...>
         double* r = out + size_t(i) * kParamGradientWords;
         r[0] = top.v;  r[1] = audit_index(top, NP, false);  r[2] = audit_index(top, NP, true);
         r[3] = scale;  r[4] = s[4];  r[5] = s[0];  r[6] = s[6];  r[7] = double(N);
+    }
+}
+
+// -----------------------------------------------------------------------------------------------------------------
+// Constant sensitivities (sddp_const_gradient_range_device): the gradient of the Lagrangian of a whole-horizon trajectory in the derived
+// constants the kernels read (ConstCol, sddp_models.hpp),
+//   C[c] = sum_{k < N} ( dL_k/dtheta_c + sum_i lambda_{k+1}[i] df_k[i]/dtheta_c ) + dL_N/dtheta_c,
+// through M::const_grad, and kConstGradientWords doubles per instance (include/sddp.h has the table).  The costates and stat are the
+// stationarity launch's, as for param_gradient_kernel; words 34 - 36 of the record are words 4, 0, 6 of stat as they are.
+// One wavefront per instance, lane l on the nodes k = l, l + 64, ...; with per-instance constants instance b reads its own row.
+// A column is a SUM over the nodes, so its order is fixed as the cost breakdown fixes it: the addends of node k go to row k of a tile
+// [N + 1][32] in dynamic LDS (the launcher refuses horizons whose tile exceeds it), from there to `nodes` when given, and lane c < 32
+// then adds column c in node order: no lane mapping enters a sum.  Inside a row the columns are rotated by the node (entry c of node k
+// at k * 32 + ((c + k) & 31)): a lane writes its row and the summing lanes walk down theirs without meeting on one bank.
+// Plain vector stores to out / nodes alone, no atomics, no work buffer.
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void const_gradient_kernel(ConstsArg<Tab...> consts, int N, int first, int count,
+                                                                const double* __restrict__ x, const double* __restrict__ u, int xoff,
+                                                                const double* __restrict__ P, const double* __restrict__ lam,
+                                                                const double* __restrict__ stat, double* __restrict__ out,
+                                                                double* __restrict__ nodes) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NCOL = kConstGradientCols;
+    static_assert(NCOL == 32, "the rotation of a row and the summing lanes");
+    extern __shared__ __attribute__((aligned(16))) double s[];
+    double* tile = s;                                      // [N + 1][NCOL] the addends
+    double* rel = tile + size_t(N + 1) * NCOL;             // [NCOL] |C theta| of the columns
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = x + size_t(xoff + i) * (N + 1) * NX;
+    const double* ub = u + size_t(xoff + i) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    const double* lb = lam + size_t(i) * (N + 1) * NX;
+    for (int k = lane; k <= N; k += kWave) {
+        double g[NCOL];
+        // (k == N: no input and no next costate; const_grad reads neither there, the pointers stay inside the buffers)
+        M::const_grad(c, xb + size_t(k) * NX, ub + size_t(k < N ? k : 0) * NU, Pb + size_t(k) * NP, k, N,
+                      lb + size_t(k < N ? k + 1 : k) * NX, g);
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) tile[k * NCOL + ((j + k) & (NCOL - 1))] = g[j];
+    }
+    wave_sync();
+    if (nodes) {
+        double* no = nodes + size_t(i) * (N + 1) * NCOL;
+        for (int e = lane; e < (N + 1) * NCOL; e += kWave) {
+            const int k = e / NCOL, j = e % NCOL;
+            no[e] = tile[k * NCOL + ((j + k) & (NCOL - 1))];
+        }
+    }
+    double* r = out + size_t(i) * kConstGradientWords;
+    if (lane < NCOL) {
+        double acc = 0.0;
+        for (int k = 0; k <= N; ++k) acc += tile[k * NCOL + ((lane + k) & (NCOL - 1))];
+        r[lane] = acc;
+        double th = 0.0;      // (a select over compile-time columns: a run-time index into the constants would put the table form's copy in scratch)
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) th = lane == j ? const_col_value(c, j) : th;
+        rel[lane] = fabs(acc * th);
+    }
+    wave_sync();
+    if (lane == 0) {
+        int best = 0;
+        bool nan = false;
+        for (int j = 0; j < NCOL; ++j) {
+            const double v = rel[j];
+            nan = nan || v != v;
+            if (v > rel[best]) best = j;
+        }
+        const double* st = stat + size_t(i) * kStationarityWords;
+        r[NCOL] = nan ? __builtin_nan("") : rel[best];
+        r[NCOL + 1] = nan ? -1.0 : double(best);
+        r[NCOL + 2] = st[4];  r[NCOL + 3] = st[0];  r[NCOL + 4] = st[6];  r[NCOL + 5] = double(N);
+        r[NCOL + 6] = 0.0;  r[NCOL + 7] = 0.0;
     }
 }
 

@@ -32,6 +32,10 @@ constexpr int kScal = 24;  // doubles per instance in the scratch `scal` record 
 constexpr int kStationarityWords = 8;      // doubles per record of the stationarity certificate (sddp.h sddp_stationarity_words)
 constexpr int kCostTermsWords = 16, kCostTermsFamilies = 13;   // ... of the cost breakdown, and its families (sddp.h sddp_cost_terms_words)
 constexpr int kParamGradientWords = 8;     // ... of the parameter sensitivities (sddp.h sddp_param_gradient_words)
+// ... of the constant sensitivities (sddp.h sddp_const_gradient_words): the kConstGradientCols columns, 6 words, 2 reserved; and the
+// dynamic LDS of its kernel: the tile of addends [N + 1][kConstGradientCols] and one row for the columns' |C theta|
+constexpr int kConstGradientWords = 40;
+constexpr size_t const_gradient_lds(int N) { return sizeof(double) * (size_t(N + 1) + 1) * kConstGradientCols; }
 
 // Diagnostic build only (-DSDDP_STAMPS): per-phase shader-cycle sums, written to `scal`; never in the shipped library.
 #ifdef SDDP_STAMPS

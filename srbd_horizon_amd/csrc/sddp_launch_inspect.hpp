@@ -45,6 +45,14 @@ int launch_param_gradient(sddp_handle* h, int first, int count, PlanSource s, co
     return launch_waves<M>(h, SDDP_PICK(param_gradient_kernel), count, 0, h->N, first, count, s.x, s.u, s.xoff, h->last_params, dlam, dstat, dout,
                            dgrad);
 }
+// the constant sensitivities: dynamic LDS sized from N (const_gradient_lds: the tile of addends); sddp_api.hip, the one caller, has
+// refused a horizon whose tile exceeds 64 KB before the stationarity launch.  dlam / dstat: see launch_param_gradient.  Not on a user
+// build (SrbdModel::const_grad)
+template <class M>
+int launch_const_gradient(sddp_handle* h, int first, int count, PlanSource s, const double* dlam, const double* dstat, double* dout, double* dnodes) {
+    return launch_waves<M>(h, SDDP_PICK(const_gradient_kernel), count, const_gradient_lds(h->N), h->N, first, count, s.x, s.u, s.xoff,
+                           h->last_params, dlam, dstat, dout, dnodes);
+}
 
 template <class M>
 int launch_model_step(sddp_handle* h, int k, const double* dx, const double* du, const double* dp, double* dxn) {
@@ -59,6 +67,7 @@ ModelOps::InspectOps inspect_ops() {
     o.stationarity = launch_stationarity<M>;
     o.cost_terms = launch_cost_terms<M>;
     if constexpr (!M::HAS_UR) o.param_gradient = launch_param_gradient<M>;
+    if constexpr (!M::HAS_UR) o.const_gradient = launch_const_gradient<M>;
     o.model_step = launch_model_step<M>;
     return o;
 }

@@ -40,6 +40,44 @@ struct DevConsts {
     int xr_n;
     const double* xr;
 };
+// The columns of the constant sensitivities (M::const_grad, const_gradient_kernel; the table of include/sddp.h
+// sddp_const_gradient_range_device): the entries of DevConsts a robot's constants reach.  w_pen and w_rv are fixed numbers,
+// inertia_mode / lever / the bounds / the user rows' tables select code or data and have no column.
+enum ConstCol {
+    CG_DT = 0, CG_INV_MS = 1, CG_IS = 2, CG_COM_Z = 11, CG_W_RZ = 12, CG_W_RXY = 13, CG_W_RD = 14, CG_W_W = 15, CG_W_REL = 16, CG_W_F = 17,
+    CG_W_SW = 18, CG_GQ = 19, CG_W_ZMP = 20, CG_ETA2 = 21, CG_D1X = 22, CG_D1Y = 23, CG_D2X = 24, CG_D2Y = 25, CG_MU_LIN = 26, CG_BAR_W = 27,
+    CG_BAR_S = 28, CG_BOX_W = 29, CG_BOX_S = 30, CG_RESERVED = 31
+};
+constexpr int kConstGradientCols = 32;
+// the value of column col in a derived record (the reserved column: 0)
+__host__ __device__ inline double const_col_value(const DevConsts& c, const int col) {
+    if (col >= CG_IS && col < CG_IS + 9) return c.Is[col - CG_IS];
+    switch (col) {
+        case CG_DT: return c.dt;
+        case CG_INV_MS: return c.inv_ms;
+        case CG_COM_Z: return c.com_z;
+        case CG_W_RZ: return c.w_rz;
+        case CG_W_RXY: return c.w_rxy;
+        case CG_W_RD: return c.w_rd;
+        case CG_W_W: return c.w_w;
+        case CG_W_REL: return c.w_rel;
+        case CG_W_F: return c.w_f;
+        case CG_W_SW: return c.w_sw;
+        case CG_GQ: return c.gq;
+        case CG_W_ZMP: return c.w_zmp;
+        case CG_ETA2: return c.eta2;
+        case CG_D1X: return c.d1x;
+        case CG_D1Y: return c.d1y;
+        case CG_D2X: return c.d2x;
+        case CG_D2Y: return c.d2y;
+        case CG_MU_LIN: return c.mu_lin;
+        case CG_BAR_W: return c.bar_w;
+        case CG_BAR_S: return c.bar_s;
+        case CG_BOX_W: return c.box_w;
+        case CG_BOX_S: return c.box_s;
+        default: return 0.0;
+    }
+}
 constexpr int kXrRows = 8, kXrStride = 128, kXrWS = kXrRows * kXrStride, kXrWG = kXrWS + 8, kXrC = kXrWG + 8, kXrWords = kXrC + 8;
 
 // The user rows of one knot: cost sum_j w_j e_j^2 with e_j = a_j . z - (p_ref[j] + const_j), w_j = the row's weight where its kind is
@@ -920,6 +958,161 @@ struct SrbdModel {
         }
     }
 
+    // Constant sensitivities of knot k (const_gradient_kernel; sddp.h sddp_const_gradient_range_device): for every column c of ConstCol
+    //   out[c] = dL_k/dtheta_c + sum_i df[i]/dtheta_c lam_next[i]   (k < N; lam_next is not read at k == N, where out[c] = dL_N/dtheta_c),
+    // entry c starting at dL/dtheta_c and adding fma(df[i]/dtheta_c, lam_next[i], .) for i = 0 .. NX - 1 in this order, the structural
+    // zeros skipped (param_grad's rule).  The node classes are derivs'.  Where a constant enters f: dt every row (df/ddt = xdot);
+    // inv_ms the rows XRD (rddot = inv_ms sum f - g); Is the rows XW through the model core: with I_w wdot = n and
+    // dI_w/dIs[3 i + j] = a b^T (inertia_mode 0: a = R_ij R_ji e_i, b = e_j; mode 1: a = R e_i, b = R e_j),
+    //   d wdot/dIs[3 i + j] = -I_w^-1 ((b . wdot) a + (b . w) w x a).
+    // Columns the model does not read stay exactly 0.0: w_rxy, w_zmp, eta2; w_rel and d1x .. d2y without contact states; mu_lin, bar_w,
+    // bar_s without the friction barrier (!BAR or weight 0: off, as the solve has it); box_w, box_s without the bound barrier.
+    // The user rows of an _x build read no constant of a column.  A user build has no such code (see param_grad).
+    __device__ __forceinline__ static void const_grad(const DevConsts& c, const double* x, const double* u, const double* p, int k, int N,
+                                                      const double* lam_next, double* out) {
+        static_assert(!HAS_UR, "a user build has no d/dtheta code");
+        double g[kConstGradientCols];
+#pragma unroll
+        for (int j = 0; j < kConstGradientCols; ++j) g[j] = 0.0;
+        if (k >= 1) {  // state residuals: com_z and w_rz, w_rd, w_w, with contact states w_rel and the foot offsets
+            const double ez = x[XR + 2] - c.com_z;
+            g[CG_COM_Z] = -2 * c.w_rz * ez;
+            g[CG_W_RZ] = ez * ez;
+            double sd = 0.0, sw = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double ed = x[XRD + a] - p_rdref(p, a), ew = x[XW + a] - p_wref(p, a);
+                sd += ed * ed;
+                sw += ew * ew;
+            }
+            g[CG_W_RD] = sd;
+            g[CG_W_W] = sw;
+            if (CS) {
+                const double r1y = -x[XC + 1] + x[XC + 7] - c.d1y, r1x = -x[XC + 0] + x[XC + 6] - c.d1x;
+                const double r2y = -x[XC + 4] + x[XC + 10] - c.d2y, r2x = -x[XC + 3] + x[XC + 9] - c.d2x;
+                g[CG_W_REL] = r1y * r1y + r1x * r1x + r2y * r2y + r2x * r2x;
+                const double s = -2 * c.w_rel;
+                g[CG_D1X] = s * r1x;  g[CG_D1Y] = s * r1y;  g[CG_D2X] = s * r2x;  g[CG_D2Y] = s * r2y;
+            }
+        }
+        if (k < N) {  // input residuals and penalties, the barriers, and the dynamics
+            double cp[NC][3], f[NC][3];
+            load_contacts(x, u, p, cp, f);
+            Core q;
+            const double o[4] = {x[XO], x[XO + 1], x[XO + 2], x[XO + 3]}, w[3] = {x[XW], x[XW + 1], x[XW + 2]};
+            core(c, x + XR, o, w, cp, f, q);
+            double fs[3] = {0.0, 0.0, 0.0}, ff = 0.0, fsw = 0.0;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const double s1 = 1.0 - p_sw(p, i), n2 = f[i][0] * f[i][0] + f[i][1] * f[i][1] + f[i][2] * f[i][2];
+                ff += n2;
+                fsw += s1 * s1 * n2;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) fs[a] += f[i][a];
+            }
+            g[CG_W_F] = ff;
+            g[CG_W_SW] = fsw;
+            double acc = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) acc += q.rddot[a] * q.rddot[a] + q.wdot[a] * q.wdot[a];
+            if (CS) {
+#pragma unroll
+                for (int i = 0; i < NC; ++i) acc += u[6 * i] * u[6 * i] + u[6 * i + 1] * u[6 * i + 1] + u[6 * i + 2] * u[6 * i + 2];
+            }
+            g[CG_GQ] = acc;
+            if (BAR) {
+                if (c.bar_w > 0.0) {  // the friction-cone barrier (barrier()): w sum_j exp(s a_j), a_j the rows' values at f
+                    double se = 0.0, sa = 0.0, sm = 0.0;
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) {
+                        const double sz = -c.mu_lin * f[i][2];
+                        const double a1 = f[i][0] + sz, a2 = -f[i][0] + sz, a3 = f[i][1] + sz, a4 = -f[i][1] + sz, a5 = -f[i][2];
+                        const double e1 = exp(c.bar_s * a1), e2 = exp(c.bar_s * a2), e3 = exp(c.bar_s * a3), e4 = exp(c.bar_s * a4);
+                        const double e5 = exp(c.bar_s * a5);
+                        se += e1 + e2 + e3 + e4 + e5;
+                        sa += a1 * e1 + a2 * e2 + a3 * e3 + a4 * e4 + a5 * e5;
+                        sm -= f[i][2] * (e1 + e2 + e3 + e4);
+                    }
+                    g[CG_BAR_W] = se;
+                    g[CG_BAR_S] = c.bar_w * sa;
+                    g[CG_MU_LIN] = c.bar_w * c.bar_s * sm;
+                }
+            }
+            if constexpr (BOX) {
+                if (c.box_w > 0.0) {  // the bound barrier (bound_cost)
+                    double se = 0.0, sa = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NZ; ++j) {
+                        const double z = j < NX ? x[j < NX ? j : 0] : u[j < NX ? 0 : j - NX];
+                        if ((c.box_um >> j) & 1) {
+                            const double a = z - c.box[64 + j], e = exp(c.box_s * a);
+                            se += e;
+                            sa += a * e;
+                        }
+                        if ((c.box_lm >> j) & 1) {
+                            const double a = c.box[j] - z, e = exp(c.box_s * a);
+                            se += e;
+                            sa += a * e;
+                        }
+                    }
+                    g[CG_BOX_W] = se;
+                    g[CG_BOX_S] = c.box_w * sa;
+                }
+            }
+            // inv_ms: L through rddot, f rows XRD
+            g[CG_INV_MS] = 2 * c.gq * (q.rddot[0] * fs[0] + q.rddot[1] * fs[1] + q.rddot[2] * fs[2]);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) g[CG_INV_MS] = fma(c.dt * fs[a], lam_next[XRD + a], g[CG_INV_MS]);
+            // Is: L through wdot, f rows XW
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const bool full = c.inertia_mode != 0;
+                    const double rho = q.R[3 * i + j] * q.R[3 * j + i];
+                    double av[3], bv[3], wa[3], v[3], dw[3];
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        av[a] = full ? q.R[3 * a + i] : (a == i ? rho : 0.0);
+                        bv[a] = full ? q.R[3 * a + j] : (a == j ? 1.0 : 0.0);
+                    }
+                    const double s1 = bv[0] * q.wdot[0] + bv[1] * q.wdot[1] + bv[2] * q.wdot[2];
+                    const double s2 = bv[0] * w[0] + bv[1] * w[1] + bv[2] * w[2];
+                    cross3(w, av, wa);
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) v[a] = -(s1 * av[a] + s2 * wa[a]);
+                    matvec3(q.Mi, v, dw);
+                    double e = 2 * c.gq * (dw[0] * q.wdot[0] + dw[1] * q.wdot[1] + dw[2] * q.wdot[2]);
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) e = fma(c.dt * dw[a], lam_next[XW + a], e);
+                    g[CG_IS + 3 * i + j] = e;
+                }
+            // dt: df/ddt = xdot, row by row in the order of the state (step())
+            double e = 0.0, wxo[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(x[XRD + a], lam_next[XR + a], e);
+            cross3(w, o, wxo);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(0.5 * (o[3] * w[a] + wxo[a]), lam_next[XO + a], e);
+            e = fma(-0.5 * (w[0] * o[0] + w[1] * o[1] + w[2] * o[2]), lam_next[XO + 3], e);
+            if (CS) {
+#pragma unroll
+                for (int i = 0; i < 3 * NC; ++i) e = fma(x[XCD + i], lam_next[XC + i], e);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(q.rddot[a], lam_next[XRD + a], e);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(q.wdot[a], lam_next[XW + a], e);
+            if (CS) {
+#pragma unroll
+                for (int i = 0; i < 3 * NC; ++i) e = fma(u[6 * (i / 3) + (i % 3)], lam_next[XCD + i], e);
+            }
+            g[CG_DT] = e;
+        }
+#pragma unroll
+        for (int j = 0; j < kConstGradientCols; ++j) out[j] = g[j];
+    }
+
     // Full second-order builds: what the sweep needs to contract the second derivatives of wdot = I_w(o)^-1 n(z),
     // n = sum s (c_i - r) x f_i - w x I_w(o) w, with a multiplier it only knows then (add_second_order).  Differentiating
     // I_w wdot = n twice (oracle/models.py srbd_wdot_hess):
@@ -1715,6 +1908,67 @@ struct LipModel {
             out[j] = g[j];
             if (mag) mag[j] = fabs(g[j]);
         }
+    }
+
+    // Constant sensitivities of knot k (see SrbdModel::const_grad).  This model reads dt, com_z, w_rz, w_rxy, w_rd, w_rel, gq, w_zmp,
+    // eta2 and the foot offsets; inv_ms, Is, w_w, w_f, w_sw and the barrier columns stay exactly 0.0.  dt enters every row of f
+    // (df/ddt = xdot), eta2 the rows XRD (rddot = eta2 (r - z) - g).
+    __device__ __forceinline__ static void const_grad(const DevConsts& c, const double* x, const double* u, const double* p, int k, int N,
+                                                      const double* lam_next, double* out) {
+        double g[kConstGradientCols];
+#pragma unroll
+        for (int j = 0; j < kConstGradientCols; ++j) g[j] = 0.0;
+        if (k >= 1) {
+            const double ez = x[2] - c.com_z;
+            g[CG_COM_Z] = -2 * c.w_rz * ez;
+            g[CG_W_RZ] = ez * ez;
+            double sxy = 0.0, sd = 0.0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const double m = 0.25 * (x[XC + a] + x[XC + 3 + a] + x[XC + 6 + a] + x[XC + 9 + a]);
+                const double e = x[a] - m;
+                sxy += e * e;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { const double e = x[XRD + a] - p[a]; sd += e * e; }
+            g[CG_W_RXY] = sxy;
+            g[CG_W_RD] = sd;
+            const double r1y = -x[XC + 1] + x[XC + 7] - c.d1y, r1x = -x[XC + 0] + x[XC + 6] - c.d1x;
+            const double r2y = -x[XC + 4] + x[XC + 10] - c.d2y, r2x = -x[XC + 3] + x[XC + 9] - c.d2x;
+            g[CG_W_REL] = r1y * r1y + r1x * r1x + r2y * r2y + r2x * r2x;
+            const double s = -2 * c.w_rel;
+            g[CG_D1X] = s * r1x;  g[CG_D1Y] = s * r1y;  g[CG_D2X] = s * r2x;  g[CG_D2Y] = s * r2y;
+        }
+        if (k < N) {
+            double rddot[3], szmp = 0.0, sq = 0.0, se = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                rddot[a] = c.eta2 * (x[a] - u[a]) - (a == 2 ? kGravity : 0.0);
+                const double m = 0.25 * (x[XC + a] + x[XC + 3 + a] + x[XC + 6 + a] + x[XC + 9 + a]);
+                const double e = u[a] - m;
+                szmp += e * e;
+                sq += rddot[a] * rddot[a];
+                se += rddot[a] * (x[a] - u[a]);
+            }
+#pragma unroll
+            for (int i = 0; i < 12; ++i) sq += u[3 + i] * u[3 + i];
+            g[CG_W_ZMP] = szmp;
+            g[CG_GQ] = sq;
+            double e = 2 * c.gq * se;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(c.dt * (x[a] - u[a]), lam_next[XRD + a], e);
+            g[CG_ETA2] = e;
+            e = 0.0;
+#pragma unroll
+            for (int i = 0; i < 15; ++i) e = fma(x[15 + i], lam_next[i], e);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) e = fma(rddot[a], lam_next[XRD + a], e);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) e = fma(u[3 + i], lam_next[XCD + i], e);
+            g[CG_DT] = e;
+        }
+#pragma unroll
+        for (int j = 0; j < kConstGradientCols; ++j) out[j] = g[j];
     }
 
     enum { V_R = 0, V_C, V_RD, V_CD, V_Z, V_CDD };

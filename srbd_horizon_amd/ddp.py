@@ -253,6 +253,21 @@ class DDPSolver:
         self.parameter_gradient_record = dict(zip(_lib.PARAM_GRADIENT_FIELDS, rec[0]))
         return self._parameter_gradient_dict(G[0], lam[0, 0])
 
+    def constant_gradient(self):
+        """The gradient of the last solve's cost in the robot's constants (sddp_const_gradient_range_device): a dict by
+        sddp_model_consts field name -- m, I [9], com [3], feet [12], dt, force_scaling, the gains, lip_height, the barrier constants --
+        through the chain rule of sddp_const_gradient_fields.  `constant_gradient_record` keeps the record by name: the columns of
+        _lib.CONST_GRADIENT_NAMES (the derived constants) and the words of _lib.CONST_GRADIENT_TAIL, whose "stationarity" and "defect"
+        say how far the plan is from the stationary point at which this is the gradient of the optimal cost.  Waits for the stream."""
+        if self.var_solution is None:
+            raise RuntimeError("constant_gradient(): no solve has run")
+        if self._user is not None:
+            raise NotImplementedError("non-linear residuals (problem.NonlinearTerm) have no derivative code in the constants")
+        from . import _lib
+        rec, fields = self.ddp_solver.const_gradient(0, 1)
+        self.constant_gradient_record = dict(zip(_lib.CONST_GRADIENT_NAMES + _lib.CONST_GRADIENT_TAIL, np.asarray(rec, dtype=float)[0]))
+        return fields[0]
+
     def _parameter_gradient_dict(self, G, lam0):
         """G [nodes, np of the handle] -> the dictionary of parameter_gradient: the columns in the order of _parameter_matrix()"""
         out, col = {}, 0

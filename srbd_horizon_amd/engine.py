@@ -24,6 +24,7 @@ class DdpEngine:
         self.nx, self.nu, self.np_ = _lib.model_dims(model)
         self.opts = _lib.default_options(**(opts or {}))
         self.consts = _lib.default_consts(model, **(consts or {}))
+        self._instance_rows = []      # (first, SddpModelConsts[count]) of every set_instance_consts, in call order
         h = C.c_void_p()
         _lib.check(self.lib.sddp_create(C.byref(h), self.model_id, self.N, self.B,
                                         C.byref(self.opts), C.byref(self.consts)))
@@ -212,7 +213,7 @@ class DdpEngine:
         return self._to_numpy(n, [(max(s, 0) + 1, self.nx), (max(s, 0), self.nu), ()],
                               lambda x, u, cost: self.policy_rollout_device(xm, x, u, cost, first, n, start, s))
 
-    # ---- the plan inspectors: audit, stationarity certificate, cost breakdown, parameter sensitivities ("Plan inspectors") ----------------
+    # ---- the plan inspectors: audit, stationarity certificate, cost breakdown, parameter and constant sensitivities ("Plan inspectors") ----------------
     # Each reads the instances [first, first + count) of a handle that has solved: the handle's own plan (x, u None) or the caller's
     # device tensors, whose block i belongs to instance first + i.  Every build has them; the *_device forms are asynchronous,
     # behind the solve, and store to nothing but their outputs.
@@ -323,6 +324,56 @@ class DdpEngine:
         lam = mk(self.N + 1, self.nx) if want_lambda else None
         self.param_gradient_device(rec, first, n, x=x, u=u, grad=grad, lam=lam)
         return (grad, rec, lam) if want_lambda else (grad, rec)
+
+    def const_gradient_device(self, out, first: int = 0, count: int | None = None, x=None, u=None, nodes=None, lam=None):
+        """The constant-sensitivity records of the instances [first, first + count) into the device tensor out [count, 40]: the 32
+        columns of _lib.CONST_GRADIENT_NAMES (the gradient of the plan's cost in the derived constants the kernels read), then the
+        words _lib.CONST_GRADIENT_TAIL.  x, u None: the handle's own plan; else device tensors x [count, N + 1, nx], u [count, N, nu], a
+        caller's whole-horizon trajectory.  nodes [count, N + 1, 32]: a device tensor for the per-node addends, whose in-order column
+        sums the record's columns are; lam [count, N + 1, nx]: one for the costates, the bits of stationarity_device's; or None."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_const_gradient_range_device(self.h, int(first), n, *self._plan(n, x, u),
+                                                            self._dev(out, (n, _lib.CONST_GRADIENT_WORDS)),
+                                                            self._dev_or_null(nodes, (n, self.N + 1, _lib.CONST_GRADIENT_COLS)),
+                                                            self._dev_or_null(lam, (n, self.N + 1, self.nx))))
+        return out
+
+    def instance_consts(self, b: int):
+        """the constants instance b is solved with: its row of set_instance_consts, else the handle's own"""
+        for first, rows in reversed(self._instance_rows):      # the last call that covers b holds its row
+            if first <= int(b) < first + len(rows):
+                return rows[int(b) - first]
+        return self.consts
+
+    def const_gradient_fields(self, derived, b: int = 0):
+        """words 0 .. 31 of a constant-sensitivity record of instance b -> a dict by sddp_model_consts field name (m, I [9], com [3],
+        feet [12], dt, force_scaling, the gains, lip_height, the barrier constants): the chain rule of sddp_const_gradient_fields with
+        the constants the engine holds for that instance.  Host code alone."""
+        c = self.instance_consts(b)
+        d = np.ascontiguousarray(derived, dtype=np.float64).reshape(-1)[:_lib.CONST_GRADIENT_COLS].copy()
+        out, n = np.zeros(len(_lib.CONST_GRADIENT_FIELD_NAMES)), C.c_int()
+        if self.lib.sddp_const_gradient_fields(C.byref(c), _lib.ptr(d), _lib.ptr(out), C.byref(n)) != 0:
+            raise RuntimeError((self.lib.sddp_last_error(None) or b"").decode())
+        fields = {}
+        for name, v in zip(_lib.CONST_GRADIENT_FIELD_NAMES, out):
+            base = name.split("[")[0]
+            if base == name:
+                fields[name] = float(v)
+            else:
+                fields.setdefault(base, []).append(float(v))
+        return {k: (np.array(v) if isinstance(v, list) else v) for k, v in fields.items()}
+
+    def const_gradient(self, first: int = 0, count: int | None = None, x=None, u=None, nodes: bool = False):
+        """The gradient of each plan's cost in the robot's constants, on the device: x, u None (the handle's own plan) or device tensors
+        as for const_gradient_device -> (record [count, 40] as a numpy array, [count] dicts by sddp_model_consts field name, each through
+        const_gradient_fields with that instance's own constants); nodes: also the addends [count, N + 1, 32].  Waits for the stream.
+        At a converged plan with closed gaps it is the gradient of the optimal cost; the record's words "stationarity" and "defect" say
+        how far from that the plan is."""
+        n = self._count(first, count)
+        shapes = [(_lib.CONST_GRADIENT_WORDS,)] + ([(self.N + 1, _lib.CONST_GRADIENT_COLS)] if nodes else [])
+        got = self._to_numpy(n, shapes, lambda out, nd=None: self.const_gradient_device(out, first, n, x=x, u=u, nodes=nd))
+        fields = [self.const_gradient_fields(got[0][i], first + i) for i in range(got[0].shape[0])]
+        return (got[0], fields, got[1]) if nodes else (got[0], fields)
 
     def is_converged(self):
         f = np.zeros(self.B, dtype=np.int32)
@@ -587,10 +638,14 @@ class DdpEngine:
         build (barrier weights, bounds, user rows) raise ValueError before any GPU call."""
         rows = _lib.pack_instance_consts(self.consts, overrides)
         self._chk(self.lib.sddp_set_instance_consts(self.h, int(first), len(rows), rows))
+        # (the packed rows as they went to the library, kept for const_gradient_fields: the chain rule needs each robot's own constants.
+        #  The library has no call that reads a row back, so a table changed past this method is not seen here)
+        self._instance_rows.append((int(first), rows))
 
     def clear_instance_consts(self):
         """Back to the handle's own constants for every instance."""
         self._chk(self.lib.sddp_clear_instance_consts(self.h))
+        self._instance_rows.clear()
 
     def instance_consts_active(self) -> bool:
         on = C.c_int()

@@ -160,6 +160,13 @@ class FleetQueue:
         server which way to move a reference or a foothold of each robot before the next tick."""
         return self._inspect(self.eng.param_gradient_device, out, grad=grad)
 
+    def const_gradient(self, out, nodes=None):
+        """The constant-sensitivity records (DdpEngine.const_gradient_device) of the instances the last flush / solve_sliced /
+        solve_within solved, into the first n rows of the device tensor out [>= n, 40] (nodes [>= n, N + 1, 32]: likewise, or None);
+        launched behind whatever that call launched.  -> n; 0, and nothing launched, before the first of them.  What tells a fleet
+        server whose payload estimate its plans' costs are most sensitive to."""
+        return self._inspect(self.eng.const_gradient_device, out, nodes=nodes)
+
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
         `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the
