@@ -263,6 +263,52 @@ int  sddp_apply_policy_device(sddp_handle* h, int first, int count, const double
 int  sddp_apply_policy_knot_device(sddp_handle* h, int first, int count, int knot, const double* d_x_meas, double* d_u_out);
 int  sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
                                 double* d_u_out, double* d_cost_out);
+/* ---- plan uncertainty (v9): closed-loop covariance under the exported policy, and the cone margin in standard deviations ---------
+ * The rollout above says where ONE measured state goes; this says what a whole distribution of them becomes: how much state-estimate
+ * and actuation noise a plan absorbs before a stance force leaves its friction cone.  For instance b = first + i, with the handle's
+ * own plan xs / us, the parameter tensor P of the last sddp_solve* launch, the policy record of b (its gains K_k and its last word
+ * ok), and 0 <= start, steps >= 1, start + steps <= knots (the knots of sddp_enable_policy), for k = start + j:
+ *       F_k = [f_x f_u] at the STORED (x_k, u_k, p_k): the handle's device model code, what sddp_eval_knots returns
+ *       A_k = f_x + f_u K_k  (ok != 0);   A_k = f_x  (ok == 0: K is not multiplied at all, 0 x NaN is not 0);   B_k = f_u
+ *       S_0 = Sigma0[i]   (the caller's [nx][nx], symmetric: only the lower triangle is read)
+ *       S_{j+1} = A_k S_j A_k^T + B_k diag(r[i]) B_k^T + diag(q[i]),   j = 0 .. steps - 1
+ *       U_j = K_k S_j K_k^T   (nu x nu; all zeros when ok == 0): the feedback's share of the input covariance at node k
+ * d_q [count][nx]: process variance added per step, NULL: 0.  d_r [count][nu]: actuation-noise variance entering through f_u, NULL: 0.
+ * With per-instance constants (sddp_set_instance_consts) instance b is linearised through its own robot.
+ * The arithmetic is fixed, so that no lane mapping, range or slot changes a bit:
+ *       A[i][j] starts at F[i][j] and adds fma(F[i][nx + r], K[r][j], .) for r = 0 .. nu - 1;
+ *       T[i][l] starts at 0.0 and adds fma(A[i][j], S[j][l], .) for j = 0 .. nx - 1;
+ *       G[i][m], m <= i, starts at (i == m ? q[i] : 0.0) and adds fma(B[i][r] * r[r], B[m][r], .) for r ascending (d_r NULL: it is the
+ *       first term); S'[i][m] starts at G[i][m] and adds fma(T[i][l], A[m][l], .) for l = 0 .. nx - 1; S'[m][i] is the same word;
+ *       U and the 3 x 3 force blocks below: TU[r][l] starts at 0.0 and adds fma(K[r][j], S[j][l], .) over j, U[r][s], s <= r, starts
+ *       at 0.0 and adds fma(TU[r][l], K[s][l], .) over l.
+ * Cone margin in standard deviations (models whose contact forces are inputs: srbd13, srbd37, srbd61): ml as in
+ * sddp_audit_range_device (the call's friction_coefficient where it is > 0, else the handle's; / sqrt(2)).  For a stage node k, a
+ * contact n in stance there (the audit's test) and the five rows of the pyramid, a_1..4 = (+-1, 0, -ml), (0, +-1, -ml), a_5 = (0, 0, -1)
+ * (rows 0 .. 4 in this order):  margin = -a . f_k,n,  spread = sqrt(a^T C a), C the 3 x 3 block of U_j of that force.  A triple with
+ * spread == 0 is skipped (the audit's deterministic answer applies there); otherwise z = margin / spread.
+ * One record is sddp_policy_covariance_words() = 16 doubles (SDDP_POLICY_COV_WORDS in the bindings):
+ *    0  min z over (node, stance contact, row); +inf if none counted (lip30, ok == 0, S == 0)
+ *    1, 2, 3  its node, contact, row (-1: none; the first in node-major order on ties)
+ *    4  max over j = 0 .. steps of trace S_j          5  its node
+ *    6  trace S_steps          7  max_i S_steps[i][i]          8  its state index
+ *    9  max over j < steps, r of U_j[r][r]          10, 11  its node, input
+ *   12  min over j, i of S_j[i][i] (negative: the recursion lost positive semi-definiteness; a diagnostic, no threshold)
+ *   13  steps          14  ok of the policy record          15  reserved, 0
+ * The NaN and tie rules are the audit's: a NaN operand makes the word NaN and its indices -1.
+ * sddp_policy_covariance_device: asynchronous on the handle's stream, behind the solve and the policy launch; it writes nothing but
+ *   d_out [count][16], d_cov [count][steps + 1][nx][nx] (row j = S_j; or NULL) and d_ucov_diag [count][steps][nu] (row j = diag U_j; or
+ *   NULL), uses none of the slots' work buffers, and the result of an instance does not depend on the range it was part of.
+ *   SDDP_ERR_ARG, with a message: sddp_enable_policy has not been called (so: every build without a policy kernel), no solve has run,
+ *   a range outside the handle, start / steps outside the kept knots, d_sigma0 or d_out NULL.  A policy buffer no policy launch has
+ *   filled is zeros with ok = 0: legal, the open-loop propagation.  It exists where the policy export does; a user build with
+ *   nx > 64, or whose covariance tiles exceed 64 KB of LDS, has the policy export and not this call (SDDP_ERR_ARG). */
+int  sddp_policy_covariance_words(sddp_handle* h, int* words);
+int  sddp_policy_covariance_device(sddp_handle* h, int first, int count, int start, int steps,
+                                   const double* d_sigma0 /*[count][nx][nx]*/, const double* d_q /*[count][nx] or NULL*/,
+                                   const double* d_r /*[count][nu] or NULL*/, double friction_coefficient,
+                                   double* d_out /*[count][16]*/, double* d_cov /*[count][steps+1][nx][nx] or NULL*/,
+                                   double* d_ucov_diag /*[count][steps][nu] or NULL*/);
 /* ---- plan audit (v9): constraint violations of a plan, computed on the device ---------------------------------------------------
  * The solver treats every inequality and every contact constraint softly (a barrier that is off by default, penalty rows, Euler
  * steps without renormalisation), so converged = 1 and a low cost do not say whether a plan is admissible.  The audit measures it:

@@ -65,6 +65,11 @@ LOG_FIELDS = ("J", "A1", "B2", "rho", "gap", "expected", "alpha", "J_accepted", 
 AUDIT_WORDS = 16
 (AUDIT_CONE, AUDIT_CONE_NODE, AUDIT_CONE_CONTACT, AUDIT_PULL, AUDIT_PULL_NODE, AUDIT_SWING_LOAD, AUDIT_QUAT_DRIFT, AUDIT_FOOT_HEIGHT,
  AUDIT_SLIP, AUDIT_RIGID_FOOT, AUDIT_DEFECT, AUDIT_DEFECT_NODE, AUDIT_NODES, AUDIT_STANCE_PAIRS) = range(14)
+# one record of the plan uncertainty (include/sddp.h sddp_policy_covariance_device), and its words by name
+POLICY_COV_WORDS = 16
+(POLICY_COV_MIN_Z, POLICY_COV_Z_NODE, POLICY_COV_Z_CONTACT, POLICY_COV_Z_ROW, POLICY_COV_MAX_TRACE, POLICY_COV_MAX_TRACE_NODE,
+ POLICY_COV_TRACE, POLICY_COV_MAX_VAR, POLICY_COV_MAX_VAR_STATE, POLICY_COV_MAX_UVAR, POLICY_COV_MAX_UVAR_NODE, POLICY_COV_MAX_UVAR_INPUT,
+ POLICY_COV_MIN_VAR, POLICY_COV_STEPS, POLICY_COV_OK) = range(15)
 # the words of one record of the stationarity certificate (include/sddp.h sddp_stationarity_range_device), by name
 STATIONARITY_FIELDS = ("stationarity", "node", "input", "scale", "lambda_0", "lambda_max", "defect", "nodes")
 # one record of the cost breakdown (include/sddp.h sddp_cost_terms_range_device): total | the families | largest | N.  The families'
@@ -127,6 +132,8 @@ SYMBOLS = {
     "sddp_apply_policy_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sddp_apply_policy_knot_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "sddp_policy_rollout_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sddp_policy_covariance_words": (C.c_int, [_vp, _P(C.c_int)]),
+    "sddp_policy_covariance_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "sddp_audit_range_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp]),
     "sddp_audit": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp]),
     "sddp_stationarity_words": (C.c_int, [_vp, _P(C.c_int)]),

@@ -1358,6 +1358,31 @@ int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, 
     return h->ops->inspect.policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
 }
 
+int sddp_policy_covariance_words(sddp_handle* h, int* words) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!words) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    *words = kPolicyCovWords;
+    return SDDP_OK;
+}
+
+int sddp_policy_covariance_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_sigma0, const double* d_q,
+                                  const double* d_r, double friction_coefficient, double* d_out, double* d_cov, double* d_ucov_diag) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (start < 0 || steps < 1 || start > h->pol.policy_knots - steps)
+        return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: start >= 0, steps >= 1 and start + steps <= " +
+                                         std::to_string(h->pol.policy_knots) + " (the knots of sddp_enable_policy)");
+    if (!d_sigma0 || !d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (!h->ops->inspect.policy_covariance)
+        return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: no kernel for this build (a user build with nx > 64, or whose tiles exceed 64 KB of LDS)");
+    // the call's coefficient, or the handle's, linearised: as sddp_audit_range_device takes it
+    const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
+    return h->ops->inspect.policy_covariance(h, first, count, start, steps, d_sigma0, d_q, d_r, mu / sqrt(2.0), d_out, d_cov,
+                                             d_ucov_diag);      // (set with launch_policy)
+}
+
 int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x, const double* d_u,
                             double friction_coefficient, double* d_out) {
     PlanSource src;

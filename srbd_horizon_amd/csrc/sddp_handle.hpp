@@ -95,6 +95,10 @@ struct ModelOps {
     struct InspectOps {
         // the policy rolled out from a measured state: first, count, start, steps, x_meas, x_out, u_out, cost_out; null with launch_policy
         int (*policy_rollout)(sddp_handle*, int, int, int, int, const double*, double*, double*, double*) = nullptr;
+        // the covariance propagated under the policy: first, count, start, steps, Sigma0, q or null, r or null, linearised friction
+        // coefficient, out, the covariances or null, diag of the input covariances or null; null with launch_policy
+        int (*policy_covariance)(sddp_handle*, int, int, int, int, const double*, const double*, const double*, double, double*, double*,
+                                 double*) = nullptr;
         // the plan inspectors (PlanSource): first, count, [audit: start, steps,] the trajectory, then the inspector's own arguments --
         // audit: linearised friction coefficient, out; stationarity: out, lambda or null, reduced gradient or null; cost breakdown: the
         // user rows' table with zero weights or null, out, the per-node addends or null

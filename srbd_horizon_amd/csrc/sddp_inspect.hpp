@@ -579,4 +579,240 @@ __global__ __launch_bounds__(kWave) void const_gradient_kernel(ConstsArg<Tab...>
     }
 }
 
+// -----------------------------------------------------------------------------------------------------------------
+// Plan uncertainty (sddp_policy_covariance_device): the covariance of the state under the exported policy, linearised along the plan,
+//   S_0 = Sigma0[i];   S_{j+1} = A_k S_j A_k^T + B_k diag(r) B_k^T + diag(q),   A_k = f_x + f_u K_k  (ok = 0: f_x),  B_k = f_u,   k = start + j,
+// [f_x f_u] = F_k at the STORED (x_k, u_k, p_k) through M::derivs + M::F_entry as stationarity_kernel takes it, the feedback's share of
+// the input covariance U_j = K_k S_j K_k^T, the cone margin of every stance force in standard deviations of it, and kPolicyCovWords
+// doubles per instance (include/sddp.h has the table and the order of every FMA chain; nothing below may change a chain).
+// One wavefront per instance, the knots forward.  Per knot, lane 0 runs M::derivs into the knot record in LDS; then
+//   U:  lane r < NU holds row r of K_k in registers and forms row r of K S_j (S_j from LDS: every lane the same word, a broadcast) into
+//       the tile; lanes then form diag U and the lower triangles of the 3 x 3 force blocks from it and K;
+//   A:  f_u goes to the tile (rows padded to an odd length: a lane walks its own row); lane m < NX forms row m of A_k in registers;
+//   G:  lane m forms G[i][m] = q / r terms, i >= m, into the NEXT triangle, where the chain of S'[i][m] starts;
+//   T:  lane i forms row i of T = A S_j into the tile, S_j again a broadcast;
+//   S': lane m adds sum_l T[i][l] A[m][l] for i >= m: T[i][.] a broadcast, A[m][.] its registers.
+// So the NX^2 products of a stage cost a lane one LDS broadcast and one FMA each, nothing crosses lanes, and a lane keeps one row of A
+// (NX doubles) and nothing else across the phases.  S is symmetric by construction (one word per pair), so it lives as two lower
+// triangles, this knot's and the next; with the one tile that K S, f_u and T share in turn, srbd61 (NX = 61) needs 62.7 KB where two
+// full S tiles and a T tile would need 89: static LDS, at most 64 KB on every build (asserted).  Nothing of the slots' work buffers,
+// plain vector stores to the caller's outputs alone (cov / ucov may be null).  The maxima are the audit's (nan_max, audit_take); a
+// minimum is the maximum of the negated operands.
+// where the mapping fits: one lane per row of A_k, of K_k and per entry of the force blocks, f_u inside the shared tile, and the static
+// LDS of one workgroup at most 64 KB.  The four models and their _x builds do; a user build that does not gets no kernel, and the call
+// answers SDDP_ERR_ARG
+template <class M>
+constexpr bool policy_covariance_fits() {
+    constexpr int NX = M::NX, NU = M::NU, NCF = M::AUDIT_FORCES ? M::NC : 0;
+    return NX <= kWave && (NU | 1) <= NX && 6 * NCF <= kWave &&
+           sizeof(double) * (M::NREC + NX * (NX + 1) + NX * NX + NU + 6 * NCF + 1) <= 64 * 1024;
+}
+// The model code of this kernel is an instantiation of its own.  Every device function is internal to the module and inlined, but until
+// it is, the compiler's interprocedural passes see M::derivs and M::F_entry with all their callers: with this kernel among them,
+// stationarity_kernel of the SRBD builds -- until now their one caller here -- came out as another instruction stream (up to every
+// line of it on the _x builds; profiles/policy_covariance).  So for the library's SRBD models the kernel calls the same code through a
+// twin type, SrbdModel<..., CovTwinTag>: the user-rows parameter set to a tag that means what void means (no such rows), hence the
+// same source, constants and layout, instantiated apart.  lip30's stationarity_kernel did not move, and a user build has no parent to
+// be compared with: they use M itself.
+struct CovTwinTag;
+template <>
+struct UrInfo<CovTwinTag> : UrInfo<void> {};
+template <class M>
+struct cov_twin { using type = M; };
+template <int NC, bool CS, bool BAR, bool SO2, int XR>
+struct cov_twin<SrbdModel<NC, CS, BAR, SO2, XR, void>> { using type = SrbdModel<NC, CS, BAR, SO2, XR, CovTwinTag>; };
+__device__ __forceinline__ int cov_tri(const int i, const int m) { return i >= m ? i * (i + 1) / 2 + m : m * (m + 1) / 2 + i; }
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void policy_covariance_kernel(ConstsArg<Tab...> consts, int N, int first, int count, int start, int steps,
+                                                                   const double* __restrict__ xs, const double* __restrict__ us,
+                                                                   const double* __restrict__ P, const double* __restrict__ pol, int pol_words,
+                                                                   const double* __restrict__ sigma0, const double* __restrict__ qv,
+                                                                   const double* __restrict__ rv, double ml, double* __restrict__ out,
+                                                                   double* __restrict__ cov, double* __restrict__ ucov) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC, NTRI = NX * (NX + 1) / 2, NUP = NU | 1;
+    using MM = typename cov_twin<M>::type;                 // derivs and F_entry: see cov_twin
+    static_assert(MM::NX == M::NX && MM::NZ == M::NZ && MM::NREC == M::NREC && MM::REC_G == M::REC_G, "the twin is the model");
+    constexpr int NCF = M::AUDIT_FORCES ? M::NC : 0;      // contacts whose force is an input
+    static_assert(policy_covariance_fits<M>(), "instantiated only where it fits (sddp_launch_inspect.hpp leaves the entry null elsewhere)");
+    __shared__ double srec[NREC];                          // the record of knot k
+    __shared__ double sS[2][NTRI];                         // S_j | S_{j+1}, swapping: lower triangles, row-major
+    __shared__ double sT[NX * NX];                         // K S_j [NU][NX], then f_u [NX][NUP], then T = A S_j [NX][NX]
+    __shared__ double sU[NU + 6 * NCF + 1];                // diag U_j | per contact the block's (0,0) (1,0) (1,1) (2,0) (2,1) (2,2)
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const DevConsts& c = consts_of(consts, b);
+    const double* xb = xs + size_t(b) * (N + 1) * NX;
+    const double* ub = us + size_t(b) * N * NU;
+    const double* Pb = P + size_t(b) * (N + 1) * NP;
+    const double* rec = pol + size_t(b) * pol_words;
+    const bool feedback = rec[pol_words - 1] != 0.0;
+    const double* qi = qv ? qv + size_t(i) * NX : nullptr;
+    const double* ri = rv ? rv + size_t(i) * NU : nullptr;
+    double* co = cov ? cov + size_t(i) * (steps + 1) * NX * NX : nullptr;
+    double* uo = ucov ? ucov + size_t(i) * steps * NU : nullptr;
+    const double inf = __builtin_huge_val();
+    AuditMax zneg{-inf, kAuditNoKey}, trmax{-inf, kAuditNoKey}, umax{-inf, kAuditNoKey};
+    double dneg = -inf;                                    // max of -S_j[i][i]
+    const double* s0 = sigma0 + size_t(i) * NX * NX;
+    for (int e = lane; e < NX * NX; e += kWave)
+        if (e % NX <= e / NX) sS[0][cov_tri(e / NX, e % NX)] = s0[e];
+    wave_sync();
+    // what the record keeps of S_j (in sS[cur]), and row j of cov
+    auto note = [&](const int cur, const int j) {
+        if (lane == 0) {
+            double tr = 0.0;
+            for (int t = 0; t < NX; ++t) tr += sS[cur][cov_tri(t, t)];
+            audit_take(trmax, tr, start + j);
+        }
+        if (lane < NX) dneg = nan_max(dneg, -sS[cur][cov_tri(lane, lane)]);
+        if (co)
+            for (int e = lane; e < NX * NX; e += kWave) co[size_t(j) * NX * NX + e] = sS[cur][cov_tri(e / NX, e % NX)];
+    };
+    for (int j = 0; j < steps; ++j) {
+        const int k = start + j, cur = j & 1, nxt = cur ^ 1;
+        const double* pk = Pb + size_t(k) * NP;
+        const double* K = rec + size_t(k) * NU * (NX + 1) + NU;
+        const double* Sc = sS[cur];
+        double* Sn = sS[nxt];
+        note(cur, j);
+        if (lane == 0) {
+            double xl[NX], ul[NU];
+#pragma unroll
+            for (int t = 0; t < NX; ++t) xl[t] = xb[size_t(k) * NX + t];
+#pragma unroll
+            for (int t = 0; t < NU; ++t) ul[t] = ub[size_t(k) * NU + t];
+            MM::derivs(c, xl, ul, pk, k, N, srec);
+        }
+        // ---- U: K S_j, then diag U and the force blocks
+        if (feedback) {
+            if (lane < NU) {
+                double kr[NX];
+#pragma unroll
+                for (int t = 0; t < NX; ++t) kr[t] = K[lane * NX + t];
+                for (int l = 0; l < NX; ++l) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int t = 0; t < NX; ++t) acc = fma(kr[t], Sc[cov_tri(t, l)], acc);
+                    sT[lane * NX + l] = acc;
+                }
+            }
+            wave_sync();
+            if (lane < NU) {
+                double acc = 0.0;
+                for (int l = 0; l < NX; ++l) acc = fma(sT[lane * NX + l], K[lane * NX + l], acc);
+                sU[lane] = acc;
+            }
+            if constexpr (NCF > 0) {
+                if (lane < 6 * NCF) {
+                    const int n = lane / 6, p = lane % 6, ra = p >= 3 ? 2 : (p >= 1 ? 1 : 0), rb = p - ra * (ra + 1) / 2;
+                    const int row = M::uf(n) + ra, col = M::uf(n) + rb;
+                    double acc = 0.0;
+                    for (int l = 0; l < NX; ++l) acc = fma(sT[row * NX + l], K[col * NX + l], acc);
+                    sU[NU + lane] = acc;
+                }
+            }
+            wave_sync();
+        }
+        if (lane < NU) {
+            const double v = feedback ? sU[lane] : 0.0;
+            if (uo) uo[size_t(j) * NU + lane] = v;
+            audit_take(umax, v, k * NU + lane);
+        }
+        if constexpr (NCF > 0) {
+            // lane = contact * 5 + row of the pyramid: a = (+-1, 0, -ml), (0, +-1, -ml), (0, 0, -1)
+            if (feedback && lane < 5 * NCF) {
+                const int n = lane / 5, row = lane % 5;
+                if (M::p_sw(pk, n) > 0.5) {
+                    const double* f = ub + size_t(k) * NU + M::uf(n);
+                    const double* C = sU + NU + 6 * n;
+                    const double a0 = row == 0 ? 1.0 : (row == 1 ? -1.0 : 0.0), a1 = row == 2 ? 1.0 : (row == 3 ? -1.0 : 0.0);
+                    const double a2 = row == 4 ? -1.0 : -ml;
+                    const double w0 = fma(C[3], a2, fma(C[1], a1, C[0] * a0));      // C a, row by row, the columns ascending
+                    const double w1 = fma(C[4], a2, fma(C[2], a1, C[1] * a0));
+                    const double w2 = fma(C[5], a2, fma(C[4], a1, C[3] * a0));
+                    const double spread = sqrt(fma(a2, w2, fma(a1, w1, a0 * w0)));
+                    const double margin = -fma(a2, f[2], fma(a1, f[1], a0 * f[0]));
+                    if (spread != 0.0) audit_take(zneg, -(margin / spread), (k * NCF + n) * 5 + row);
+                }
+            }
+        }
+        wave_sync();                                       // the record is in LDS, and the tile is free for f_u
+        // ---- A: row m of A_k in registers
+        const bool noise = ri != nullptr;
+        if (feedback || noise) {
+            for (int e = lane; e < NX * NU; e += kWave) sT[(e / NU) * NUP + e % NU] = MM::F_entry(c, srec, e / NU, NX + e % NU);
+            wave_sync();
+        }
+        double a[NX];
+        if (lane < NX) {
+#pragma unroll
+            for (int t = 0; t < NX; ++t) a[t] = MM::F_entry(c, srec, lane, t);
+            if (feedback) {
+                for (int r = 0; r < NU; ++r) {
+                    const double br = sT[lane * NUP + r];
+#pragma unroll
+                    for (int t = 0; t < NX; ++t) a[t] = fma(br, K[r * NX + t], a[t]);
+                }
+            }
+            // ---- G: where the chain of S'[i][lane] starts, i >= lane
+            // (r2 runs over every row in every lane, the lanes below it masked: sT[r2][.] is then one word for the wave, a broadcast)
+            for (int r2 = 0; r2 < NX; ++r2) {
+                if (r2 < lane) continue;
+                double g = r2 == lane && qi ? qi[r2] : 0.0;
+                if (noise)
+                    for (int r = 0; r < NU; ++r) g = fma(sT[r2 * NUP + r] * ri[r], sT[lane * NUP + r], g);
+                Sn[cov_tri(r2, lane)] = g;
+            }
+        }
+        wave_sync();                                       // f_u has been read: the tile is free for T
+        // ---- T = A S_j, row by row
+        if (lane < NX) {
+            for (int l = 0; l < NX; ++l) {
+                double acc = 0.0;
+#pragma unroll
+                for (int t = 0; t < NX; ++t) acc = fma(a[t], Sc[cov_tri(t, l)], acc);
+                sT[lane * NX + l] = acc;
+            }
+        }
+        wave_sync();
+        // ---- S'[i][lane] += sum_l T[i][l] A[lane][l], i >= lane
+        if (lane < NX) {
+            for (int r2 = 0; r2 < NX; ++r2) {
+                if (r2 < lane) continue;
+                double acc = Sn[cov_tri(r2, lane)];
+#pragma unroll
+                for (int t = 0; t < NX; ++t) acc = fma(sT[r2 * NX + t], a[t], acc);
+                Sn[cov_tri(r2, lane)] = acc;
+            }
+        }
+        wave_sync();                                       // S_{j+1} is in LDS, and the record is free for knot k + 1
+    }
+    const int last = steps & 1;
+    note(last, steps);
+    AuditMax dtop{-inf, kAuditNoKey};
+    double trace = 0.0;
+    if (lane < NX) audit_take(dtop, sS[last][cov_tri(lane, lane)], lane);
+    if (lane == 0)
+        for (int t = 0; t < NX; ++t) trace += sS[last][cov_tri(t, t)];
+    audit_merge(zneg);
+    audit_merge(trmax);
+    audit_merge(umax);
+    audit_merge(dtop);
+    dneg = audit_merge(dneg);
+    if (lane == 0) {
+        double* r = out + size_t(i) * kPolicyCovWords;
+        const bool none = zneg.v != zneg.v || zneg.key == kAuditNoKey;
+        r[0] = -zneg.v;
+        r[1] = none ? -1.0 : double(zneg.key / (5 * (NCF > 0 ? NCF : 1)));
+        r[2] = none ? -1.0 : double(zneg.key / 5 % (NCF > 0 ? NCF : 1));
+        r[3] = none ? -1.0 : double(zneg.key % 5);
+        r[4] = trmax.v;  r[5] = audit_index(trmax, 1, false);
+        r[6] = trace;  r[7] = dtop.v;  r[8] = audit_index(dtop, 1, false);
+        r[9] = umax.v;  r[10] = audit_index(umax, NU, false);  r[11] = audit_index(umax, NU, true);
+        r[12] = -dneg;
+        r[13] = double(steps);  r[14] = feedback ? rec[pol_words - 1] : 0.0;  r[15] = 0.0;
+    }
+}
+
 }  // namespace sddp

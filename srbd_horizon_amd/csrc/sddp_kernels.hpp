@@ -35,6 +35,7 @@ constexpr int kParamGradientWords = 8;     // ... of the parameter sensitivities
 // ... of the constant sensitivities (sddp.h sddp_const_gradient_words): the kConstGradientCols columns, 6 words, 2 reserved; and the
 // dynamic LDS of its kernel: the tile of addends [N + 1][kConstGradientCols] and one row for the columns' |C theta|
 constexpr int kConstGradientWords = 40;
+constexpr int kPolicyCovWords = 16;        // ... of the plan uncertainty (sddp.h sddp_policy_covariance_words, SDDP_POLICY_COV_WORDS there)
 constexpr size_t const_gradient_lds(int N) { return sizeof(double) * (size_t(N + 1) + 1) * kConstGradientCols; }
 
 // Diagnostic build only (-DSDDP_STAMPS): per-phase shader-cycle sums, written to `scal`; never in the shipped library.

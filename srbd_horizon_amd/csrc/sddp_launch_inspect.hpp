@@ -16,6 +16,16 @@ int launch_policy_rollout(sddp_handle* h, int first, int count, int start, int s
                            (const double*)h->pol.policy, h->policy_words(), dxm, dx, du, dcost);
 }
 
+// the plan uncertainty under the exported policy: one wavefront per instance of the range, static LDS only (at most 64 KB: asserted in
+// the kernel).  dq / dr / dcov / ducov may be null.  has_policy<M>() builds that the mapping fits
+// (policy_covariance_fits<M>(): nx <= 64 and 64 KB of LDS), else the entry stays null.
+template <class M>
+int launch_policy_covariance(sddp_handle* h, int first, int count, int start, int steps, const double* dsigma0, const double* dq, const double* dr,
+                             double ml, double* dout, double* dcov, double* ducov) {
+    return launch_waves<M>(h, SDDP_PICK(policy_covariance_kernel), count, 0, h->N, first, count, start, steps, h->xs, h->us, h->last_params,
+                           (const double*)h->pol.policy, h->policy_words(), dsigma0, dq, dr, ml, dout, dcov, ducov);
+}
+
 // The plan inspectors (sddp_handle.hpp PlanSource): one wavefront per instance of the range.  Every build has them.
 // the plan audit: nothing but registers
 template <class M>
@@ -63,6 +73,7 @@ template <class M>
 ModelOps::InspectOps inspect_ops() {
     ModelOps::InspectOps o;
     if constexpr (has_policy<M>()) o.policy_rollout = launch_policy_rollout<M>;
+    if constexpr (has_policy<M>() && policy_covariance_fits<M>()) o.policy_covariance = launch_policy_covariance<M>;
     o.audit = launch_audit<M>;
     o.stationarity = launch_stationarity<M>;
     o.cost_terms = launch_cost_terms<M>;

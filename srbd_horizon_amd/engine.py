@@ -213,6 +213,37 @@ class DdpEngine:
         return self._to_numpy(n, [(max(s, 0) + 1, self.nx), (max(s, 0), self.nu), ()],
                               lambda x, u, cost: self.policy_rollout_device(xm, x, u, cost, first, n, start, s))
 
+    def policy_covariance_device(self, sigma0, out, q=None, r=None, cov=None, ucov_diag=None, first: int = 0, count: int | None = None,
+                                 start: int = 0, steps: int | None = None, friction: float = 0.0):
+        """The covariance of the state under the exported policy, linearised along the plan (include/sddp.h, "plan uncertainty"):
+        from sigma0 [count, nx, nx] at node `start` (symmetric; its lower triangle is read), S_{j+1} = A_k S_j A_k^T + B_k diag(r) B_k^T +
+        diag(q) with A_k = f_x + f_u K_k, B_k = f_u, k = start + j.  out [count, POLICY_COV_WORDS]: the records (_lib.POLICY_COV_* words;
+        word 0 the smallest cone margin of a stance force in standard deviations).  q [count, nx] / r [count, nu]: process / actuation
+        variances, or None: 0.  cov [count, steps + 1, nx, nx] (row j = S_j) / ucov_diag [count, steps, nu] (row j = diag K_k S_j K_k^T),
+        or None.  Device tensors; steps None: to the last kept knot.  friction > 0: the ground's coefficient for this call, else the
+        handle's.  Asynchronous, behind the solve and the policy launch."""
+        n = self._count(first, count)
+        s = int(self.policy_words()[1] - start if steps is None else steps)
+        rows = max(s, 0)                      # (a refused steps < 1 reaches the library, which says what is allowed)
+        self._chk(self.lib.sddp_policy_covariance_device(
+            self.h, int(first), n, int(start), s, self._dev(sigma0, (n, self.nx, self.nx)), self._dev_or_null(q, (n, self.nx)),
+            self._dev_or_null(r, (n, self.nu)), float(friction), self._dev(out, (n, _lib.POLICY_COV_WORDS)),
+            self._dev_or_null(cov, (n, rows + 1, self.nx, self.nx)), self._dev_or_null(ucov_diag, (n, rows, self.nu))))
+        return out
+
+    def policy_covariance(self, sigma0, q=None, r=None, first: int = 0, count: int | None = None, start: int = 0, steps: int | None = None,
+                          friction: float = 0.0):
+        """policy_covariance_device from and to numpy: sigma0 [n, nx, nx], q [n, nx] or None, r [n, nu] or None ->
+        dict(record [n, POLICY_COV_WORDS], cov [n, steps + 1, nx, nx], ucov_diag [n, steps, nu]); waits for the stream."""
+        import torch
+        n = self._count(first, count)
+        s = int(self.policy_words()[1] - start if steps is None else steps)
+        up = lambda a, shape: None if a is None else torch.from_numpy(self._c(a, shape)).cuda()      # noqa: E731
+        s0, dq, dr = up(sigma0, (n, self.nx, self.nx)), up(q, (n, self.nx)), up(r, (n, self.nu))
+        rec, cov, ud = self._to_numpy(n, [(_lib.POLICY_COV_WORDS,), (max(s, 0) + 1, self.nx, self.nx), (max(s, 0), self.nu)],
+                                      lambda out, cv, uc: self.policy_covariance_device(s0, out, dq, dr, cv, uc, first, n, start, s, friction))
+        return dict(record=rec, cov=cov, ucov_diag=ud)
+
     # ---- the plan inspectors: audit, stationarity certificate, cost breakdown, parameter and constant sensitivities (DESIGN.md section 5, "Plan inspectors") ----------------
     # Each reads the instances [first, first + count) of a handle that has solved: the handle's own plan (x, u None) or the caller's
     # device tensors, whose block i belongs to instance first + i.  Every build has them; the *_device forms are asynchronous,

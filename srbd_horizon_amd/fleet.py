@@ -167,6 +167,18 @@ class FleetQueue:
         server whose payload estimate its plans' costs are most sensitive to."""
         return self._inspect(self.eng.const_gradient_device, out, nodes=nodes)
 
+    def policy_covariance(self, sigma0, out, q=None, r=None, cov=None, ucov_diag=None, start: int = 0, steps: int | None = None,
+                          friction: float = 0.0):
+        """The plan-uncertainty records (DdpEngine.policy_covariance_device) of the instances the last flush / solve_sliced /
+        solve_within solved, from the first n rows of the device tensor sigma0 [>= n, nx, nx] (q [>= n, nx], r [>= n, nu]: likewise, or
+        None) into the first n rows of out [>= n, 16] (cov [>= n, steps + 1, nx, nx], ucov_diag [>= n, steps, nu]: likewise, or None);
+        launched behind whatever that call launched (a queue with policy=True: behind its policy launch; without one the records say
+        ok = 0 and the propagation is the open-loop one).  -> n; 0, and nothing launched, before the first of them.  What tells a
+        fleet server which robots' plans do not absorb the estimator's noise."""
+        def launch(o, first, n, sigma0, **opt):
+            return self.eng.policy_covariance_device(sigma0, o, first=first, count=n, start=start, steps=steps, friction=friction, **opt)
+        return self._inspect(launch, out, sigma0=sigma0, q=q, r=r, cov=cov, ucov_diag=ucov_diag)
+
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
         `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the
