@@ -309,6 +309,50 @@ int  sddp_policy_covariance_device(sddp_handle* h, int first, int count, int sta
                                    const double* d_r /*[count][nu] or NULL*/, double friction_coefficient,
                                    double* d_out /*[count][16]*/, double* d_cov /*[count][steps+1][nx][nx] or NULL*/,
                                    double* d_ucov_diag /*[count][steps][nu] or NULL*/);
+/* ---- cost-to-go export (v9): the value function per node, and its prediction at a measured state ----------------------------------
+ * The policy says what to do about a disturbance; this says what the disturbance COSTS.  The sweep of sddp_policy_range_device holds,
+ * at every node k, the quadratic model of the cost-to-go around the stored trajectory,
+ *       V_k(x_k + d) ~ c_k + expected_k + vx_k . d + 1/2 d^T Vxx_k d,
+ * in its tiles, next to the gains it derives from them.  With the value export enabled, the SAME launch stores that model for the
+ * nodes 0 .. nodes - 1 of every instance of its range -- the sweep the policy record describes (mu_used, theta_used, the defect rule,
+ * the retry ladder: the values are those of the sweep that passed) -- and nothing else changes: the solve results and the policy
+ * records are bit for bit what they are without it.
+ *     value [B][words],  words = nodes * (nx * nx + nx + 2), node-major; per node k:
+ *         0               c_k: the cost of the stored trajectory from node k on; c_N = L_N, c_k = L_k + c_{k+1}, added in this order, L
+ *                         the model's own stage / terminal cost (what sddp_eval_knots returns)
+ *         1               expected_k = -(dV1 + dV2) of the knots j >= k (the sweep's running sums; expected_N = 0).  At node 0 it has the
+ *                         bits of the policy record's `expected` word
+ *         2 .. nx + 1     vx_k: Vx after knot k (oracle/ddp.py backward_pass): Qx + Qux^T kff, with open gaps including the Vxx d term
+ *                         carried from node k + 1; at node N it is l_x,N
+ *         then nx * nx    Vxx_k, row-major, symmetric bit for bit (the pad row / column of an odd nx is not stored)
+ *     Where the policy record says ok = 0 (status 3, or the regularisation overflowed) every value word of the instance is 0.0.
+ * The approximation, plainly: Vxx is the sweep's own second order -- Gauss-Newton, plus the exact torque term where theta_used = 1
+ * (second_order = 1 after a full step) -- regularised by mu_used in Quu only.  It is exact for a linear-quadratic problem (lip30) and
+ * first-order correct elsewhere: c_k + vx_k . d matches the re-solved cost to O(|d|^2), the quadratic term is a model, not the Hessian
+ * of the optimal cost.
+ * Size: srbd61 costs 3 784 doubles (30 KB) per node and instance, srbd37 1 408, lip30 932, srbd13 184.
+ * sddp_enable_value: allocates the buffer (zeros); nodes in 1..N+1 keeps the nodes 0 .. nodes - 1, independent of the policy's knots;
+ *   0 frees it.  It needs sddp_enable_policy first (SDDP_ERR_ARG otherwise, so: on every build without a policy kernel), and
+ *   sddp_enable_policy(h, 0) frees the value buffer too.
+ * sddp_value_words: doubles per instance, and the nodes kept.
+ * sddp_fetch_value: records [first, first + count) to a host pointer [count][words]; waits for the stream.
+ * sddp_value_at_device: for b = first + i and the kept node k = node, d = x_meas[i] - x_k[b] (the handle's xs), with fixed arithmetic,
+ * so that no lane mapping, range or slot changes a bit:
+ *       t[r] starts at 0.0 and adds fma(Vxx[r][j], d[j], .) for j = 0 .. nx - 1;
+ *       lin starts at 0.0 and adds fma(vx[r], d[r], .), r ascending;   q2 starts at 0.0 and adds fma(d[r], t[r], .), r ascending;
+ *       quad = 0.5 * q2.
+ *   d_out [count][8]:
+ *    0  c_k + expected_k + lin + quad, added left to right        1  lin        2  quad        3  c_k        4  expected_k
+ *    5  max_r |d[r]| (NaN propagates)        6  ok of the policy record        7  k
+ *   ok = 0: words 0 .. 4 are 0.0.  A NaN in x_meas or in the record propagates into the words it enters.
+ *   Asynchronous on the handle's stream, behind the solve and the policy launch; it writes nothing but d_out, uses none of the slots'
+ *   work buffers, and the result of an instance does not depend on the range it was part of.  SDDP_ERR_ARG, with a message:
+ *   sddp_enable_value has not been called, no solve has run, a range outside the handle, a node that is not kept, a NULL pointer.  A
+ *   value buffer no policy launch has filled is zeros (with ok = 0 in the policy record): legal, all zeros. */
+int  sddp_enable_value(sddp_handle* h, int nodes);
+int  sddp_value_words(sddp_handle* h, int* words, int* nodes);
+int  sddp_fetch_value(sddp_handle* h, int first, int count, double* out /*[count][words]*/);
+int  sddp_value_at_device(sddp_handle* h, int first, int count, int node, const double* d_x_meas /*[count][nx]*/, double* d_out /*[count][8]*/);
 /* ---- plan audit (v9): constraint violations of a plan, computed on the device ---------------------------------------------------
  * The solver treats every inequality and every contact constraint softly (a barrier that is off by default, penalty rows, Euler
  * steps without renormalisation), so converged = 1 and a low cost do not say whether a plan is admissible.  The audit measures it:
@@ -720,6 +764,8 @@ int  sddp_fetch(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats 
                                   sddp_enable_resume */
 #define SDDP_BUF_CLASSES 12    /* class labels [B] (int, -1: unlabelled: the caller's, or the handle's own under
                                   sddp_enable_auto_classes); SDDP_ERR_ARG without a class table */
+#define SDDP_BUF_VALUE (SDDP_BUF_CLASSES + 1) /* = 13: value records [B][words] (the cost-to-go export above); SDDP_ERR_ARG without
+                                                 sddp_enable_value */
 int  sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes);
 /* average device time (ms) of the last `sddp_solve*` kernel launch measured with HIP events on the handle's stream */
 int  sddp_last_kernel_ms(sddp_handle* h, double* ms);

@@ -24,6 +24,9 @@ MODEL_IDS = {"srbd13": 0, "srbd37": 1, "lip30": 2, "srbd61": 3}
 # the buffer ids of sddp_device_ptr (include/sddp.h SDDP_BUF_*; engine.device_buffer)
 (BUF_XS, BUF_US, BUF_STATS, BUF_GAINS, BUF_X0, BUF_PARAMS, BUF_ORDER, BUF_SLOT_TIMES, BUF_POLICY, BUF_LOG, BUF_LOG_COUNTS, BUF_CLOCK,
  BUF_CLASSES) = range(13)
+# ... and the value records (SDDP_BUF_VALUE, which the header derives from SDDP_BUF_CLASSES: the thirteen above are the ids that
+# callers once passed as bare numbers, and tests/test_abi.py pins that set)
+DEVICE_BUF_VALUE = BUF_CLASSES + 1
 
 
 class SddpOptions(C.Structure):
@@ -70,6 +73,15 @@ POLICY_COV_WORDS = 16
 (POLICY_COV_MIN_Z, POLICY_COV_Z_NODE, POLICY_COV_Z_CONTACT, POLICY_COV_Z_ROW, POLICY_COV_MAX_TRACE, POLICY_COV_MAX_TRACE_NODE,
  POLICY_COV_TRACE, POLICY_COV_MAX_VAR, POLICY_COV_MAX_VAR_STATE, POLICY_COV_MAX_UVAR, POLICY_COV_MAX_UVAR_NODE, POLICY_COV_MAX_UVAR_INPUT,
  POLICY_COV_MIN_VAR, POLICY_COV_STEPS, POLICY_COV_OK) = range(15)
+# one row of sddp_value_at_device (include/sddp.h), its words by name, and the doubles per node of a value record (sddp_value_words)
+VALUE_AT_WORDS = 8
+VALUE_AT_FIELDS = ("value", "lin", "quad", "c", "expected", "delta_inf", "ok", "node")
+
+
+def value_node_words(nx: int) -> int:
+    return nx * nx + nx + 2
+
+
 # the words of one record of the stationarity certificate (include/sddp.h sddp_stationarity_range_device), by name
 STATIONARITY_FIELDS = ("stationarity", "node", "input", "scale", "lambda_0", "lambda_max", "defect", "nodes")
 # one record of the cost breakdown (include/sddp.h sddp_cost_terms_range_device): total | the families | largest | N.  The families'
@@ -132,6 +144,10 @@ SYMBOLS = {
     "sddp_apply_policy_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "sddp_apply_policy_knot_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "sddp_policy_rollout_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sddp_enable_value": (C.c_int, [_vp, C.c_int]),
+    "sddp_value_words": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "sddp_fetch_value": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_value_at_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "sddp_policy_covariance_words": (C.c_int, [_vp, _P(C.c_int)]),
     "sddp_policy_covariance_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "sddp_audit_range_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp]),

@@ -130,6 +130,7 @@ int quiesce(sddp_handle* h) {
 // Giving a group up: its buffers released, its scalars as sddp_create left them.  The caller has quiesced the handle.
 void drop_log(sddp_handle* h) { release(h, h->log.ilog); release(h, h->log.ilog_n); h->log.ilog_rows = 0; }
 void drop_policy(sddp_handle* h) { release(h, h->pol.policy); h->pol.policy_knots = 0; }
+void drop_value(sddp_handle* h) { release(h, h->val.value); h->val.nodes = 0; }
 void drop_table(sddp_handle* h) { release(h, h->table.ctab); }
 // THE statement of what rides on the resumable kernels: the time budget is disarmed and the iteration log goes with them
 void drop_resume(sddp_handle* h) {
@@ -1295,7 +1296,7 @@ int sddp_enable_policy(sddp_handle* h, int knots) {
     if (knots == h->pol.policy_knots) return SDDP_OK;
     if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still write the old buffer
     drop_policy(h);
-    if (knots == 0) return SDDP_OK;
+    if (knots == 0) { drop_value(h); return SDDP_OK; }      // the value export rides on the policy sweep: it goes with the policy
     GroupBuf g[] = {{size_t(h->B) * (size_t(knots) * h->d.nu * (h->d.nx + 1) + 4) * sizeof(double), 0x00}};      // ok = 0 until a policy launch covered the instance
     if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_policy: out of device memory");
     h->pol = {g[0], knots};
@@ -1316,7 +1317,52 @@ int sddp_policy_range_device(sddp_handle* h, int first, int count) {
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_range_device: no solve has run on this handle");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, h->last_params);
-    return h->ops->launch_policy(h, a, first, count, h->pol.policy, h->pol.policy_knots);
+    return h->ops->launch_policy(h, a, first, count, h->pol.policy, h->pol.policy_knots, h->val.value, h->val.nodes);
+}
+
+// ---- value export: the quadratic model of the cost-to-go per node, out of the policy sweep ------------------------------------------
+int sddp_enable_value(sddp_handle* h, int nodes) {
+    if (!h) return SDDP_ERR_ARG;
+    if (nodes < 0 || nodes > h->N + 1) return fail(h, SDDP_ERR_ARG, "sddp_enable_value: nodes must be in 1..N+1 (0 frees the buffer)");
+    if (nodes > 0 && !h->pol.on())
+        return fail(h, SDDP_ERR_ARG, "sddp_enable_value: call sddp_enable_policy first (the value records are stored by the policy sweep)");
+    if (nodes == h->val.nodes) return SDDP_OK;
+    if (const int rc = quiesce(h); rc != SDDP_OK) return rc;      // a launch in flight may still write the old buffer
+    drop_value(h);
+    if (nodes == 0) return SDDP_OK;
+    GroupBuf g[] = {{size_t(h->B) * size_t(nodes) * value_words(h->d.nx) * sizeof(double), 0x00}};
+    if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_enable_value: out of device memory");
+    h->val = {g[0], nodes};
+    return SDDP_OK;
+}
+
+int sddp_value_words(sddp_handle* h, int* words, int* nodes) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->val.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_value has not been called");
+    if (words) *words = h->value_words();
+    if (nodes) *nodes = h->val.nodes;
+    return SDDP_OK;
+}
+
+int sddp_fetch_value(sddp_handle* h, int first, int count, double* out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->val.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_value has not been called");
+    if (!out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    const size_t w = size_t(h->value_words());
+    return download(h, out, h->val.value + size_t(first) * w, size_t(count) * w * sizeof(double));
+}
+
+int sddp_value_at_device(sddp_handle* h, int first, int count, int node, const double* d_x_meas, double* d_out) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->val.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_value has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_value_at_device: no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (node < 0 || node >= h->val.nodes)
+        return fail(h, SDDP_ERR_ARG, "sddp_value_at_device: node must be a kept node, 0 <= node < " + std::to_string(h->val.nodes) +
+                                         " (the nodes of sddp_enable_value)");
+    if (!d_x_meas || !d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    return h->ops->inspect.value_at(h, first, count, node, d_x_meas, d_out);      // (set with launch_policy)
 }
 
 int sddp_fetch_policy(sddp_handle* h, int first, int count, double* out) {
@@ -1649,6 +1695,9 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
         case SDDP_BUF_POLICY:   // the policy buffer [B][words] of sddp_enable_policy / sddp_policy_range_device
             if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
             *ptr = h->pol.policy; n = (long long)(size_t(h->B) * h->policy_words() * sizeof(double)); break;
+        case SDDP_BUF_VALUE:   // the value buffer [B][words] of sddp_enable_value / sddp_policy_range_device
+            if (!h->val.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_value has not been called");
+            *ptr = h->val.value; n = (long long)(size_t(h->B) * h->value_words() * sizeof(double)); break;
         case SDDP_BUF_LOG:   // the iteration log [B][rows][16] and its record counts [B] of sddp_enable_iteration_log
         case SDDP_BUF_LOG_COUNTS:
             if (!h->log.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_iteration_log has not been called");

@@ -85,7 +85,8 @@ struct ModelOps {
     int (*launch_cost_keys)(sddp_handle*, const SolveArgs&, int, int) = nullptr;
     int (*launch_backward)(sddp_handle*, const SolveArgs&);
     int (*launch_forward)(sddp_handle*, const SolveArgs&);
-    int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int) = nullptr;   // policy export; null: the build has none
+    // policy export: first, count, the policy buffer and its knots, the value buffer (or null) and its nodes; null: the build has none
+    int (*launch_policy)(sddp_handle*, SolveArgs, int, int, double*, int, double*, int) = nullptr;
     // the knot evaluation of the parity tests (sddp_eval_knots; main unit, on purpose: sddp_kernels.hpp eval_knots_kernel)
     void (*launch_eval_knots)(const DevConsts&, int, int, const int*, const double*, const double*, const double*, double*, double*,
                               double*, double*, double*, double*);
@@ -99,6 +100,8 @@ struct ModelOps {
         // coefficient, out, the covariances or null, diag of the input covariances or null; null with launch_policy
         int (*policy_covariance)(sddp_handle*, int, int, int, int, const double*, const double*, const double*, double, double*, double*,
                                  double*) = nullptr;
+        // the value records evaluated at a measured state: first, count, node, x_meas, out; null with launch_policy
+        int (*value_at)(sddp_handle*, int, int, int, const double*, double*) = nullptr;
         // the plan inspectors (PlanSource): first, count, [audit: start, steps,] the trajectory, then the inspector's own arguments --
         // audit: linearised friction coefficient, out; stationarity: out, lambda or null, reduced gradient or null; cost breakdown: the
         // user rows' table with zero weights or null, out, the per-node addends or null
@@ -205,6 +208,12 @@ struct sddp_handle {
         int policy_knots = 0;
         bool on() const { return policy != nullptr; }
     } pol;
+    // value export (sddp_enable_value; needs `pol`): on = every policy launch stores the value records of its range as well
+    struct Value {
+        double* value = nullptr;        // [B][nodes][nx * nx + nx + 2]
+        int nodes = 0;
+        bool on() const { return value != nullptr; }
+    } val;
     // heterogeneous fleet (sddp_set_instance_consts): one DevConsts row per instance; on = every kernel of the handle is launched in
     // its table instantiation, which reads instance b's row instead of the kernel-argument copy of `dc`
     struct InstanceTable {
@@ -237,6 +246,7 @@ struct sddp_handle {
     size_t n_u() const { return size_t(B) * N * d.nu; }
     size_t n_p() const { return size_t(B) * (N + 1) * d.np; }
     int policy_words() const { return pol.policy_knots * d.nu * (d.nx + 1) + 4; }
+    int value_words() const { return val.nodes * sddp::value_words(d.nx); }      // per instance
     size_t n_g() const { return size_t(B) * N * d.nu * (d.nx + 1); }
 };
 

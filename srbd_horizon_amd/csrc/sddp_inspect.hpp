@@ -815,4 +815,65 @@ __global__ __launch_bounds__(kWave) void policy_covariance_kernel(ConstsArg<Tab.
     }
 }
 
+// -----------------------------------------------------------------------------------------------------------------
+// Cost-to-go at a measured state (sddp_value_at_device): the quadratic model of the value record `val` [B][vnodes][value_words(NX)]
+// (sddp_enable_value: per node c | expected | Vx | Vxx) of instance b = first + i at node `node`, evaluated at
+// delta = x_meas[i] - x_node[b]:
+//     t[r] = sum_j Vxx[r][j] delta[j];   lin = sum_r Vx[r] delta[r];   quad = 0.5 * sum_r delta[r] t[r]
+// every sum one FMA chain from 0.0 in ascending index order (include/sddp.h has the table of the eight output words), so that no
+// lane mapping, range or slot changes a bit.  ok = 0 in the policy record `pol` [B][pol_words]: words 0 .. 4 are 0.0.
+// One wavefront per instance, no model code: the constants argument is the launcher's (launch_waves) and is not read.  The node's
+// Vxx is fetched once by coalesced loads into LDS with an odd row stride, so that the row products -- lane r owns row r, delta read
+// as a broadcast -- are LDS reads without a bank conflict: 61 x 61 words of LDS traffic for 2 x 61 x 61 flops on srbd61, the reads
+// are the cost.  The two short chains over r run in every lane on broadcasts; lane 0 stores.  Static LDS only, nothing of the slots'
+// work buffers, plain vector stores to the caller's output alone.
+template <class M, class... Tab>
+__global__ __launch_bounds__(kWave) void value_at_kernel(ConstsArg<Tab...>, int N, int first, int count, int node,
+                                                         const double* __restrict__ xs, const double* __restrict__ val, int vnodes,
+                                                         const double* __restrict__ pol, int pol_words,
+                                                         const double* __restrict__ x_meas, double* __restrict__ out) {
+    constexpr int NX = M::NX, SV = NX | 1, VW = value_words(NX);
+    static_assert(NX <= kWave, "one lane per row of Vxx");
+    static_assert(sizeof(double) * (NX * SV + 3 * NX) <= 64 * 1024, "static LDS");
+    __shared__ double sV[NX * SV];                         // Vxx, row stride SV
+    __shared__ double sx[3 * NX];                          // Vx | delta | t
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= count) return;
+    const int b = first + i;
+    const double* rec = val + (size_t(b) * vnodes + node) * VW;
+    const double* xk = xs + (size_t(b) * (N + 1) + node) * NX;
+    const bool ok = pol[size_t(b) * pol_words + pol_words - 1] != 0.0;
+    for (int e = lane; e < NX * NX; e += kWave) sV[(e / NX) * SV + e % NX] = rec[2 + NX + e];
+    if (lane < NX) {
+        sx[lane] = rec[2 + lane];
+        sx[NX + lane] = x_meas[size_t(i) * NX + lane] - xk[lane];
+    }
+    wave_sync();
+    if (lane < NX) {
+        double t = 0.0;
+        for (int j = 0; j < NX; ++j) t = fma(sV[lane * SV + j], sx[NX + j], t);
+        sx[2 * NX + lane] = t;
+    }
+    wave_sync();
+    double lin = 0.0, q2 = 0.0, dinf = 0.0;
+    for (int r = 0; r < NX; ++r) {
+        const double d = sx[NX + r];
+        lin = fma(sx[r], d, lin);
+        q2 = fma(d, sx[2 * NX + r], q2);
+        dinf = nan_max(dinf, fabs(d));
+    }
+    if (lane == 0) {
+        double* o = out + size_t(i) * kValueAtWords;
+        const double quad = 0.5 * q2, c = rec[0], expected = rec[1];
+        o[0] = ok ? ((c + expected) + lin) + quad : 0.0;
+        o[1] = ok ? lin : 0.0;
+        o[2] = ok ? quad : 0.0;
+        o[3] = ok ? c : 0.0;
+        o[4] = ok ? expected : 0.0;
+        o[5] = dinf;
+        o[6] = ok ? 1.0 : 0.0;
+        o[7] = double(node);
+    }
+}
+
 }  // namespace sddp

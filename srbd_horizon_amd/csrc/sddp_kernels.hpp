@@ -35,6 +35,9 @@ constexpr int kParamGradientWords = 8;     // ... of the parameter sensitivities
 // ... of the constant sensitivities (sddp.h sddp_const_gradient_words): the kConstGradientCols columns, 6 words, 2 reserved; and the
 // dynamic LDS of its kernel: the tile of addends [N + 1][kConstGradientCols] and one row for the columns' |C theta|
 constexpr int kConstGradientWords = 40;
+// doubles per node of a value record (sddp.h sddp_value_words): c | expected | Vx [nx] | Vxx [nx][nx]; and of one sddp_value_at_device row
+__host__ __device__ constexpr int value_words(int nx) { return nx * nx + nx + 2; }
+constexpr int kValueAtWords = 8;
 constexpr int kPolicyCovWords = 16;        // ... of the plan uncertainty (sddp.h sddp_policy_covariance_words, SDDP_POLICY_COV_WORDS there)
 constexpr size_t const_gradient_lds(int N) { return sizeof(double) * (size_t(N + 1) + 1) * kConstGradientCols; }
 
@@ -397,9 +400,11 @@ __device__ void sweep_tables(const DevConsts& c, double* s, int lane) {
 template <class M, bool KEEP = false>
 __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restrict__ P, const double* __restrict__ dft,
                                const double* __restrict__ rec, double* __restrict__ gains, double mu, double theta, double* s,
-                               int lane, double& dV1, double& G1, double& G2, double& qu_inf, bool has_gap SDDP_T_ARG, int keep = 0) {
+                               int lane, double& dV1, double& G1, double& G2, double& qu_inf, bool has_gap SDDP_T_ARG, int keep = 0,
+                               double* __restrict__ val = nullptr, int vnodes = 0) {
     // has_gap = false: all defects are zero (every iteration after the first full step): v' = Vx, no Vxx d product
     // KEEP (policy export, policy_kernel): only the gains of the knots < keep are stored; `gains` then holds `keep` knots
+    // val (KEEP only; value export, sddp_enable_value; null: off): the instance's value record, the nodes < vnodes of it (store_value)
     using L = Lds<M>;
     constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NE = M::NE, NEV = M::NEV, NREC = M::NREC, NP = M::NP;
     constexpr int NXP = L::NXP, NIP = L::NIP, NZP = L::NZP, NUP = L::NUP, SQ = L::SQ;
@@ -518,6 +523,22 @@ __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restri
         for (int t = 0; t < RGW; ++t)
             if (lane + t * kWave < NGW) gk[lane + t * kWave] = v[t];
     };
+    // value export: the quadratic model of the cost-to-go at node kk as the tiles hold it, LDS -> HBM/L2, whole-wave contiguous stores:
+    // word 1 = expected_kk = -(dV1 + dV2) of the knots >= kk, then Vx (NX), then Vxx (NX x NX) row-major without the pad row / column of
+    // an odd NX.  Entry (i, j) is read from the lower triangle, so the record is symmetric bit for bit at the terminal node as well.
+    // Word 0 (the cost from node kk on) is policy_instance's (value_costs).
+    auto store_value = [&](int kk, double expected) {
+        if constexpr (KEEP) {
+            if (val == nullptr || kk >= vnodes) return;
+            double* vk = val + size_t(kk) * value_words(NX);
+            for (int e = lane; e < NX + NX * NX; e += kWave) {
+                const int i = e < NX ? 0 : (e - NX) / NX, j = e < NX ? 0 : (e - NX) % NX;
+                vk[2 + e] = e < NX ? s[L::VX + e] : s[L::VXX + (i > j ? i : j) * NXP + (i > j ? j : i)];
+            }
+            if (lane == 0) vk[1] = expected;
+        }
+    };
+    store_value(N, 0.0);
     drain_vmem();
     fetch(N - 1);
     for (int k = N - 1; k >= 0; --k) {
@@ -765,6 +786,7 @@ __device__ bool backward_sweep(const DevConsts& c, int N, const double* __restri
         }
         wave_sync();
         SDDP_TICK(6)
+        store_value(k, -0.5 * dV1);
     }
     store_gains(0);
     G1 = wave_sum(G1);
@@ -1251,9 +1273,43 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2))) void
 // slot's gains buffer (sddp_device_ptr(3)) is not touched.
 // -----------------------------------------------------------------------------------------------------------------
 constexpr int kPolicyTail = 4;
+// Value export (sddp_enable_value): word 0 of the nodes < vnodes of an instance's value record, c_k = the cost of the stored trajectory
+// from node k on: c_N = L_N, c_k = L_k + c_{k+1}, added in this order.  L is the model code's own (M::step / M::term_cost: what
+// sddp_eval_knots returns), one lane per knot, 64 knots at a time from the horizon's end; the running sum passes through the lanes in
+// knot order (one shuffle and one add per knot), so the sum does not depend on N's relation to the wavefront.  Called by ONE wavefront.
+template <class M>
+__device__ __forceinline__ void value_costs(const DevConsts& c, const int N, const double* __restrict__ xs, const double* __restrict__ us,
+                                            const double* __restrict__ P, double* __restrict__ vout, const int vnodes, const int lane) {
+    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
+    double run = 0.0;                                    // c_{k+1}: wave-uniform
+    for (int base = (N / kWave) * kWave; base >= 0; base -= kWave) {
+        const int k = base + lane;
+        double Lk = 0.0;
+        if (k <= N) {
+            double x[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = xs[k * NX + i];
+            if (k < N) {
+                double u[NU], xn[NX];
+#pragma unroll
+                for (int i = 0; i < NU; ++i) u[i] = us[k * NU + i];
+                Lk = M::step(c, x, u, P + k * NP, k, xn);
+            } else {
+                Lk = M::term_cost(c, x, P + k * NP);
+            }
+        }
+        double ck = 0.0;
+        for (int j = (N - base < kWave - 1 ? N - base : kWave - 1); j >= 0; --j) {
+            const double Lj = __shfl(Lk, j, kWave);
+            run = base + j == N ? Lj : Lj + run;
+            if (lane == j) ck = run;
+        }
+        if (k <= N && k < vnodes) vout[size_t(k) * value_words(NX)] = ck;
+    }
+}
 template <class M>
 __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, const int b, const int slot, double* __restrict__ pol,
-                                                const int keep) {
+                                                const int keep, double* __restrict__ val, const int vnodes) {
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC, NGW = NU * (NX + 1);
     const int lane = threadIdx.x;
     const int N = A.N;
@@ -1264,6 +1320,7 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     double* dft = A.dft + size_t(slot) * N * NX;
     double* rec = A.rec + size_t(slot) * (N + 1) * NREC;
     double* out = pol + size_t(b) * (size_t(keep) * NGW + kPolicyTail);
+    double* vout = val ? val + size_t(b) * vnodes * value_words(NX) : nullptr;      // value export: null = off (wave-uniform)
     const sddp_stats st = A.stats[b];
     sweep_tables<M>(A.c, s, lane);
     const bool has_gap = st.gap > o.gap_tol;
@@ -1280,7 +1337,7 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     // an iterate the solve refused for its non-finite cost (status 3) has no policy: the solve makes no sweep there, and a sweep
     // whose Quu happens to stay finite would pass and put the NaN into the gains.  Wave-uniform: one record read by every lane.
     if (st.status != 3) while (true) {
-        ok = backward_sweep<M, true>(A.c, N, P, dft, rec, out, mu, theta, s, lane, dV1, G1, G2, qu_inf, has_gap SDDP_T_PASS, keep);
+        ok = backward_sweep<M, true>(A.c, N, P, dft, rec, out, mu, theta, s, lane, dV1, G1, G2, qu_inf, has_gap SDDP_T_PASS, keep, vout, vnodes);
         if (ok) break;
         if (theta != 0.0) { theta = 0.0; continue; }
         mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
@@ -1289,6 +1346,10 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     if (!ok) {   // regularisation overflow or a status-3 iterate: zeros, never the rows a failed sweep left behind
         drain_vmem();
         for (int e = lane; e < keep * NGW; e += kWave) out[e] = 0.0;
+    }
+    if (vout) {   // the value record of the sweep that passed: its costs c_k; ok = 0: every word 0.0, like the gains
+        if (ok) value_costs<M>(A.c, N, xs, us, P, vout, vnodes, lane);
+        else for (int e = lane; e < vnodes * value_words(NX); e += kWave) vout[e] = 0.0;
     }
     if (lane == 0) {
         double* tail = out + size_t(keep) * NGW;
@@ -1301,7 +1362,7 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
 // out beside the plain one: every form that folded the two into one template moved the register allocation of one of them
 // (profiles/hetero_merge/README.md).
 template <class M>
-__global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __restrict__ pol, int keep) {
+__global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __restrict__ pol, int keep, double* __restrict__ val, int vnodes) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     const int slot = blockIdx.x;
     const bool queued = A.qhead != nullptr;
@@ -1311,14 +1372,15 @@ __global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __re
         i = __builtin_amdgcn_readfirstlane(i);
     }
     while (i < A.count) {
-        policy_instance<M>(A, s, A.first + i, slot, pol, keep);
+        policy_instance<M>(A, s, A.first + i, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
     }
 }
 template <class M>
-__global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __restrict__ pol, int keep, const DevConsts* __restrict__ ctab) {
+__global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __restrict__ pol, int keep, double* __restrict__ val, int vnodes,
+                                                         const DevConsts* __restrict__ ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     const int slot = blockIdx.x;
     const bool queued = A.qhead != nullptr;
@@ -1329,7 +1391,7 @@ __global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __
     }
     while (i < A.count) {
         const int b = index_of(A.first + i, ctab);
-        policy_instance<M>(args_of(A, b, ctab), s, b, slot, pol, keep);
+        policy_instance<M>(args_of(A, b, ctab), s, b, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);

@@ -274,8 +274,10 @@ template <class M, bool SINK = false, bool KEEP = false>
 __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, const double* __restrict__ P, const double* __restrict__ dft,
                                   const double* __restrict__ rec, double* __restrict__ gains, double mu, double theta,
                                   double* s, int tid, double& dV1, double& G1, double& G2, double& qu_inf,
-                                  const double (&qconst)[LdsMW<M>::TQ][3][3] SDDP_T_ARG, int keep = 0) {
+                                  const double (&qconst)[LdsMW<M>::TQ][3][3] SDDP_T_ARG, int keep = 0,
+                                  double* __restrict__ val = nullptr, int vnodes = 0) {
     // KEEP (policy export, policy_kernel_mw): only the gains of the knots < keep are stored; `gains` then holds `keep` knots
+    // val (KEEP only; value export, sddp_enable_value; null: off): the instance's value record, the nodes < vnodes of it (store_value)
     // qconst: the constant extra rows' share of this thread's 3x3 Q blocks (mw_const_block, once per kernel)
     using L = LdsMW<M>;
     constexpr int NX = M::NX, NU = M::NU, NZ = M::NZ, NE = M::NE, NEV = M::NEV, NREC = M::NREC, NP = M::NP;
@@ -350,6 +352,27 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
         for (int e = tid; e < NGW; e += kThreadsMW) gk[e] = e < NU ? s[L::KF + e] : s[L::KT + ((e - NU) % NX) * SK + (e - NU) / NX];
     };
     __syncthreads();
+    // value export (backward_sweep's store_value: same record): the tiles of node kk as the barrier in front of the call left them,
+    // by all four waves.  expected_kk sums the waves' running dV1 shares (published in CTL + 4 .. 7 behind the knot's Gauss-Jordan) in
+    // the order of the sweep's own final sum, so that node 0 has the bits of the policy record's word.  Nothing writes VX / VXX / those
+    // control words between that barrier and the next one.
+    auto store_value = [&](int kk, bool terminal) {
+        if constexpr (KEEP) {
+            if (val == nullptr || kk >= vnodes) return;
+            double* vk = val + size_t(kk) * value_words(NX);
+            for (int e = tid; e < NX + NX * NX; e += kThreadsMW) {
+                const int i = e < NX ? 0 : (e - NX) / NX, j = e < NX ? 0 : (e - NX) % NX;
+                vk[2 + e] = e < NX ? s[L::VX + e] : s[L::VXX + (i > j ? i : j) * SV + (i > j ? j : i)];
+            }
+            if (tid == 0) {
+                double dv = 0.0;
+#pragma unroll
+                for (int w = 0; w < kWavesMW; ++w) dv += s[L::CTL + 4 + w];
+                vk[1] = terminal ? 0.0 : -0.5 * dv;
+            }
+        }
+    };
+    store_value(N, true);
     for (int k = N - 1; k >= 0; --k) {
         if constexpr (SINK) {   // (mw_sink: nothing derived from the thread index is carried across knots -- it would be spilled)
             asm volatile("" : "+v"(tid));
@@ -750,6 +773,7 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
                 }
             }
             dv_acc += dv;                                 // only lane NU's value is used
+            if constexpr (KEEP) { if (val != nullptr && lane == NU) s[L::CTL + 4 + wave] = dv_acc; }      // value export: store_value
         }
         SDDP_TICK(20)
         __syncthreads();
@@ -854,6 +878,7 @@ __device__ __forceinline__ bool backward_sweep_mw(const DevConsts& c, int N, con
         }
         __syncthreads();
         SDDP_TICK(6)
+        store_value(k, false);
     }
     store_gains(0);
     // ---- combine the per-wave partial sums (same values, same order in every thread)
@@ -1400,7 +1425,7 @@ __global__ __launch_bounds__(kThreadsMW) __attribute__((amdgpu_waves_per_eu(2)))
 // policy export on 4 waves (policy_instance in sddp_kernels.hpp: same record, same rule); called by every thread
 template <class M, bool SINK>
 __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s, const int b, const int slot, double* __restrict__ pol,
-                                                   const int keep) {
+                                                   const int keep, double* __restrict__ val, const int vnodes) {
     constexpr int NX = M::NX, NU = M::NU, NP = M::NP, NREC = M::NREC, NGW = NU * (NX + 1);
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid / kWave);
     const int N = A.N;
@@ -1411,6 +1436,7 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
     double* dft = A.dft + size_t(slot) * N * NX;
     double* rec = A.rec + size_t(slot) * (N + 1) * NREC;
     double* out = pol + size_t(b) * (size_t(keep) * NGW + kPolicyTail);
+    double* vout = val ? val + size_t(b) * vnodes * value_words(NX) : nullptr;      // value export: null = off (workgroup-uniform)
     const sddp_stats st = A.stats[b];
     SDDP_T_DECL
     sweep_tables_mw<M>(A.c, s, tid);
@@ -1428,7 +1454,7 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
     double dV1, G1, G2, qu_inf;
     bool ok = false;
     if (st.status != 3) while (true) {   // a status-3 iterate has no policy (policy_instance); workgroup-uniform
-        ok = backward_sweep_mw<M, SINK, true>(A.c, N, P, dft, rec, out, mu, theta, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS, keep);
+        ok = backward_sweep_mw<M, SINK, true>(A.c, N, P, dft, rec, out, mu, theta, s, tid, dV1, G1, G2, qu_inf, qconst SDDP_T_PASS, keep, vout, vnodes);
         if (ok) break;
         if (theta != 0.0) { theta = 0.0; continue; }
         mu = fmax(mu, 0.0) * 10.0 + o.mu_min;
@@ -1437,6 +1463,10 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
     if (!ok) {   // regularisation overflow or a status-3 iterate: zeros, never the rows a failed sweep left behind
         __syncthreads();
         for (int e = tid; e < keep * NGW; e += kThreadsMW) out[e] = 0.0;
+    }
+    if (vout) {   // the value record of the sweep that passed: its costs c_k (one wavefront); ok = 0: every word 0.0, like the gains
+        if (ok) { if (wave == 0) value_costs<M>(A.c, N, xs, us, P, vout, vnodes, lane); }
+        else for (int e = tid; e < vnodes * value_words(NX); e += kThreadsMW) vout[e] = 0.0;
     }
     if (tid == 0) {
         double* tail = out + size_t(keep) * NGW;
@@ -1447,7 +1477,7 @@ __device__ __forceinline__ void policy_instance_mw(const SolveArgs& A, double* s
 
 // (two kernels, like policy_kernel / policy_kernel_h in sddp_kernels.hpp)
 template <class M>
-__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, double* __restrict__ pol, int keep) {
+__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, double* __restrict__ pol, int keep, double* __restrict__ val, int vnodes) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);      // the queue position travels through LDS (solve_queue_mw)
     const int slot = blockIdx.x;
@@ -1457,7 +1487,7 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, doub
     int i = queued ? *q_pos : slot;
     __syncthreads();
     while (i < A.count) {
-        policy_instance_mw<M, mw_sink<M>(false)>(A, s, A.first + i, slot, pol, keep);
+        policy_instance_mw<M, mw_sink<M>(false)>(A, s, A.first + i, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1466,7 +1496,8 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, doub
     }
 }
 template <class M>
-__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, double* __restrict__ pol, int keep, const DevConsts* __restrict__ ctab) {
+__global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, double* __restrict__ pol, int keep, double* __restrict__ val, int vnodes,
+                                                                   const DevConsts* __restrict__ ctab) {
     extern __shared__ __attribute__((aligned(16))) double s[];
     int* q_pos = reinterpret_cast<int*>(s + LdsMW<M>::CTL + 15);
     const int slot = blockIdx.x;
@@ -1477,7 +1508,7 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, do
     __syncthreads();
     while (i < A.count) {
         const int b = index_of(A.first + i, ctab);
-        policy_instance_mw<M, mw_sink<M>(false)>(args_of(A, b, ctab), s, b, slot, pol, keep);
+        policy_instance_mw<M, mw_sink<M>(false)>(args_of(A, b, ctab), s, b, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();

@@ -212,8 +212,9 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
 // policy export behind a solve: one sweep per instance of [first, first + count) at the returned iterate (policy_kernel /
 // policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel (the one-wave kernel: at most 8 per CU); the work
 // buffers dft / rec are the solve's, per slot.  has_policy<M>() builds only: make_ops leaves the entry null elsewhere.
+// val: the value buffer (sddp_enable_value) and the nodes it keeps, filled for the range by the same sweep; null: the export is off.
 template <class M>
-int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep) {
+int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep, double* val, int vnodes) {
     return with_table<M>(h, [&](auto... tab) {
         auto kern = pick_policy<M, decltype(tab)...>();
         int slots = 0;
@@ -223,7 +224,7 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
         int grid = 0;
         rc = queue_grid(h, a, slots, count, &grid);
         if (rc != SDDP_OK) return rc;
-        return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep, tab...);
+        return launch(h, kern, grid, threads_of<M>(), lds_bytes<M>(), a, pol, keep, val, vnodes, tab...);
     });
 }
 

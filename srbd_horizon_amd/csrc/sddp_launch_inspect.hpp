@@ -26,6 +26,14 @@ int launch_policy_covariance(sddp_handle* h, int first, int count, int start, in
                            (const double*)h->pol.policy, h->policy_words(), dsigma0, dq, dr, ml, dout, dcov, ducov);
 }
 
+// the value records of the range evaluated at measured states (sddp_value_at_device): one wavefront per instance, static LDS only.
+// has_policy<M>() builds only, like launch_policy.
+template <class M>
+int launch_value_at(sddp_handle* h, int first, int count, int node, const double* dxm, double* dout) {
+    return launch_waves<M>(h, SDDP_PICK(value_at_kernel), count, 0, h->N, first, count, node, (const double*)h->xs, (const double*)h->val.value,
+                           h->val.nodes, (const double*)h->pol.policy, h->policy_words(), dxm, dout);
+}
+
 // The plan inspectors (sddp_handle.hpp PlanSource): one wavefront per instance of the range.  Every build has them.
 // the plan audit: nothing but registers
 template <class M>
@@ -73,6 +81,7 @@ template <class M>
 ModelOps::InspectOps inspect_ops() {
     ModelOps::InspectOps o;
     if constexpr (has_policy<M>()) o.policy_rollout = launch_policy_rollout<M>;
+    if constexpr (has_policy<M>()) o.value_at = launch_value_at<M>;
     if constexpr (has_policy<M>() && policy_covariance_fits<M>()) o.policy_covariance = launch_policy_covariance<M>;
     o.audit = launch_audit<M>;
     o.stationarity = launch_stationarity<M>;

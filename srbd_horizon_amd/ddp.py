@@ -234,6 +234,25 @@ class DDPSolver:
         self.policy_info = dict(mu_used=info[0, 0], theta_used=info[0, 1], expected=info[0, 2], ok=bool(info[0, 3]))
         return [K[0, k] for k in range(M)]
 
+    def cost_to_go(self, x_meas):
+        """What starting from x_meas [nx] instead of the plan's x_0 is predicted to cost: the value function of the last solve at node 0,
+        V_0(x_meas) ~ c_0 + expected_0 + vx_0 . d + 1/2 d^T Vxx_0 d with d = x_meas - x_0 (sddp_value_at_device), from one
+        backward sweep at the RETURNED iterate.  -> a dict by _lib.VALUE_AT_FIELDS: "value" the prediction, "c" the plan's own cost,
+        "lin" / "quad" its first- and second-order parts, "ok" 0 where the sweep found no policy (then the other words are 0).  The
+        second order is the sweep's Gauss-Newton one: exact on a linear-quadratic problem, a model elsewhere.  Waits for the stream."""
+        if self.var_solution is None:
+            raise RuntimeError("cost_to_go(): no solve has run")
+        from . import _lib
+        eng = self.ddp_solver
+        try:
+            eng.policy_words()                 # keep the knots a caller of get_feedback_gains asked for
+        except RuntimeError:
+            eng.enable_policy(1)
+        eng.enable_value(1)
+        eng.policy_range_device(0, 1)
+        rec = eng.value_at(np.asarray(x_meas, dtype=float).reshape(1, eng.nx), node=0, first=0, count=1)
+        return dict(zip(_lib.VALUE_AT_FIELDS, rec[0]))
+
     def parameter_gradient(self):
         """The gradient of the last solve's cost in the problem's parameters (sddp_param_gradient_range_device): a dict
         from every Parameter's name -- rdot_ref, w_ref, orientation_tracking_gain, oref, c_ref<i>, cdot_switch<i>, on srbd13 c<i>, and

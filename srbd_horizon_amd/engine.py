@@ -244,6 +244,59 @@ class DdpEngine:
                                       lambda out, cv, uc: self.policy_covariance_device(s0, out, dq, dr, cv, uc, first, n, start, s, friction))
         return dict(record=rec, cov=cov, ucov_diag=ud)
 
+    # ---- cost-to-go export: the value function per node out of the policy sweep (include/sddp.h, "cost-to-go export") ------------
+    def enable_value(self, nodes: int):
+        """Allocate the per-instance value buffer for the nodes 0 .. nodes - 1 (1..N+1; 0 frees it).  Needs enable_policy first: every
+        policy_range_device then stores the value records of its range in the same launch."""
+        self._chk(self.lib.sddp_enable_value(self.h, int(nodes)))
+
+    def value_words(self):
+        """-> (doubles per instance record, nodes kept)"""
+        w, k = C.c_int(), C.c_int()
+        self._chk(self.lib.sddp_value_words(self.h, C.byref(w), C.byref(k)))
+        return w.value, k.value
+
+    def fetch_value(self, first: int = 0, count: int | None = None):
+        """The raw value records [count, nodes, nx * nx + nx + 2] of the last policy launch, on the host (waits for the stream)."""
+        n = self._count(first, count)
+        nodes = self.value_words()[1]
+        out = np.empty((max(n, 0), nodes, _lib.value_node_words(self.nx)))
+        self._chk(self.lib.sddp_fetch_value(self.h, int(first), n, _lib.ptr(out)))
+        return out
+
+    def value(self, first: int = 0, count: int | None = None):
+        """-> dict of CUDA tensors c [n, nodes], expected [n, nodes], vx [n, nodes, nx], Vxx [n, nodes, nx, nx] of the instances
+        [first, first + count), as the last policy launch left them: V_k(x_k + d) ~ c_k + expected_k + vx_k . d + 1/2 d^T Vxx_k d, the
+        sweep's own (Gauss-Newton) model.  Copies of the handle's buffer; waits for the stream."""
+        n = self._count(first, count)
+        nodes = self.value_words()[1]
+        if n < 1 or first < 0 or first > self.B - n:
+            raise ValueError("instance range outside the batch")
+        self.synchronize()
+        rec = self.device_view(_lib.DEVICE_BUF_VALUE, (self.B, nodes, _lib.value_node_words(self.nx)))[first:first + n]
+        nx = self.nx
+        return dict(c=rec[:, :, 0].clone(), expected=rec[:, :, 1].clone(), vx=rec[:, :, 2:2 + nx].clone(),
+                    Vxx=rec[:, :, 2 + nx:].reshape(n, nodes, nx, nx).clone())
+
+    def value_at_device(self, x_meas, out, node: int = 0, first: int = 0, count: int | None = None):
+        """The value record of node `node` evaluated at the measured states x_meas [count, nx] -> out [count, VALUE_AT_WORDS]
+        (_lib.VALUE_AT_FIELDS: value, lin, quad, c, expected, |delta|_inf, ok, node).  Device tensors; asynchronous, behind the solve and
+        the policy launch."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_value_at_device(self.h, int(first), n, int(node), self._dev(x_meas, (n, self.nx)),
+                                                self._dev(out, (n, _lib.VALUE_AT_WORDS))))
+        return out
+
+    def value_at(self, x_meas, node: int = 0, first: int = 0, count: int | None = None):
+        """value_at_device for x_meas [n, nx] as a CUDA tensor (-> a CUDA tensor [n, VALUE_AT_WORDS], asynchronous) or as a numpy array
+        (-> numpy; waits for the stream)."""
+        import torch
+        n = self._count(first, count)
+        if isinstance(x_meas, torch.Tensor):
+            return self.value_at_device(x_meas, torch.empty((max(n, 0), _lib.VALUE_AT_WORDS), dtype=torch.float64, device="cuda"), node, first, n)
+        xm = torch.from_numpy(self._c(x_meas, (n, self.nx))).cuda()
+        return self._to_numpy(n, [(_lib.VALUE_AT_WORDS,)], lambda out: self.value_at_device(xm, out, node, first, n))[0]
+
     # ---- the plan inspectors: audit, stationarity certificate, cost breakdown, parameter and constant sensitivities (DESIGN.md section 5, "Plan inspectors") ----------------
     # Each reads the instances [first, first + count) of a handle that has solved: the handle's own plan (x, u None) or the caller's
     # device tensors, whose block i belongs to instance first + i.  Every build has them; the *_device forms are asynchronous,

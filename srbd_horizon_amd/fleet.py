@@ -179,6 +179,17 @@ class FleetQueue:
             return self.eng.policy_covariance_device(sigma0, o, first=first, count=n, start=start, steps=steps, friction=friction, **opt)
         return self._inspect(launch, out, sigma0=sigma0, q=q, r=r, cov=cov, ucov_diag=ucov_diag)
 
+    def value_at(self, x_meas, out, node: int = 0):
+        """The cost-to-go records (DdpEngine.value_at_device) of the instances the last flush / solve_sliced / solve_within solved, at the
+        first n rows of the device tensor x_meas [>= n, nx] (the states measured at node `node` of each plan) into the first n rows of
+        out [>= n, 8]; launched behind whatever that call launched.  It needs the engine's enable_value and a queue with policy=True,
+        whose policy launch fills the value records (without one they are zeros with ok = 0).  -> n; 0, and nothing launched, before the
+        first of them.  What tells a fleet server, in cost units, whose plan a tick's measurements have invalidated most: word 0 - word 3
+        of a record is the predicted cost increase, and ranks the robots for the next re-solve."""
+        def launch(o, first, n, x_meas):
+            return self.eng.value_at_device(x_meas, o, node=node, first=first, count=n)
+        return self._inspect(launch, out, x_meas=x_meas)
+
     def solve_sliced(self, first_slice: int, max_iters: int):
         """The pending batches in two slices (resumable solves, include/sddp.h): ONE launch runs every instance for at most
         `first_slice` iterations and the first-knot records (u_0 | x_1 | cost | iterations) are packed behind it -- those of the
