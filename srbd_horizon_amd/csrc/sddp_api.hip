@@ -449,6 +449,37 @@ int inspect_to_host(sddp_handle* h, int first, int count, int words, double* out
     return rc;
 }
 
+// The costates of a call, for the two sensitivities <fn>: the stationarity certificate's, by its own launch for the range into the handle's
+// costate group (made here by the first call), so lambda has the bits that certificate writes; copied to d_lambda when that is given
+int costates(sddp_handle* h, const char* fn, int first, int count, const PlanSource& src, double* d_lambda) {
+    if (!h->costate.on()) {
+        GroupBuf g[] = {{h->n_x() * sizeof(double)}, {size_t(h->B) * kStationarityWords * sizeof(double)}};
+        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, std::string(fn) + ": out of device memory");
+        h->costate = {g[0], g[1]};
+    }
+    if (const int rc = h->ops->inspect.stationarity(h, first, count, src, h->costate.stat, h->costate.lam, nullptr); rc != SDDP_OK) return rc;
+    if (d_lambda)
+        HIP_TRY(h, hipMemcpyAsync(d_lambda, h->costate.lam, size_t(count) * (h->N + 1) * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return SDDP_OK;
+}
+
+// The policy-window entry points <fn> (sddp_policy_rollout_device, sddp_policy_covariance_device): what each checks first, as
+// plan_source is for the plan inspectors.  `given`: every argument of the call that may not be NULL is there
+int policy_window(sddp_handle* h, const char* fn, int first, int count, int start, int steps, bool given) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, std::string(fn) + ": no solve has run on this handle");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    if (start < 0 || steps < 1 || start > h->pol.policy_knots - steps)
+        return fail(h, SDDP_ERR_ARG, std::string(fn) + ": start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->pol.policy_knots) +
+                                         " (the knots of sddp_enable_policy)");
+    if (!given) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    return SDDP_OK;
+}
+
+// the friction coefficient of a call (its own when > 0, or the handle's), linearised as DevConsts::mu_lin is
+double call_mu_lin(const sddp_handle* h, double mu) { return (mu > 0.0 ? mu : h->consts.friction_cone_coefficient) / sqrt(2.0); }
+
 // h->xr_zero, made by the first cost breakdown of a handle with user rows: their table once more, its weight words (state rows | stage
 // rows) zero: a group of one buffer
 int make_xr_zero(sddp_handle* h) {
@@ -1393,14 +1424,8 @@ int sddp_apply_policy_device(sddp_handle* h, int first, int count, const double*
 
 int sddp_policy_rollout_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_x_meas, double* d_x_out,
                                double* d_u_out, double* d_cost_out) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
-    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: no solve has run on this handle");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (start < 0 || steps < 1 || start > h->pol.policy_knots - steps)
-        return fail(h, SDDP_ERR_ARG, "sddp_policy_rollout_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->pol.policy_knots) +
-                                         " (the knots of sddp_enable_policy)");
-    if (!d_x_meas || !d_x_out || !d_u_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    const bool given = d_x_meas && d_x_out && d_u_out;
+    if (const int rc = policy_window(h, "sddp_policy_rollout_device", first, count, start, steps, given); rc != SDDP_OK) return rc;
     return h->ops->inspect.policy_rollout(h, first, count, start, steps, d_x_meas, d_x_out, d_u_out, d_cost_out);      // (set with launch_policy)
 }
 
@@ -1413,19 +1438,10 @@ int sddp_policy_covariance_words(sddp_handle* h, int* words) {
 
 int sddp_policy_covariance_device(sddp_handle* h, int first, int count, int start, int steps, const double* d_sigma0, const double* d_q,
                                   const double* d_r, double friction_coefficient, double* d_out, double* d_cov, double* d_ucov_diag) {
-    if (!h) return SDDP_ERR_ARG;
-    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
-    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: no solve has run on this handle");
-    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
-    if (start < 0 || steps < 1 || start > h->pol.policy_knots - steps)
-        return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: start >= 0, steps >= 1 and start + steps <= " +
-                                         std::to_string(h->pol.policy_knots) + " (the knots of sddp_enable_policy)");
-    if (!d_sigma0 || !d_out) return fail(h, SDDP_ERR_ARG, "NULL argument");
+    if (const int rc = policy_window(h, "sddp_policy_covariance_device", first, count, start, steps, d_sigma0 && d_out); rc != SDDP_OK) return rc;
     if (!h->ops->inspect.policy_covariance)
         return fail(h, SDDP_ERR_ARG, "sddp_policy_covariance_device: no kernel for this build (a user build with nx > 64, or whose tiles exceed 64 KB of LDS)");
-    // the call's coefficient, or the handle's, linearised: as sddp_audit_range_device takes it
-    const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
-    return h->ops->inspect.policy_covariance(h, first, count, start, steps, d_sigma0, d_q, d_r, mu / sqrt(2.0), d_out, d_cov,
+    return h->ops->inspect.policy_covariance(h, first, count, start, steps, d_sigma0, d_q, d_r, call_mu_lin(h, friction_coefficient), d_out, d_cov,
                                              d_ucov_diag);      // (set with launch_policy)
 }
 
@@ -1437,9 +1453,7 @@ int sddp_audit_range_device(sddp_handle* h, int first, int count, int start, int
         return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: the handle's own plan is audited whole, start = 0 and steps = " + std::to_string(h->N));
     if (start < 0 || steps < 1 || start > h->N - steps)
         return fail(h, SDDP_ERR_ARG, "sddp_audit_range_device: start >= 0, steps >= 1 and start + steps <= " + std::to_string(h->N));
-    // the call's coefficient, or the handle's: linearised as DevConsts::mu_lin is
-    const double mu = friction_coefficient > 0.0 ? friction_coefficient : h->consts.friction_cone_coefficient;
-    return h->ops->inspect.audit(h, first, count, start, steps, src, mu / sqrt(2.0), d_out);
+    return h->ops->inspect.audit(h, first, count, start, steps, src, call_mu_lin(h, friction_coefficient), d_out);
 }
 
 int sddp_audit(sddp_handle* h, int first, int count, double friction_coefficient, double* out) {
@@ -1514,16 +1528,8 @@ int sddp_param_gradient_range_device(sddp_handle* h, int first, int count, const
     if (const int rc = plan_source(h, "sddp_param_gradient_range_device", first, count, d_x, d_u, d_out, &src); rc != SDDP_OK) return rc;
     if (!h->ops->inspect.param_gradient)
         return fail(h, SDDP_ERR_ARG, "sddp_param_gradient_range_device: a user build's non-linear rows have no derivative in the parameters");
-    if (!h->pgrad.on()) {      // the costates and the stationarity record of a call, for the kernel behind them
-        GroupBuf g[] = {{h->n_x() * sizeof(double)}, {size_t(h->B) * kStationarityWords * sizeof(double)}};
-        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_param_gradient_range_device: out of device memory");
-        h->pgrad = {g[0], g[1]};
-    }
-    // the costates are the stationarity certificate's, by its own launch: lambda has the bits it writes to d_lambda
-    if (const int rc = h->ops->inspect.stationarity(h, first, count, src, h->pgrad.stat, h->pgrad.lam, nullptr); rc != SDDP_OK) return rc;
-    if (d_lambda)
-        HIP_TRY(h, hipMemcpyAsync(d_lambda, h->pgrad.lam, size_t(count) * (h->N + 1) * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    return h->ops->inspect.param_gradient(h, first, count, src, h->pgrad.lam, h->pgrad.stat, d_out, d_grad);
+    if (const int rc = costates(h, "sddp_param_gradient_range_device", first, count, src, d_lambda); rc != SDDP_OK) return rc;
+    return h->ops->inspect.param_gradient(h, first, count, src, h->costate.lam, h->costate.stat, d_out, d_grad);
 }
 
 int sddp_param_gradient(sddp_handle* h, int first, int count, double* out, double* grad) {
@@ -1576,16 +1582,8 @@ int sddp_const_gradient_range_device(sddp_handle* h, int first, int count, const
     if (const size_t lds = const_gradient_lds(h->N); lds > size_t(64) * 1024)      // before anything is launched
         return fail(h, SDDP_ERR_ARG, "sddp_const_gradient_range_device: the horizon's tile of addends needs " + std::to_string(lds) +
                                          " bytes of LDS, more than the 65536 one workgroup has here");
-    if (!h->pgrad.on()) {      // the costates and the stationarity record of a call (the parameter sensitivities' group)
-        GroupBuf g[] = {{h->n_x() * sizeof(double)}, {size_t(h->B) * kStationarityWords * sizeof(double)}};
-        if (acquire_group(h, g) != hipSuccess) return fail(h, SDDP_ERR_NOMEM, "sddp_const_gradient_range_device: out of device memory");
-        h->pgrad = {g[0], g[1]};
-    }
-    // the costates are the stationarity certificate's, by its own launch: lambda has the bits it writes to d_lambda
-    if (const int rc = h->ops->inspect.stationarity(h, first, count, src, h->pgrad.stat, h->pgrad.lam, nullptr); rc != SDDP_OK) return rc;
-    if (d_lambda)
-        HIP_TRY(h, hipMemcpyAsync(d_lambda, h->pgrad.lam, size_t(count) * (h->N + 1) * h->d.nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    return h->ops->inspect.const_gradient(h, first, count, src, h->pgrad.lam, h->pgrad.stat, d_out, d_nodes);
+    if (const int rc = costates(h, "sddp_const_gradient_range_device", first, count, src, d_lambda); rc != SDDP_OK) return rc;
+    return h->ops->inspect.const_gradient(h, first, count, src, h->costate.lam, h->costate.stat, d_out, d_nodes);
 }
 
 int sddp_const_gradient(sddp_handle* h, int first, int count, double* out) {

@@ -220,13 +220,14 @@ struct sddp_handle {
         sddp::DevConsts* ctab = nullptr;   // [B]
         bool on() const { return ctab != nullptr; }
     } table;
-    // parameter sensitivities (sddp_param_gradient_range_device): where the stationarity launch of a call leaves the costates and its
-    // record for the kernel behind it; made by the first call, for the handle's life.  Block i belongs to instance first + i of the call
-    struct ParamGradient {
+    // costates of a call (sddp_api.hip costates: the parameter and the constant sensitivities): where the stationarity launch of a call
+    // leaves the costates and its record for the kernel behind it; made by the first call, for the handle's life.  Block i belongs to
+    // instance first + i of the call
+    struct Costates {
         double* lam = nullptr;          // [B][N + 1][nx]
         double* stat = nullptr;         // [B][kStationarityWords]
         bool on() const { return lam != nullptr; }
-    } pgrad;
+    } costate;
     // host staging: each buffer is made by the first call that uses it and kept for the handle's life, so there is nothing to switch
     // and no on(); a pinned buffer that could not be had stays null and its caller takes the pageable path (sddp_api.hip staging)
     struct Staging {

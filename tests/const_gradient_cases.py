@@ -9,15 +9,15 @@ entry c of A_k starting at dL/dtheta_c and adding df[i]/dtheta_c lam_{k+1}[i] fo
 THE RECORD (40 doubles): 0 .. 31 C; 32 max_c |C[c] theta_c|, 33 its column (-1 where word 32 is NaN); 34 - 36 words 4, 0, 6 of the
 stationarity record; 37 N; 38, 39 zero.
 
-Where the symbols come from.  The building blocks of tests/sym_models.py (_srbd, _state_res, _force_res, _penalties, _relpos) take a
-constants object and read its fields; here they are handed one whose fields are sympy SYMBOLS arranged so that what the blocks derive
-from them are the derived constants themselves (force_scaling = 1, m = 1 / inv_ms, I = Is, min_f_gain = w_f, feet = the offsets, ...), in
-the order tests/param_gradient_cases.py assemble() puts them together.  The LIP rows are written out, as there, with w_rz and w_rxy
-apart (sym_models has one r_tracking_gain for both).  The two barriers are no residual rows of sym_models: they are oracle/models.py's
-formulas (_force_rows, friction_cone_rows, _bound_rows), present where the weight is > 0 as there.  One block is not sym_models': _srbd
-takes symbols for the inertia, but with them its adjugate / determinant of R(o) Is R(o)^T takes minutes per model (inertia_mode 1); the
-accelerations are written here from oracle/models.py srbd_acc's formulas with the rotation matrix as nine PLACEHOLDER symbols, filled with
-quat_to_rot(o) when a function is called: R does not depend on a constant, so the derivative in theta at fixed R is the derivative.  The cost is the sum of the squared
+Where the symbols come from.  tests/sym_models.py assemble(), the one statement of every model's layout, takes a constants object and
+reads its fields; here it is handed one whose fields are sympy SYMBOLS arranged so that what it derives from them are the derived
+constants themselves (force_scaling = 1, m = 1 / inv_ms, I = Is, min_f_gain = w_f, feet = the offsets, ...; w_rz, w_rxy and eta2 as
+fields of their own, where a robot has one r_tracking_gain and a lip_height).  The two barriers are no residual rows of sym_models:
+they are oracle/models.py's formulas (_force_rows, friction_cone_rows, _bound_rows), present where the weight is > 0 as there.  One
+block is not sym_models': _srbd takes symbols for the inertia, but with them its adjugate / determinant of R(o) Is R(o)^T takes minutes
+per model (inertia_mode 1); the accelerations are written here from oracle/models.py srbd_acc's formulas with the rotation matrix as
+nine PLACEHOLDER symbols, filled with quat_to_rot(o) when a function is called, and handed to assemble() as its dynamics hook: R does
+not depend on a constant, so the derivative in theta at fixed R is the derivative.  The cost is the sum of the squared
 rows, so sqrt(gain)^2 = gain and no square root of a constant is left to differentiate.  What selects code has no symbol: inertia_mode,
 lever_sign, relative_velocity_constraints, the bounds; an expression set is cached per such selection, whatever the numbers.
 """
@@ -29,12 +29,12 @@ import sympy as sp
 
 from oracle import models as omodels
 from srbd_horizon_amd import _lib
-from tests import sym_models as sm
+from tests import param_gradient_cases as pg, sym_models as sm
+from tests.param_gradient_cases import _arr, node_class
 
 W, COLS = _lib.CONST_GRADIENT_WORDS, _lib.CONST_GRADIENT_COLS
 REL, COLUMN, LAM0, STAT, DEFECT, NODES = range(COLS, COLS + 6)
 MODELS = ("srbd13", "srbd37", "lip30", "srbd61")
-DIMS = {"srbd13": (13, 6, 19), "srbd37": (37, 24, 19), "lip30": (30, 15, 11), "srbd61": (61, 48, 27)}
 RTOL = 1e-11      # the inspectors' tolerance (tests/param_gradient_cases.py RTOL), here of a column's magnitude sum
 G = 9.81
 
@@ -109,25 +109,26 @@ def _sym_consts(inertia_mode, lever_sign, rel_vel):
         force_scaling=sp.Integer(1), m=1 / t["inv_ms"], I=np.array([t[f"Is[{i}]"] for i in range(9)], dtype=object).reshape(3, 3),
         inertia_mode=inertia_mode, lever_sign=lever_sign, relative_velocity_constraints=rel_vel, com=(0, 0, t["com_z"]),
         r_tracking_gain=t["w_rz"], rdot_tracking_gain=t["w_rd"], w_tracking_gain=t["w_w"], rel_pos_gain=t["w_rel"], min_f_gain=t["w_f"],
-        force_switch_weight=t["w_sw"], min_qddot_gain=t["gq"], feet=feet, feet8=np.vstack([feet, feet]), dt=t["dt"]), t
+        force_switch_weight=t["w_sw"], min_qddot_gain=t["gq"], feet=feet, feet8=np.vstack([feet, feet]), dt=t["dt"],
+        zmp_tracking_gain=t["w_zmp"], w_rz=t["w_rz"], w_rxy=t["w_rxy"], eta2=t["eta2"]), t
 
 
 RS = sp.symbols("R0:9")                         # the rotation matrix of the state's quaternion, row-major: placeholders (see above)
 
 
-def _srbd(t, inertia_mode, lever_sign, r, w, cs, fs):
+def _srbd(t, cst, r, o, w, cs, fs):
     """rddot, wdot of oracle/models.py srbd_acc / world_inertia in the derived constants: rddot = inv_ms sum f - g e_z,
-    I_w wdot = s sum (c_i - r) x f_i - w x I_w w, I_w = R o Is o R^T element-wise (inertia_mode 0) or R Is R^T (1)"""
+    I_w wdot = s sum (c_i - r) x f_i - w x I_w w, I_w = R o Is o R^T element-wise (inertia_mode 0) or R Is R^T (1); and odot"""
     R = sp.Matrix(3, 3, RS)
     Is = sp.Matrix(3, 3, [t[f"Is[{i}]"] for i in range(9)])
-    M = sp.Matrix(3, 3, lambda i, j: R[i, j] * Is[i, j] * R[j, i]) if inertia_mode == 0 else R * Is * R.T
+    M = sp.Matrix(3, 3, lambda i, j: R[i, j] * Is[i, j] * R[j, i]) if cst.inertia_mode == 0 else R * Is * R.T
     rddot = sp.Matrix([0, 0, -sm.G])
     tau = sp.zeros(3, 1)
     for c, f in zip(cs, fs):
         rddot += t["inv_ms"] * f
-        tau += lever_sign * (c - r).cross(f)
+        tau += cst.lever_sign * (c - r).cross(f)
     tau -= w.cross(M * w)
-    return rddot, (M.adjugate() / M.det()) * tau
+    return rddot, (M.adjugate() / M.det()) * tau, sp.Rational(1, 2) * sm._qmul(sp.Matrix([w[0], w[1], w[2], 0]), o)
 
 
 def _sq(rows):
@@ -137,49 +138,9 @@ def _sq(rows):
 def assemble(name, inertia_mode=0, lever_sign=1.0, rel_vel=True, friction=False, bounds=None):
     """(x, u, p, f, Li, Ls): the symbols, the model step and the cost of the input and of the state class in TH.  friction: the
     friction-cone barrier is on; bounds: (lower, upper) of the bound barrier, or None where it is off"""
-    nx, nu, npar = DIMS[name]
     cst, t = _sym_consts(inertia_mode, lever_sign, rel_vel)
-    x, u, p = (sp.Matrix(sp.symbols(f"{s}0:{n}")) for s, n in (("x", nx), ("u", nu), ("p", npar)))
-    fs = []
-    if name == "srbd13":
-        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[7:10, 0], x[10:13, 0]
-        fs = [u[0:3, 0], u[3:6, 0]]
-        rddot, wdot = _srbd(t, inertia_mode, lever_sign, r, w, [p[11:14, 0], p[14:17, 0]], fs)
-        odot = sp.Rational(1, 2) * sm._qmul(sp.Matrix([w[0], w[1], w[2], 0]), o)
-        xdot = sp.Matrix([*rd, *odot, *rddot, *wdot])
-        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7:11, 0])
-        ires = [*(sp.sqrt(t["gq"]) * sp.Matrix([*rddot, *wdot]))]
-        for i in range(2):
-            ires += sm._force_res(cst, fs[i], p[17 + i])
-    elif name in ("srbd37", "srbd61"):
-        nc = 4 if name == "srbd37" else 8
-        rd0 = 7 + 3 * nc
-        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[rd0:rd0 + 3, 0], x[rd0 + 3:rd0 + 6, 0]
-        cs = [x[7 + 3 * i:10 + 3 * i, 0] for i in range(nc)]
-        cds = [x[rd0 + 6 + 3 * i:rd0 + 9 + 3 * i, 0] for i in range(nc)]
-        cdd = [u[6 * i:6 * i + 3, 0] for i in range(nc)]
-        fs = [u[6 * i + 3:6 * i + 6, 0] for i in range(nc)]
-        rddot, wdot = _srbd(t, inertia_mode, lever_sign, r, w, cs, fs)
-        odot = sp.Rational(1, 2) * sm._qmul(sp.Matrix([w[0], w[1], w[2], 0]), o)
-        xdot = sp.Matrix([*rd, *odot, *[e for c in cds for e in c], *rddot, *wdot, *[e for c in cdd for e in c]])
-        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7 + 2 * nc:11 + 2 * nc, 0]) + sm._relpos(cst, cs)
-        ires = [*(sp.sqrt(t["gq"]) * sp.Matrix([*rddot, *wdot, *[e for c in cdd for e in c]]))]
-        for i in range(nc):
-            ires += sm._force_res(cst, fs[i], p[8 + 2 * i])
-        ires += sm._penalties(cs, cds, [p[7 + 2 * i] for i in range(nc)], [p[8 + 2 * i] for i in range(nc)], rel_vel)
-    else:
-        r, rd = x[0:3, 0], x[15:18, 0]
-        cs = [x[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
-        cds = [x[18 + 3 * i:21 + 3 * i, 0] for i in range(4)]
-        z = u[0:3, 0]
-        cdd = [u[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
-        rddot = t["eta2"] * (r - z) - sp.Matrix([0, 0, sm.G])
-        xdot = sp.Matrix([*rd, *cds[0], *cds[1], *cds[2], *cds[3], *rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]])
-        mean_c = (cs[0] + cs[1] + cs[2] + cs[3]) / 4
-        sres = [sp.sqrt(t["w_rz"]) * (r[2] - t["com_z"]), *(sp.sqrt(t["w_rxy"]) * (r[0:2, 0] - mean_c[0:2, 0])),
-                *(sp.sqrt(t["w_rd"]) * (rd - p[0:3, 0]))] + sm._relpos(cst, cs)
-        ires = [*(sp.sqrt(t["w_zmp"]) * (z - mean_c)), *(sp.sqrt(t["gq"]) * sp.Matrix([*rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]]))]
-        ires += sm._penalties(cs, cds, [p[3 + 2 * i] for i in range(4)], [p[4 + 2 * i] for i in range(4)], rel_vel)
+    x, u, p, f, ires, sres, fs = sm.assemble(name, cst, srbd=functools.partial(_srbd, t))
+    nx, nu = len(x), len(u)
     Li, Ls = _sq(ires), _sq(sres)
     if friction:      # oracle/models.py _force_rows: w sum_j exp(s a_j . f), a_j the rows of friction_cone_rows with mu / sqrt(2) = mu_lin
         ml = t["mu_lin"]
@@ -195,7 +156,7 @@ def assemble(name, inertia_mode=0, lever_sign=1.0, rel_vel=True, friction=False,
             if np.isfinite(lb[j]):
                 Li += t["box_w"] * sp.exp(t["box_s"] * (float(lb[j]) - zz[j]))
     assert not any(q.exp == sp.Rational(1, 2) for e in (Li, Ls) for q in e.atoms(sp.Pow)), "a square root of a constant is left"
-    return x, u, p, x + t["dt"] * xdot, Li, Ls
+    return x, u, p, f, Li, Ls
 
 
 def _bounds_key(bounds):
@@ -226,15 +187,6 @@ def gradients(name, cst):
                       bool(cst.friction_barrier_weight > 0.0), _bounds_key(bounds))
 
 
-def _arr(v, shape=None):
-    a = np.asarray(v, dtype=float)
-    return a.reshape(-1) if shape is None else a.reshape(shape).astype(float)
-
-
-def node_class(k, N):
-    return "N" if k == N else ("0" if k == 0 else "k")
-
-
 def cost(J, key, x, u, p, th):
     u = np.zeros(J["nu"]) if u is None else u
     p, t = p[:J["np"]], th[:COLS - 1]
@@ -247,9 +199,9 @@ def dL_dtheta(J, key, x, u, p, th):
     p, t = p[:J["np"]], th[:COLS - 1]
     g = np.zeros(COLS)
     if key != "N":
-        g[:COLS - 1] += _arr(J["dLi"](x, u, p, t), (COLS - 1,))
+        g[:COLS - 1] += _arr(J["dLi"](x, u, p, t), (1, COLS - 1))[0]
     if key != "0":
-        g[:COLS - 1] += _arr(J["dLs"](x, u, p, t), (COLS - 1,))
+        g[:COLS - 1] += _arr(J["dLs"](x, u, p, t), (1, COLS - 1))[0]
     return g
 
 
@@ -392,13 +344,11 @@ FIELDS_RTOL = 1e-8
 
 def envelope_discrepancy(D, delta, Jp, Jm, h):
     """the figure of every instance: D [B, 41] the gradients in the fields, the costs J*(+h), J*(-h) [B] -> [B]"""
-    pred = D @ delta
-    return np.abs(pred - (Jp - Jm) / (2.0 * h)) / np.sum(np.abs(D * delta[None]), axis=1)
+    return pg.central_discrepancy(D @ delta, np.sum(np.abs(D * delta[None]), axis=1), Jp, Jm, h)
 
 
 def envelope_problem():
     """-> (batch, delta [41]): the start of tests/param_gradient_cases.py's experiment and the direction in the fields"""
-    from tests import param_gradient_cases as pg
     batch = pg.envelope_problem()[0]
     return batch, envelope_direction(batch["consts"])
 
@@ -406,25 +356,17 @@ def envelope_problem():
 def envelope_scan(steps=ENVELOPE_STEPS):
     """the experiment on the CPU with the C oracle's solves and the symbolic reference -> {h: the figure [B]}; asserts that all three
     solves of every instance converge with closed gaps"""
-    from oracle import cport
-    from tests import oracle_refs as refs, param_gradient_cases as pg, stationarity_cases as sc
+    from tests import stationarity_cases as sc
     batch, delta = envelope_problem()
-
-    def solve(consts, xs, us):
-        x, u, st = refs.c_oracle(pg.ENVELOPE_MODEL, batch, pg.ENVELOPE_OPTS, cst=omodels.RobotConsts(**consts), xs=xs, us=us)
-        assert (cport.stat(st, "converged") == 1).all() and (cport.stat(st, "status") == 0).all(), st
-        assert (cport.stat(st, "gap") <= pg.ENVELOPE_GAP).all(), cport.stat(st, "gap")
-        return x, u, cport.stat(st, "cost").copy()
-
-    x, u, _ = solve(batch["consts"], batch["xs"], batch["us"])
     cst = omodels.RobotConsts(**batch["consts"])
+    x, u, _ = pg.converged_solve(batch, batch["xs"], batch["us"], cst=cst)
     J, th, m = gradients(pg.ENVELOPE_MODEL, cst), derived(batch["consts"]), omodels.make_model(pg.ENVELOPE_MODEL, cst)
     D = np.stack([fields_of(batch["consts"], reference(J, th, x[b], u[b], batch["params"][b],
                                                        sc.model_reference(m, x[b], u[b], batch["params"][b])[1])[1])[0]
                   for b in range(x.shape[0])])
     out = {}
     for h in steps:
-        Jp, Jm = (solve(moved_consts(batch["consts"], delta, s * h), x, u)[2] for s in (1.0, -1.0))
+        Jp, Jm = (pg.converged_solve(batch, x, u, cst=omodels.RobotConsts(**moved_consts(batch["consts"], delta, s * h)))[2] for s in (1.0, -1.0))
         out[h] = envelope_discrepancy(D, delta, Jp, Jm, h)
     return out
 

@@ -1,7 +1,7 @@
 """What the GPU tests share: loading and solving a batch on a handle, a whole solve compared with the C oracle's (the cases of
 tests/whole_solve_cases.py), cutting and continuing a solve, the byte comparison of two results, the references several modules
 compare against (computed once per key, read-only), what the plan inspectors' modules share (the contract of DESIGN.md section 5,
-"Plan inspectors", as three routines), and the explanation of an instance on another iteration count than the oracle.  Plain
+"Plan inspectors", as three routines), what the two sensitivities' modules share, and the explanation of an instance on another iteration count than the oracle.  Plain
 functions, no fixtures; no test module imports another."""
 import functools
 from typing import Callable, NamedTuple
@@ -181,6 +181,62 @@ STATIONARITY = Inspector("stationarity", len(_lib.STATIONARITY_FIELDS), dict(lam
                          lambda e, f, n, dx, du, out: e.lib.sddp_stationarity_range_device(e.h, f, n, dx, du, out, None, None))
 COST_TERMS = Inspector("cost_terms", _lib.COST_TERMS_WORDS, dict(nodes=lambda e: (e.N + 1, _lib.COST_TERMS_COLS)),
                        lambda e, f, n, dx, du, out: e.lib.sddp_cost_terms_range_device(e.h, f, n, dx, du, out, None))
+
+
+# ---- the two sensitivities (parameter and constant gradient): what their two test modules share, by the Inspector they drive ------------------
+def run(insp, eng, first=0, count=None, x=None, u=None, full=True):
+    """<name>_device on fresh device tensors -> numpy (record, the per-node output, lambda [n, N + 1, nx]); None for the two without full"""
+    return insp.device(eng, first, count, x, u, optional=full)
+
+
+def engine_with_plan(model, N, B, consts, P, batch, opts=None, solve_it=False):
+    """a handle whose last solve launch carried P: at max_iters = 0 (the plan is then the warm start) unless solve_it"""
+    eng = DdpEngine(model, N, B, opts=dict(pac.OPTS, **({} if solve_it else dict(max_iters=0)), **(opts or {})), consts=consts)
+    eng.load(batch["x0"], batch["xs"], batch["us"])
+    eng.solve(P)
+    return eng
+
+
+def assert_same_costates(words, eng, got, x=None, u=None, first=0, count=None):
+    """lambda and the record's `words` (|| lambda_0 ||, stationarity, defect) are the stationarity certificate's, bit for bit"""
+    srec, slam, _ = STATIONARITY.device(eng, first, count, x, u)
+    assert got[2].tobytes() == slam.tobytes()
+    assert got[0][:, list(words)].tobytes() == srec[:, [4, 0, 6]].tobytes()
+
+
+def assert_a_user_build_is_refused(insp, match):
+    """a user build (non-linear rows) has no derivative code: RuntimeError `match`, SDDP_ERR_ARG, and the handle still works"""
+    from tests import user_terms_defs as ud
+    N, B = 20, 2
+    spec, mid = ud.user_case("srbd13_terrain", N)
+    batch = workload.make_batch("srbd13", N, [0, 1])
+    eng = DdpEngine("srbd13", N, B, opts=dict(pac.OPTS, max_iters=0), consts=dict(batch["consts"], extra_rows=spec.extra_rows()), model_id=mid)
+    eng.load(batch["x0"], batch["xs"], batch["us"])
+    eng.solve(ud.widen(batch["params"], spec))
+    out = torch.zeros((B, insp.words), dtype=torch.float64, device="cuda")
+    with pytest.raises(RuntimeError, match=match):
+        getattr(eng, insp.name + "_device")(out)
+    assert insp.raw(eng, 0, B, None, None, eng._dev(out, out.shape)) == -1      # SDDP_ERR_ARG
+    assert STATIONARITY.device(eng)[0].shape == (B, 8)                           # and the handle still works
+    eng.close()
+
+
+def assert_a_nan_stays_on_its_instance(insp, random_plan, nan_word, place_words, nodes_word):
+    """one NaN state entry (instance 1, node 2): that instance's record says so (word nan_word NaN, its place_words -1, nodes_word
+    N), the other instances keep their bits, and the nodes behind node 2 do not see it"""
+    model, N, B = "srbd13", 6, 3
+    batch, x, u, P = random_plan(model, N, B, seed=5)
+    eng = engine_with_plan(model, N, B, batch["consts"], P, batch)
+    clean = run(insp, eng, x=x, u=u)
+    bad = x.copy()
+    bad[1, 2, 4] = np.nan                                                       # instance 1, node 2, one state (quaternion) entry
+    got = run(insp, eng, x=bad, u=u)
+    assert np.isnan(got[0][1, nan_word]) and all(got[0][1, w] == -1 for w in place_words)
+    assert got[0][1, nodes_word] == N
+    keep = [0, 2]
+    assert all(a[keep].tobytes() == b_[keep].tobytes() for a, b_ in zip(got, clean))
+    assert np.isnan(got[1][1, 2]).any() and not np.isnan(got[1][1, 3:]).any()    # the nodes behind it do not see node 2
+    eng.close()
 
 
 def touch_with(insp, **sub):

@@ -9,12 +9,11 @@ entry j starting at dL/dp[j] and adding df[i]/dp[j] lam_{k+1}[i] for i = 0 .. nx
 THE RECORD (8 doubles, _lib.PARAM_GRADIENT_FIELDS): 0 max |G_k[j]|, 1, 2 its node and column (first in node-major order; -1 where word 0
 is NaN), 3 max of |dL/dp[j]| + sum_i |df[i]/dp[j]| |lam_{k+1}[i]|, 4 - 6 words 4, 0, 6 of the stationarity record, 7 N.
 
-Where the symbols come from.  tests/sym_models.py symbolic(...)[0]["_sym"] holds f and the residual rows as sympy expressions, and
-jacobians() differentiates them in p.  symbolic() also differentiates and compiles everything in z, which takes 7 - 10 s per model at
-inertia_mode 0, about 4 minutes per model at inertia_mode 1, and it has no argument for the gains; so the expressions of a constant
-set are assembled here by assemble(), from the same building blocks of tests/sym_models.py (_srbd, _state_res, _force_res, _penalties,
-_relpos) in the order _build puts them together, and tests/test_param_gradient_cpu.py checks that assembly against symbolic()'s own
-"_sym" on the default constants of every model.
+Where the symbols come from.  tests/sym_models.py assemble() states f and the residual rows of a constant set as sympy expressions,
+once for every user, and jacobians() differentiates them in p.  (symbolic() compiles the same expressions and their derivatives in z,
+which takes 7 - 10 s per model at inertia_mode 0 and about 4 minutes at inertia_mode 1, and has no argument for the gains: it is not
+called here.)  Also here, for tests/const_gradient_cases.py as well: node_class, _arr and the common part of the two envelope
+experiments (converged_solve, central_discrepancy).
 """
 import functools
 
@@ -28,7 +27,6 @@ from tests import sym_models as sm
 W = len(_lib.PARAM_GRADIENT_FIELDS)
 GRAD, NODE, COLUMN, SCALE, LAM0, STAT, DEFECT, NODES = range(8)
 MODELS = ("srbd13", "srbd37", "lip30", "srbd61")
-DIMS = {"srbd13": (13, 6, 19), "srbd37": (37, 24, 19), "lip30": (30, 15, 11), "srbd61": (61, 48, 27)}
 RTOL = 1e-11      # tests/test_gpu_parity.py test_eval_knots_matches_oracle: the relative tolerance of g and F, here of word 3
 
 # the constant sets of the tests, by key: the defaults, and one set away from them (inertia_mode 1, lever_sign -1, no relative-velocity
@@ -55,67 +53,11 @@ def robot(name, key):
     return omodels.RobotConsts(**kw)
 
 
-def assemble(name, cst):
-    """(x, u, p, f, ires, sres): the state, input and parameter symbols, the model step and the residual rows of the input and of the
-    state class, as tests/sym_models.py _build assembles them"""
-    nx, nu, npar = DIMS[name]
-    rows = list(getattr(cst, "extra_rows", None) or ())
-    npb = npar
-    if rows:
-        npar += 8
-    x, u, p = (sp.Matrix(sp.symbols(f"{s}0:{n}")) for s, n in (("x", nx), ("u", nu), ("p", npar)))
-    rel_vel = bool(getattr(cst, "relative_velocity_constraints", True))
-    if name == "srbd13":
-        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[7:10, 0], x[10:13, 0]
-        fs = [u[0:3, 0], u[3:6, 0]]
-        rddot, wdot, odot = sm._srbd(cst, r, o, w, [p[11:14, 0], p[14:17, 0]], fs)
-        xdot = sp.Matrix([*rd, *odot, *rddot, *wdot])
-        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7:11, 0])
-        ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot]))]
-        for i in range(2):
-            ires += sm._force_res(cst, fs[i], p[17 + i])
-    elif name in ("srbd37", "srbd61"):
-        nc = 4 if name == "srbd37" else 8
-        rd0 = 7 + 3 * nc
-        r, o, rd, w = x[0:3, 0], x[3:7, 0], x[rd0:rd0 + 3, 0], x[rd0 + 3:rd0 + 6, 0]
-        cs = [x[7 + 3 * i:10 + 3 * i, 0] for i in range(nc)]
-        cds = [x[rd0 + 6 + 3 * i:rd0 + 9 + 3 * i, 0] for i in range(nc)]
-        cdd = [u[6 * i:6 * i + 3, 0] for i in range(nc)]
-        fs = [u[6 * i + 3:6 * i + 6, 0] for i in range(nc)]
-        rddot, wdot, odot = sm._srbd(cst, r, o, w, cs, fs)
-        xdot = sp.Matrix([*rd, *odot, *[e for c in cds for e in c], *rddot, *wdot, *[e for c in cdd for e in c]])
-        sres = sm._state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7 + 2 * nc:11 + 2 * nc, 0]) + sm._relpos(cst, cs)
-        ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot, *[e for c in cdd for e in c]]))]
-        for i in range(nc):
-            ires += sm._force_res(cst, fs[i], p[8 + 2 * i])
-        ires += sm._penalties(cs, cds, [p[7 + 2 * i] for i in range(nc)], [p[8 + 2 * i] for i in range(nc)], rel_vel)
-    else:
-        r, rd = x[0:3, 0], x[15:18, 0]
-        cs = [x[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
-        cds = [x[18 + 3 * i:21 + 3 * i, 0] for i in range(4)]
-        z = u[0:3, 0]
-        cdd = [u[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
-        rddot = (9.81 / cst.lip_height) * (r - z) - sp.Matrix([0, 0, sm.G])
-        xdot = sp.Matrix([*rd, *cds[0], *cds[1], *cds[2], *cds[3], *rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]])
-        mean_c = (cs[0] + cs[1] + cs[2] + cs[3]) / 4
-        sres = [sp.sqrt(cst.r_tracking_gain) * (r[2] - cst.com[2]), *(sp.sqrt(cst.r_tracking_gain) * (r[0:2, 0] - mean_c[0:2, 0])),
-                *(sp.sqrt(cst.rdot_tracking_gain) * (rd - p[0:3, 0]))] + sm._relpos(cst, cs)
-        ires = [*(sp.sqrt(cst.zmp_tracking_gain) * (z - mean_c)),
-                *(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]]))]
-        ires += sm._penalties(cs, cds, [p[3 + 2 * i] for i in range(4)], [p[4 + 2 * i] for i in range(4)], rel_vel)
-    z_all = [*x, *u]
-    for j, row in enumerate(rows):
-        a = np.asarray(row["a"], dtype=float)
-        e = sp.sqrt(row["w"]) * (sum(float(a[i]) * z_all[i] for i in range(nx + nu) if a[i] != 0.0) - p[npb + j] - float(row.get("const", 0.0)))
-        (sres if row["kind"] == "state" else ires).append(e)
-    return x, u, p, x + cst.dt * xdot, sp.Matrix(ires), sp.Matrix(sres)
-
-
 @functools.lru_cache(maxsize=None)
 def jacobians(name, key="default"):
     """the compiled residual rows and the SYMBOLIC Jacobians in p of f, ires and sres for the constant set `key`: a dict of functions
     of (x, u, p): "f" [nx], "ires", "sres", "Fp" [nx, np], "Jip", "Jsp"; and "np", "nx", "nu"; computed once"""
-    x, u, p, f, ires, sres = assemble(name, robot(name, key))
+    x, u, p, f, ires, sres, _ = sm.assemble(name, robot(name, key))
     args = (list(x), list(u), list(p))
     lam = lambda e: sp.lambdify(args, e, "numpy", cse=True)      # noqa: E731
     out = dict(f=lam(f), ires=lam(ires), sres=lam(sres), Fp=lam(f.jacobian(p)), Jip=lam(ires.jacobian(p)), Jsp=lam(sres.jacobian(p)))
@@ -250,32 +192,39 @@ def envelope_problem():
     return batch, dP
 
 
+def central_discrepancy(pred, mag, Jp, Jm, h):
+    """| predicted slope - central difference of the optimal costs J*(+h), J*(-h) | / mag, per instance: the figure of both experiments"""
+    return np.abs(pred - (Jp - Jm) / (2.0 * h)) / mag
+
+
 def envelope_discrepancy(G, dP, Jp, Jm, h):
     """the figure of every instance: G [B, N + 1, np], the costs J*(p + h dp), J*(p - h dp) [B] -> [B]"""
-    pred = np.sum(G * dP, axis=(1, 2))
-    return np.abs(pred - (Jp - Jm) / (2.0 * h)) / np.sum(np.abs(G * dP), axis=(1, 2))
+    return central_discrepancy(np.sum(G * dP, axis=(1, 2)), np.sum(np.abs(G * dP), axis=(1, 2)), Jp, Jm, h)
+
+
+def converged_solve(batch, xs, us, **problem):
+    """a solve of the experiment on the C oracle from the warm start xs, us; problem: params= or cst= of tests/oracle_refs.py c_oracle
+    -> (x, u, costs [B]); asserts that every instance converges with closed gaps"""
+    from oracle import cport
+    from tests import oracle_refs as refs
+    x, u, st = refs.c_oracle(ENVELOPE_MODEL, batch, ENVELOPE_OPTS, xs=xs, us=us, **problem)
+    assert (cport.stat(st, "converged") == 1).all() and (cport.stat(st, "status") == 0).all(), st
+    assert (cport.stat(st, "gap") <= ENVELOPE_GAP).all(), cport.stat(st, "gap")
+    return x, u, cport.stat(st, "cost").copy()
 
 
 def envelope_scan(steps=ENVELOPE_STEPS):
     """the experiment on the CPU -> {h: the figure [B]}; asserts that all three solves of every instance converge with closed gaps"""
-    from oracle import cport
     from tests import oracle_refs as refs, stationarity_cases as sc
     batch, dP = envelope_problem()
     cst = refs.consts(batch)
-
-    def solve(P, xs, us):
-        x, u, st = refs.c_oracle(ENVELOPE_MODEL, batch, ENVELOPE_OPTS, params=P, xs=xs, us=us)
-        assert (cport.stat(st, "converged") == 1).all() and (cport.stat(st, "status") == 0).all(), st
-        assert (cport.stat(st, "gap") <= ENVELOPE_GAP).all(), cport.stat(st, "gap")
-        return x, u, cport.stat(st, "cost").copy()
-
-    x, u, _ = solve(batch["params"], batch["xs"], batch["us"])
+    x, u, _ = converged_solve(batch, batch["xs"], batch["us"], params=batch["params"])
     J = jacobians(ENVELOPE_MODEL, register("srbd13:envelope", batch["consts"]))
     m = omodels.make_model(ENVELOPE_MODEL, cst)
     G = np.stack([reference(J, x[b], u[b], batch["params"][b], sc.model_reference(m, x[b], u[b], batch["params"][b])[1])[0]
                   for b in range(x.shape[0])])
     out = {}
     for h in steps:
-        Jp, Jm = (solve(batch["params"] + s * h * dP, x, u)[2] for s in (1.0, -1.0))
+        Jp, Jm = (converged_solve(batch, x, u, params=batch["params"] + s * h * dP)[2] for s in (1.0, -1.0))
         out[h] = envelope_discrepancy(G, dP, Jp, Jm, h)
     return out

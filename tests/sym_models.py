@@ -82,28 +82,28 @@ def _relpos(cst, cs):
             g * (-cs[1][1] + cs[3][1] - d2[1]), g * (-cs[1][0] + cs[3][0] - d2[0])]
 
 
-def _build(name, cst):
-    if name == "srbd13":
-        nx, nu, npar = 13, 6, 19
-    elif name == "srbd37":
-        nx, nu, npar = 37, 24, 19
-    elif name == "srbd61":
-        nx, nu, npar = 61, 48, 27
-    else:
-        nx, nu, npar = 30, 15, 11
+DIMS = {"srbd13": (13, 6, 19), "srbd37": (37, 24, 19), "lip30": (30, 15, 11), "srbd61": (61, 48, 27)}      # nx, nu, np
+
+
+def assemble(name, cst, srbd=_srbd):
+    """THE layout of every model, stated once: (x, u, p, f, ires, sres, fs): the state, input and parameter symbols, the model step,
+    the residual rows of the input and of the state class as column matrices, and the contact forces (for the barriers of
+    tests/const_gradient_cases.py; none on lip30).  cst: a constants object whose fields are numbers or sympy symbols.  The LIP rows
+    read w_rz, w_rxy (the tracking gain of r_z and of r_xy) and eta2 where cst has them, else r_tracking_gain for both and
+    9.81 / lip_height.  srbd: the SRBD accelerations, (cst, r, o, w, cs, fs) -> (rddot, wdot, odot), a hook for a caller whose
+    constants make _srbd's symbolic inverse too slow"""
+    nx, nu, npar = DIMS[name]
     rows = list(getattr(cst, "extra_rows", None) or ())      # user-declared linear residual rows: 8 more parameter columns
     npb = npar
     if rows:
         npar += 8
-    x = sp.Matrix(sp.symbols(f"x0:{nx}"))
-    u = sp.Matrix(sp.symbols(f"u0:{nu}"))
-    p = sp.Matrix(sp.symbols(f"p0:{npar}"))
-    dt = cst.dt
+    x, u, p = (sp.Matrix(sp.symbols(f"{s}0:{n}")) for s, n in (("x", nx), ("u", nu), ("p", npar)))
+    rel_vel = getattr(cst, "relative_velocity_constraints", True)
     if name == "srbd13":
         r, o, rd, w = x[0:3, 0], x[3:7, 0], x[7:10, 0], x[10:13, 0]
         cs = [p[11:14, 0], p[14:17, 0]]
         fs = [u[0:3, 0], u[3:6, 0]]
-        rddot, wdot, odot = _srbd(cst, r, o, w, cs, fs)
+        rddot, wdot, odot = srbd(cst, r, o, w, cs, fs)
         xdot = sp.Matrix([*rd, *odot, *rddot, *wdot])
         sres = _state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7:11, 0])
         ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot]))]
@@ -118,47 +118,51 @@ def _build(name, cst):
         cds = [x[rd0 + 6 + 3 * i:rd0 + 9 + 3 * i, 0] for i in range(nc)]
         cdd = [u[6 * i:6 * i + 3, 0] for i in range(nc)]
         fs = [u[6 * i + 3:6 * i + 6, 0] for i in range(nc)]
-        rddot, wdot, odot = _srbd(cst, r, o, w, cs, fs)
+        rddot, wdot, odot = srbd(cst, r, o, w, cs, fs)
         xdot = sp.Matrix([*rd, *odot, *[e for c in cds for e in c], *rddot, *wdot, *[e for c in cdd for e in c]])
         sres = _state_res(cst, r, o, rd, w, p[0:3, 0], p[3:6, 0], p[6], p[7 + 2 * nc:11 + 2 * nc, 0]) + _relpos(cst, cs)
         ires = [*(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *wdot, *[e for c in cdd for e in c]]))]
         for i in range(nc):
             ires += _force_res(cst, fs[i], p[8 + 2 * i])
-        ires += _penalties(cs, cds, [p[7 + 2 * i] for i in range(nc)], [p[8 + 2 * i] for i in range(nc)],
-                           getattr(cst, "relative_velocity_constraints", True))
+        ires += _penalties(cs, cds, [p[7 + 2 * i] for i in range(nc)], [p[8 + 2 * i] for i in range(nc)], rel_vel)
     else:
         r, rd = x[0:3, 0], x[15:18, 0]
         cs = [x[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
         cds = [x[18 + 3 * i:21 + 3 * i, 0] for i in range(4)]
         z = u[0:3, 0]
         cdd = [u[3 + 3 * i:6 + 3 * i, 0] for i in range(4)]
-        eta2 = 9.81 / cst.lip_height
+        fs = []
+        w_rz, w_rxy = (getattr(cst, k, cst.r_tracking_gain) for k in ("w_rz", "w_rxy"))
+        eta2 = cst.eta2 if hasattr(cst, "eta2") else 9.81 / cst.lip_height
         rddot = eta2 * (r - z) - sp.Matrix([0, 0, G])
         xdot = sp.Matrix([*rd, *cds[0], *cds[1], *cds[2], *cds[3], *rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]])
         mean_c = (cs[0] + cs[1] + cs[2] + cs[3]) / 4
-        sres = [sp.sqrt(cst.r_tracking_gain) * (r[2] - cst.com[2]),
-                *(sp.sqrt(cst.r_tracking_gain) * (r[0:2, 0] - mean_c[0:2, 0])),
+        sres = [sp.sqrt(w_rz) * (r[2] - cst.com[2]),
+                *(sp.sqrt(w_rxy) * (r[0:2, 0] - mean_c[0:2, 0])),
                 *(sp.sqrt(cst.rdot_tracking_gain) * (rd - p[0:3, 0]))] + _relpos(cst, cs)
         ires = [*(sp.sqrt(cst.zmp_tracking_gain) * (z - mean_c)),
                 *(sp.sqrt(cst.min_qddot_gain) * sp.Matrix([*rddot, *cdd[0], *cdd[1], *cdd[2], *cdd[3]]))]
-        ires += _penalties(cs, cds, [p[3 + 2 * i] for i in range(4)], [p[4 + 2 * i] for i in range(4)],
-                           getattr(cst, "relative_velocity_constraints", True))
+        ires += _penalties(cs, cds, [p[3 + 2 * i] for i in range(4)], [p[4 + 2 * i] for i in range(4)], rel_vel)
+    z_all = [*x, *u]
+    for j, row in enumerate(rows):                           # sqrt(w) (a . z - (p[np + j] + const)): state rows (nodes 1..N) or stage rows
+        a = np.asarray(row["a"], dtype=float)
+        e = sp.sqrt(row["w"]) * (sum(float(a[i]) * z_all[i] for i in range(nx + nu) if a[i] != 0.0) - p[npb + j] - float(row.get("const", 0.0)))
+        (sres if row["kind"] == "state" else ires).append(e)
+    return x, u, p, x + cst.dt * xdot, sp.Matrix(ires), sp.Matrix(sres), fs
+
+
+def _build(name, cst):
+    x, u, p, f, ires_m, sres_m, _ = assemble(name, cst)
     z_all = sp.Matrix([*x, *u])
-    for j, r in enumerate(rows):                             # sqrt(w) (a . z - (p[np + j] + const)): state rows (nodes 1..N) or stage rows
-        a = np.asarray(r["a"], dtype=float)
-        e = sp.sqrt(r["w"]) * (sum(float(a[i]) * z_all[i] for i in range(nx + nu) if a[i] != 0.0) - p[npb + j] - float(r.get("const", 0.0)))
-        (sres if r["kind"] == "state" else ires).append(e)
-    f = x + dt * xdot
     out = {}
     args = (list(x), list(u), list(p))
     lam = lambda e: sp.lambdify(args, e, "numpy", cse=True)
     out["f"] = lam(f)
     out["F"] = lam(f.jacobian(z_all))
     # residual vectors and their SYMBOLIC Jacobians; costs / gradients / GN Hessians are assembled numerically
-    ires_m, sres_m = sp.Matrix(ires), sp.Matrix(sres)
     out["ires"], out["sres"] = lam(ires_m), lam(sres_m)
     out["Ji"], out["Js"] = lam(ires_m.jacobian(z_all)), lam(sres_m.jacobian(z_all))
-    out["nx"] = nx
+    out["nx"] = len(x)
     out["_sym"] = (x, u, p, f, ires_m, sres_m, z_all)
     return out
 

@@ -142,7 +142,7 @@ def _check_against_the_oracle(name, cst, label, columns=None):
             return np.array(f, dtype=float), L
 
         f0, L0 = both(th0)
-        key = cg.node_class(k, N)
+        key = pg.node_class(k, N)
         assert abs(cg.cost(J, key, x, None if terminal else u, p, th0) - L0) <= E * EPS * max(1.0, abs(L0)), (label, k)
         g = cg.dL_dtheta(J, key, x, None if terminal else u, p, th0)
         F = cg.df_dtheta(J, x, uu, p, th0)

@@ -11,6 +11,7 @@ with moved constants; its step and its bound come from the same experiment on th
 ENVELOPE_DISCREPANCY; profiles/const_gradient/README.md).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -19,8 +20,10 @@ import torch
 from srbd_horizon_amd import _lib
 from srbd_horizon_amd.engine import DdpEngine
 from tests import consts_cases as kc, const_gradient_cases as cg, param_gradient_cases as pg, plan_audit_cases as pac
-from tests.gpu_support import (COST_TERMS, STATIONARITY, Inspector, assert_common_refusals, assert_fleet_queue_follows_the_last_flush,
-                               assert_nothing_else_moves, touch_with)
+from tests.gpu_support import (COST_TERMS, STATIONARITY, Inspector, assert_a_nan_stays_on_its_instance, assert_a_user_build_is_refused,
+                               assert_common_refusals, assert_fleet_queue_follows_the_last_flush, assert_nothing_else_moves,
+                               assert_same_costates, run, touch_with)
+from tests.gpu_support import engine_with_plan as _engine
 from tests.variant_cases import draw
 
 pytestmark = pytest.mark.gpu
@@ -40,17 +43,9 @@ CONST_GRADIENT = _ConstGradient("const_gradient", cg.W, dict(nodes=lambda e: (e.
                                 lambda e, f, n, dx, du, out: e.lib.sddp_const_gradient_range_device(e.h, f, n, dx, du, out, None, None))
 
 
-def _run(eng, first=0, count=None, x=None, u=None, full=True):
-    """const_gradient_device on fresh device tensors -> numpy (record [n, 40], addends [n, N + 1, 32], lambda [n, N + 1, nx])"""
-    return CONST_GRADIENT.device(eng, first, count, x, u, optional=full)
-
-
-def _engine(model, N, B, consts, P, batch, opts=None, solve_it=False):
-    """a handle whose last solve launch carried P: at max_iters = 0 (the plan is then the warm start) unless solve_it"""
-    eng = DdpEngine(model, N, B, opts=dict(OPTS, **({} if solve_it else dict(max_iters=0)), **(opts or {})), consts=consts)
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    eng.solve(P)
-    return eng
+# (record [n, 40], addends [n, N + 1, 32], lambda [n, N + 1, nx]); lambda and words 34, 35, 36 are the stationarity certificate's
+_run = functools.partial(run, CONST_GRADIENT)
+_same_costates = functools.partial(assert_same_costates, (cg.LAM0, cg.STAT, cg.DEFECT))
 
 
 def _check(model, csts, got, x, u, P, label):
@@ -65,13 +60,6 @@ def _check(model, csts, got, x, u, P, label):
         refs.append(ref)
     print(f"{label}: worst error / tolerance {worst:.3e}")
     return refs
-
-
-def _same_costates(eng, got, x=None, u=None, first=0, count=None):
-    """lambda and words 34, 35, 36 are the stationarity certificate's, bit for bit"""
-    srec, slam, _ = STATIONARITY.device(eng, first, count, x, u)
-    assert got[2].tobytes() == slam.tobytes()
-    assert got[0][:, [cg.LAM0, cg.STAT, cg.DEFECT]].tobytes() == srec[:, [4, 0, 6]].tobytes()
 
 
 def _consts(model, key):
@@ -226,20 +214,7 @@ def test_cross_check_with_the_cost_breakdown():
 
 
 def test_a_user_build_is_refused():
-    from srbd_horizon_amd import workload
-    from tests import user_terms_defs as ud
-    N, B = 20, 2
-    spec, mid = ud.user_case("srbd13_terrain", N)
-    batch = workload.make_batch("srbd13", N, [0, 1])
-    eng = DdpEngine("srbd13", N, B, opts=dict(OPTS, max_iters=0), consts=dict(batch["consts"], extra_rows=spec.extra_rows()), model_id=mid)
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    eng.solve(ud.widen(batch["params"], spec))
-    out = torch.zeros((B, cg.W), dtype=torch.float64, device="cuda")
-    with pytest.raises(RuntimeError, match="no derivative code"):
-        eng.const_gradient_device(out)
-    assert CONST_GRADIENT.raw(eng, 0, B, None, None, eng._dev(out, out.shape)) == -1      # SDDP_ERR_ARG
-    assert STATIONARITY.device(eng)[0].shape == (B, 8)                           # and the handle still works
-    eng.close()
+    assert_a_user_build_is_refused(CONST_GRADIENT, "no derivative code")
 
 
 def test_a_horizon_past_the_lds_limit_is_refused():
@@ -265,18 +240,7 @@ def test_a_horizon_past_the_lds_limit_is_refused():
 
 
 def test_a_nan_stays_on_its_instance():
-    model, N, B = "srbd13", 6, 3
-    batch, x, u, P = pg.random_plan(model, N, B, seed=5)
-    eng = _engine(model, N, B, batch["consts"], P, batch)
-    clean = _run(eng, x=x, u=u)
-    bad = x.copy()
-    bad[1, 2, 4] = np.nan                                                       # instance 1, node 2, one quaternion entry
-    got = _run(eng, x=bad, u=u)
-    assert np.isnan(got[0][1, cg.REL]) and got[0][1, cg.COLUMN] == -1 and got[0][1, cg.NODES] == N
-    keep = [0, 2]
-    assert all(a[keep].tobytes() == b_[keep].tobytes() for a, b_ in zip(got, clean))
-    assert np.isnan(got[1][1, 2]).any() and not np.isnan(got[1][1, 3:]).any()    # the nodes behind it do not see node 2
-    eng.close()
+    assert_a_nan_stays_on_its_instance(CONST_GRADIENT, pg.random_plan, cg.REL, (cg.COLUMN,), cg.NODES)
 
 
 def test_envelope_of_the_optimal_cost():

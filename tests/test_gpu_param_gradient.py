@@ -10,16 +10,17 @@ The envelope check compares sum G . dp with central differences of the converged
 come from the same experiment on the C oracle (param_gradient_cases.ENVELOPE_H, ENVELOPE_DISCREPANCY; profiles/param_gradient/README.md).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
-import torch
 
 from srbd_horizon_amd import _lib
 from srbd_horizon_amd.engine import DdpEngine
 from tests import param_gradient_cases as pg, plan_audit_cases as pac
-from tests.gpu_support import (STATIONARITY, Inspector, assert_common_refusals, assert_fleet_queue_follows_the_last_flush,
-                               assert_nothing_else_moves, dev, solve, touch_with)
+from tests.gpu_support import (Inspector, assert_a_nan_stays_on_its_instance, assert_a_user_build_is_refused, assert_common_refusals,
+                               assert_fleet_queue_follows_the_last_flush, assert_nothing_else_moves, assert_same_costates, run, touch_with)
+from tests.gpu_support import engine_with_plan as _engine
 from tests.variant_cases import TRACKING, draw
 
 pytestmark = pytest.mark.gpu
@@ -42,17 +43,9 @@ PARAM_GRADIENT = _ParamGradient("param_gradient", pg.W, dict(grad=lambda e: (e.N
                                 lambda e, f, n, dx, du, out: e.lib.sddp_param_gradient_range_device(e.h, f, n, dx, du, out, None, None))
 
 
-def _run(eng, first=0, count=None, x=None, u=None, full=True):
-    """param_gradient_device on fresh device tensors -> numpy (record [n, 8], G [n, N + 1, np], lambda [n, N + 1, nx])"""
-    return PARAM_GRADIENT.device(eng, first, count, x, u, optional=full)
-
-
-def _engine(model, N, B, consts, P, batch, opts=None, solve_it=False):
-    """a handle whose last solve launch carried P: at max_iters = 0 (the plan is then the warm start) unless solve_it"""
-    eng = DdpEngine(model, N, B, opts=dict(OPTS, **({} if solve_it else dict(max_iters=0)), **(opts or {})), consts=consts)
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    eng.solve(P)
-    return eng
+# (record [n, 8], G [n, N + 1, np], lambda [n, N + 1, nx]); lambda and words 4, 5, 6 are the stationarity certificate's
+_run = functools.partial(run, PARAM_GRADIENT)
+_same_costates = functools.partial(assert_same_costates, (pg.LAM0, pg.STAT, pg.DEFECT))
 
 
 def _check(J, got, x, u, P, label):
@@ -62,13 +55,6 @@ def _check(J, got, x, u, P, label):
         worst = max(worst, pg.assert_result(rec[b], G[b], pg.reference(J, x[b], u[b], P[b], lam[b]), f"{label} instance {b}"))
         assert rec[b, pg.NODES] == u.shape[1]
     print(f"{label}: worst error / tolerance {worst:.3e}")
-
-
-def _same_costates(eng, got, x=None, u=None, first=0, count=None):
-    """lambda and words 4, 5, 6 are the stationarity certificate's, bit for bit"""
-    srec, slam, _ = STATIONARITY.device(eng, first, count, x, u)
-    assert got[2].tobytes() == slam.tobytes()
-    assert got[0][:, [pg.LAM0, pg.STAT, pg.DEFECT]].tobytes() == srec[:, [4, 0, 6]].tobytes()
 
 
 @pytest.mark.parametrize("N", (1, 2, 65))
@@ -178,19 +164,7 @@ def test_nothing_else_moves():
 
 
 def test_a_nan_stays_on_its_instance():
-    model, N, B = "srbd13", 6, 3
-    batch, x, u, P = pg.random_plan(model, N, B, seed=5)
-    eng = _engine(model, N, B, batch["consts"], P, batch)
-    clean = _run(eng, x=x, u=u)
-    bad = x.copy()
-    bad[1, 2, 4] = np.nan                                                       # instance 1, node 2, one state entry
-    got = _run(eng, x=bad, u=u)
-    assert np.isnan(got[0][1, pg.GRAD]) and got[0][1, pg.NODE] == -1 and got[0][1, pg.COLUMN] == -1
-    assert got[0][1, pg.NODES] == N
-    keep = [0, 2]
-    assert all(a[keep].tobytes() == b_[keep].tobytes() for a, b_ in zip(got, clean))
-    assert np.isnan(got[1][1, 2]).any() and not np.isnan(got[1][1, 3:]).any()    # the nodes behind it do not see node 2
-    eng.close()
+    assert_a_nan_stays_on_its_instance(PARAM_GRADIENT, pg.random_plan, pg.GRAD, (pg.NODE, pg.COLUMN), pg.NODES)
 
 
 def test_refusals():
@@ -198,20 +172,7 @@ def test_refusals():
 
 
 def test_a_user_build_is_refused():
-    from srbd_horizon_amd import workload
-    from tests import user_terms_defs as ud
-    N, B = 20, 2
-    spec, mid = ud.user_case("srbd13_terrain", N)
-    batch = workload.make_batch("srbd13", N, [0, 1])
-    eng = DdpEngine("srbd13", N, B, opts=dict(OPTS, max_iters=0), consts=dict(batch["consts"], extra_rows=spec.extra_rows()), model_id=mid)
-    eng.load(batch["x0"], batch["xs"], batch["us"])
-    eng.solve(ud.widen(batch["params"], spec))
-    out = torch.zeros((B, pg.W), dtype=torch.float64, device="cuda")
-    with pytest.raises(RuntimeError, match="no derivative in the parameters"):
-        eng.param_gradient_device(out)
-    assert PARAM_GRADIENT.raw(eng, 0, B, None, None, eng._dev(out, out.shape)) == -1      # SDDP_ERR_ARG
-    assert STATIONARITY.device(eng)[0].shape == (B, 8)                           # and the handle still works
-    eng.close()
+    assert_a_user_build_is_refused(PARAM_GRADIENT, "no derivative in the parameters")
 
 
 def test_envelope_of_the_optimal_cost():

@@ -31,8 +31,8 @@ def _point(name, key, seed):
 
 @pytest.mark.parametrize("name", pg.MODELS)
 def test_the_assembly_is_sym_models_own(name):
-    """assemble() on the default constants gives the expressions of sym_models.symbolic(name)[0]["_sym"]: f and both residual vectors
-    agree at random points to rounding"""
+    """jacobians() on the default constants compiles the expressions of sym_models.symbolic(name)[0]["_sym"] (both are
+    sym_models.assemble's): f and both residual vectors agree at random points to rounding"""
     xs, us, ps, f, ires, sres, _ = sm.symbolic(name)[0]["_sym"]
     import sympy as sp
     own = pg.jacobians(name)
@@ -131,7 +131,7 @@ def _adapter(prb, np_model, nx, extra_refs=(), user=None):
                                          (lambda: __import__("srbd_horizon_amd.prb", fromlist=["x"]).LIPProblem().createLIPProblem(6, 1.0), "lip30")])
 def test_parameter_names_follow_the_parameter_matrix(maker, model):
     prb = maker()
-    nx, _, np_ = pg.DIMS[model]
+    nx, _, np_ = sm.DIMS[model]
     s = _adapter(prb, np_, nx)
     out = s.parameter_gradient()
     # the columns of parameter_matrix(): every Parameter row by row in creation order.  Assigning column index j to every node of the
