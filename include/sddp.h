@@ -624,6 +624,49 @@ int  sddp_unfinished_count(sddp_handle* h, int first, int count, int* n);
  *     instance when it leaves status 1) work behind a time cut as behind a max_iters cut.  (v9) */
 int  sddp_set_time_budget(sddp_handle* h, double budget_us, int min_iters);
 int  sddp_time_budget_info(sddp_handle* h, double* budget_us, int* min_iters);
+/* ---- masked launches: solve, continue, export and advance ANY subset of a range (v9) ---------------------------------------------
+ * The stationarity certificate, the cost-to-go at a measured state and the time budget tell a fleet server which robots deserve a
+ * solve now; robots of one handle may also tick at different rates.  A mask lets the caller act on that without a second handle:
+ * d_mask is a DEVICE array of `count` ints, d_mask[i] != 0 selects instance first + i.  A mask holds no index: there is nothing in it
+ * to validate and no value of it can make a kernel read or write outside the range.  The four launches are asynchronous on the
+ * handle's stream and make no host synchronisation: the selected count never travels to the host before the launch.
+ * How: a queued solve launch hands out order[i] for queue positions i = head++, while i < count.  A masked launch is always such a queue
+ * (also when count <= slots): a pre-pass behind the deadline stamp and the class labelling builds `order` with every unselected
+ * instance at [0, count - n_selected) and the selected ones behind them, in the order options.queue_order asks for (0: index order;
+ * 1: previous iteration count; 2: initial cost; 3: class history, the cost breaking ties), and sets the queue head to
+ * count - n_selected.  The partition is exact: for order 1 the unselected instances have a bin of their own, for orders 2 / 3 the cost
+ * keys of the WHOLE range are evaluated, the unselected ones' discarded for +infinity and the selected ones' clamped to the finite
+ * doubles (a NaN or infinite initial cost: DBL_MAX, first among the selected), so no selected key ties with an unselected one.  The
+ * solve kernels are the range launch's, on min(slots, count) workgroups; those that find the queue empty leave at once.
+ * sddp_solve_masked_device: a selected instance gets exactly what sddp_solve_range_device gives it, bit for bit -- xs, us, every
+ *   field of sddp_stats, its resume flag and carry row, its log records -- whatever the mask, queue order, slot count or kernel build.
+ *   Every byte the handle keeps for an UNSELECTED instance is unchanged: xs, us, stats, the previous iteration count that queue_order
+ *   = 1 sorts by, resume flag and carry row, log rows and count, policy and value records, and its class label (under
+ *   sddp_enable_auto_classes the selected instances alone are relabelled).  The class history counts selected instances only, under
+ *   the resume rule above.  With a time budget armed the deadline stamp stays the first kernel: the budget covers the mask pre-pass.
+ * sddp_continue_masked_device: runs the instances that are selected AND have flag 1; everything else is untouched.  SDDP_ERR_ARG
+ *   without sddp_enable_resume or before any solve, like sddp_continue_range_device.
+ * sddp_policy_masked_device: policy records (and, with sddp_enable_value, value records) of the selected instances alone, the bytes
+ *   sddp_policy_range_device writes; the others keep theirs.  SDDP_ERR_ARG without sddp_enable_policy or before any solve.  It keeps
+ *   an order array of its own: SDDP_BUF_ORDER / SDDP_BUF_SELECTED stay those of the last solve launch.
+ * sddp_advance_masked_device: sddp_advance for the selected instances, from device rows indexed like the mask: the resident
+ *   parameter rows shift and node N becomes d_p_last[i]; xs / us shift with the last row kept; x0 becomes d_x0[i]; the resume flag is
+ *   cleared.  For an unselected instance it writes nothing.  Both pointers are required (SDDP_ERR_ARG if either is NULL); SDDP_ERR_ARG
+ *   without resident parameters (sddp_set_params) or a previous solution / warm start.  One difference from sddp_advance: it
+ *   writes x0 for the selected instances only, so it does not stand in for sddp_set_initial_state -- a handle whose initial
+ *   states were never set still refuses to solve after it.
+ * Every one of them: SDDP_ERR_ARG, with a message, for a NULL mask or a range outside the handle.
+ * Edges: an all-zero mask launches nothing that writes a result (n_selected = 0); an all-ones mask gives the range launch's results.
+ * Bookkeeping after a masked solve or continue launch: sddp_queue_info reports last_queued = count; SDDP_BUF_ORDER is the whole [count]
+ *   array, its last n_selected entries the hand-out order; SDDP_BUF_GAINS is refused, as after any queued launch.
+ * sddp_last_selected: *n_selected of the last masked solve / continue launch (0 before the first); waits for the stream.  On the
+ *   device: SDDP_BUF_SELECTED. */
+int  sddp_solve_masked_device(sddp_handle* h, const double* d_params, int first, int count, const int* d_mask);
+int  sddp_continue_masked_device(sddp_handle* h, const double* d_params, int first, int count, const int* d_mask);
+int  sddp_policy_masked_device(sddp_handle* h, int first, int count, const int* d_mask);
+int  sddp_advance_masked_device(sddp_handle* h, int first, int count, const int* d_mask, const double* d_p_last /*[count][np]*/,
+                                const double* d_x0 /*[count][nx]*/);
+int  sddp_last_selected(sddp_handle* h, int* n_selected);
 /* ---- iteration log: one record per line search of every solve, kept on the device (opt-in; a handle that never calls
  * sddp_enable_iteration_log launches exactly the kernels it always did) ---------------------------------------------------------
  * What an instance did on its way through a solve: the step lengths, mu bumps, theta drops, the growth of rho, expected against
@@ -766,6 +809,8 @@ int  sddp_fetch(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats 
                                   sddp_enable_auto_classes); SDDP_ERR_ARG without a class table */
 #define SDDP_BUF_VALUE (SDDP_BUF_CLASSES + 1) /* = 13: value records [B][words] (the cost-to-go export above); SDDP_ERR_ARG without
                                                  sddp_enable_value */
+#define SDDP_BUF_SELECTED (SDDP_BUF_CLASSES + 2) /* = 14: int [2]: n_selected, queue start (= count - n_selected) of the last masked solve /
+                                                    continue launch; zeros before the first */
 int  sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes);
 /* average device time (ms) of the last `sddp_solve*` kernel launch measured with HIP events on the handle's stream */
 int  sddp_last_kernel_ms(sddp_handle* h, double* ms);

@@ -27,6 +27,8 @@ MODEL_IDS = {"srbd13": 0, "srbd37": 1, "lip30": 2, "srbd61": 3}
 # ... and the value records (SDDP_BUF_VALUE, which the header derives from SDDP_BUF_CLASSES: the thirteen above are the ids that
 # callers once passed as bare numbers, and tests/test_abi.py pins that set)
 DEVICE_BUF_VALUE = BUF_CLASSES + 1
+# ... and the two words of the last masked launch, n_selected | queue start (SDDP_BUF_SELECTED, derived in the header the same way)
+DEVICE_BUF_SELECTED = BUF_CLASSES + 2
 
 
 class SddpOptions(C.Structure):
@@ -175,6 +177,11 @@ SYMBOLS = {
     "sddp_unfinished_count": (C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_int)]),
     "sddp_set_time_budget": (C.c_int, [_vp, C.c_double, C.c_int]),
     "sddp_time_budget_info": (C.c_int, [_vp, _P(C.c_double), _P(C.c_int)]),
+    "sddp_solve_masked_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "sddp_continue_masked_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "sddp_policy_masked_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "sddp_advance_masked_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "sddp_last_selected": (C.c_int, [_vp, _P(C.c_int)]),
     "sddp_enable_iteration_log": (C.c_int, [_vp, C.c_int]),
     "sddp_iteration_log_info": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
     "sddp_fetch_iteration_log": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),

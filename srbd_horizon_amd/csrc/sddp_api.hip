@@ -68,6 +68,19 @@ int launch_class_labels(sddp_handle* h, const double* P, int first, int count) {
                   count, P, h->classes.cls);
 }
 
+// the masked forms (sddp_*_masked_device): labels and class statistics of the selected instances alone
+int launch_class_labels_masked(sddp_handle* h, const double* P, int first, int count, const int* mask) {
+    const ModelOps* o = h->ops;
+    return launch(h, class_label_masked_kernel, (count + 3) / 4, 256, 0, h->N, h->d.np, o->col_cmd[0], o->col_cmd[1], o->col_sw[0], o->col_sw[1],
+                  first, count, mask, P, h->classes.cls);
+}
+int launch_class_update_masked(sddp_handle* h, int first, int count, const int* mask) {
+    const auto& c = h->classes;
+    const int* res = h->resume.on() ? h->resume.resumable : nullptr;      // the resume rule, as launch_class_update
+    return launch(h, class_update_masked_kernel, (count + 255) / 256, 256, 0, first, count, mask, c.cls, c.n_cls, h->stats, c.cls_stat, res,
+                  res ? res + ResumeLayout::ran(size_t(h->B)) : nullptr, h->resume.continuing ? 1 : 0);
+}
+
 // Buffer ownership: every device and pinned allocation of a handle is made by acquire(), which registers it in h->owned.
 // sddp_destroy frees what is registered; release() frees what a handle gives up earlier, and nulls the pointer.
 // sddp_create reserves kOwnedReserve entries (host out-of-memory is SDDP_ERR_NOMEM there), more than a handle has buffers, so the
@@ -266,10 +279,35 @@ int invalidate_resume(sddp_handle* h, int first, int count) {
 unsigned long long* clock_words(sddp_handle* h) {
     return reinterpret_cast<unsigned long long*>(h->resume.resumable + ResumeLayout::clock_words(h->B));
 }
+// The pre-pass of a masked launch: `order` [count] with every unselected instance of the range at [0, count - n_selected) and the
+// selected ones behind them, in the order queue_order asks for (0: index order, 1: previous iteration count, 2: initial cost, 3: class
+// history with the cost tie-break; ties in arbitrary order), then the queue head at count - n_selected and, sel != null, the two
+// words of SDDP_BUF_SELECTED.  The selected count stays on the device.  Orders 2 / 3 evaluate the cost key of EVERY instance of the
+// range with the build's own key kernel and discard the unselected ones (masked_key_kernel).
+int launch_masked_order(sddp_handle* h, const SolveArgs& a, int first, int count, const int* mask, int queue_order, int* order, int* sel) {
+    int rc = SDDP_OK;
+    if (queue_order <= 0) {
+        return launch(h, queue_index_masked_kernel, 1, 1024, 0, first, count, mask, order, h->qhead, sel);      // (writes the head itself)
+    } else if (queue_order == 1) {
+        return launch(h, queue_order_masked_kernel, 1, 1024, 0, first, count, (const int*)h->hist, mask, order, h->qhead, sel);      // (likewise)
+    } else {
+        rc = alloc_cold_queue(h);
+        if (rc == SDDP_OK) rc = h->ops->launch_cost_keys(h, a, first, count);
+        if (rc == SDDP_OK && queue_order == 3 && h->classes.on()) rc = launch_class_keys(h, count);
+        if (rc == SDDP_OK) rc = launch(h, masked_key_kernel, (count + 255) / 256, 256, 0, count, mask, h->cold.qkey);
+        if (rc == SDDP_OK)
+            HIP_TRY(h, sort_pairs_desc(h->cold.sort_tmp, h->cold.sort_tmp_bytes, h->cold.qkey, h->cold.qkey2, h->cold.order_in, order, count, h->stream));
+    }
+    if (rc != SDDP_OK) return rc;
+    return launch(h, mask_head_kernel, 1, 256, 0, count, mask, h->qhead, sel);
+}
+
 // Where the solve and the continue entry points meet: one launch over the instances [first, first + count), as a sequence on the
 // handle's stream.  The build says which solve kernel runs, launches it (ModelOps::solve of the variant the handle's state asks for)
 // and has the cost-key kernel; the rest is here.  More instances than the grid -> work queue, in the order opts.queue_order asks for.
-int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
+// mask != null (a device array of `count` words): a masked launch -- the instances with mask[i] != 0 alone are labelled, handed out
+// and counted; always a queue, whose head starts behind the unselected instances (launch_masked_order).
+int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count, const int* mask = nullptr) {
     // with a time budget armed (sddp_set_time_budget) the deadline stamp leads: in front of the queue_order pre-pass and the sort,
     // which the budget therefore covers
     if (h->resume.budget_us > 0.0 && h->resume.on()) {
@@ -294,13 +332,19 @@ int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
         HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending], h->stream));
     }
     if (h->classes.auto_cls && !h->resume.continuing) {   // auto classes: a fresh solve labels its instances first, from the tensor it runs on; a
-        rc = launch_class_labels(h, a.P, first, count);      // continue launch keeps the labels of the solve that was cut
+        rc = mask ? launch_class_labels_masked(h, a.P, first, count, mask)      // continue launch keeps the labels of the solve that was cut
+                  : launch_class_labels(h, a.P, first, count);
         if (rc != SDDP_OK) return rc;
+    }
+    if (mask) {
+        rc = launch_masked_order(h, a, first, count, mask, h->opts.queue_order, h->order, h->qhead + sddp_handle::kQheadSelected);
+        if (rc != SDDP_OK) return rc;
+        a.order = h->order;
     }
     int grid = 0;
     rc = queue_grid(h, a, k.slots, count, &grid);
     if (rc != SDDP_OK) return rc;
-    if (count > grid && h->opts.queue_order >= 1) {
+    if (!mask && count > grid && h->opts.queue_order >= 1) {
         if (h->opts.queue_order == 1) {            // longest previous solve first
             rc = launch_queue_order(h, first, count);
         } else {                                   // largest initial cost first: keys by a pre-pass over the launch's instances
@@ -314,14 +358,16 @@ int launch_solve_sequence(sddp_handle* h, SolveArgs a, int first, int count) {
         if (rc != SDDP_OK) return rc;
         a.order = h->order;
     }
-    h->last_grid = grid; h->last_queued = count > grid ? count : 0;
+    h->last_grid = grid; h->last_queued = (mask || count > grid) ? count : 0;
+    h->last_masked = mask != nullptr;
     h->last_build = k.wps;
     h->last_kernel = k.kern;
     h->last_lds = int(k.lds);
     h->last_per_cu = k.slots / std::max(1, h->cus);
-    h->gains_by_instance = (count <= grid && first == 0);
+    h->gains_by_instance = (!mask && count <= grid && first == 0);
     rc = solve.launch(h, k, grid, a);
-    if (rc == SDDP_OK && h->classes.on()) rc = launch_class_update(h, first, count);      // labelled instances feed the class statistics
+    if (rc == SDDP_OK && h->classes.on())      // labelled instances feed the class statistics
+        rc = mask ? launch_class_update_masked(h, first, count, mask) : launch_class_update(h, first, count);
     if (rc != SDDP_OK) return rc;
     if (h->timing) {
         HIP_TRY(h, hipEventRecord(h->ev[2 * h->pending + 1], h->stream));
@@ -705,7 +751,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     if (e == hipSuccess) e = alloc(h->gains, W * N * d.nu * (d.nx + 1) * D);
     if (e == hipSuccess) e = alloc(h->rec, W * (N + 1) * d.nrec * D);
     if (e == hipSuccess) e = alloc(h->scal, size_t(batch) * kScal * D);
-    if (e == hipSuccess) e = alloc(h->qhead, sizeof(int));
+    if (e == hipSuccess) e = alloc(h->qhead, sddp_handle::kQheadInts * sizeof(int));      // the head, and the words of SDDP_BUF_SELECTED
     if (e == hipSuccess) e = alloc(h->order, size_t(batch) * sizeof(int));
     if (e == hipSuccess) e = alloc(h->hist, HistLayout::bytes(batch, h->wslots));      // the iteration counts, then the slot clocks
     // on the handle's own stream, and complete before sddp_create returns: a null-stream hipMemset is asynchronous to the host
@@ -715,7 +761,7 @@ int sddp_create(sddp_handle** out, int model_id, int N, int batch, const sddp_op
     if (e == hipSuccess) e = hipMemsetAsync(h->dft, 0, W * N * d.nx * D, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->gains, 0, W * N * d.nu * (d.nx + 1) * D, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->hist, 0xff, size_t(batch) * sizeof(int), h->stream);      // -1: never solved
-    if (e == hipSuccess) e = hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->qhead, 0, sddp_handle::kQheadInts * sizeof(int), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         create_error() = std::string("sddp_create: ") + hipGetErrorString(e);
@@ -832,15 +878,23 @@ int sddp_set_u_warmstart_device(sddp_handle* h, const double* d) {
     return sddp_load_range_device(h, 0, h->B, nullptr, nullptr, d);
 }
 
-int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, int count) {
+// a fresh solve launch over [first, first + count); mask: null, or the device mask of a masked launch
+static int solve_range(sddp_handle* h, const double* d_params, int first, int count, const int* mask) {
     int rc = check_ready(h);
     if (rc != SDDP_OK) return rc;
     if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
-    rc = launch_solve_sequence(h, a, first, count);
+    rc = launch_solve_sequence(h, a, first, count, mask);
     if (rc == SDDP_OK) h->last_params = d_params;      // what sddp_policy_range_device differentiates against
     return rc;
+}
+int sddp_solve_range_device(sddp_handle* h, const double* d_params, int first, int count) { return solve_range(h, d_params, first, count, nullptr); }
+
+int sddp_solve_masked_device(sddp_handle* h, const double* d_params, int first, int count, const int* d_mask) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!d_mask) return fail(h, SDDP_ERR_ARG, "sddp_solve_masked_device: the mask is NULL");
+    return solve_range(h, d_params, first, count, d_mask);
 }
 
 int sddp_solve_device(sddp_handle* h, const double* d_params) {
@@ -868,7 +922,7 @@ int sddp_enable_resume(sddp_handle* h, int on) {
     return SDDP_OK;
 }
 
-int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first, int count) {
+static int continue_range(sddp_handle* h, const double* d_params, int first, int count, const int* mask) {
     int rc = check_ready(h);
     if (rc != SDDP_OK) return rc;
     if (!h->resume.on()) return fail(h, SDDP_ERR_ARG, "sddp_continue: sddp_enable_resume has not been called (plain builds only: no barrier, no "
@@ -877,13 +931,28 @@ int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first
     if (!d_params) return fail(h, SDDP_ERR_ARG, "params is NULL");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, d_params);
-    if (h->classes.on())   // which instances this launch resumes: the class statistics count those that it also finishes
+    // which instances this launch resumes: the class statistics count those that it also finishes.  (A masked continue clears the
+    // words of its whole range, unselected instances included: `ran` is scratch of the launch in flight, rewritten by every continue
+    // launch, and no part of what the handle KEEPS for an instance -- outside the masked launches' contract.)
+    if (h->classes.on())
         HIP_TRY(h, hipMemsetAsync(h->resume.resumable + ResumeLayout::ran(size_t(h->B)) + first, 0, size_t(count) * sizeof(int), h->stream));
     h->resume.continuing = true;
-    rc = launch_solve_sequence(h, a, first, count);
+    rc = launch_solve_sequence(h, a, first, count, mask);
     h->resume.continuing = false;
     if (rc == SDDP_OK) h->last_params = d_params;
     return rc;
+}
+int sddp_continue_range_device(sddp_handle* h, const double* d_params, int first, int count) { return continue_range(h, d_params, first, count, nullptr); }
+
+int sddp_continue_masked_device(sddp_handle* h, const double* d_params, int first, int count, const int* d_mask) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!d_mask) return fail(h, SDDP_ERR_ARG, "sddp_continue_masked_device: the mask is NULL");
+    return continue_range(h, d_params, first, count, d_mask);
+}
+
+int sddp_last_selected(sddp_handle* h, int* n_selected) {
+    if (!h || !n_selected) return SDDP_ERR_ARG;
+    return download(h, n_selected, h->qhead + sddp_handle::kQheadSelected, sizeof(int));
 }
 
 int sddp_continue_device(sddp_handle* h, const double* d_params) {
@@ -1098,6 +1167,20 @@ int sddp_advance(sddp_handle* h, const double* p_last, const double* x0) {
     const int rc = launch(h, advance_kernel, h->B, 256, 0, h->N, h->d.nx, h->d.nu, h->d.np, h->P, h->xs, h->us, h->x0, d_pl, d_x0);
     if (rc == SDDP_OK) h->have_x0 = true;
     return rc == SDDP_OK ? invalidate_resume(h, 0, h->B) : rc;
+}
+
+int sddp_advance_masked_device(sddp_handle* h, int first, int count, const int* d_mask, const double* d_p_last, const double* d_x0) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!d_mask) return fail(h, SDDP_ERR_ARG, "sddp_advance_masked_device: the mask is NULL");
+    if (!d_p_last || !d_x0) return fail(h, SDDP_ERR_ARG, "sddp_advance_masked_device: d_p_last and d_x0 are both required");
+    if (!h->have_params) return fail(h, SDDP_ERR_ARG, "sddp_advance_masked_device: no resident parameters (sddp_set_params has not been called)");
+    if (!h->have_xws || !h->have_uws) return fail(h, SDDP_ERR_ARG, "sddp_advance_masked_device needs a previous solution or warm start");
+    if ((h->N + 1) * std::max(h->d.np, h->d.nx) > kAdvanceWords) return fail(h, SDDP_ERR_ARG, "horizon too long for sddp_advance");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    int* flags = h->resume.on() ? h->resume.resumable + ResumeLayout::flags(size_t(h->B)) : nullptr;      // invalidation, selected instances alone
+    const int rc = launch(h, advance_masked_kernel, count, 256, 0, h->N, h->d.nx, h->d.nu, h->d.np, h->P, h->xs, h->us, h->x0, d_p_last, d_x0, first,
+                          d_mask, flags);
+    return rc;
 }
 
 int sddp_solve_resident(sddp_handle* h, double* x_out, double* u_out, sddp_stats* stats) {
@@ -1348,6 +1431,21 @@ int sddp_policy_range_device(sddp_handle* h, int first, int count) {
     if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_range_device: no solve has run on this handle");
     if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
     SolveArgs a = make_args(h, h->last_params);
+    return h->ops->launch_policy(h, a, first, count, h->pol.policy, h->pol.policy_knots, h->val.value, h->val.nodes);
+}
+
+int sddp_policy_masked_device(sddp_handle* h, int first, int count, const int* d_mask) {
+    if (!h) return SDDP_ERR_ARG;
+    if (!h->pol.on()) return fail(h, SDDP_ERR_ARG, "sddp_enable_policy has not been called");
+    if (!h->last_params) return fail(h, SDDP_ERR_ARG, "sddp_policy_masked_device: no solve has run on this handle");
+    if (!d_mask) return fail(h, SDDP_ERR_ARG, "sddp_policy_masked_device: the mask is NULL");
+    if (check_range(h, first, count) != SDDP_OK) return SDDP_ERR_ARG;
+    // an order array of its own: SDDP_BUF_ORDER and SDDP_BUF_SELECTED go on describing the last solve launch
+    if (!h->pol_order) ACQUIRE_TRY(h, h->pol_order, size_t(h->B) * sizeof(int));
+    SolveArgs a = make_args(h, h->last_params);
+    const int rc = launch_masked_order(h, a, first, count, d_mask, 0, h->pol_order, nullptr);      // every instance costs one sweep: index order
+    if (rc != SDDP_OK) return rc;
+    a.order = h->pol_order;
     return h->ops->launch_policy(h, a, first, count, h->pol.policy, h->pol.policy_knots, h->val.value, h->val.nodes);
 }
 
@@ -1685,8 +1783,11 @@ int sddp_device_ptr(sddp_handle* h, int which, void** ptr, long long* bytes) {
         case SDDP_BUF_X0: *ptr = h->x0; n = (long long)(size_t(h->B) * h->d.nx * sizeof(double)); break;
         case SDDP_BUF_PARAMS: *ptr = h->P; n = (long long)(h->n_p() * sizeof(double)); break;
         case SDDP_BUF_ORDER:   // the order the last queued launch handed its instances out in (absolute instance indices)
-            if (!h->last_queued || h->opts.queue_order == 0) return fail(h, SDDP_ERR_ARG, "the last solve launch had no ordered queue");
+            // (a masked launch has one whatever queue_order: the whole [count] array, the hand-out order its last n_selected entries)
+            if (!h->last_queued || (h->opts.queue_order == 0 && !h->last_masked)) return fail(h, SDDP_ERR_ARG, "the last solve launch had no ordered queue");
             *ptr = h->order; n = (long long)(size_t(h->last_queued) * sizeof(int)); break;
+        case SDDP_BUF_SELECTED:   // n_selected | queue start of the last masked solve / continue launch (zeros before the first)
+            *ptr = h->qhead + sddp_handle::kQheadSelected; n = (long long)(2 * sizeof(int)); break;
         case SDDP_BUF_SLOT_TIMES:   // per slot of the last solve launch: (start, queue found empty) on the 100 MHz constant-rate clock
             if (h->last_grid < 1) return fail(h, SDDP_ERR_ARG, "no solve launch yet");
             *ptr = h->hist + HistLayout::counts(h->B); n =(long long)(size_t(h->last_grid) * 2 * sizeof(unsigned long long)); break;

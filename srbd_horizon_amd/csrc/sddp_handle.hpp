@@ -143,8 +143,11 @@ struct sddp_handle {
     // work queue: the solve launch runs on `slots` resident workgroups that pull instances from a queue
     int wslots = 0;                 // slots the work buffers (xn un xc uc dft gains rec) are allocated for = min(B, resident capacity)
     int cus = 0;
-    int* qhead = nullptr;           // device queue head
+    int* qhead = nullptr;           // device queue head; behind it (kQheadSelected) the two words of SDDP_BUF_SELECTED
+    static constexpr int kQheadSelected = 2, kQheadInts = 4;
     int* order = nullptr;           // [B] queue order of the next launch
+    int* pol_order = nullptr;       // [B] the order of a masked policy launch (made by the first one): `order` stays the last solve launch's
+    bool last_masked = false;       // the last solve launch was a masked one: its order array is whole ([count]) whatever queue_order
     int* hist = nullptr;            // iterations of each instance's previous solve (-1: none), then the slot clocks (HistLayout)
     bool gains_by_instance = false; // the last solve launch ran instance b on slot b (no queue, first = 0): sddp_device_ptr(3)
     // every kernel of the model build that this handle has launched (solve builds, policy, backward, forward, without and with
@@ -273,10 +276,15 @@ int launch(sddp_handle* h, Fn kern, int grid, int threads, size_t lds, const A&.
 
 // The grid of a launch over `count` instances by a kernel with `slots` resident workgroups: at most the slots the work buffers exist
 // for, and opts.max_slots.  More instances than that make a work queue: its head is zeroed on the stream and entered in `a`.
+// A masked launch (a.order set by its pre-pass, sddp_api.hip launch_masked_order) is a queue whatever its size, and its head is
+// already on the stream: the pre-pass wrote it (the order kernel of orders 0 / 1 and of a policy launch, mask_head_kernel behind the
+// sort of orders 2 / 3).
 inline int queue_grid(sddp_handle* h, SolveArgs& a, int slots, int count, int* grid) {
     *grid = std::min(count, std::min(slots, h->wslots));
     if (h->opts.max_slots > 0) *grid = std::min(*grid, h->opts.max_slots);
-    if (count > *grid) {
+    if (a.order) {
+        a.qhead = h->qhead;
+    } else if (count > *grid) {
         HIP_TRY(h, hipMemsetAsync(h->qhead, 0, sizeof(int), h->stream));
         a.qhead = h->qhead;
     }

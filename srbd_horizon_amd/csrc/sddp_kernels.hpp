@@ -1358,9 +1358,9 @@ __device__ __forceinline__ void policy_instance(const SolveArgs& A, double* s, c
     wave_sync();
 }
 
-// a work queue like the solve launch (solve_queue), in index order: every instance costs one sweep.  The table kernel is written
-// out beside the plain one: every form that folded the two into one template moved the register allocation of one of them
-// (profiles/hetero_merge/README.md).
+// a work queue like the solve launch (solve_queue), in index order: every instance costs one sweep (A.order set: a masked launch, the
+// solve's hand-out).  The table kernel is written out beside the plain one: every form that folded the two into one template moved
+// the register allocation of one of them (profiles/hetero_merge/README.md).
 template <class M>
 __global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __restrict__ pol, int keep, double* __restrict__ val, int vnodes) {
     extern __shared__ __attribute__((aligned(16))) double s[];
@@ -1372,7 +1372,7 @@ __global__ __launch_bounds__(kWave) void policy_kernel(SolveArgs A, double* __re
         i = __builtin_amdgcn_readfirstlane(i);
     }
     while (i < A.count) {
-        policy_instance<M>(A, s, A.first + i, slot, pol, keep, val, vnodes);
+        policy_instance<M>(A, s, A.order ? A.order[i] : A.first + i, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);
         i = __builtin_amdgcn_readfirstlane(i);
@@ -1390,7 +1390,7 @@ __global__ __launch_bounds__(kWave) void policy_kernel_h(SolveArgs A, double* __
         i = __builtin_amdgcn_readfirstlane(i);
     }
     while (i < A.count) {
-        const int b = index_of(A.first + i, ctab);
+        const int b = index_of(A.order ? A.order[i] : A.first + i, ctab);
         policy_instance<M>(args_of(A, b, ctab), s, b, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) i = atomicAdd(A.qhead, 1);

@@ -82,11 +82,9 @@ __global__ __launch_bounds__(256) void class_update_resume_kernel(int first, int
 // One wavefront per instance, four per workgroup: lane l looks at node 64 c + l of chunk c and compares its two switches with node 0's,
 // lane 0's of chunk 0; the first set bit of the first non-empty ballot is first_change (node 0 never differs from itself).  np: the
 // handle's parameter row width.  About N + 1 cache lines per instance are touched, two words of each.
-__global__ __launch_bounds__(256) void class_label_kernel(int N, int np, int col_cmd0, int col_cmd1, int col_sw0, int col_sw1, int first, int count,
-                                                          const double* __restrict__ P, int* __restrict__ cls) {
-    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= count) return;                                    // (the whole wavefront)
-    const int b = first + i;
+// (the label of ONE instance, by one whole wavefront: the range kernel and the masked one below call it)
+__device__ __forceinline__ void class_label_instance(int N, int np, int col_cmd0, int col_cmd1, int col_sw0, int col_sw1, int b, int lane,
+                                                     const double* __restrict__ P, int* __restrict__ cls) {
     const double* Pb = P + size_t(b) * (N + 1) * np;
     int s0 = 0, first_change = N + 1;
     for (int k0 = 0; k0 <= N; k0 += 64) {
@@ -105,6 +103,126 @@ __global__ __launch_bounds__(256) void class_label_kernel(int N, int np, int col
         const int cx = vx > 1e-12 ? 1 : (vx < -1e-12 ? 2 : 0), cy = vy > 1e-12 ? 1 : (vy < -1e-12 ? 2 : 0);
         cls[b] = ((s0 * (N + 2) + first_change) * 3 + cx) * 3 + cy;
     }
+}
+__global__ __launch_bounds__(256) void class_label_kernel(int N, int np, int col_cmd0, int col_cmd1, int col_sw0, int col_sw1, int first, int count,
+                                                          const double* __restrict__ P, int* __restrict__ cls) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= count) return;                                    // (the whole wavefront)
+    class_label_instance(N, np, col_cmd0, col_cmd1, col_sw0, col_sw1, first + i, lane, P, cls);
+}
+
+// ---- masked launches (sddp_*_masked_device): mask[i] != 0 selects instance first + i of the range; every other instance of it is
+// handed out by no queue and written by no kernel below.  A mask is `count` words that are only compared with 0: there is no index in
+// it to validate, so whatever it holds no kernel here reads or writes outside [first, first + count).
+// The solve kernels take queue positions i = atomicAdd(qhead, 1) while i < count and solve order[i].  A masked launch is therefore an
+// order array whose first count - n_selected entries are the unselected instances and a queue head that STARTS at count - n_selected:
+// the kernels below build exactly that, and the solve kernels do not know.
+//
+// auto classes: the labels of the selected instances alone (class_label_kernel's, by the same code)
+__global__ __launch_bounds__(256) void class_label_masked_kernel(int N, int np, int col_cmd0, int col_cmd1, int col_sw0, int col_sw1, int first,
+                                                                 int count, const int* __restrict__ mask, const double* __restrict__ P,
+                                                                 int* __restrict__ cls) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= count || mask[i] == 0) return;                    // (the whole wavefront)
+    class_label_instance(N, np, col_cmd0, col_cmd1, col_sw0, col_sw1, first + i, lane, P, cls);
+}
+// the head of a masked launch's queue, by ONE thread: qhead = count - n_selected, and sel = n_selected | queue start
+// (SDDP_BUF_SELECTED; null: a policy launch, which leaves the words of the last solve launch alone).  Ordinary vector stores.
+__device__ __forceinline__ void write_mask_head(int count, int n_selected, int* __restrict__ qhead, int* __restrict__ sel) {
+    *qhead = count - n_selected;
+    if (sel) { sel[0] = n_selected; sel[1] = count - n_selected; }
+}
+// queue order 0 under a mask, and the order of a masked policy launch: a STABLE partition in one workgroup -- the unselected
+// instances in index order at [0, count - n_selected), the selected ones in index order behind them.  Thread t owns the contiguous
+// chunk [t per, (t + 1) per) of the range; an inclusive scan of the chunks' selected counts gives every chunk its two write positions,
+// and its last word is n_selected: the kernel writes the queue head itself.
+__global__ __launch_bounds__(1024) void queue_index_masked_kernel(int first, int count, const int* __restrict__ mask, int* __restrict__ order,
+                                                                  int* __restrict__ qhead, int* __restrict__ sel) {
+    __shared__ int part[1024];
+    const int tid = threadIdx.x;
+    const int per = (count + 1023) / 1024;
+    const int lo = min(tid * per, count), hi = min(lo + per, count);
+    int n = 0;
+    for (int i = lo; i < hi; ++i) n += mask[i] != 0 ? 1 : 0;
+    part[tid] = n;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    const int n_uns = count - part[1023];
+    if (tid == 0) write_mask_head(count, part[1023], qhead, sel);
+    int s = part[tid] - n;                                     // selected instances in front of this chunk
+    for (int i = lo; i < hi; ++i) {
+        if (mask[i] != 0) order[n_uns + s++] = first + i;
+        else order[i - s] = first + i;
+    }
+}
+// queue order 1 under a mask: queue_order_kernel's counting sort with one more bin, in front of all others, for the unselected
+// instances: the partition is a bin of its own and no property of a key, and that bin's count gives the queue head
+__global__ __launch_bounds__(1024) void queue_order_masked_kernel(int first, int count, const int* __restrict__ hist, const int* __restrict__ mask,
+                                                                  int* __restrict__ order, int* __restrict__ qhead, int* __restrict__ sel) {
+    __shared__ int bins[kOrderBins + 1];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < kOrderBins + 1; i += 1024) bins[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < count; i += 1024) {
+        const int h = hist[first + i];
+        atomicAdd(&bins[mask[i] == 0 ? kOrderBins : (h < 0 ? kOrderBins - 1 : (h > 256 ? 256 : h))], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {   // exclusive prefix, the unselected bin, then the largest key first
+        write_mask_head(count, count - bins[kOrderBins], qhead, sel);
+        int run = 0;
+        for (int k = kOrderBins; k >= 0; --k) { const int n = bins[k]; bins[k] = run; run += n; }
+    }
+    __syncthreads();
+    for (int i = tid; i < count; i += 1024) {
+        const int h = hist[first + i];
+        const int pos = atomicAdd(&bins[mask[i] == 0 ? kOrderBins : (h < 0 ? kOrderBins - 1 : (h > 256 ? 256 : h))], 1);
+        order[pos] = first + i;
+    }
+}
+// queue orders 2 and 3 under a mask: the keys of the whole range are evaluated as for a range launch (the unselected instances' keys
+// are computed and discarded here: the model's key kernel stays as it is), then mapped so that the descending sort IS the partition:
+// an unselected instance gets +infinity, a selected one its key clamped into [-DBL_MAX, DBL_MAX] -- a non-finite initial cost
+// ("stays first" in a range launch: +infinity, or NaN) becomes DBL_MAX: first among the SELECTED, and strictly behind every
+// unselected instance.  No selected key can tie with the sentinel.
+__global__ __launch_bounds__(256) void masked_key_kernel(int count, const int* __restrict__ mask, double* __restrict__ key) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    constexpr double kMax = 1.7976931348623157e308;
+    const double k = key[i];
+    key[i] = mask[i] == 0 ? __builtin_huge_val() : (k == k ? fmin(fmax(k, -kMax), kMax) : kMax);
+}
+// the head of a masked launch's queue for the orders whose order array comes out of the sort (2, 3): one workgroup counts the mask
+__global__ __launch_bounds__(256) void mask_head_kernel(int count, const int* __restrict__ mask, int* __restrict__ qhead, int* __restrict__ sel) {
+    __shared__ int part[256];
+    int n = 0;
+    for (int i = threadIdx.x; i < count; i += 256) n += mask[i] != 0 ? 1 : 0;
+    part[threadIdx.x] = n;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) write_mask_head(count, part[0], qhead, sel);
+}
+// the class statistics behind a masked launch: class_update_kernel / class_update_resume_kernel (resumable != null) for the selected
+// instances alone
+__global__ __launch_bounds__(256) void class_update_masked_kernel(int first, int count, const int* __restrict__ mask, const int* __restrict__ cls,
+                                                                  int n_cls, const sddp_stats* __restrict__ st,
+                                                                  unsigned long long* __restrict__ cls_stat, const int* __restrict__ resumable,
+                                                                  const int* __restrict__ ran, int cont) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count || mask[i] == 0) return;
+    const int b = first + i, c = cls[b];
+    if (c < 0 || c >= n_cls) return;
+    if (resumable && (resumable[b] == 1 || (cont && ran[b] != 1))) return;
+    atomicAdd(&cls_stat[2 * c], (unsigned long long)st[b].iters);
+    atomicAdd(&cls_stat[2 * c + 1], 1ull);
 }
 
 // sddp_add_class_stats: another handle's history (sums of iterations, solves; both additive) onto the words [2 first_class, ...) of
@@ -220,10 +338,11 @@ constexpr int kAdvanceWords = 4096;   // longest array advance_kernel shifts in 
 
 // receding-horizon tick on the device: shift parameters and warm start by one knot (one workgroup per instance; every element
 // is read before the barrier and written after it, so the in-place shift is safe)
-__global__ __launch_bounds__(256) void advance_kernel(int N, int nx, int nu, int np, double* __restrict__ P, double* __restrict__ xs,
-                                                      double* __restrict__ us, double* __restrict__ x0, const double* __restrict__ p_last,
-                                                      const double* __restrict__ x0_new) {
-    const int b = blockIdx.x, tid = threadIdx.x;
+// (instance b by one whole workgroup; row `src` of p_last / x0_new is its new last parameter row and its new initial state)
+__device__ __forceinline__ void advance_instance(int N, int nx, int nu, int np, double* __restrict__ P, double* __restrict__ xs,
+                                                 double* __restrict__ us, double* __restrict__ x0, const double* __restrict__ p_last,
+                                                 const double* __restrict__ x0_new, const int b, const int src) {
+    const int tid = threadIdx.x;
     double* Pb = P + size_t(b) * (N + 1) * np;
     double* xb = xs + size_t(b) * (N + 1) * nx;
     double* ub = us + size_t(b) * N * nu;
@@ -233,7 +352,7 @@ __global__ __launch_bounds__(256) void advance_kernel(int N, int nx, int nu, int
 #pragma unroll
     for (int t = 0; t < R; ++t) {
         const int e = tid + t * 256;
-        rp[t] = e < np_all ? (e + np < np_all ? Pb[e + np] : p_last[size_t(b) * np + (e - N * np)]) : 0.0;
+        rp[t] = e < np_all ? (e + np < np_all ? Pb[e + np] : p_last[size_t(src) * np + (e - N * np)]) : 0.0;
         rx[t] = e < nx_all ? xb[e + nx < nx_all ? e + nx : e] : 0.0;
         ru[t] = e < nu_all ? ub[e + nu < nu_all ? e + nu : e] : 0.0;
     }
@@ -245,7 +364,24 @@ __global__ __launch_bounds__(256) void advance_kernel(int N, int nx, int nu, int
         if (e < nx_all) xb[e] = rx[t];
         if (e < nu_all) ub[e] = ru[t];
     }
-    if (tid < nx) x0[size_t(b) * nx + tid] = x0_new[size_t(b) * nx + tid];
+    if (tid < nx) x0[size_t(b) * nx + tid] = x0_new[size_t(src) * nx + tid];
+}
+__global__ __launch_bounds__(256) void advance_kernel(int N, int nx, int nu, int np, double* __restrict__ P, double* __restrict__ xs,
+                                                      double* __restrict__ us, double* __restrict__ x0, const double* __restrict__ p_last,
+                                                      const double* __restrict__ x0_new) {
+    advance_instance(N, nx, nu, np, P, xs, us, x0, p_last, x0_new, blockIdx.x, blockIdx.x);
+}
+// sddp_advance_masked_device: the same tick for the selected instances of [first, first + count) alone, from device rows [count][np]
+// / [count][nx] indexed like the mask; and (resumable != null: sddp_enable_resume) their resume flags cleared, as the invalidation
+// behind sddp_advance does for the whole batch.  An unselected instance's workgroup leaves before the barrier, whole.
+__global__ __launch_bounds__(256) void advance_masked_kernel(int N, int nx, int nu, int np, double* __restrict__ P, double* __restrict__ xs,
+                                                             double* __restrict__ us, double* __restrict__ x0, const double* __restrict__ p_last,
+                                                             const double* __restrict__ x0_new, int first, const int* __restrict__ mask,
+                                                             int* __restrict__ resumable) {
+    const int i = blockIdx.x;
+    if (mask[i] == 0) return;                              // (the whole workgroup)
+    advance_instance(N, nx, nu, np, P, xs, us, x0, p_last, x0_new, first + i, i);
+    if (resumable && threadIdx.x == 0) resumable[first + i] = 0;
 }
 
 }  // namespace sddp

@@ -1487,7 +1487,7 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw(SolveArgs A, doub
     int i = queued ? *q_pos : slot;
     __syncthreads();
     while (i < A.count) {
-        policy_instance_mw<M, mw_sink<M>(false)>(A, s, A.first + i, slot, pol, keep, val, vnodes);
+        policy_instance_mw<M, mw_sink<M>(false)>(A, s, A.order ? A.order[i] : A.first + i, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);
         __syncthreads();
@@ -1507,7 +1507,7 @@ __global__ __launch_bounds__(kThreadsMW) void policy_kernel_mw_h(SolveArgs A, do
     int i = queued ? *q_pos : slot;
     __syncthreads();
     while (i < A.count) {
-        const int b = index_of(A.first + i, ctab);
+        const int b = index_of(A.order ? A.order[i] : A.first + i, ctab);
         policy_instance_mw<M, mw_sink<M>(false)>(args_of(A, b, ctab), s, b, slot, pol, keep, val, vnodes);
         if (!queued) break;
         if (threadIdx.x == 0) *q_pos = atomicAdd(A.qhead, 1);

@@ -213,6 +213,7 @@ int launch_forward(sddp_handle* h, const SolveArgs& a) {
 // policy_kernel_mw), as a work queue over the resident workgroups of THAT kernel (the one-wave kernel: at most 8 per CU); the work
 // buffers dft / rec are the solve's, per slot.  has_policy<M>() builds only: make_ops leaves the entry null elsewhere.
 // val: the value buffer (sddp_enable_value) and the nodes it keeps, filled for the range by the same sweep; null: the export is off.
+// a.order set: a masked launch -- the queue hands out order[i] from the head its pre-pass left on the stream (queue_grid).
 template <class M>
 int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol, int keep, double* val, int vnodes) {
     return with_table<M>(h, [&](auto... tab) {
@@ -220,7 +221,7 @@ int launch_policy(sddp_handle* h, SolveArgs a, int first, int count, double* pol
         int slots = 0;
         int rc = kernel_slots<M>(h, kern, use_mw<M>() ? 0 : 8, &slots);
         if (rc != SDDP_OK) return rc;
-        a.first = first; a.count = count; a.order = nullptr; a.qhead = nullptr;
+        a.first = first; a.count = count; a.qhead = nullptr;      // a.order: null, or the order of a masked launch (sddp_policy_masked_device)
         int grid = 0;
         rc = queue_grid(h, a, slots, count, &grid);
         if (rc != SDDP_OK) return rc;

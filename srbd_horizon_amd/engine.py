@@ -592,6 +592,52 @@ class DdpEngine:
         """One asynchronous launch over the instances [first, first + count); `params` is the whole [B, N+1, np] tensor."""
         self._chk(self.lib.sddp_solve_range_device(self.h, self._dev(params, (self.B, self.N + 1, self.np_)), int(first), int(count)))
 
+    # ---- masked launches: solve, continue, export and advance any subset of a range (include/sddp.h) ---------------------------
+    @staticmethod
+    def _mask(mask, count):
+        """the device pointer of a mask: a contiguous int32 CUDA tensor of `count` words, non-zero = selected"""
+        import torch
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.int32 and mask.is_contiguous()):
+            raise ValueError("expected a contiguous int32 CUDA tensor as the mask")
+        if tuple(mask.shape) != (count,):
+            raise ValueError(f"expected a mask of shape {(count,)}, got {tuple(mask.shape)}")
+        return C.c_void_p(mask.data_ptr())
+
+    def _params_or_resident(self, params):
+        if params is None:
+            return C.c_void_p(self.device_buffer(_lib.BUF_PARAMS)[0])
+        return self._dev(params, (self.B, self.N + 1, self.np_))
+
+    def solve_masked_device(self, params, mask, first: int = 0, count: int | None = None):
+        """One asynchronous launch over the instances of [first, first + count) that `mask` selects (int32 device tensor [count],
+        non-zero = selected): each gets what solve_range_device gives it, bit for bit; every other instance is untouched.  params:
+        the whole [B, N+1, np] device tensor, None = the resident one.  No host synchronisation."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_solve_masked_device(self.h, self._params_or_resident(params), int(first), n, self._mask(mask, n)))
+
+    def continue_masked(self, mask, params=None, first: int = 0, count: int | None = None):
+        """continue_solve for the selected instances alone: those that are selected and unfinished are taken up where they stopped."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_continue_masked_device(self.h, self._params_or_resident(params), int(first), n, self._mask(mask, n)))
+
+    def policy_masked_device(self, mask, first: int = 0, count: int | None = None):
+        """policy_range_device for the selected instances alone; the records (and value records) of the others keep their bytes."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_policy_masked_device(self.h, int(first), n, self._mask(mask, n)))
+
+    def advance_masked_device(self, mask, p_last, x0, first: int = 0, count: int | None = None):
+        """advance() for the selected instances alone, from device tensors p_last [count, np] and x0 [count, nx] indexed like the
+        mask (rows of unselected instances are not read); their resume flags are cleared.  Asynchronous."""
+        n = self._count(first, count)
+        self._chk(self.lib.sddp_advance_masked_device(self.h, int(first), n, self._mask(mask, n), self._dev(p_last, (n, self.np_)),
+                                                      self._dev(x0, (n, self.nx))))
+
+    def last_selected(self) -> int:
+        """How many instances the last masked solve / continue launch selected (waits for the stream)."""
+        n = C.c_int()
+        self._chk(self.lib.sddp_last_selected(self.h, C.byref(n)))
+        return n.value
+
     # ---- resumable solves: continue a solve cut at max_iters, bit for bit (include/sddp.h) -------------------------------------
     def enable_resume(self, on: bool = True):
         """Every later solve launch of the handle can be continued: an instance that ends with status 1 (max_iters) keeps what the
