@@ -165,7 +165,9 @@ class Inspector(NamedTuple):
         n = eng.B - first if count is None else count
         mk = lambda *shape: torch.full((n, *shape), 7.0, dtype=torch.float64, device="cuda")      # noqa: E731
         out, opt = mk(self.words), {k: mk(*shape(eng)) if optional else None for k, shape in self.optional.items()}
-        getattr(eng, self.name + "_device")(out, first, n, x=dev(x), u=dev(u), **opt, **kw)
+        x, u = dev(x), dev(u)
+        torch.cuda.synchronize()      # the fills and uploads are on torch's stream, the kernel on the handle's: torch finishes first
+        getattr(eng, self.name + "_device")(out, first, n, x=x, u=u, **opt, **kw)
         eng.synchronize()
         return (out.cpu().numpy(), *(None if t is None else t.cpu().numpy() for t in opt.values()))
 

@@ -1,5 +1,6 @@
 """The three ways a solve gives up -- status 2 (regularisation overflow), 3 (non-finite cost), 4 (line search exhausted, at iteration 0
-and after accepted steps) -- on every kernel build, against the plain-C oracle, and what a failed instance leaves behind: for the
+and after accepted steps) -- on the four PLAIN kernel builds (the builds with traits -- user rows, barriers, second_order = 2, user
+builds: tests/test_gpu_failure_exits_builds.py), against the plain-C oracle, and what a failed instance leaves behind: for the
 healthy instances that run after it in the same queue slot (the same LDS tiles, dft / rec / gains / candidate buffers) and for the
 features behind a solve (resume flag and continue launch, iteration log, class history, policy export, record packing, the
 first-knot fetch).  The inputs are the table of tests/failure_cases.py; what the oracle does on each is asserted on the CPU by
